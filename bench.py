@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py — single-source FORA queries/sec on a synthetic R-MAT graph (BASELINE.json metric).
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR]
 
 Workload (N = 1): R-MAT scale 22 (n = 4 194 304, m = 67 108 864, generator seed 1), single-source FORA with
 alpha = 0.15, eps = 0.5.  A *step* is one batch of `--queries-per-step` sources drawn uniformly (seed 2) from the
@@ -41,6 +41,10 @@ Extra objects on the JSON line:
               measurements go on, the hash-map-shaped faithful port run to the end of two queries (one thread each,
               both times printed) and the dense-array port on two sources; after them, the array port on every core this job may use (its cgroup
               CPU quota), one query per core.
+`--dump-outputs DIR` writes what the last timed step returned on rank 0 (its own results and, at N > 1, the top-k
+blocks it gathered from every rank) as DIR/<name>.npy in float64, 64 MB at most (dump_outputs):
+with the same arguments the graph, the sources and the seeds are the same from run to run, so two builds can be
+compared output for output.  `ms_per_step` is the wall time of one timed step.
 After the timed region, at N = 1: `one_query_at_a_time` (the drop-in path, pprhip_fora_single_source), `topk_sample`
 (FORA top-32), `all_pair_sample` (All-Pair-Backward-Search on 2^18 targets) and `all_pair_rmat24` (config #5's graph
 on one GPU, in a child process), each with its own `roofline` incl. counter traffic.
@@ -157,6 +161,9 @@ def main():
     ap.add_argument("--cpu-walk-divisor", type=int, default=32)
     ap.add_argument("--tuning", default="", help="cost-model overrides, e.g. c_dense_edge_ns=0.002,max_rounds=30")
     ap.add_argument("--backend", default="nccl", help="torch.distributed backend for N > 1 (nccl = RCCL)")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="write what the last timed step returned on rank 0 (its own results and, at N > 1, the "
+                         "gathered top-k blocks) as DIR/<name>.npy, float64, at most 64 MB")
     args = ap.parse_args()
     if args.all_pair_child:
         return all_pair_child(args)
@@ -290,6 +297,7 @@ def main():
            "sweep_min_bytes": 0, "call_ms": 0.0, "walk_loads": 0, "walk_load_lanes": 0}
     last = {}
     gathered = {}
+    gathered_dump = {}  # (the gloo rehearsal's gathered blocks, kept for --dump-outputs only)
 
     def record_stats(st, nq):
         for c in range(8):
@@ -313,6 +321,7 @@ def main():
                 record_stats(st, q)
             ids_blk, vals_blk = ids, vals
         else:
+            nsel_blk = np.zeros(q, dtype=np.int32)
             for j in range(q):
                 s = int(srcs[i, j])
                 _, st = g.fora_single_source(s, EPS, ALPHA, seed=3 + i, n_rounds=args.rounds, conf=conf, fetch=False)
@@ -321,6 +330,8 @@ def main():
                 nsel, ids, vals, _, _ = g.topk_select(TOPK)
                 ids_blk[j, :len(ids)] = ids
                 vals_blk[j, :len(vals)] = vals
+                nsel_blk[j] = nsel
+            last.update(step=i, ids=ids_blk, vals=vals_blk, nsel=nsel_blk)
         if world > 1:  # the only exchange on the path: top-k blocks to rank 0
             if comm is not None:
                 got = comm.topk_gather(ids_blk, vals_blk, rows_max=q)  # pprhip_topk_gather (RCCL inside the library)
@@ -332,6 +343,8 @@ def main():
                 gl_v = [torch.empty_like(tv) for _ in range(world)] if rank == 0 else None
                 dist.gather(ti, gl_i, dst=0)
                 dist.gather(tv, gl_v, dst=0)
+                if rank == 0 and args.dump_outputs:
+                    gathered_dump.update(ids=torch.stack(gl_i).numpy(), vals=torch.stack(gl_v).numpy())
 
     for i in range(args.warmup):
         run_step(i, False)
@@ -353,6 +366,10 @@ def main():
 
     if rank == 0:
         note("timed region done: %.1f queries/s" % (args.steps * q * world / elapsed))
+    dumped = None
+    if args.dump_outputs and rank == 0:  # (before the step below: the store still holds the last timed step's vectors)
+        dumped = dump_outputs(args.dump_outputs, srcs[last["step"]], last, store, host.n,
+                              gathered=(gathered or gathered_dump) if world > 1 else None)
     acc_timed = acc
     if extra_step and bench_timing == "2":
         # per-class times of the same workload: one more step, every class timed, outside the timed region
@@ -494,6 +511,8 @@ def main():
             out["all_pair_scaling"] = all_pair_scaling
         if config4_strong is not None:
             out["config4_strong_scaling"] = config4_strong
+        if dumped is not None:
+            out["dumped_outputs"] = dumped
         extras = solo and not args.no_extras
         if extras:
             out.update(q50_sample(pkg, g, store, rng, live_ids, conf, value))
@@ -543,6 +562,45 @@ def main():
         g.close()
     if world > 1:
         dist.destroy_process_group()
+
+
+DUMP_BYTES = 64 << 20  # everything --dump-outputs writes, .npy headers included
+DUMP_HEADER_BYTES = 256  # allowance per .npy file for its header (numpy writes 128 bytes for these shapes)
+DUMP_SAMPLE_SEED = 11
+
+
+def dump_outputs(out_dir, srcs, last, store, n, gathered=None):
+    """What the last timed step handed its caller, as float64 .npy files in out_dir, DUMP_BYTES at most: the sources,
+    the top-k blocks (ids, values, number of entries >= the k-th value), at N > 1 the blocks rank 0 gathered from every
+    rank ([world, rows, k]), and, in batch mode, each query's vector from the result store - its mass (device-side
+    sum) and its entries at a fixed sample of nodes (seed DUMP_SAMPLE_SEED; every node when the graph is small
+    enough).  The sample takes what the other files leave of DUMP_BYTES, its node list included."""
+    q = len(srcs)
+    arrays = {"sources": srcs, "topk_ids": last["ids"], "topk_vals": last["vals"], "topk_count": last["nsel"]}
+    if gathered:
+        arrays.update(gathered_topk_ids=gathered["ids"], gathered_topk_vals=gathered["vals"])
+    n_files = len(arrays) + (3 if store is not None else 0)
+    fixed = 8 * (sum(np.size(a) for a in arrays.values()) + (q if store is not None else 0)) + DUMP_HEADER_BYTES * n_files
+    if fixed > DUMP_BYTES:
+        raise SystemExit("--dump-outputs: the top-k blocks of %d queries alone exceed %d bytes" % (q, DUMP_BYTES))
+    if store is not None:
+        per_row = min(n, (DUMP_BYTES - fixed) // (8 * (q + 1)))  # vector_sample [q, per_row] + vector_sample_nodes
+        nodes = np.arange(n) if per_row == n else \
+            np.sort(np.random.default_rng(DUMP_SAMPLE_SEED).choice(n, size=per_row, replace=False))
+        sample = np.empty((q, nodes.size))
+        for i in range(q):
+            sample[i] = store.fetch(i)[nodes]
+        arrays.update(vector_sample_nodes=nodes, vector_sample=sample,
+                      vector_mass=np.array([store.sum(i) for i in range(q)]))
+    os.makedirs(out_dir, exist_ok=True)
+    total = 0
+    for name, a in arrays.items():
+        path = os.path.join(out_dir, name + ".npy")
+        np.save(path, np.ascontiguousarray(a, dtype=np.float64))
+        total += os.path.getsize(path)
+    assert total <= DUMP_BYTES, total
+    return {"dir": os.path.abspath(out_dir), "files": sorted(k + ".npy" for k in arrays), "bytes": total,
+            "step": int(last["step"])}
 
 
 def host_gap(wall_ms, kernel_ms):
