@@ -390,6 +390,35 @@ int pprhip_fora_stream_close(pprhip_stream_t* s);
 int pprhip_fora_batch_topk(pprhip_graph_t* g, const int32_t* srcs, int q, int k, double eps, double alpha,
                            uint64_t seed, int32_t* ids_out, double* vals_out, pprhip_stats_t* stats_sum);
 
+/* ---------------------------------------------------------------- seed sets (beyond the reference)
+ * PPR personalized to a weighted node set, as Neo4j's PageRank takes it (sourceNodes; the reference passes one node,
+ * Neo4j_Method.java:73-77).  seeds: n_seeds >= 1 original ids; weights: n_seeds finite values >= 0, or NULL (uniform).
+ * Duplicates are summed, the weights normalized by their sum into p; zero weights are dropped.  An empty set, an id out
+ * of range, a negative / NaN / infinite weight or weights summing to 0 is PPRHIP_ERR_INVALID, the graph untouched.
+ * The target is pi_p of the walk that starts at a node drawn from p, stops with probability alpha per step and jumps
+ * to a node drawn from p at a dead end: the push starts from r = p and lands every level's dead-end mass x on p
+ * (r(s_i) += x p_i, with the threshold test of a push); a dead-end seed's share is resolved in closed form
+ * (DESIGN.md §2 "Seed sets").  The walks of FORA are the single-source path's: they start at residue nodes with the
+ * same counters and restart at their start node at a dead end (Monte_Carlo.java:87-90; the same walk quirk as the
+ * single-source path).  A set of one seed reduces to the single-source call (same levels, rounds and walks, reserve
+ * up to fp64 addition order).  One query at a time per handle; pprhip_get_reserve / _get_residue / pprhip_topk_select
+ * work on the result as after the single-source calls.  Generalized calls: pprhip_forward_push, pprhip_fora_single_source,
+ * pprhip_fora_topk. */
+/* pprhip_forward_push from p; outputs as there. */
+int pprhip_forward_push_seeds(pprhip_graph_t* g, const int32_t* seeds, const double* weights, int n_seeds,
+                              double alpha, double rmax, double* reserve_out, double* residue_out,
+                              double* rsum_out, pprhip_stats_t* stats);
+/* pprhip_fora_single_source from p (conf, eps, n_rounds, seed and the cost model as there); outputs as there. */
+int pprhip_fora_seeds(pprhip_graph_t* g, const int32_t* seeds, const double* weights, int n_seeds, double eps,
+                      const pprhip_fora_conf_t* conf, uint64_t seed, int n_rounds, double* reserve_out,
+                      pprhip_stats_t* stats);
+/* pprhip_fora_topk from p: the live seeds start parked, as {s} does for one source (Fora_Topk.java:117-118); outputs,
+ * selection rule and the state pprhip_get_reserve / pprhip_topk_select see afterwards as there.  The push session
+ * ends with the call (pprhip_fwdpush_topk_round needs a pprhip_fwdpush_topk_reset after it). */
+int pprhip_fora_topk_seeds(pprhip_graph_t* g, const int32_t* seeds, const double* weights, int n_seeds,
+                           double eps, const pprhip_fora_conf_t* conf, uint64_t seed, int32_t* ids_out,
+                           double* vals_out, int cap, int* n_out, double* reserve_out, pprhip_stats_t* stats);
+
 /* ---------------------------------------------------------------- backward search (a8, a9) */
 /* Backward_Search.backward_search_whole_graph(Long t) (Backward_Search.java:38-100). */
 int pprhip_backward_push(pprhip_graph_t* g, int32_t target, double alpha, double rmax, double* reserve_out,

@@ -83,7 +83,8 @@ EXPORTS = [
     "pprhip_topk_gather", "pprhip_comm_abort", "pprhip_owner_partition", "pprhip_index_from_entries",
     "pprhip_device_memory", "pprhip_graph_lift_host", "pprhip_lift_array", "pprhip_lift_destroy",
     "pprhip_fora_stream_open", "pprhip_fora_stream_submit", "pprhip_fora_stream_wait", "pprhip_fora_stream_close",
-    "pprhip_set_kernel_timing", "pprhip_shard_target_cuts",
+    "pprhip_set_kernel_timing", "pprhip_shard_target_cuts", "pprhip_forward_push_seeds", "pprhip_fora_seeds",
+    "pprhip_fora_topk_seeds",
 ]
 COMM_ID_BYTES = 128
 
@@ -140,6 +141,9 @@ def lib():
     L.pprhip_fwdpush_topk_round.argtypes = [vp, dbl, dbl, P(dbl), P(Stats)]
     L.pprhip_random_walk_batch.argtypes = [vp, vp, vp, u64, dbl, u64, u32, ci, vp, vp]
     L.pprhip_fora_single_source.argtypes = [vp, i32, dbl, P(ForaConf), u64, ci, vp, P(Stats)]
+    L.pprhip_forward_push_seeds.argtypes = [vp, vp, vp, ci, dbl, dbl, vp, vp, P(dbl), P(Stats)]
+    L.pprhip_fora_seeds.argtypes = [vp, vp, vp, ci, dbl, P(ForaConf), u64, ci, vp, P(Stats)]
+    L.pprhip_fora_topk_seeds.argtypes = [vp, vp, vp, ci, dbl, P(ForaConf), u64, vp, vp, ci, P(ci), vp, P(Stats)]
     L.pprhip_fora_topk.argtypes = [vp, i32, dbl, P(ForaConf), u64, vp, vp, ci, P(ci), vp, P(Stats)]
     L.pprhip_topk_select.argtypes = [vp, ci, vp, vp, ci, P(ci), P(dbl), P(Stats)]
     L.pprhip_monte_carlo.argtypes = [vp, i32, dbl, P(ForaConf), u64, vp, P(Stats)]
@@ -202,6 +206,15 @@ def _check(rc):
 
 def _ptr(a):
     return None if a is None else a.ctypes.data_as(C.c_void_p)
+
+
+def _seed_arrays(seeds, weights):
+    """A seed set as the C ABI takes it: int32 ids and float64 weights of the same length (None: uniform)."""
+    s = np.ascontiguousarray(np.atleast_1d(seeds), dtype=np.int32)
+    w = None if weights is None else np.ascontiguousarray(np.atleast_1d(weights), dtype=np.float64)
+    if w is not None and w.size != s.size:
+        raise ValueError("weights: %d entries for %d seeds" % (w.size, s.size))
+    return s, w
 
 
 def set_kernel_timing(on):
@@ -729,6 +742,40 @@ class Graph:
         _check(lib().pprhip_fora_single_source(self.h, src, eps, C.byref(conf), seed, n_rounds, _ptr(out),
                                                C.byref(st)))
         return out, st
+
+    def forward_push_seeds(self, seeds, alpha, rmax, weights=None, fetch=True):
+        """forward_push personalized to a seed set (weights None: uniform); the same return shape."""
+        s, w = _seed_arrays(seeds, weights)
+        reserve = np.empty(self.n) if fetch else None
+        residue = np.empty(self.n) if fetch else None
+        rsum, st = C.c_double(), Stats()
+        _check(lib().pprhip_forward_push_seeds(self.h, _ptr(s), _ptr(w), s.size, alpha, rmax, _ptr(reserve),
+                                               _ptr(residue), C.byref(rsum), C.byref(st)))
+        return reserve, residue, rsum.value, st
+
+    def fora_seeds(self, seeds, eps, alpha, seed, weights=None, n_rounds=0, conf=None, fetch=True):
+        """fora_single_source personalized to a seed set (weights None: uniform); the same return shape."""
+        s, w = _seed_arrays(seeds, weights)
+        conf = conf or conf_whole_graph(self.n, self.m, alpha)
+        out = np.empty(self.n) if fetch else None
+        st = Stats()
+        _check(lib().pprhip_fora_seeds(self.h, _ptr(s), _ptr(w), s.size, eps, C.byref(conf), seed, n_rounds,
+                                       _ptr(out), C.byref(st)))
+        return out, st
+
+    def fora_topk_seeds(self, seeds, eps, alpha, k, seed, weights=None, cap=None, conf=None, fetch=False):
+        """fora_topk personalized to a seed set (weights None: uniform); the same return shape."""
+        s, w = _seed_arrays(seeds, weights)
+        conf = conf or conf_topk(self.n, self.m, k, alpha)
+        cap = cap if cap is not None else k
+        ids = np.empty(max(cap, 1), dtype=np.int32)
+        vals = np.empty(max(cap, 1))
+        nsel, st = C.c_int(0), Stats()
+        out = np.empty(self.n) if fetch else None
+        _check(lib().pprhip_fora_topk_seeds(self.h, _ptr(s), _ptr(w), s.size, eps, C.byref(conf), seed, _ptr(ids),
+                                            _ptr(vals), cap, C.byref(nsel), _ptr(out), C.byref(st)))
+        w_ = min(nsel.value, cap)
+        return nsel.value, ids[:w_].copy(), vals[:w_].copy(), out, st
 
     def fora_topk(self, src, eps, alpha, k, seed, cap=None, conf=None, fetch=False):
         conf = conf or conf_topk(self.n, self.m, k, alpha)

@@ -571,7 +571,10 @@ int run_levels(pprhip_graph* g, const PushArgs& a, LevelCtx& L, pprhip_stats_t& 
     static const bool wg_on = !(hook_env("PPRHIP_SPARSE_WG") && hook_env("PPRHIP_SPARSE_WG")[0] == '0');
     constexpr unsigned long long kWgCap = 4096;
     const unsigned long long size0 = (unsigned long long)L.nf + L.ef;
-    const int wg_from = (!wg_on || cut_check) ? n_batch
+    // (a seed set lands each level's dead-end mass in a launch of its own between the level's two kernels: no
+    // one-workgroup levels)
+    const bool seeded = g->seed_on && !bwd;
+    const int wg_from = (!wg_on || cut_check || seeded) ? n_batch
                         : (!first_prepared && size0 < kWgCap) ? 0
                         : size0 < 65536                        ? 1
                                                                : 2;
@@ -582,6 +585,7 @@ int run_levels(pprhip_graph* g, const PushArgs& a, LevelCtx& L, pprhip_stats_t& 
       if (!(i == 0 && first_prepared))
         PPRHIP_TRY(launch_sparse_prepare(g, a, fb, i, i == 0 ? L.nf : 32768, dense_thresh, false, 0, L.dslot,
                                          i == 0 ? pk0 : ~0ull));
+      if (seeded) PPRHIP_TRY(launch_seed_land_sparse(g, a, fb, i, dense_thresh, L.dslot, i == 0 ? pk0 : ~0ull));
       PPRHIP_TRY(launch_sparse_push(g, a, fb, i, i == 0 ? L.ef : (1u << 20), dense_thresh, L.dslot, i == 0 ? pk0 : ~0ull));
     }
     if (wg_from < n_batch)
@@ -1669,6 +1673,7 @@ void pprhip_graph_destroy(pprhip_graph_t* g) {
     delete g->pn;
     g->pn = nullptr;
   }
+  seed_free(g);
   free_workspace(g);
   if (g->stream) (void)hipStreamDestroy(g->stream);
   delete g;
@@ -1797,6 +1802,7 @@ int pprhip_fwdpush_topk_reset(pprhip_graph_t* g, int32_t src, double alpha) {
   g->topk_active = true;
   g->topk_first = true;
   g->topk_src = src;
+  g->topk_seeded = false;
   g->topk_alpha = alpha;
   g->topk_rsum = 1.0;
   return PPRHIP_OK;
@@ -1806,15 +1812,19 @@ int pprhip_fwdpush_topk_reset(pprhip_graph_t* g, int32_t src, double alpha) {
 // DevCounters::sum_out for the walk plan; kSumNone: the caller sums later (a push run ahead of its round)
 enum { kSumRead = 0, kSumLaunch = 1, kSumNone = 2 };
 static int topk_round_impl(pprhip_graph_t* g, double min_rmax, double rmax, pprhip_stats_t& st, int sum_mode = kSumRead) {
-  const int32_t src = g->topk_src;
-  if (hdeg_out(g, src) == 0) {  // Forward_Push.java:149-153
+  const int32_t src = g->topk_src;  // (-1: a seed set, g->seeds)
+  if (!g->topk_seeded && hdeg_out(g, src) == 0) {  // Forward_Push.java:149-153
     PPRHIP_TRY(launch_set_f64(g, g->reserve, (uint32_t)src, 1.0));
     g->topk_rsum = 0.0;
     return PPRHIP_OK;
   }
-  if (g->topk_first) PPRHIP_TRY(launch_set_f64(g, g->residue, (uint32_t)src, 1.0));  // :155-156
+  if (g->topk_first) {
+    if (g->topk_seeded) PPRHIP_TRY(launch_seed_init(g, 0, true));  // r = p resolved, the live seeds parked
+    else PPRHIP_TRY(launch_set_f64(g, g->residue, (uint32_t)src, 1.0));  // :155-156
+  }
   PushArgs a{g->topk_alpha, rmax, min_rmax, src, kFwdTopk};
   LevelCtx L;
+  SeedScope scope(g, g->topk_seeded);
   PPRHIP_TRY(seed_scan(g, a, 1, L));
   PPRHIP_TRY(run_levels(g, a, L, st, nullptr));
   if (sum_mode == kSumRead) PPRHIP_TRY(device_sum(g, g->residue, &g->topk_rsum));
@@ -1979,20 +1989,23 @@ struct SpecContext {
 };
 }  // namespace
 
-int pprhip_fora_topk(pprhip_graph_t* g, int32_t src, double eps, const pprhip_fora_conf_t* conf, uint64_t seed,
-                     int32_t* ids_out, double* vals_out, int cap, int* n_out, double* reserve_out,
-                     pprhip_stats_t* stats) {
-  PPRHIP_TRY(check_graph(g, "pprhip_fora_topk"));
-  PPRHIP_TRY(check_node(g, src, "pprhip_fora_topk"));
+static bool fora_topk_args_ok(const pprhip_fora_conf_t* conf, double eps, int cap, const int32_t* ids_out,
+                              const double* vals_out, const char* fn) {
   if (!conf || conf->k < 1 || !(eps > 0.0) || cap < 0 || (cap > 0 && (!ids_out || !vals_out))) {
-    set_error("pprhip_fora_topk: bad arguments");
-    return PPRHIP_ERR_INVALID;
+    set_error("%s: bad arguments", fn);
+    return false;
   }
+  return true;
+}
+
+// Fora_Topk.computeTopKPPR's loop on the push session the caller has just reset: from one source (internal id src),
+// or from the seed table (src = -1, g->topk_seeded)
+static int fora_topk_run(pprhip_graph_t* g, int32_t src, double eps, const pprhip_fora_conf_t* conf, uint64_t seed,
+                         int32_t* ids_out, double* vals_out, int cap, int* n_out, double* reserve_out,
+                         pprhip_stats_t* stats) {
   pprhip_stats_t st;
   std::memset(&st, 0, sizeof st);
-  PPRHIP_TRY(pprhip_fwdpush_topk_reset(g, src, conf->alpha));
   g->topk_rsum = conf->rsum;
-  src = g->h_old2new[src];  // internal (degree-sorted) id
   CallTimer tm(g);
   const double alpha = conf->alpha;
   const double epsilon = eps * 0.5;  // Fora_Topk.java:109-110
@@ -2031,9 +2044,16 @@ int pprhip_fora_topk(pprhip_graph_t* g, int32_t src, double eps, const pprhip_fo
   while (delta_local >= min_delta) {  // :123
     rmax_local = epsilon * std::sqrt(delta_local / 3.0 / (double)conf->m / std::log(2.0 / conf->pfail));  // :124
     omega_local = (epsilon + 2.0) * std::log(2.0 / conf->pfail) / epsilon / epsilon / delta_local;          // :125
-    if (hdeg_out(g, src) == 0) {  // :126-132
+    // :126-132; a seed set whose seeds are all dead ends: the estimate is p (the reserve its start writes)
+    const bool all_dead = src < 0 ? g->seeds->n_live == 0 : hdeg_out(g, src) == 0;
+    if (all_dead) {
       PPRHIP_CHECK_HIP(hipMemsetAsync(g->est, 0, nd, g->stream));
-      PPRHIP_TRY(launch_set_f64(g, g->est, (uint32_t)src, 1.0));
+      if (src >= 0) {
+        PPRHIP_TRY(launch_set_f64(g, g->est, (uint32_t)src, 1.0));
+      } else {
+        PPRHIP_TRY(launch_seed_init(g, 0, true));
+        PPRHIP_CHECK_HIP(hipMemcpyAsync(g->est, g->reserve, nd, hipMemcpyDeviceToDevice, g->stream));
+      }
       rsum_local = 0.0;
       dead_src = true;
       break;
@@ -2162,6 +2182,38 @@ int pprhip_fora_topk(pprhip_graph_t* g, int32_t src, double eps, const pprhip_fo
   PPRHIP_TRY(copy_out(g, g->est, reserve_out));
   if (stats) *stats = st;
   return PPRHIP_OK;
+}
+
+int pprhip_fora_topk(pprhip_graph_t* g, int32_t src, double eps, const pprhip_fora_conf_t* conf, uint64_t seed,
+                     int32_t* ids_out, double* vals_out, int cap, int* n_out, double* reserve_out,
+                     pprhip_stats_t* stats) {
+  PPRHIP_TRY(check_graph(g, "pprhip_fora_topk"));
+  PPRHIP_TRY(check_node(g, src, "pprhip_fora_topk"));
+  if (!fora_topk_args_ok(conf, eps, cap, ids_out, vals_out, "pprhip_fora_topk")) return PPRHIP_ERR_INVALID;
+  PPRHIP_TRY(pprhip_fwdpush_topk_reset(g, src, conf->alpha));
+  return fora_topk_run(g, g->h_old2new[src], eps, conf, seed, ids_out, vals_out, cap, n_out, reserve_out, stats);
+}
+
+// pprhip_fora_topk from a seed set: the push session starts from p (the live seeds parked, as {s} is for one source)
+int pprhip_fora_topk_seeds(pprhip_graph_t* g, const int32_t* seeds, const double* weights, int n_seeds, double eps,
+                           const pprhip_fora_conf_t* conf, uint64_t seed, int32_t* ids_out, double* vals_out, int cap,
+                           int* n_out, double* reserve_out, pprhip_stats_t* stats) {
+  static const char* fn = "pprhip_fora_topk_seeds";
+  PPRHIP_TRY(check_graph(g, fn));
+  if (!fora_topk_args_ok(conf, eps, cap, ids_out, vals_out, fn)) return PPRHIP_ERR_INVALID;
+  SeedTable plan;
+  PPRHIP_TRY(seed_plan(g, seeds, weights, n_seeds, conf->alpha, fn, plan));
+  PPRHIP_TRY(reset_query_state(g, true, plan.max_id));
+  PPRHIP_TRY(seed_upload(g, plan));
+  g->topk_active = true;
+  g->topk_first = true;
+  g->topk_src = -1;
+  g->topk_seeded = true;
+  g->topk_alpha = conf->alpha;
+  g->topk_rsum = 1.0;
+  const int rc = fora_topk_run(g, -1, eps, conf, seed, ids_out, vals_out, cap, n_out, reserve_out, stats);
+  g->topk_active = false;  // (no public round continues a seed-set session)
+  return rc;
 }
 
 // ------------------------------------------------------------------ pure Monte-Carlo

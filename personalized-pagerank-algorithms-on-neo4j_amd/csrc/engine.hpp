@@ -3,6 +3,7 @@
 
 #include <atomic>
 #include <cstdlib>
+#include <vector>
 
 #include "common.hpp"
 
@@ -108,6 +109,26 @@ struct PanelLayout {
 };
 
 enum PushMode : int { kFwdWhole = 0, kFwdTopk = 1, kBackward = 2, kPower = 3 };
+
+// Seed table of a query personalized to a weighted node set (seeds.cpp; DESIGN.md §2 "Seed sets").  p is resolved for
+// the dead-end seeds: with D = the weight of the dead-end seeds, mass x landing on p gives a live seed i the residue
+// x * q_i, q_i = p_i / (1 - (1 - alpha) D), and a dead-end seed j the reserve x * e_j, e_j = alpha p_j / (1 - (1 - alpha) D).
+// Arrays in HBM, allocated on first use and grown; freed with the graph.
+struct SeedTable {
+  uint32_t cap = 0;               // entries id / w / eoff / zin hold
+  int32_t* id = nullptr;          // internal ids: the live seeds (ascending), then the dead-end seeds
+  double* w = nullptr;            // q_i of a live seed, e_j of a dead-end seed
+  uint32_t* eoff = nullptr;       // [n_live] the live seeds' edge offsets as the first frontier list
+  int32_t* zin = nullptr;         // [n_zin] live seeds without in-edges (extra rows of the dense apply)
+  double* w_node = nullptr;       // [n] q per node, zero elsewhere: the dense apply's landing weights
+  unsigned int* done = nullptr;   // workgroups of a landing launch that have read the dead-mass cell
+  uint32_t n_live = 0, n_dead = 0, n_zin = 0;
+  uint64_t e_live = 0;            // out-edges of the live seeds
+  int32_t max_id = -1;            // largest internal id of the set
+  std::vector<int32_t> h_id, h_zin;  // host staging of the arrays above
+  std::vector<double> h_w;
+  std::vector<uint32_t> h_eoff;
+};
 
 struct SelRec {  // one candidate of a top-k selection / one entry >= threshold of a backward search
   int32_t id, pad;
@@ -460,10 +481,14 @@ struct pprhip_graph {
   bool topk_active = false;
   bool topk_first = true;
   int32_t topk_src = -1;
+  bool topk_seeded = false;  // the session runs from the seed table (topk_src is -1)
   double topk_alpha = 0.0;
   double topk_rsum = 1.0;
   // what `reserve`/`est` currently hold
   bool result_in_est = false;
+  // seed-set query in progress (seeds.cpp: SeedScope): dead-end mass lands on the seed table, PushArgs::src is -1
+  pprhip::SeedTable* seeds = nullptr;
+  bool seed_on = false;
 };
 
 namespace pprhip {
@@ -518,6 +543,14 @@ bool old_small_kernels();
 inline uint32_t act_n(const pprhip_graph* g) { return g->n_act ? g->n_act : g->n; }  // entries a query's passes cover
 int launch_set_f64(pprhip_graph* g, double* p, uint32_t idx, double value);
 int launch_permute_out(pprhip_graph* g, const double* x, double* out);  // out[old] = x[old2new[old]]
+// seed sets (g->seeds): the query's start from p (residue, dead-end reserves, landing weights, and the frontier list
+// fbuf - top-k: the parked flags instead), the landing weights of the set before cleared (its first `count` entries), and
+// the landing of a sparse level's dead-end mass on p (between the level's two kernels; the dense levels land in
+// launch_dense_level)
+int launch_seed_init(pprhip_graph* g, int fbuf, bool topk = false);
+int launch_seed_clear(pprhip_graph* g, uint32_t count);
+int launch_seed_land_sparse(pprhip_graph* g, const PushArgs& a, int fbuf, int level, unsigned long long dense_thresh,
+                            int dead_slot, unsigned long long pk0);
 // Once per device, from the thread that lifts the first graph onto it: loads the code object of every
 // kernel file and opts the persistent sweep kernels into their large dynamic LDS, so that no launch
 // path sets function attributes or triggers a module load later (worker threads launch concurrently).

@@ -415,5 +415,29 @@ int index_from_device(pprhip_graph* g, const TripleRec* rec, unsigned long long 
                       pprhip_index_t** out);
 int index_concat(const std::vector<pprhip_index_t*>& parts, pprhip_index_t** out);
 
+// ---- seed sets (seeds.cpp)
+// the caller's seeds / weights (NULL: uniform) / count as p: distinct original ids ascending and their normalized
+// weights, duplicates summed, zero weights dropped; PPRHIP_ERR_INVALID for an empty set, an id outside [0, n), a
+// negative or non-finite weight, or weights that sum to 0
+int seed_normalize(uint32_t n, const int32_t* seeds, const double* weights, int k, const char* fn,
+                   std::vector<int32_t>& ids, std::vector<double>& p);
+// ... resolved for the dead-end seeds under alpha into the host half of a seed table (h_* arrays and counts)
+int seed_plan(pprhip_graph* g, const int32_t* seeds, const double* weights, int k, double alpha, const char* fn,
+              SeedTable& plan);
+int seed_upload(pprhip_graph* g, SeedTable& plan);  // plan -> g->seeds (HBM; allocated on first use, grown)
+int seed_start(pprhip_graph* g, LevelCtx& L);       // r = p resolved, the live seeds as L's frontier
+void seed_free(pprhip_graph* g);
+// the push levels of the calling query land dead-end mass on the seed table while the scope lasts
+struct SeedScope {
+  pprhip_graph* g;
+  bool on;
+  explicit SeedScope(pprhip_graph* g_, bool on_ = true) : g(g_), on(on_) {
+    if (on) g->seed_on = true;
+  }
+  ~SeedScope() {
+    if (on) g->seed_on = false;
+  }
+};
+
 }  // namespace detail
 }  // namespace pprhip

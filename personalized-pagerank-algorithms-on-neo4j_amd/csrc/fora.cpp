@@ -35,6 +35,7 @@ struct ForaRun {
   double alpha = 0, rsum_local = 0, rmax_local = 0, omega_local = 0, rmax_used = 0, model_cost = 0;
   int rounds = 0;
   bool dead_src = false;
+  bool seeded = false;  // a seed set (g->seeds) instead of src: src = -1 in the push arguments
   LevelCtx L;
   PushArgs a;
   RoundCut cut;
@@ -78,16 +79,18 @@ void leave_push(ForaRun& r) {
   }
 }
 
-int fora_begin(ForaRun& r, pprhip_graph* g, int32_t src_internal, double eps, const pprhip_fora_conf_t* conf,
-               uint64_t seed, int n_rounds) {
+// src_internal -1: the query runs from the seed table (g->seeds), whose largest id bounds the reset (reset_node)
+static int fora_begin_at(ForaRun& r, pprhip_graph* g, int32_t src_internal, int32_t reset_node, double eps,
+                         const pprhip_fora_conf_t* conf, uint64_t seed, int n_rounds) {
   r.g = g;
   r.src = src_internal;
+  r.seeded = src_internal < 0;
   r.conf = conf;
   r.seed = seed;
   r.n_rounds = n_rounds;
   std::memset(&r.st, 0, sizeof r.st);
   g->topk_active = false;
-  PPRHIP_TRY(reset_query_state(g, false, src_internal));
+  PPRHIP_TRY(reset_query_state(g, false, reset_node));
   r.alpha = conf->alpha;
   r.rsum_local = conf->rsum;
   PPRHIP_TRY(pprhip_fora_whole_params(conf, eps, &r.rmax_local, &r.omega_local));  // Fora_Whole_Graph.java:86-87
@@ -107,12 +110,24 @@ int fora_begin(ForaRun& r, pprhip_graph* g, int32_t src_internal, double eps, co
   r.rmax_used = r.rmax_local;
   r.model_cost = 0.0;
   r.rounds = 0;
-  r.dead_src = hdeg_out(g, src_internal) == 0;
+  r.dead_src = !r.seeded && hdeg_out(g, src_internal) == 0;
   r.L = LevelCtx();
   r.phase = ForaRun::kRoundStart;
   r.waiting = false;
   r.in_push = true;
   return PPRHIP_OK;
+}
+
+int fora_begin(ForaRun& r, pprhip_graph* g, int32_t src_internal, double eps, const pprhip_fora_conf_t* conf,
+               uint64_t seed, int n_rounds) {
+  return fora_begin_at(r, g, src_internal, src_internal, eps, conf, seed, n_rounds);
+}
+
+// the same query from a seed set: the table is installed here, the push starts from it in round 0 (seed_start)
+int fora_begin_seeds(ForaRun& r, pprhip_graph* g, SeedTable& plan, double eps, const pprhip_fora_conf_t* conf,
+                     uint64_t seed, int n_rounds) {
+  PPRHIP_TRY(fora_begin_at(r, g, -1, plan.max_id, eps, conf, seed, n_rounds));
+  return seed_upload(g, plan);
 }
 
 int fora_step(ForaRun& r, bool yield_dense) {
@@ -134,14 +149,16 @@ int fora_step(ForaRun& r, bool yield_dense) {
         r.phase = ForaRun::kWalks;
         continue;
       }
-      r.a = PushArgs{r.alpha, r.rmax_local, 0.0, r.src, kFwdWhole};
+      r.a = PushArgs{r.alpha, r.rmax_local, 0.0, r.seeded ? -1 : r.src, kFwdWhole};
       r.cut = RoundCut();
       r.cut.fixed = r.n_rounds > 0;
       r.cut.enabled = r.n_rounds > 0 ? r.rounds + 1 < r.n_rounds : r.rounds + 1 < g->tun.max_rounds;
       r.cut.omega = r.omega_local;
       r.cut.c_walk = g->tun.c_walk_ns;
       r.cut.alpha = r.alpha;
-      if (r.rounds == 0) {
+      if (r.rounds == 0 && r.seeded) {
+        PPRHIP_TRY(seed_start(g, r.L));
+      } else if (r.rounds == 0) {
         PPRHIP_TRY(launch_set_f64(g, g->residue, (uint32_t)r.src, 1.0));
         PPRHIP_TRY(seed_single(g, r.L, r.src, hdeg_out(g, r.src)));
       } else {
@@ -248,6 +265,7 @@ int topk_begin(ForaRun& r, pprhip_graph* g, int32_t src_internal, double eps, co
   g->topk_active = true;
   g->topk_first = true;
   g->topk_src = src_internal;
+  g->topk_seeded = false;
   g->topk_alpha = conf->alpha;
   g->topk_rsum = conf->rsum;
   r.alpha = conf->alpha;
@@ -439,6 +457,35 @@ int pprhip_fora_single_source(pprhip_graph_t* g, int32_t src, double eps, const 
   CallTimer tm(g);
   r.tm = &tm;
   PPRHIP_TRY(fora_step(r, false));
+  tm.finish(r.st);
+  r.st.push_ms = CallTimer::ms(g->ev[0], g->ev[1]);
+  r.st.mc_ms = CallTimer::ms(g->ev[1], g->ev[2]);
+  PPRHIP_TRY(copy_out(g, g->reserve, reserve_out));
+  if (stats) *stats = r.st;
+  return PPRHIP_OK;
+}
+
+// Fora_Whole_Graph.computeWholeGraphPPR from a seed set: the same rounds, thresholds, cost model and walks, the push
+// started from p and its dead-end mass landed on p (seeds.cpp)
+int pprhip_fora_seeds(pprhip_graph_t* g, const int32_t* seeds, const double* weights, int n_seeds, double eps,
+                      const pprhip_fora_conf_t* conf, uint64_t seed, int n_rounds, double* reserve_out,
+                      pprhip_stats_t* stats) {
+  static const char* fn = "pprhip_fora_seeds";
+  PPRHIP_TRY(check_graph(g, fn));
+  if (!conf || !(eps > 0.0) || n_rounds < 0) {
+    set_error("%s: bad arguments (eps=%g n_rounds=%d)", fn, eps, n_rounds);
+    return PPRHIP_ERR_INVALID;
+  }
+  SeedTable plan;
+  PPRHIP_TRY(seed_plan(g, seeds, weights, n_seeds, conf->alpha, fn, plan));
+  ForaRun r;
+  PPRHIP_TRY(fora_begin_seeds(r, g, plan, eps, conf, seed, n_rounds));
+  CallTimer tm(g);
+  r.tm = &tm;
+  {
+    SeedScope scope(g);
+    PPRHIP_TRY(fora_step(r, false));
+  }
   tm.finish(r.st);
   r.st.push_ms = CallTimer::ms(g->ev[0], g->ev[1]);
   r.st.mc_ms = CallTimer::ms(g->ev[1], g->ev[2]);

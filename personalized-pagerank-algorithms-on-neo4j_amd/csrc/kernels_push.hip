@@ -272,8 +272,8 @@ __device__ __forceinline__ void sparse_push_body(const int32_t* __restrict__ F, 
     }
   __syncthreads();
 
-  if (MODE != kBackward && bid == 0) {
-    // dead-end mass of this level lands on the source (Forward_Push.java:101-113)
+  if (MODE != kBackward && bid == 0 && a.src >= 0) {
+    // dead-end mass of this level lands on the source (Forward_Push.java:101-113; seed sets: k_seed_land_sparse)
     if (tid == 0) {
       const double dead = ctr->dead[dead_slot];
       if (dead > 0.0) {
@@ -962,7 +962,9 @@ __global__ __launch_bounds__(256) void k_dense_apply(const int32_t* __restrict__
                                                       DevCounters* ctr, unsigned long long* __restrict__ blk_pack,
                                                       double* __restrict__ blk_dead, uint32_t* __restrict__ blk_ndead,
                                                       int dead_slot, int src_extra, PushArgs a,
-                                                      const int* state_in, int state0, int last_block) {
+                                                      const int* state_in, int state0, int last_block,
+                                                      const double* __restrict__ seed_w,
+                                                      const int32_t* __restrict__ extra_rows) {
   // rows [j_lo, n_nz) of one block (n_nz = the block's end; + the source without in-edges behind the last block)
   __shared__ double s_red[4];
   __shared__ unsigned long long s_red2[4];
@@ -992,8 +994,8 @@ __global__ __launch_bounds__(256) void k_dense_apply(const int32_t* __restrict__
       acc_nz[j] = 0.0;
     }
     have = true;
-  } else if (j == n_nz && src_extra) {
-    u = a.src;
+  } else if (j - n_nz < (uint32_t)src_extra) {  // (j >= n_nz here)
+    u = extra_rows ? extra_rows[j - n_nz] : a.src;
     have = true;
   }
   double dead_next = 0.0;
@@ -1004,6 +1006,13 @@ __global__ __launch_bounds__(256) void k_dense_apply(const int32_t* __restrict__
       if (dd > 0.0) {
         acc += dd;
         ctr->dead[dead_slot] = 0.0;
+      }
+    } else if (MODE != kBackward && seed_w) {
+      // seed set: the level's dead-end mass lands on the live seeds as p does (k_seed_land_dense zeroes the cell)
+      const double w = seed_w[u];
+      if (w != 0.0) {
+        const double dd = ctr->dead[dead_slot];
+        if (dd > 0.0) acc += dd * w;
       }
     }
     const uint32_t d = out_rp[u + 1] - out_rp[u];
@@ -1652,6 +1661,99 @@ __global__ __launch_bounds__(256) void k_permute_out(const double* __restrict__ 
 }
 
 // ------------------------------------------------------------------------------------------------
+// seed sets (engine.hpp: SeedTable): a query personalized to a weighted node set p
+// ------------------------------------------------------------------------------------------------
+// Query start: r = q on the live seeds, reserve = e on the dead-end seeds (p resolved once, as if mass 1 landed on it),
+// the live seeds' landing weights per node, and the live seeds as the first frontier list (edge offsets from the host)
+// - or, top-k (flags != nullptr), as the parked set the first round starts from (Fora_Topk.java:117-118 for one seed).
+__global__ __launch_bounds__(256) void k_seed_init(const int32_t* __restrict__ id, const double* __restrict__ w,
+                                                    const uint32_t* __restrict__ eoff_in, uint32_t n_live, uint32_t n_all,
+                                                    double* __restrict__ res, double* __restrict__ reserve,
+                                                    double* __restrict__ w_node, int32_t* __restrict__ F,
+                                                    uint32_t* __restrict__ eoff, uint8_t* __restrict__ flags) {
+  for (uint32_t i = blockIdx.x * blockDim.x + threadIdx.x; i < n_all; i += gridDim.x * blockDim.x) {
+    const int32_t u = id[i];
+    const double x = w[i];
+    if (i < n_live) {
+      res[u] = x;
+      w_node[u] = x;
+      if (flags) {
+        flags[u] = 1;
+      } else {
+        F[i] = u;
+        eoff[i] = eoff_in[i];
+      }
+    } else {
+      reserve[u] = x;
+    }
+  }
+}
+
+// The landing weights of the set before go back to zero (the first `count` entries of its table: its live seeds).
+__global__ __launch_bounds__(256) void k_seed_clear(const int32_t* __restrict__ id, uint32_t count,
+                                                     double* __restrict__ w_node) {
+  for (uint32_t i = blockIdx.x * blockDim.x + threadIdx.x; i < count; i += gridDim.x * blockDim.x) w_node[id[i]] = 0.0;
+}
+
+// The dead-mass cell is read by every workgroup of a landing launch and zeroed by the last one to finish.
+__device__ __forceinline__ void seed_land_done(unsigned int* done, DevCounters* ctr, int dead_slot) {
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    __threadfence();
+    if (atomicAdd(done, 1u) == gridDim.x - 1) {
+      ctr->dead[dead_slot] = 0.0;
+      *done = 0u;
+    }
+  }
+}
+
+// A sparse level's dead-end mass x lands on p, between the level's prepare and push kernels (the push kernel's inline
+// landing on a.src stays off: a.src = -1): r(i) += x q_i with push_one's threshold test, enqueue and parking for every
+// live seed, reserve(j) += x e_j for every dead-end seed.  Runs iff the level runs (level_runs), returns at once when the
+// level returned no mass.
+template <int MODE>
+__global__ __launch_bounds__(256) void k_seed_land_sparse(const int32_t* __restrict__ id, const double* __restrict__ w,
+                                                           uint32_t n_live, uint32_t n_all, unsigned int* done,
+                                                           const unsigned long long* __restrict__ out_ext,
+                                                           const uint32_t* __restrict__ in_rp, double* __restrict__ res,
+                                                           double* __restrict__ reserve, uint8_t* __restrict__ flags,
+                                                           uint32_t* __restrict__ armed, int32_t* __restrict__ Fn,
+                                                           uint32_t* __restrict__ eoffn, DevCounters* ctr, int level,
+                                                           unsigned long long dense_thresh, int dead_slot,
+                                                           unsigned long long pk0, PushArgs a) {
+  __shared__ NewList s_new;
+  const unsigned long long pk = (level == 0 && pk0 != ~0ull) ? pk0 : ctr->hist[level];
+  if (!level_runs(pk, level, dense_thresh)) return;
+  const double x = ctr->dead[dead_slot];
+  if (!(x > 0.0)) return;
+  if (threadIdx.x == 0) s_new.count = 0;
+  __syncthreads();
+  for (uint32_t base = blockIdx.x * blockDim.x; base < n_all; base += gridDim.x * blockDim.x) {  // (uniform trip count)
+    const uint32_t i = base + threadIdx.x;
+    if (i < n_live)
+      push_one<MODE>(id[i], x * w[i], out_ext, in_rp, res, flags, armed, &s_new, a);
+    else if (i < n_all)
+      reserve[id[i]] = reserve[id[i]] + x * w[i];  // (a dead-end seed is listed once; nothing else writes reserve now)
+    flush_new(&s_new, Fn, eoffn, &ctr->hist[level + 1]);
+  }
+  seed_land_done(done, ctr, dead_slot);
+}
+
+// After a dense level's apply kernels: the live seeds took their share x q_i inside the apply (seed_w), like the source
+// row of a single-source query; here the dead-end seeds take x e_j and the cell is cleared.
+__global__ __launch_bounds__(256) void k_seed_land_dense(const int32_t* __restrict__ id, const double* __restrict__ w,
+                                                          uint32_t n_live, uint32_t n_all, unsigned int* done,
+                                                          double* __restrict__ reserve, DevCounters* ctr, int dead_slot,
+                                                          const int* state_in, int state0) {
+  if (dense_state(state_in, state0) == kGsNone) return;
+  const double x = ctr->dead[dead_slot];
+  if (!(x > 0.0)) return;
+  for (uint32_t i = n_live + blockIdx.x * blockDim.x + threadIdx.x; i < n_all; i += gridDim.x * blockDim.x)
+    reserve[id[i]] = reserve[id[i]] + x * w[i];
+  seed_land_done(done, ctr, dead_slot);
+}
+
+// ------------------------------------------------------------------------------------------------
 // launchers
 // ------------------------------------------------------------------------------------------------
 static inline uint32_t grid_for(uint64_t work, uint32_t per_block, uint32_t cap) {
@@ -1730,7 +1832,11 @@ int launch_dense_level(pprhip_graph* g, const PushArgs& a, int cbuf, int out_slo
   const int32_t* nz = bwd ? g->nz_rows_o : g->nz_rows;
   const uint32_t n_nz = bwd ? g->n_nz_o : g->n_nz;
   // a source without in-edges still receives returned dead-end mass: one extra apply thread, behind the last block
-  const int src_extra = (!bwd && a.src >= 0 && g->h_in_rp[a.src + 1] == g->h_in_rp[a.src]) ? 1 : 0;
+  // (a seed set: one per live seed without in-edges; the live seeds' landing weights go to the apply kernel)
+  const SeedTable* sd = (!bwd && g->seed_on) ? g->seeds : nullptr;
+  const int src_extra = sd ? (int)sd->n_zin : (!bwd && a.src >= 0 && g->h_in_rp[a.src + 1] == g->h_in_rp[a.src]) ? 1 : 0;
+  const double* seed_w = sd ? sd->w_node : nullptr;
+  const int32_t* extra_rows = sd ? sd->zin : nullptr;
   const GsBlock whole{0u, n_nz, 0ull, (unsigned long long)g->m};
   const GsBlock* blocks = (dl.blocks && dl.n_blocks > 1 && !bwd) ? dl.blocks : &whole;
   const int nb = blocks == &whole ? 1 : dl.n_blocks;
@@ -1812,17 +1918,22 @@ int launch_dense_level(pprhip_graph* g, const PushArgs& a, int cbuf, int out_slo
                                   nz, B.j_lo, B.j_hi, g->pn_part, pn->panels, g->out_rp, g->in_rp, g->cdense[cbuf],
                                   g->cdense[cbuf ^ 1], g->residue, g->reserve, g->flags, g->armed, g->ctr,
                                   g->blk_pack + part_base, g->blk_dead + part_base, g->blk_ndead + part_base, dead_slot,
-                                  extra, a, dl.state_in, dl.state0, b == nb - 1 ? 1 : 0)));
+                                  extra, a, dl.state_in, dl.state0, b == nb - 1 ? 1 : 0, seed_w, extra_rows)));
       } else {
         DISPATCH_MODE(a.mode, (k_dense_apply<M, false><<<dim3(grid), dim3(256), 0, g->stream>>>(
                                   nz, B.j_lo, B.j_hi, g->acc_nz, nullptr, g->out_rp, g->in_rp, g->cdense[cbuf],
                                   g->cdense[cbuf ^ 1], g->residue, g->reserve, g->flags, g->armed, g->ctr,
                                   g->blk_pack + part_base, g->blk_dead + part_base, g->blk_ndead + part_base, dead_slot,
-                                  extra, a, dl.state_in, dl.state0, b == nb - 1 ? 1 : 0)));
+                                  extra, a, dl.state_in, dl.state0, b == nb - 1 ? 1 : 0, seed_w, extra_rows)));
       }
       PPRHIP_CHECK_HIP(hipGetLastError());
       part_base += grid;
     }
+  }
+  if (sd) {
+    k_seed_land_dense<<<dim3(grid_for(sd->n_dead, 256, 1024)), dim3(256), 0, g->stream>>>(
+        sd->id, sd->w, sd->n_live, sd->n_live + sd->n_dead, sd->done, g->reserve, g->ctr, dead_slot, dl.state_in, dl.state0);
+    PPRHIP_CHECK_HIP(hipGetLastError());
   }
   k_dense_reduce<<<dim3(1), dim3(1024), 0, g->stream>>>(g->blk_pack, g->blk_dead, g->blk_ndead, part_base, g->ctr,
                                                         out_slot, dead_slot ^ 1, dl.state_in, dl.state0, dl.hist_out,
@@ -2072,6 +2183,37 @@ int init_kernels_push() {
   hipFuncAttributes fa;
   PPRHIP_CHECK_HIP(hipFuncGetAttributes(&fa, reinterpret_cast<const void*>(&k_sparse_push<kBackward>)));
   PPRHIP_CHECK_HIP(hipFuncGetAttributes(&fa, reinterpret_cast<const void*>(&k_dense_apply_batch)));
+  return PPRHIP_OK;
+}
+
+int launch_seed_init(pprhip_graph* g, int fbuf, bool topk) {
+  const SeedTable* sd = g->seeds;
+  const uint32_t n_all = sd->n_live + sd->n_dead;
+  k_seed_init<<<dim3(grid_for(n_all, 256, 4096)), dim3(256), 0, g->stream>>>(
+      sd->id, sd->w, sd->eoff, sd->n_live, n_all, g->residue, g->reserve, sd->w_node, g->F[fbuf], g->eoff[fbuf],
+      topk ? g->flags : nullptr);
+  PPRHIP_CHECK_HIP(hipGetLastError());
+  return PPRHIP_OK;
+}
+
+int launch_seed_clear(pprhip_graph* g, uint32_t count) {
+  if (!count) return PPRHIP_OK;
+  const SeedTable* sd = g->seeds;
+  k_seed_clear<<<dim3(grid_for(count, 256, 4096)), dim3(256), 0, g->stream>>>(sd->id, count, sd->w_node);
+  PPRHIP_CHECK_HIP(hipGetLastError());
+  return PPRHIP_OK;
+}
+
+int launch_seed_land_sparse(pprhip_graph* g, const PushArgs& a, int fbuf, int level, unsigned long long dense_thresh,
+                            int dead_slot, unsigned long long pk0) {
+  const SeedTable* sd = g->seeds;
+  const uint32_t n_all = sd->n_live + sd->n_dead;
+  const uint32_t grid = grid_for(n_all, 256, 1024);
+  DISPATCH_MODE(a.mode, k_seed_land_sparse<M><<<dim3(grid), dim3(256), 0, g->stream>>>(
+                            sd->id, sd->w, sd->n_live, n_all, sd->done, g->out_ext, g->in_rp, g->residue, g->reserve,
+                            g->flags, g->armed, g->F[fbuf ^ 1], g->eoff[fbuf ^ 1], g->ctr, level, dense_thresh, dead_slot,
+                            pk0, a));
+  PPRHIP_CHECK_HIP(hipGetLastError());
   return PPRHIP_OK;
 }
 

@@ -1,0 +1,244 @@
+// seeds.cpp — queries personalized to a weighted node set (Neo4j PageRank's sourceNodes, which the reference only ever
+// passes one node: Neo4j_Method.java:73-77): the caller's arrays normalized into p, p resolved for the dead-end seeds,
+// the seed table in HBM, and the forward push from p (FORA: fora.cpp, top-k: engine.cpp).  DESIGN.md §2 "Seed sets"
+// states the rule.
+#include <algorithm>
+#include <cmath>
+#include <cstring>
+
+#include "engine_internal.hpp"
+
+namespace pprhip {
+namespace detail {
+
+int seed_normalize(uint32_t n, const int32_t* seeds, const double* weights, int k, const char* fn,
+                   std::vector<int32_t>& ids, std::vector<double>& p) {
+  ids.clear();
+  p.clear();
+  if (k <= 0 || !seeds) {
+    set_error("%s: a seed set needs at least one seed (n_seeds=%d)", fn, k);
+    return PPRHIP_ERR_INVALID;
+  }
+  std::vector<std::pair<int32_t, double>> e((size_t)k);
+  for (int i = 0; i < k; ++i) {
+    const int32_t v = seeds[i];
+    if (v < 0 || (uint32_t)v >= n) {
+      set_error("%s: seed %d: node id %d outside [0, %u)", fn, i, v, n);
+      return PPRHIP_ERR_INVALID;
+    }
+    const double w = weights ? weights[i] : 1.0;
+    if (!std::isfinite(w) || w < 0.0) {
+      set_error("%s: seed %d: weight %g is not a finite non-negative number", fn, i, w);
+      return PPRHIP_ERR_INVALID;
+    }
+    e[(size_t)i] = {v, w};
+  }
+  std::sort(e.begin(), e.end(), [](const std::pair<int32_t, double>& a, const std::pair<int32_t, double>& b) {
+    return a.first < b.first;
+  });
+  double sum = 0.0;
+  for (const auto& x : e) sum += x.second;
+  if (!(sum > 0.0) || !std::isfinite(sum)) {
+    set_error("%s: the seed weights sum to %g", fn, sum);
+    return PPRHIP_ERR_INVALID;
+  }
+  for (size_t i = 0; i < e.size();) {  // duplicates are summed, zero weights dropped
+    size_t j = i;
+    double w = 0.0;
+    for (; j < e.size() && e[j].first == e[i].first; ++j) w += e[j].second;
+    if (w > 0.0) {
+      ids.push_back(e[i].first);
+      p.push_back(w / sum);
+    }
+    i = j;
+  }
+  return PPRHIP_OK;
+}
+
+int seed_plan(pprhip_graph* g, const int32_t* seeds, const double* weights, int k, double alpha, const char* fn,
+              SeedTable& t) {
+  std::vector<int32_t> ids;
+  std::vector<double> p;
+  PPRHIP_TRY(seed_normalize(g->n, seeds, weights, k, fn, ids, p));
+  struct E {
+    int32_t v;
+    double p;
+  };
+  std::vector<E> live, dead;
+  double D = 0.0;
+  for (size_t i = 0; i < ids.size(); ++i) {
+    const int32_t v = g->h_old2new[ids[i]];
+    if (hdeg_out(g, v) == 0) {
+      dead.push_back({v, p[i]});
+      D += p[i];
+    } else {
+      live.push_back({v, p[i]});
+    }
+  }
+  auto by_id = [](const E& a, const E& b) { return a.v < b.v; };
+  std::sort(live.begin(), live.end(), by_id);
+  std::sort(dead.begin(), dead.end(), by_id);
+  // mass x landing on p: live seed i gets x p_i / (1 - (1 - alpha) D) as residue, dead-end seed j alpha x p_j / (...)
+  // as reserve - the closed form of landing, taking alpha, and landing again at the dead-end seeds
+  const double den = 1.0 - (1.0 - alpha) * D;
+  t.h_id.clear();
+  t.h_w.clear();
+  t.h_eoff.clear();
+  t.h_zin.clear();
+  t.e_live = 0;
+  t.max_id = -1;
+  for (const E& x : live) {
+    t.h_id.push_back(x.v);
+    t.h_w.push_back(x.p / den);
+    t.h_eoff.push_back((uint32_t)t.e_live);
+    t.e_live += hdeg_out(g, x.v);
+    if (hdeg_in(g, x.v) == 0) t.h_zin.push_back(x.v);
+    t.max_id = std::max(t.max_id, x.v);
+  }
+  for (const E& x : dead) {
+    t.h_id.push_back(x.v);
+    t.h_w.push_back(live.empty() ? x.p : alpha * x.p / den);  // (every seed a dead end: the result is p itself)
+    t.max_id = std::max(t.max_id, x.v);
+  }
+  t.n_live = (uint32_t)live.size();
+  t.n_dead = (uint32_t)dead.size();
+  t.n_zin = (uint32_t)t.h_zin.size();
+  return PPRHIP_OK;
+}
+
+int seed_upload(pprhip_graph* g, SeedTable& plan) {
+  if (!g->seeds) {
+    g->seeds = new (std::nothrow) SeedTable();
+    if (!g->seeds) return PPRHIP_ERR_OOM;
+  }
+  SeedTable& t = *g->seeds;
+  const uint32_t count = plan.n_live + plan.n_dead;
+  if (!t.w_node) {  // (all-zero from here on: each upload clears the entries of the set before)
+    PPRHIP_TRY(alloc_dev((void**)&t.w_node, sizeof(double) * (size_t)g->n));
+    PPRHIP_TRY(alloc_dev((void**)&t.done, sizeof(unsigned int)));
+    PPRHIP_CHECK_HIP(hipMemsetAsync(t.w_node, 0, sizeof(double) * (size_t)g->n, g->stream));
+    PPRHIP_CHECK_HIP(hipMemsetAsync(t.done, 0, sizeof(unsigned int), g->stream));
+  }
+  PPRHIP_TRY(launch_seed_clear(g, t.n_live));  // the set before's landing weights, while its ids are still in the table
+  if (count > t.cap) {
+    void* old[] = {t.id, t.w, t.eoff, t.zin};
+    for (void* q : old)
+      if (q) (void)hipFree(q);  // (hipFree waits for the work queued on them)
+    t.id = nullptr;
+    t.w = nullptr;
+    t.eoff = nullptr;
+    t.zin = nullptr;
+    t.cap = 0;
+    const uint32_t cap = std::max<uint32_t>(count, 1024u);
+    PPRHIP_TRY(alloc_dev((void**)&t.id, sizeof(int32_t) * cap));
+    PPRHIP_TRY(alloc_dev((void**)&t.w, sizeof(double) * cap));
+    PPRHIP_TRY(alloc_dev((void**)&t.eoff, sizeof(uint32_t) * cap));
+    PPRHIP_TRY(alloc_dev((void**)&t.zin, sizeof(int32_t) * cap));
+    t.cap = cap;
+  }
+  // Copies from pageable memory: the runtime has taken the bytes when the call returns, so the staging vectors (kept in
+  // the table until the next upload) may change at once; no wait on the stream.
+  t.h_id.swap(plan.h_id);
+  t.h_w.swap(plan.h_w);
+  t.h_eoff.swap(plan.h_eoff);
+  t.h_zin.swap(plan.h_zin);
+  t.n_live = plan.n_live;
+  t.n_dead = plan.n_dead;
+  t.n_zin = plan.n_zin;
+  t.e_live = plan.e_live;
+  t.max_id = plan.max_id;
+  if (count) {
+    PPRHIP_CHECK_HIP(hipMemcpyAsync(t.id, t.h_id.data(), sizeof(int32_t) * count, hipMemcpyHostToDevice, g->stream));
+    PPRHIP_CHECK_HIP(hipMemcpyAsync(t.w, t.h_w.data(), sizeof(double) * count, hipMemcpyHostToDevice, g->stream));
+  }
+  if (t.n_live)
+    PPRHIP_CHECK_HIP(hipMemcpyAsync(t.eoff, t.h_eoff.data(), sizeof(uint32_t) * t.n_live, hipMemcpyHostToDevice, g->stream));
+  if (t.n_zin)
+    PPRHIP_CHECK_HIP(hipMemcpyAsync(t.zin, t.h_zin.data(), sizeof(int32_t) * t.n_zin, hipMemcpyHostToDevice, g->stream));
+  return PPRHIP_OK;
+}
+
+int seed_start(pprhip_graph* g, LevelCtx& L) {
+  const SeedTable& t = *g->seeds;
+  if (t.n_live + t.n_dead) PPRHIP_TRY(launch_seed_init(g, L.fcur));
+  L.nf = t.n_live;
+  L.ef = t.e_live;
+  L.dense_prepared = false;
+  L.gs_dirty = false;
+  return PPRHIP_OK;
+}
+
+void seed_free(pprhip_graph* g) {
+  if (!g->seeds) return;
+  void* ptrs[] = {g->seeds->id, g->seeds->w, g->seeds->eoff, g->seeds->zin, g->seeds->w_node, g->seeds->done};
+  for (void* q : ptrs)
+    if (q) (void)hipFree(q);
+  delete g->seeds;
+  g->seeds = nullptr;
+  g->seed_on = false;
+}
+
+}  // namespace detail
+}  // namespace pprhip
+
+using namespace pprhip;
+using namespace pprhip::detail;
+
+extern "C" {
+
+int pprhip_forward_push_seeds(pprhip_graph_t* g, const int32_t* seeds, const double* weights, int n_seeds,
+                              double alpha, double rmax, double* reserve_out, double* residue_out, double* rsum_out,
+                              pprhip_stats_t* stats) {
+  static const char* fn = "pprhip_forward_push_seeds";
+  PPRHIP_TRY(check_graph(g, fn));
+  SeedTable plan;
+  PPRHIP_TRY(seed_plan(g, seeds, weights, n_seeds, alpha, fn, plan));
+  pprhip_stats_t st;
+  std::memset(&st, 0, sizeof st);
+  g->topk_active = false;
+  PPRHIP_TRY(reset_query_state(g, false, plan.max_id));
+  PPRHIP_TRY(seed_upload(g, plan));
+  CallTimer tm(g);
+  double rsum = 0.0;
+  {
+    SeedScope scope(g);
+    PushArgs a{alpha, rmax, 0.0, -1, kFwdWhole};
+    LevelCtx L;
+    PPRHIP_TRY(seed_start(g, L));
+    if (L.nf) {
+      PPRHIP_TRY(run_levels(g, a, L, st, nullptr));
+      PPRHIP_TRY(device_sum(g, g->residue, &rsum));
+      PPRHIP_TRY(read_dead_pops(g, st));
+    }
+  }
+  tm.mark(1);
+  tm.finish(st);
+  st.push_ms = CallTimer::ms(g->ev[0], g->ev[1]);
+  st.rsum = rsum;
+  st.rmax_final = rmax;
+  st.rounds = 1;
+  if (rsum_out) *rsum_out = rsum;
+  PPRHIP_TRY(copy_out(g, g->reserve, reserve_out));
+  PPRHIP_TRY(copy_out(g, g->residue, residue_out));
+  if (stats) *stats = st;
+  return PPRHIP_OK;
+}
+
+#ifdef PPRHIP_TEST_HOOKS
+// Test hook (libpprhip_hooks.so only): the argument normalization of the seed-set entry points, without a device.
+// ids_out / p_out hold n_seeds entries; *count_out receives the distinct seeds of non-zero weight.
+int pprhip_hook_seed_normalize(uint32_t n, const int32_t* seeds, const double* weights, int n_seeds, int32_t* ids_out,
+                               double* p_out, int* count_out) {
+  std::vector<int32_t> ids;
+  std::vector<double> p;
+  PPRHIP_TRY(seed_normalize(n, seeds, weights, n_seeds, "pprhip_hook_seed_normalize", ids, p));
+  for (size_t i = 0; i < ids.size(); ++i) {
+    if (ids_out) ids_out[i] = ids[i];
+    if (p_out) p_out[i] = p[i];
+  }
+  if (count_out) *count_out = (int)ids.size();
+  return PPRHIP_OK;
+}
+#endif
+
+}  // extern "C"
