@@ -121,6 +121,19 @@ def lib():
         L.orc_tuning_default.restype = None
         L.orc_set_sync_tuning.argtypes = [C.POINTER(Tuning)]
         L.orc_set_sync_tuning.restype = None
+        L.orc_seed_plan.restype = C.c_int
+        L.orc_seed_plan.argtypes = [C.POINTER(Graph), C.c_void_p, C.c_void_p, C.c_int, C.c_double, C.c_void_p,
+                                    C.c_void_p, C.c_void_p, C.POINTER(C.c_int), C.POINTER(C.c_int)]
+        L.orc_forward_push_seeds.restype = C.c_int
+        L.orc_forward_push_seeds.argtypes = [C.POINTER(Graph), C.c_void_p, C.c_void_p, C.c_int, C.c_double, C.c_double,
+                                             C.c_void_p, C.c_void_p, dp, C.POINTER(Stats)]
+        L.orc_fora_whole_seeds.restype = C.c_int
+        L.orc_fora_whole_seeds.argtypes = [C.POINTER(Graph), C.c_void_p, C.c_void_p, C.c_int, C.c_double,
+                                           C.POINTER(Conf), C.c_uint64, C.c_int, C.POINTER(Tuning), C.c_void_p,
+                                           C.POINTER(Stats)]
+        L.orc_fora_topk_seeds.restype = C.c_int
+        L.orc_fora_topk_seeds.argtypes = [C.POINTER(Graph), C.c_void_p, C.c_void_p, C.c_int, C.c_double,
+                                          C.POINTER(Conf), C.c_uint64, C.c_void_p, C.POINTER(Stats)]
         L.orc_max_err.restype = C.c_double
         L.orc_max_err.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32]
         L.orc_precision.restype = C.c_double
@@ -133,6 +146,18 @@ def lib():
 
 def _ptr(a):
     return a.ctypes.data_as(C.c_void_p)
+
+
+class SeedSetError(ValueError):
+    """The twin rejected a seed set (empty, an id out of range, a negative or non-finite weight, a zero sum)."""
+
+
+def _seed_args(seeds, weights):
+    s = np.ascontiguousarray(np.atleast_1d(np.asarray(seeds)), dtype=np.int32)
+    w = None if weights is None else np.ascontiguousarray(np.atleast_1d(np.asarray(weights)), dtype=np.float64)
+    if w is not None and w.size != s.size:
+        raise SeedSetError("%d seeds, %d weights" % (s.size, w.size))
+    return s, w, (_ptr(s) if s.size else None), (None if w is None else _ptr(w))
 
 
 class OracleGraph:
@@ -230,6 +255,49 @@ class OracleGraph:
         for p in (po, pt, pv):
             lib().orc_free(p)
         return off, tg, vl
+
+    # -- seed sets (SYNC schedule only; SeedSetError for a set the rule rejects)
+    def seed_plan(self, seeds, weights, alpha):
+        """(ids, p, landing weights, n_live): the live seeds then the dead-end seeds, ascending ids in each part."""
+        s, w, sp, wp = _seed_args(seeds, weights)
+        k = max(s.size, 1)
+        ids, p, lw = np.zeros(k, dtype=np.int32), np.zeros(k), np.zeros(k)
+        nl, nd = C.c_int(0), C.c_int(0)
+        if lib().orc_seed_plan(C.byref(self.c), sp, wp, s.size, alpha, _ptr(ids), _ptr(p), _ptr(lw), C.byref(nl),
+                               C.byref(nd)) != 0:
+            raise SeedSetError("rejected seed set")
+        c = nl.value + nd.value
+        return ids[:c], p[:c], lw[:c], nl.value
+
+    def forward_push_seeds(self, seeds, alpha, rmax, weights=None):
+        s, w, sp, wp = _seed_args(seeds, weights)
+        reserve, residue = np.zeros(self.n), np.zeros(self.n)
+        rsum = C.c_double(0.0)
+        st = Stats()
+        if lib().orc_forward_push_seeds(C.byref(self.c), sp, wp, s.size, alpha, rmax, _ptr(reserve), _ptr(residue),
+                                        C.byref(rsum), C.byref(st)) != 0:
+            raise SeedSetError("rejected seed set")
+        return reserve, residue, rsum.value, st
+
+    def fora_whole_seeds(self, seeds, eps, alpha, seed, weights=None, n_rounds=1, tuning=None, conf=None):
+        s, w, sp, wp = _seed_args(seeds, weights)
+        conf = conf or self.conf_whole(alpha)
+        out = np.zeros(self.n)
+        st = Stats()
+        if lib().orc_fora_whole_seeds(C.byref(self.c), sp, wp, s.size, eps, C.byref(conf), seed, n_rounds,
+                                      C.byref(tuning) if tuning is not None else None, _ptr(out), C.byref(st)) != 0:
+            raise SeedSetError("rejected seed set")
+        return out, st
+
+    def fora_topk_seeds(self, seeds, eps, alpha, k, seed, weights=None, conf=None):
+        s, w, sp, wp = _seed_args(seeds, weights)
+        conf = conf or self.conf_topk(k, alpha)
+        out = np.zeros(self.n)
+        st = Stats()
+        if lib().orc_fora_topk_seeds(C.byref(self.c), sp, wp, s.size, eps, C.byref(conf), seed, _ptr(out),
+                                     C.byref(st)) != 0:
+            raise SeedSetError("rejected seed set")
+        return out, st
 
     def topk_push(self, src, alpha, schedule=SYNC):
         return TopkPush(self, src, alpha, schedule)

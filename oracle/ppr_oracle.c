@@ -228,6 +228,111 @@ static double fwd_push_fifo(const orc_graph* g, int32_t s, double alpha, double 
   return rsum;
 }
 
+/* ------------------------------------------------------------------ seed sets (DESIGN.md §2 "Seed sets") */
+
+/* A query personalized to a weighted node set, resolved for the push: the live seeds first (landing weights
+ * q_i = p_i / (1 - (1 - alpha) D)), then the dead-end seeds (reserve credits e_j = alpha p_j / (1 - (1 - alpha) D), or
+ * p_j itself when every seed is a dead end); D is the weight of the dead-end seeds.  wn[v] = q_v for a live seed v,
+ * else 0. */
+typedef struct seedset {
+  uint32_t n_live, n_all;
+  int32_t* id;
+  double* w;
+  double* wn;
+} seedset;
+
+typedef struct seed_entry { int32_t id; double w; } seed_entry;
+static int cmp_seed_entry(const void* a, const void* b) {
+  const seed_entry* x = (const seed_entry*)a; const seed_entry* y = (const seed_entry*)b;
+  if (x->id != y->id) return (x->id > y->id) - (x->id < y->id);
+  return (x->w > y->w) - (x->w < y->w);
+}
+
+int orc_seed_plan(const orc_graph* g, const int32_t* seeds, const double* weights, int k, double alpha,
+                  int32_t* ids_out, double* p_out, double* w_out, int* n_live_out, int* n_dead_out) {
+  if (k <= 0 || !seeds) return -1;
+  seed_entry* e = (seed_entry*)xmalloc((size_t)k * sizeof(seed_entry));
+  for (int i = 0; i < k; ++i) {
+    double w = weights ? weights[i] : 1.0;
+    if (seeds[i] < 0 || (uint32_t)seeds[i] >= g->n || !isfinite(w) || w < 0.0) { free(e); return -1; }
+    e[i].id = seeds[i];
+    e[i].w = w;
+  }
+  /* ids ascending (duplicates by weight), so the sums below do not depend on the order the caller listed the set in */
+  qsort(e, (size_t)k, sizeof(seed_entry), cmp_seed_entry);
+  double sum = 0.0;
+  for (int i = 0; i < k; ++i) sum += e[i].w;
+  if (!(sum > 0.0) || !isfinite(sum)) { free(e); return -1; }
+  /* p: duplicates summed, zero weights dropped; live seeds to the front, dead-end seeds behind (both ascending) */
+  int cnt = 0, n_live = 0;
+  int32_t* ids = (int32_t*)xmalloc((size_t)k * sizeof(int32_t));
+  double* p = (double*)xmalloc((size_t)k * sizeof(double));
+  int32_t* dids = (int32_t*)xmalloc((size_t)k * sizeof(int32_t));
+  double* dp = (double*)xmalloc((size_t)k * sizeof(double));
+  int n_dead = 0;
+  double D = 0.0;
+  for (int i = 0; i < k;) {
+    int j = i;
+    double w = 0.0;
+    for (; j < k && e[j].id == e[i].id; ++j) w += e[j].w;
+    if (w > 0.0) {
+      if (deg_out(g, e[i].id) > 0) { ids[n_live] = e[i].id; p[n_live++] = w / sum; }
+      else { dids[n_dead] = e[i].id; dp[n_dead] = w / sum; D += dp[n_dead]; n_dead++; }
+    }
+    i = j;
+  }
+  cnt = n_live + n_dead;
+  const double den = 1.0 - (1.0 - alpha) * D;
+  for (int i = 0; i < n_live; ++i) {
+    if (ids_out) ids_out[i] = ids[i];
+    if (p_out) p_out[i] = p[i];
+    if (w_out) w_out[i] = p[i] / den;
+  }
+  for (int i = 0; i < n_dead; ++i) {
+    if (ids_out) ids_out[n_live + i] = dids[i];
+    if (p_out) p_out[n_live + i] = dp[i];
+    if (w_out) w_out[n_live + i] = n_live ? alpha * dp[i] / den : dp[i];
+  }
+  if (n_live_out) *n_live_out = n_live;
+  if (n_dead_out) *n_dead_out = n_dead;
+  (void)cnt;
+  free(e); free(ids); free(p); free(dids); free(dp);
+  return 0;
+}
+
+static int seedset_build(const orc_graph* g, const int32_t* seeds, const double* weights, int k, double alpha,
+                         seedset* sd) {
+  memset(sd, 0, sizeof *sd);
+  int32_t* id = (int32_t*)xmalloc((size_t)(k > 0 ? k : 1) * sizeof(int32_t));
+  double* w = (double*)xmalloc((size_t)(k > 0 ? k : 1) * sizeof(double));
+  int nl = 0, nd = 0;
+  if (orc_seed_plan(g, seeds, weights, k, alpha, id, NULL, w, &nl, &nd) != 0) { free(id); free(w); return -1; }
+  sd->n_live = (uint32_t)nl;
+  sd->n_all = (uint32_t)(nl + nd);
+  sd->id = id;
+  sd->w = w;
+  sd->wn = (double*)xcalloc(g->n, sizeof(double));
+  for (int i = 0; i < nl; ++i) sd->wn[id[i]] = w[i];
+  return 0;
+}
+static void seedset_free(seedset* sd) {
+  free(sd->id);
+  free(sd->wn);
+  free(sd->w);
+  memset(sd, 0, sizeof *sd);
+}
+/* The query start: p resolved as if mass 1 landed on it (r = q on the live seeds, reserve = e on the dead-end seeds). */
+static void seedset_start(const seedset* sd, double* reserve, double* residue) {
+  for (uint32_t i = 0; i < sd->n_all; ++i) {
+    if (i < sd->n_live) residue[sd->id[i]] = sd->w[i];
+    else reserve[sd->id[i]] = sd->w[i];
+  }
+}
+/* Dead-end mass x landing on the dead-end seeds: their closed-form reserve credit (they never enter a frontier). */
+static void seedset_credit_dead(const seedset* sd, double x, double* reserve) {
+  for (uint32_t i = sd->n_live; i < sd->n_all; ++i) reserve[sd->id[i]] = reserve[sd->id[i]] + x * sd->w[i];
+}
+
 /* ------------------------------------------------------------------ forward push, level-synchronous twin */
 
 typedef struct sync_ws {
@@ -343,7 +448,7 @@ enum { GS_J = 0, GS_E = 1, GS_G = 2, GS_F = 3 }; /* Jacobi, entry, in-place, flu
  *   in-place P[u]  = new: P holds contributions that still have to reach the blocks up to their own;
  *   flush    P[u]  = 0: pending contributions are delivered, new ones reach nobody in this sweep (clean state).
  * Returns the frontier the sweep leaves in *nf / *ef; dead-end mass of prepared nodes goes to *dead_next. */
-static void dense_sweep(const orc_graph* g, int32_t s, double alpha, double rmax, double* reserve, double* residue,
+static void dense_sweep(const orc_graph* g, int32_t s, const seedset* sd, double alpha, double rmax, double* reserve, double* residue,
                         sync_ws* w, uint8_t* parked, double min_rmax, int general, int B, int state, double* dead_cell,
                         double* dead_next, uint64_t* nf, uint64_t* ef, orc_stats* st) {
   uint32_t n = g->n;
@@ -359,7 +464,14 @@ static void dense_sweep(const orc_graph* g, int32_t s, double alpha, double rmax
     for (uint32_t u = 0; u < n; ++u) { /* k_dense_apply over the block's rows */
       if (B > 1 && w->blk[u] != b) continue;
       double a = acc[u];
-      if ((int32_t)u == s && *dead_cell > 0.0) { a += *dead_cell; *dead_cell = 0.0; } /* Forward_Push.java:101-113 */
+      if (sd) {
+        /* a seed set: every live seed's row takes its share of the level-start cell, in whichever block holds it (the
+         * engine's k_dense_apply); the caller credits the dead-end seeds and clears the cell after the sweep */
+        if (sd->wn[u] != 0.0 && *dead_cell > 0.0) a += *dead_cell * sd->wn[u];
+      } else if ((int32_t)u == s && *dead_cell > 0.0) {
+        a += *dead_cell; /* Forward_Push.java:101-113 */
+        *dead_cell = 0.0;
+      }
       double cn = 0.0;
       if (a > 0.0) {
         uint32_t d = deg_out(g, (int32_t)u);
@@ -389,12 +501,13 @@ static void dense_sweep(const orc_graph* g, int32_t s, double alpha, double rmax
 /* Runs levels from the frontier in w->cur until it is empty.  One level = every frontier node
  * pushed at once from its residue at level start (Forward_Push.java:86-139 per node); a level that touches a large
  * part of the graph runs as a dense sweep (above), others edge by edge.
- * parked/min_rmax != NULL adds the second threshold of forward_push_topk (:226-237). */
-static void fwd_levels_sync(const orc_graph* g, int32_t s, double alpha, double rmax, double* reserve, double* residue,
+ * parked/min_rmax != NULL adds the second threshold of forward_push_topk (:226-237).
+ * sd != NULL: a seed set; each level's dead-end mass lands on p instead of on s (DESIGN.md §2 "Seed sets"). */
+static void fwd_levels_sync(const orc_graph* g, int32_t s, const seedset* sd, double alpha, double rmax, double* reserve, double* residue,
                             sync_ws* w, uint8_t* parked, double min_rmax, const orc_tuning* tun, orc_stats* st,
                             round_cut* cut) {
   uint32_t n = g->n;
-  uint32_t d_s = deg_out(g, s);
+  uint32_t d_s = sd ? 0 : deg_out(g, s);
   /* Only a top-k round whose threshold lies below min_rmax can hold a node that meets the threshold without being
    * queued; everywhere else the membership rule and the crossing rule pick the same nodes, and the crossing rule also
    * ends on the degenerate configurations (n div k = 1 makes pfail infinite and every threshold 0, where the
@@ -434,8 +547,12 @@ static void fwd_levels_sync(const orc_graph* g, int32_t s, double alpha, double 
       else state = big ? GS_E : GS_J;
       uint64_t nf2 = 0, ef2 = 0;
       double dead_next = 0.0;
-      dense_sweep(g, s, alpha, rmax, reserve, residue, w, parked, min_rmax, general, B, state, &dead, &dead_next, &nf2,
+      dense_sweep(g, s, sd, alpha, rmax, reserve, residue, w, parked, min_rmax, general, B, state, &dead, &dead_next, &nf2,
                   &ef2, st);
+      if (sd && dead > 0.0) { /* the level-start cell: dead-end seeds credited, cell cleared (k_seed_land_dense) */
+        seedset_credit_dead(sd, dead, reserve);
+        dead = 0.0;
+      }
       dead += dead_next; /* lands with the next level */
       double* t = w->P; w->P = w->Q; w->Q = t;
       /* what the sweep left in the other buffer is overwritten by the next sweep; nodes that no sweep applies
@@ -505,17 +622,27 @@ static void fwd_levels_sync(const orc_graph* g, int32_t s, double alpha, double 
       }
     }
     if (dead > 0.0) { /* Forward_Push.java:101-113 */
-      double old = residue[s];
-      double nr = old + dead;
-      residue[s] = nr;
-      dead = 0.0;
-      int join = general ? (active_fwd(nr, d_s, rmax) && !w->inq[s])
-                         : (!active_fwd(old, d_s, rmax) && active_fwd(nr, d_s, rmax));
-      if (join) {
-        w->nxt[w->nnxt++] = s;
-        if (general) w->inq[s] = 1;
+      /* A seed set: x = dead lands on p, x q_i on every live seed with the test a push applies, x e_j on every
+       * dead-end seed's reserve.  The engine lands it before the level's edge contributions (k_seed_land_sparse runs
+       * between the prepare and push kernels, and the single-source landing is the push kernel's first step), this
+       * twin after them: the sums differ in fp64 addition order only; the join and parking tests see the same mass. */
+      const uint32_t nland = sd ? sd->n_live : 1;
+      for (uint32_t i = 0; i < nland; ++i) {
+        const int32_t v = sd ? sd->id[i] : s;
+        const uint32_t dv = sd ? deg_out(g, v) : d_s;
+        double old = residue[v];
+        double nr = old + (sd ? dead * sd->w[i] : dead);
+        residue[v] = nr;
+        int join = general ? (active_fwd(nr, dv, rmax) && !w->inq[v])
+                           : (!active_fwd(old, dv, rmax) && active_fwd(nr, dv, rmax));
+        if (join) {
+          w->nxt[w->nnxt++] = v;
+          if (general) w->inq[v] = 1;
+        }
+        if (parked && active_fwd(nr, dv, min_rmax)) parked[v] = 1;
       }
-      if (parked && active_fwd(nr, d_s, min_rmax)) parked[s] = 1;
+      if (sd) seedset_credit_dead(sd, dead, reserve);
+      dead = 0.0;
     }
     if (general) /* the next level pops these: they leave the queue */
       for (uint32_t i = 0; i < w->nnxt; ++i) w->inq[w->nxt[i]] = 0;
@@ -564,7 +691,7 @@ static double fwd_push_sync(const orc_graph* g, int32_t s, double alpha, double 
   residue[s] = 1.0;
   w.cur[0] = s; /* the source is pushed unconditionally first (:81-86) */
   w.ncur = 1;
-  fwd_levels_sync(g, s, alpha, rmax, reserve, residue, &w, NULL, 0.0, tun, st, NULL);
+  fwd_levels_sync(g, s, NULL, alpha, rmax, reserve, residue, &w, NULL, 0.0, tun, st, NULL);
   sync_ws_free(&w);
   return sum_array(residue, n);
 }
@@ -583,6 +710,36 @@ double orc_forward_push(const orc_graph* g, int schedule, int32_t src, double al
   return rsum;
 }
 
+int orc_forward_push_seeds(const orc_graph* g, const int32_t* seeds, const double* weights, int k, double alpha,
+                           double rmax, double* reserve, double* residue, double* rsum_out, orc_stats* st) {
+  if (st) memset(st, 0, sizeof *st);
+  seedset sd;
+  if (seedset_build(g, seeds, weights, k, alpha, &sd) != 0) return -1;
+  uint32_t n = g->n;
+  orc_tuning tun;
+  sync_tuning(&tun);
+  memset(reserve, 0, n * sizeof(double));
+  memset(residue, 0, n * sizeof(double));
+  seedset_start(&sd, reserve, residue);
+  double rsum = 0.0;
+  if (sd.n_live) { /* the live seeds are pushed unconditionally first, as the source is */
+    sync_ws w;
+    sync_ws_init(&w, n);
+    for (uint32_t i = 0; i < sd.n_live; ++i) w.cur[i] = sd.id[i];
+    w.ncur = sd.n_live;
+    fwd_levels_sync(g, -1, &sd, alpha, rmax, reserve, residue, &w, NULL, 0.0, &tun, st, NULL);
+    sync_ws_free(&w);
+    rsum = sum_array(residue, n);
+  }
+  seedset_free(&sd);
+  if (st) {
+    st->rsum = rsum;
+    st->rmax_final = rmax;
+  }
+  if (rsum_out) *rsum_out = rsum;
+  return 0;
+}
+
 /* ------------------------------------------------------------------ forward push top-k (a2) */
 
 struct orc_topk_push {
@@ -598,6 +755,7 @@ struct orc_topk_push {
   uint32_t nqnext;
   uint8_t* parked;
   sync_ws w;
+  const seedset* sd; /* a seed set (SYNC only): the push starts from p, the live seeds parked */
 };
 
 orc_topk_push* orc_topk_push_new(const orc_graph* g, int schedule, int32_t src, double alpha) {
@@ -617,6 +775,17 @@ orc_topk_push* orc_topk_push_new(const orc_graph* g, int schedule, int32_t src, 
   p->nqnext = 1;
   p->parked[src] = 1;
   sync_ws_init(&p->w, g->n);
+  return p;
+}
+
+/* The top-k push session of a seed set with at least one live seed: Q = the live seeds, parked (as {s} is for one source,
+ * Fora_Topk.java:117-118); the first round starts from p resolved. */
+static orc_topk_push* topk_push_new_seeds(const orc_graph* g, const seedset* sd, double alpha) {
+  orc_topk_push* p = orc_topk_push_new(g, ORC_SYNC, sd->id[0], alpha);
+  p->src = -1;
+  p->sd = sd;
+  p->parked[sd->id[0]] = 0;
+  for (uint32_t i = 0; i < sd->n_live; ++i) p->parked[sd->id[i]] = 1;
   return p;
 }
 
@@ -729,12 +898,15 @@ static double topk_round_sync(orc_topk_push* p, double min_rmax, double rmax, or
   const orc_graph* g = p->g;
   uint32_t n = g->n;
   int32_t s = p->src;
-  if (deg_out(g, s) == 0) {
+  if (!p->sd && deg_out(g, s) == 0) {
     p->reserve[s] = 1.0;
     p->rsum = 0.0;
     return 0.0;
   }
-  if (p->first) p->residue[s] = 1.0;
+  if (p->first) {
+    if (p->sd) seedset_start(p->sd, p->reserve, p->residue); /* r = p resolved (k_seed_init) */
+    else p->residue[s] = 1.0;
+  }
   p->w.ncur = 0;
   for (uint32_t v = 0; v < n; ++v) {
     if (!p->parked[v]) continue;
@@ -749,7 +921,7 @@ static double topk_round_sync(orc_topk_push* p, double min_rmax, double rmax, or
   }
   orc_tuning tun;
   sync_tuning(&tun);
-  fwd_levels_sync(g, s, p->alpha, rmax, p->reserve, p->residue, &p->w, p->parked, min_rmax, &tun, st, NULL);
+  fwd_levels_sync(g, s, p->sd, p->alpha, rmax, p->reserve, p->residue, &p->w, p->parked, min_rmax, &tun, st, NULL);
   p->rsum = sum_array(p->residue, n);
   p->first = 0;
   return p->rsum;
@@ -829,8 +1001,10 @@ static void fora_mc_phase(const orc_graph* g, const double* residue, double rsum
   }
 }
 
-void orc_fora_whole(const orc_graph* g, int schedule, int32_t src, double eps, const orc_conf* c, uint64_t seed,
-                    int n_rounds, const orc_tuning* tun_in, double* reserve, orc_stats* st) {
+/* sd != NULL: from a seed set (SYNC only; src unused) */
+static void fora_whole_impl(const orc_graph* g, int schedule, int32_t src, const seedset* sd, double eps,
+                            const orc_conf* c, uint64_t seed, int n_rounds, const orc_tuning* tun_in, double* reserve,
+                            orc_stats* st) {
   /* Fora_Whole_Graph.java:82-146 */
   uint32_t n = g->n;
   orc_tuning tun;
@@ -869,7 +1043,7 @@ void orc_fora_whole(const orc_graph* g, int schedule, int32_t src, double eps, c
     /* resumed rounds: push to rmax0, then continue to rmax0/2, ... on the same state */
     sync_ws w;
     sync_ws_init(&w, n);
-    int dead_src = deg_out(g, src) == 0;
+    int dead_src = !sd && deg_out(g, src) == 0;
     if (n_rounds == 0 && tun.prior_levels > 0 && tun.halving_ratio > 1.0) {
       /* Loop turns that are known to pass before any push: after a push at rmax every r(v) < rmax * d(v), so
        * rsum <= rmax * m and the walks cost at most c_walk * omega * (1 - alpha) * rmax * m; while that bound
@@ -894,7 +1068,11 @@ void orc_fora_whole(const orc_graph* g, int schedule, int32_t src, double eps, c
         rounds++;
         break;
       }
-      if (rounds == 0) {
+      if (rounds == 0 && sd) { /* the push starts from p resolved; the live seeds are the first frontier */
+        seedset_start(sd, reserve, residue);
+        for (uint32_t i = 0; i < sd->n_live; ++i) w.cur[i] = sd->id[i];
+        w.ncur = sd->n_live;
+      } else if (rounds == 0) {
         residue[src] = 1.0;
         w.cur[0] = src;
         w.ncur = 1;
@@ -909,7 +1087,7 @@ void orc_fora_whole(const orc_graph* g, int schedule, int32_t src, double eps, c
       cut.enabled = n_rounds > 0 ? rounds + 1 < n_rounds : rounds + 1 < tun.max_rounds;
       cut.omega = omega_local;
       cut.c_walk = tun.c_walk_ns;
-      fwd_levels_sync(g, src, alpha, rmax_local, reserve, residue, &w, NULL, 0.0, &tun, st, &cut);
+      fwd_levels_sync(g, src, sd, alpha, rmax_local, reserve, residue, &w, NULL, 0.0, &tun, st, &cut);
       rsum_local = sum_array(residue, n) * (1 - alpha);
       rmax_used = rmax_local;
       rmax_local /= 2.0;
@@ -934,6 +1112,21 @@ void orc_fora_whole(const orc_graph* g, int schedule, int32_t src, double eps, c
   st->omega = omega_local;
   fora_mc_phase(g, residue, rsum_local, omega_local, alpha, seed, reserve, st);
   free(residue);
+}
+
+void orc_fora_whole(const orc_graph* g, int schedule, int32_t src, double eps, const orc_conf* c, uint64_t seed,
+                    int n_rounds, const orc_tuning* tun_in, double* reserve, orc_stats* st) {
+  fora_whole_impl(g, schedule, src, NULL, eps, c, seed, n_rounds, tun_in, reserve, st);
+}
+
+int orc_fora_whole_seeds(const orc_graph* g, const int32_t* seeds, const double* weights, int k, double eps,
+                         const orc_conf* c, uint64_t seed, int n_rounds, const orc_tuning* tun, double* reserve,
+                         orc_stats* st) {
+  seedset sd;
+  if (seedset_build(g, seeds, weights, k, c->alpha, &sd) != 0) return -1;
+  fora_whole_impl(g, ORC_SYNC, -1, &sd, eps, c, seed, n_rounds, tun, reserve, st);
+  seedset_free(&sd);
+  return 0;
 }
 
 /* ------------------------------------------------------------------ k-th largest / top-k (a7) */
@@ -986,8 +1179,9 @@ int orc_topk(const double* v, uint32_t n, int k, int32_t* ids, double* vals, int
 
 /* ------------------------------------------------------------------ FORA top-k (a6) */
 
-void orc_fora_topk(const orc_graph* g, int schedule, int32_t src, double eps, const orc_conf* c, uint64_t seed,
-                   double* reserve, orc_stats* st) {
+/* sd != NULL: from a seed set (SYNC only; src unused) */
+static void fora_topk_impl(const orc_graph* g, int schedule, int32_t src, const seedset* sd, double eps,
+                           const orc_conf* c, uint64_t seed, double* reserve, orc_stats* st) {
   /* Fora_Topk.java:102-184 */
   uint32_t n = g->n;
   orc_stats local;
@@ -1000,15 +1194,18 @@ void orc_fora_topk(const orc_graph* g, int schedule, int32_t src, double eps, co
   double rsum_local = c->rsum;
   double omega_local = 0.0, rmax_local = 0.0;
   memset(reserve, 0, n * sizeof(double));
-  orc_topk_push* fp = orc_topk_push_new(g, schedule, src, alpha);
+  const int all_dead = sd ? sd->n_live == 0 : deg_out(g, src) == 0;
+  orc_topk_push* fp = (sd && !all_dead) ? topk_push_new_seeds(g, sd, alpha)
+                                        : orc_topk_push_new(g, schedule, sd ? 0 : src, alpha);
   fp->rsum = rsum_local;
   uint32_t round = 0;
   while (delta_local >= min_delta) { /* :123 */
     rmax_local = epsilon * sqrt(delta_local / 3.0 / (double)c->m / log(2.0 / c->pfail)); /* :124 */
     omega_local = (epsilon + 2.0) * log(2.0 / c->pfail) / epsilon / epsilon / delta_local; /* :125 */
-    if (deg_out(g, src) == 0) { /* :126-132 */
+    if (all_dead) { /* :126-132; a seed set whose seeds are all dead ends: the estimate is p */
       memset(reserve, 0, n * sizeof(double));
-      reserve[src] = 1.0;
+      if (sd) seedset_start(sd, reserve, fp->residue);
+      else reserve[src] = 1.0;
       rsum_local = 0.0;
       break;
     }
@@ -1045,6 +1242,20 @@ void orc_fora_topk(const orc_graph* g, int schedule, int32_t src, double eps, co
   st->rmax_final = rmax_local;
   st->omega = omega_local;
   orc_topk_push_free(fp);
+}
+
+void orc_fora_topk(const orc_graph* g, int schedule, int32_t src, double eps, const orc_conf* c, uint64_t seed,
+                   double* reserve, orc_stats* st) {
+  fora_topk_impl(g, schedule, src, NULL, eps, c, seed, reserve, st);
+}
+
+int orc_fora_topk_seeds(const orc_graph* g, const int32_t* seeds, const double* weights, int k, double eps,
+                        const orc_conf* c, uint64_t seed, double* reserve, orc_stats* st) {
+  seedset sd;
+  if (seedset_build(g, seeds, weights, k, c->alpha, &sd) != 0) return -1;
+  fora_topk_impl(g, ORC_SYNC, -1, &sd, eps, c, seed, reserve, st);
+  seedset_free(&sd);
+  return 0;
 }
 
 /* ------------------------------------------------------------------ pure Monte-Carlo */

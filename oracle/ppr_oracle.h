@@ -115,6 +115,25 @@ void orc_fora_whole_baseline(const orc_graph* g, int32_t src, double eps, const 
 void orc_fora_topk(const orc_graph* g, int schedule, int32_t src, double eps, const orc_conf* c, uint64_t seed,
                    double* reserve, orc_stats* st);
 
+/* Seed sets (DESIGN.md §2 "Seed sets"), written from the rule: a query personalized to p, the weights normalized by
+ * their sum (duplicates summed, zero weights dropped), whose dead-end mass lands on p.  With D the weight of the
+ * dead-end seeds, mass x landing on p gives each live seed i x q_i = x p_i / (1 - (1 - alpha) D) as residue and each
+ * dead-end seed j x e_j = x alpha p_j / (1 - (1 - alpha) D) as reserve (every seed a dead end: e = p).
+ * orc_seed_plan writes the live seeds (ascending ids) then the dead-end seeds (ascending ids): ids, p and the landing
+ * weights q / e; each array holds n_seeds entries.  Every seed-set entry point returns 0, or -1 for an empty set, an id
+ * out of range, a negative or non-finite weight, or a sum that is not a positive finite number.  SYNC schedule only:
+ * orc_forward_push_seeds follows orc_set_sync_tuning as orc_forward_push does, orc_fora_whole_seeds takes tuning and
+ * n_rounds as orc_fora_whole does, orc_fora_topk_seeds starts with the live seeds parked. */
+int orc_seed_plan(const orc_graph* g, const int32_t* seeds, const double* weights, int n_seeds, double alpha,
+                  int32_t* ids_out, double* p_out, double* w_out, int* n_live_out, int* n_dead_out);
+int orc_forward_push_seeds(const orc_graph* g, const int32_t* seeds, const double* weights, int n_seeds, double alpha,
+                           double rmax, double* reserve, double* residue, double* rsum_out, orc_stats* st);
+int orc_fora_whole_seeds(const orc_graph* g, const int32_t* seeds, const double* weights, int n_seeds, double eps,
+                         const orc_conf* c, uint64_t seed, int n_rounds, const orc_tuning* tun, double* reserve,
+                         orc_stats* st);
+int orc_fora_topk_seeds(const orc_graph* g, const int32_t* seeds, const double* weights, int n_seeds, double eps,
+                        const orc_conf* c, uint64_t seed, double* reserve, orc_stats* st);
+
 /* Monte_Carlo.java:136-158 */
 void orc_monte_carlo(const orc_graph* g, int32_t src, double eps, const orc_conf* c, uint64_t seed, double* ppr,
                      orc_stats* st);

@@ -385,9 +385,15 @@ static int upload_panel_layout(pprhip_graph* G, HostLift& H) {
 // the buffer the items of a panel sweep leave their sums in: per handle, on its first forward dense level
 int ensure_panel_part(pprhip_graph* g) {
   if (!g->pn || g->pn_part) return PPRHIP_OK;
+  // (pn_part last: its presence means both exist; a failed second allocation leaves neither behind)
   PPRHIP_TRY(alloc_dev((void**)&g->pn_ctr, kPanelQueues * sizeof(uint32_t)));
   PPRHIP_CHECK_HIP(hipMemsetAsync(g->pn_ctr, 0, kPanelQueues * sizeof(uint32_t), g->stream));
-  return alloc_dev((void**)&g->pn_part, sizeof(double) * (size_t)g->pn->n_part);
+  const int rc = alloc_dev((void**)&g->pn_part, sizeof(double) * (size_t)g->pn->n_part);
+  if (rc != PPRHIP_OK) {
+    (void)hipFree(g->pn_ctr);
+    g->pn_ctr = nullptr;
+  }
+  return rc;
 }
 
 int ensure_bwd_layout(pprhip_graph* P);
@@ -659,6 +665,9 @@ int reset_query_state(pprhip_graph* g, bool clear_flags, int32_t node) {
   add(g->reserve, sizeof(double) * clr);
   add(g->ctr, sizeof(DevCounters));
   if (clear_flags) add(g->flags, clr);
+  // the panel sweep's item queues: a level's closing k_dense_reduce zeroes them, but a query whose level stopped between
+  // its edge and reduce launches must not leave them to the next one
+  if (g->pn_ctr) add(g->pn_ctr, kPanelQueues * sizeof(uint32_t));
   // the top-k estimate is rewritten over the new query's n_act entries only: what the query before left beyond them goes
   if (clr > g->n_act) add(g->est + g->n_act, sizeof(double) * (clr - g->n_act));
   {

@@ -4,7 +4,7 @@ import numpy as np
 import pytest
 
 from conftest import shared_graph
-from test_seeds import rule_b
+from test_seeds import exact_invariant_err, rule_b, seed_p
 
 pytestmark = pytest.mark.gpu
 
@@ -67,7 +67,9 @@ def same_stats(a, b, what):
         assert getattr(a, f) == getattr(b, f), (what, f, getattr(a, f), getattr(b, f))
 
 
-def check_invariant(host, p, r, rsum, rmax, pi=None, tol=1e-12):
+def check_invariant(host, p, r, rsum, rmax, pi=None, tol=1e-12, seeds=None, weights=None):
+    """The band 0 <= pi_p - reserve <= rsum, and - given the set, on graphs up to R-MAT 12 - the exact invariant
+    p^T Pi_p = reserve + r^T Pi_p (tests/test_seeds.py), which a landing error smaller than rsum breaks as well."""
     dout, _ = degrees(host)
     assert abs(p.sum() + rsum - 1.0) <= tol
     assert abs(r.sum() - rsum) <= tol
@@ -78,6 +80,9 @@ def check_invariant(host, p, r, rsum, rmax, pi=None, tol=1e-12):
     if pi is not None:
         gap = pi - p
         assert np.all(gap >= -tol) and np.all(gap <= rsum + tol)
+    if seeds is not None and host.n <= 4096:
+        err = exact_invariant_err(host, seed_p(host.n, seeds, weights), p, r, A)
+        assert err <= tol, ("exact invariant", err)
 
 
 def topk_ok(host, seeds, weights, eps, k, n_sel, ids, vals, est, what):
@@ -152,7 +157,7 @@ def test_push_invariant_mixed_sets(pkg, got, dev_got, rmat12, dev_rmat12, dense_
                 pi = rule_b(host, s, w, A)
                 for rmax in (1e-3, 1e-6, 1e-9):
                     p, r, rsum, st = dev.forward_push_seeds(s, A, rmax, weights=w)
-                    check_invariant(host, p, r, rsum, rmax, pi)
+                    check_invariant(host, p, r, rsum, rmax, pi, seeds=s, weights=w)
                     assert np.array_equal(dev.residue(), r)
                     dense_seen += st.dense_levels
                 # the same sets through the top-k push (parking, arming and landing in top-k mode)
@@ -206,7 +211,7 @@ def test_fora_seeds_at_scale(pkg):
             est, st = g.fora_seeds(s, EPS, A, seed=7, weights=w)
             assert fora_bound_ok(est, pi, EPS, 1.0 / host.n), k
             p, r, rsum, st = g.forward_push_seeds(s, A, 1e-9, weights=w)
-            check_invariant(host, p, r, rsum, 1e-9, pi)
+            check_invariant(host, p, r, rsum, 1e-9, pi, seeds=s, weights=w)
             assert st.dense_levels > 0
 
 

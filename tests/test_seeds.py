@@ -38,6 +38,43 @@ def rule_b(host, seeds, weights, alpha, tol=1e-14):
     return pi
 
 
+def seed_p(n, seeds, weights):
+    """p: the weights normalized by their sum, duplicates summed (the dense vector of DESIGN §2 "Seed sets")."""
+    seeds = np.atleast_1d(np.asarray(seeds, dtype=np.int64))
+    w = np.ones(seeds.size) if weights is None else np.atleast_1d(np.asarray(weights, dtype=np.float64))
+    p = np.bincount(seeds, weights=w, minlength=n).astype(np.float64)
+    return p / p.sum()
+
+
+def pi_p_left(host, p, x, alpha, tol=1e-18):
+    """x^T Pi_p with Pi_p = alpha (I - (1 - alpha) P_p)^-1, P_p the random-walk matrix whose dead-end rows are p (row v of
+    Pi_p: the walk from v that stops with probability alpha per step and restarts at p at a dead end).  Summed as the
+    Neumann series alpha sum_t (1 - alpha)^t x^T P_p^t until the part not yet summed, (1 - alpha)^t |x|_1, is below tol:
+    the same matrix as a dense solve (tests/test_oracle_seeds.py checks both agree), at the cost of sparse products."""
+    n = host.n
+    out_rp = np.asarray(host.out_rp, dtype=np.int64)
+    deg = np.diff(out_rp)
+    src = np.repeat(np.arange(n), deg)
+    dst = np.asarray(host.out_ci, dtype=np.int64)
+    dead = deg == 0
+    inv = np.where(dead, 0.0, 1.0 / np.maximum(deg, 1))
+    x = np.asarray(x, dtype=np.float64).copy()
+    pi = np.zeros(n)
+    left = float(np.abs(x).sum())
+    while left > tol:
+        pi += alpha * x
+        x = (1.0 - alpha) * (np.bincount(dst, weights=(x * inv)[src], minlength=n) + x[dead].sum() * p)
+        left *= 1.0 - alpha
+    return pi
+
+
+def exact_invariant_err(host, p, reserve, residue, alpha):
+    """max |p^T Pi_p - (reserve + r^T Pi_p)|: the push invariant of a seed-set push, which holds at every rmax (the dead-end
+    seeds' closed form keeps it exact); a landing error of any size shows here, not only one larger than rsum."""
+    return float(np.max(np.abs(pi_p_left(host, p, p, alpha) - (reserve + pi_p_left(host, p, residue, alpha))),
+                        initial=0.0))
+
+
 def test_libraries_export_the_seed_entry_points(pkg_product):
     lib = pkg_product.lib()
     hooks = load_hooks_pkg().lib()
