@@ -1400,6 +1400,40 @@ int make_side_stream(pprhip_graph* g, hipStream_t* out, hipStream_t also) {
   return PPRHIP_OK;
 }
 
+// ------------------------------------------------------------------ the top-k push session
+int topk_session_reset(pprhip_graph* g, int32_t src, SeedTable* plan, double alpha, double rsum) {
+  PPRHIP_TRY(reset_query_state(g, true, plan ? plan->max_id : src));
+  if (plan) PPRHIP_TRY(seed_upload(g, *plan));
+  else PPRHIP_CHECK_HIP(hipMemsetAsync(g->flags + src, 1, 1, g->stream));  // Q = {s} (Fora_Topk.java:117-118): parked
+  g->topk_active = true;
+  g->topk_first = true;
+  g->topk_src = plan ? -1 : src;
+  g->topk_seeded = plan != nullptr;
+  g->topk_alpha = alpha;
+  g->topk_rsum = rsum;
+  return PPRHIP_OK;
+}
+
+int topk_push_start(pprhip_graph* g, double min_rmax, double rmax, PushArgs& a, LevelCtx& L, bool* pushing) {
+  const int32_t src = g->topk_src;  // (-1: a seed set, g->seeds)
+  *pushing = false;
+  if (!g->topk_seeded && hdeg_out(g, src) == 0) {  // Forward_Push.java:149-153
+    PPRHIP_TRY(launch_set_f64(g, g->reserve, (uint32_t)src, 1.0));
+    g->topk_rsum = 0.0;
+    return PPRHIP_OK;
+  }
+  if (g->topk_first) {
+    if (g->topk_seeded) PPRHIP_TRY(launch_seed_init(g, 0, true));  // r = p resolved, the live seeds parked
+    else PPRHIP_TRY(launch_set_f64(g, g->residue, (uint32_t)src, 1.0));  // :155-156
+    g->topk_first = false;
+  }
+  a = PushArgs{g->topk_alpha, rmax, min_rmax, src, kFwdTopk};
+  L = LevelCtx();
+  PPRHIP_TRY(seed_scan(g, a, 1, L));
+  *pushing = true;
+  return PPRHIP_OK;
+}
+
 }  // namespace detail
 }  // namespace pprhip
 
@@ -1804,42 +1838,7 @@ int pprhip_forward_push(pprhip_graph_t* g, int32_t src, double alpha, double rma
 int pprhip_fwdpush_topk_reset(pprhip_graph_t* g, int32_t src, double alpha) {
   PPRHIP_TRY(check_graph(g, "pprhip_fwdpush_topk_reset"));
   PPRHIP_TRY(check_node(g, src, "pprhip_fwdpush_topk_reset"));
-  src = g->h_old2new[src];  // internal (degree-sorted) id
-  PPRHIP_TRY(reset_query_state(g, true, src));
-  // Q = {s} (Fora_Topk.java:117-118): the source starts parked
-  PPRHIP_CHECK_HIP(hipMemsetAsync(g->flags + src, 1, 1, g->stream));
-  g->topk_active = true;
-  g->topk_first = true;
-  g->topk_src = src;
-  g->topk_seeded = false;
-  g->topk_alpha = alpha;
-  g->topk_rsum = 1.0;
-  return PPRHIP_OK;
-}
-
-// kSumRead: bring the residue sum to the host (the public round-by-round entry point); kSumLaunch: leave it in
-// DevCounters::sum_out for the walk plan; kSumNone: the caller sums later (a push run ahead of its round)
-enum { kSumRead = 0, kSumLaunch = 1, kSumNone = 2 };
-static int topk_round_impl(pprhip_graph_t* g, double min_rmax, double rmax, pprhip_stats_t& st, int sum_mode = kSumRead) {
-  const int32_t src = g->topk_src;  // (-1: a seed set, g->seeds)
-  if (!g->topk_seeded && hdeg_out(g, src) == 0) {  // Forward_Push.java:149-153
-    PPRHIP_TRY(launch_set_f64(g, g->reserve, (uint32_t)src, 1.0));
-    g->topk_rsum = 0.0;
-    return PPRHIP_OK;
-  }
-  if (g->topk_first) {
-    if (g->topk_seeded) PPRHIP_TRY(launch_seed_init(g, 0, true));  // r = p resolved, the live seeds parked
-    else PPRHIP_TRY(launch_set_f64(g, g->residue, (uint32_t)src, 1.0));  // :155-156
-  }
-  PushArgs a{g->topk_alpha, rmax, min_rmax, src, kFwdTopk};
-  LevelCtx L;
-  SeedScope scope(g, g->topk_seeded);
-  PPRHIP_TRY(seed_scan(g, a, 1, L));
-  PPRHIP_TRY(run_levels(g, a, L, st, nullptr));
-  if (sum_mode == kSumRead) PPRHIP_TRY(device_sum(g, g->residue, &g->topk_rsum));
-  else if (sum_mode == kSumLaunch) PPRHIP_TRY(launch_sum_partial(g, g->residue, act_n(g)));  // (the plan adds them up)
-  g->topk_first = false;
-  return PPRHIP_OK;
+  return topk_session_reset(g, g->h_old2new[src], nullptr, alpha, 1.0);
 }
 
 int pprhip_fwdpush_topk_round(pprhip_graph_t* g, double min_rmax, double rmax, double* rsum_out,
@@ -1852,7 +1851,17 @@ int pprhip_fwdpush_topk_round(pprhip_graph_t* g, double min_rmax, double rmax, d
   pprhip_stats_t st;
   std::memset(&st, 0, sizeof st);
   CallTimer tm(g);
-  PPRHIP_TRY(topk_round_impl(g, min_rmax, rmax, st));
+  {
+    SeedScope scope(g, g->topk_seeded);
+    PushArgs a;
+    LevelCtx L;
+    bool pushing = false;
+    PPRHIP_TRY(topk_push_start(g, min_rmax, rmax, a, L, &pushing));
+    if (pushing) {
+      PPRHIP_TRY(run_levels(g, a, L, st, nullptr));
+      PPRHIP_TRY(device_sum(g, g->residue, &g->topk_rsum));
+    }
+  }
   PPRHIP_TRY(read_dead_pops(g, st));
   tm.mark(1);
   tm.finish(st);
@@ -1932,297 +1941,6 @@ int pprhip_topk_select(pprhip_graph_t* g, int k, int32_t* ids_out, double* vals_
   st.select_ms = CallTimer::ms(g->ev[0], g->ev[1]);
   if (stats) *stats = st;
   return PPRHIP_OK;
-}
-
-// ------------------------------------------------------------------ FORA top-k (a6)
-// The second stream of pprhip_fora_topk (make_side_stream picks one that runs beside the compute stream), its host
-// mail, its plan record buffer and its events.
-static int ensure_spec(pprhip_graph* g) {
-  if (g->spec_stream) return PPRHIP_OK;
-  if (g->spec_failed) return PPRHIP_ERR_STATE;
-  int prio_lo = 0, prio_hi = 0;
-  (void)hipDeviceGetStreamPriorityRange(&prio_lo, &prio_hi);
-  if (prio_lo == prio_hi) return PPRHIP_ERR_STATE;  // no second queue to be had: the rounds run one after another
-  if (!g->spec_mail) {
-    if (hipHostMalloc((void**)&g->spec_mail, sizeof(HostMail), hipHostMallocMapped) != hipSuccess) {
-      (void)hipGetLastError();
-      g->spec_mail = nullptr;
-      return PPRHIP_ERR_OOM;
-    }
-    std::memset(g->spec_mail, 0, sizeof(HostMail));
-  }
-  if (hipHostGetDevicePointer((void**)&g->spec_mail_dev, g->spec_mail, 0) != hipSuccess) return PPRHIP_ERR_HIP;
-  if (!g->mc_plan_rec2 && alloc_dev((void**)&g->mc_plan_rec2, sizeof(WalkPlanRec) * (size_t)g->n) != PPRHIP_OK) {
-    g->mc_plan_rec2 = nullptr;
-    return PPRHIP_ERR_OOM;
-  }
-  for (auto& e : g->spec_ev)
-    if (!e && hipEventCreateWithFlags(&e, hipEventDisableTiming) != hipSuccess) {
-      e = nullptr;
-      return PPRHIP_ERR_HIP;
-    }
-  PPRHIP_TRY(make_side_stream(g, &g->spec_stream));
-  if (!g->spec_stream) {
-    g->spec_failed = true;  // no stream of this process runs beside the compute stream: the rounds run in order
-    return PPRHIP_ERR_STATE;
-  }
-  return PPRHIP_OK;
-}
-
-namespace {
-// While it lives, the handle launches on its second stream, reads back through that stream's mail and the calling
-// thread times with that stream's timer.
-struct SpecContext {
-  pprhip_graph* g;
-  hipStream_t stream;
-  HostMail *mail, *mail_dev;
-  unsigned long long seq;
-  KernelTimer* timer;
-  explicit SpecContext(pprhip_graph* g_) : g(g_), stream(g_->stream), mail(g_->mail), mail_dev(g_->mail_dev), seq(g_->mail_seq), timer(g_timer_cur) {
-    g->stream = g->spec_stream;
-    g->mail = g->spec_mail;
-    g->mail_dev = g->spec_mail_dev;
-    g->mail_seq = g->spec_mail_seq;
-    g->spec_timer.stream = g->spec_stream;
-    g->spec_timer.off = true;  // (its kernels run beside the compute stream's: their time is not the query's)
-    g_timer_cur = &g->spec_timer;
-  }
-  ~SpecContext() {
-    g->spec_mail_seq = g->mail_seq;
-    g->stream = stream;
-    g->mail = mail;
-    g->mail_dev = mail_dev;
-    g->mail_seq = seq;
-    g_timer_cur = timer;
-  }
-};
-}  // namespace
-
-static bool fora_topk_args_ok(const pprhip_fora_conf_t* conf, double eps, int cap, const int32_t* ids_out,
-                              const double* vals_out, const char* fn) {
-  if (!conf || conf->k < 1 || !(eps > 0.0) || cap < 0 || (cap > 0 && (!ids_out || !vals_out))) {
-    set_error("%s: bad arguments", fn);
-    return false;
-  }
-  return true;
-}
-
-// Fora_Topk.computeTopKPPR's loop on the push session the caller has just reset: from one source (internal id src),
-// or from the seed table (src = -1, g->topk_seeded)
-static int fora_topk_run(pprhip_graph_t* g, int32_t src, double eps, const pprhip_fora_conf_t* conf, uint64_t seed,
-                         int32_t* ids_out, double* vals_out, int cap, int* n_out, double* reserve_out,
-                         pprhip_stats_t* stats) {
-  pprhip_stats_t st;
-  std::memset(&st, 0, sizeof st);
-  g->topk_rsum = conf->rsum;
-  CallTimer tm(g);
-  const double alpha = conf->alpha;
-  const double epsilon = eps * 0.5;  // Fora_Topk.java:109-110
-  double delta_local = conf->delta;
-  const double min_delta = conf->min_delta;
-  const double min_rmax = epsilon * std::sqrt(min_delta / 3 / (double)conf->m / std::log(2 / conf->pfail));  // :113
-  double rsum_local = conf->rsum, omega_local = 0.0, rmax_local = 0.0;
-  double push_ms = 0.0, mc_ms = 0.0, sel_ms = 0.0;
-  uint32_t round = 0;
-  const size_t nd = sizeof(double) * (size_t)act_n(g);  // (est beyond the query's scan bound is zero and stays so)
-  bool dead_src = false;
-  // A round's walks and selection do not touch what the next round's push works on (residue, reserve, frontier
-  // lists, parked flags: the plan has read the residues and the estimate is a copy of the reserve by then), and the
-  // next threshold is known beforehand (:178).  So while this round's walk kernel - bound by its longest walk, with
-  // most of the chip idle - and selection run on the compute stream, the next round's push runs on a
-  // second stream, with counters of its own that only join the query's when the round turns out to be needed.  The
-  // one push that was not (after the last round) costs no time: it ends before that round's walks do.
-  const char* spec_env = hook_env("PPRHIP_TOPK_AHEAD");
-  const bool spec_on = !(spec_env && spec_env[0] == '0') && ensure_spec(g) == PPRHIP_OK;
-  bool pushed_ahead = false;        // this round's push, residue sum and walk plan have already run (second stream)
-  bool ahead_discarded = false;     // the last push ahead was not needed
-  // A push queued ahead on the second stream works on this handle's residues, reserve and lists: whatever way this
-  // function is left - an error return from any call below included - nothing may follow on the compute stream (the
-  // next query's reset first of all) before that push has ended.  Joined: the compute stream waits for spec_ev[1]
-  // (the round is taken, or the unused push is waited for at the end); otherwise the guard drains the second stream.
-  struct SpecJoin {
-    pprhip_graph* g;
-    bool pending = false;
-    ~SpecJoin() {
-      if (pending && g->spec_stream) (void)hipStreamSynchronize(g->spec_stream);
-    }
-  } spec_join{g};
-  unsigned long long dead_before_ahead = 0;
-  int nsel_round = 0;
-  double kth_prev = -1.0;  // the k-th estimate of the round before (none yet)
-  while (delta_local >= min_delta) {  // :123
-    rmax_local = epsilon * std::sqrt(delta_local / 3.0 / (double)conf->m / std::log(2.0 / conf->pfail));  // :124
-    omega_local = (epsilon + 2.0) * std::log(2.0 / conf->pfail) / epsilon / epsilon / delta_local;          // :125
-    // :126-132; a seed set whose seeds are all dead ends: the estimate is p (the reserve its start writes)
-    const bool all_dead = src < 0 ? g->seeds->n_live == 0 : hdeg_out(g, src) == 0;
-    if (all_dead) {
-      PPRHIP_CHECK_HIP(hipMemsetAsync(g->est, 0, nd, g->stream));
-      if (src >= 0) {
-        PPRHIP_TRY(launch_set_f64(g, g->est, (uint32_t)src, 1.0));
-      } else {
-        PPRHIP_TRY(launch_seed_init(g, 0, true));
-        PPRHIP_CHECK_HIP(hipMemcpyAsync(g->est, g->reserve, nd, hipMemcpyDeviceToDevice, g->stream));
-      }
-      rsum_local = 0.0;
-      dead_src = true;
-      break;
-    }
-    rmax_local *= std::sqrt((double)conf->m * rmax_local) * 3.0;  // :133
-    if (!spec_on) (void)hipEventRecord(g->ev[1], g->stream);
-    if (pushed_ahead) {
-      PPRHIP_CHECK_HIP(hipStreamWaitEvent(g->stream, g->spec_ev[1], 0));
-      spec_join.pending = false;
-    } else {
-      PPRHIP_TRY(topk_round_impl(g, min_rmax, rmax_local, st, kSumLaunch));  // :137; the residue sum stays on the device
-      // :148-151: the plan derives rsum and the walk budget from the sum on the device; :143 the estimate := copy of
-      // the push reserve (walk increments of earlier rounds are dropped), taken in the plan's pass
-      PPRHIP_TRY(launch_walk_plan(g, 1, alpha, 0.0, 0, g->est, omega_local, g->reserve, g->est));
-    }
-    if (!spec_on) (void)hipEventRecord(g->ev[2], g->stream);
-    // a plan that ran ahead could not touch the estimate (the round before was still reading it): :143 here
-    if (pushed_ahead) PPRHIP_CHECK_HIP(hipMemcpyAsync(g->est, g->reserve, nd, hipMemcpyDeviceToDevice, g->stream));
-    pushed_ahead = false;
-    if (spec_on) PPRHIP_CHECK_HIP(hipEventRecord(g->spec_ev[0], g->stream));  // residues and reserve have been read
-    // :155-168: the walk kernel reads the plan's counts on the device: no host round trip between push and selection
-    static const uint32_t topk_waves = [] {  // PPRHIP_TOPK_WALK_WAVES: measurement switch
-      const char* e = hook_env("PPRHIP_TOPK_WALK_WAVES");
-      return e && atoi(e) > 0 ? (uint32_t)atoi(e) : 8u;
-    }();
-    g->walk_waves = spec_on ? topk_waves : 0u;  // (the next round's push runs beside these walks: leave it room)
-    const int wrc = launch_walk_run(g, 1, alpha, seed, round, g->est);
-    g->walk_waves = 0;
-    PPRHIP_TRY(wrc);
-    if (!spec_on) (void)hipEventRecord(g->ev[3], g->stream);
-    round++;
-    double kth = 0.0;
-    bool have = false;
-    unsigned long long sel_seq = 0;
-    PPRHIP_TRY(select_launch(g, g->est, conf->k, &sel_seq, true));  // :173; the round's residue sum comes back with it
-    // ---- the next round's push, residue sum and walk plan, ahead of the decision whether there is a next round
-    const double delta_next = std::max(min_delta, delta_local / 4.0);  // :178
-    pprhip_stats_t st_ahead;
-    std::memset(&st_ahead, 0, sizeof st_ahead);
-    bool ahead = false;
-    // Not when this round is expected to be the last: at min_delta the loop ends whatever the selection says
-    // (:175-176), and the k-th estimate hardly moves from round to round, so a round whose threshold the last k-th
-    // value already meets is (almost always) final - its push ahead would be the largest of the query, and unused.
-    const bool likely_final = delta_local <= min_delta || (kth_prev >= 0.0 && kth_prev >= (1 + epsilon) * delta_local);
-    if (spec_on && !likely_final) {
-      double rmax_next = epsilon * std::sqrt(delta_next / 3.0 / (double)conf->m / std::log(2.0 / conf->pfail));
-      const double omega_next = (epsilon + 2.0) * std::log(2.0 / conf->pfail) / epsilon / epsilon / delta_next;
-      rmax_next *= std::sqrt((double)conf->m * rmax_next) * 3.0;
-      SpecContext ctx(g);  // g->stream, the mail and the calling thread's timer are the second stream's until it ends
-      PPRHIP_CHECK_HIP(hipStreamWaitEvent(g->stream, g->spec_ev[0], 0));
-      spec_join.pending = true;  // (from the first launch on the second stream on)
-      PPRHIP_TRY(fetch_small(g, &g->ctr->dead_pops, &dead_before_ahead, sizeof dead_before_ahead));
-      PPRHIP_TRY(topk_round_impl(g, min_rmax, rmax_next, st_ahead, kSumLaunch));
-      PPRHIP_TRY(launch_walk_plan(g, 1, alpha, 0.0, 0, g->est, omega_next));
-      PPRHIP_CHECK_HIP(hipEventRecord(g->spec_ev[1], g->stream));
-      ahead = true;
-    }
-    PPRHIP_TRY(select_finish(g, sel_seq, g->est, conf->k, ids_out, vals_out, cap, &nsel_round, &kth, &have, st));
-    g->topk_rsum = g->sel_plan_sum;  // (the sum this round's plan was derived from, in the selection's header)
-    rsum_local = g->topk_rsum;       // :142
-    if (!have) kth = 0.0;                                                                        // :174
-    if (!spec_on) {
-      (void)hipEventRecord(g->ev[4], g->stream);
-      PPRHIP_CHECK_HIP(hipStreamSynchronize(g->stream));
-      push_ms += CallTimer::ms(g->ev[1], g->ev[2]);
-      mc_ms += CallTimer::ms(g->ev[2], g->ev[3]);
-      sel_ms += CallTimer::ms(g->ev[3], g->ev[4]);
-    }
-    st.kth_value = kth;
-    kth_prev = kth;
-    if (kth >= (1 + epsilon) * delta_local || delta_local <= min_delta) {  // :175-176
-      ahead_discarded = ahead;
-      break;
-    }
-    if (ahead) {  // the push ahead was this round's: its counters join the query's
-      st.pops += st_ahead.pops;
-      st.edge_pushes += st_ahead.edge_pushes;
-      st.enqueues += st_ahead.enqueues;
-      st.dense_nodes += st_ahead.dense_nodes;
-      st.dense_edges += st_ahead.dense_edges;
-      st.levels += st_ahead.levels;
-      st.dense_levels += st_ahead.dense_levels;
-      st.sweep_min_bytes += st_ahead.sweep_min_bytes;
-      st.push_bytes += st_ahead.push_bytes;
-      pushed_ahead = true;
-    }
-    delta_local = delta_next;
-  }
-  if (round == 0 && !dead_src) {  // delta below min_delta from the start: nothing ran
-    PPRHIP_CHECK_HIP(hipMemsetAsync(g->est, 0, nd, g->stream));
-  }
-  g->result_in_est = true;
-  if (ahead_discarded) {  // before the next query clears
-    PPRHIP_CHECK_HIP(hipStreamWaitEvent(g->stream, g->spec_ev[1], 0));
-    spec_join.pending = false;
-  }
-  PPRHIP_TRY(read_dead_pops(g, st));
-  if (ahead_discarded && st.dead_end_pops >= dead_before_ahead) {  // the unused push's dead-end pops are not the query's
-    st.push_bytes -= 16ull * (st.dead_end_pops - dead_before_ahead);
-    st.dead_end_pops = dead_before_ahead;
-  }
-  int nsel = nsel_round;
-  (void)hipEventRecord(g->ev[3], g->stream);
-  if (round == 0 || dead_src) {  // no round selected anything yet (the last round's selection is the result otherwise)
-    bool have = false;
-    double kth = 0.0;
-    PPRHIP_TRY(select_topk(g, g->est, conf->k, ids_out, vals_out, cap, &nsel, &kth, &have, st));
-  }
-  (void)hipEventRecord(g->ev[4], g->stream);
-  tm.finish(st);
-  if (spec_on) {  // phases of different rounds run side by side: the per-class kernel times stand for the phases
-    push_ms = st.class_ms[PPRHIP_KERNEL_SPARSE_PUSH] + st.class_ms[PPRHIP_KERNEL_DENSE_PULL];
-    mc_ms = st.class_ms[PPRHIP_KERNEL_WALK];
-    sel_ms = st.class_ms[PPRHIP_KERNEL_QUERY_SETUP];
-  } else {
-    sel_ms += CallTimer::ms(g->ev[3], g->ev[4]);
-  }
-  st.push_ms = push_ms;
-  st.mc_ms = mc_ms;
-  st.select_ms = sel_ms;
-  st.rounds = round;
-  st.rsum = rsum_local;
-  st.rmax_final = rmax_local;
-  st.omega = omega_local;
-  if (n_out) *n_out = nsel;
-  PPRHIP_TRY(copy_out(g, g->est, reserve_out));
-  if (stats) *stats = st;
-  return PPRHIP_OK;
-}
-
-int pprhip_fora_topk(pprhip_graph_t* g, int32_t src, double eps, const pprhip_fora_conf_t* conf, uint64_t seed,
-                     int32_t* ids_out, double* vals_out, int cap, int* n_out, double* reserve_out,
-                     pprhip_stats_t* stats) {
-  PPRHIP_TRY(check_graph(g, "pprhip_fora_topk"));
-  PPRHIP_TRY(check_node(g, src, "pprhip_fora_topk"));
-  if (!fora_topk_args_ok(conf, eps, cap, ids_out, vals_out, "pprhip_fora_topk")) return PPRHIP_ERR_INVALID;
-  PPRHIP_TRY(pprhip_fwdpush_topk_reset(g, src, conf->alpha));
-  return fora_topk_run(g, g->h_old2new[src], eps, conf, seed, ids_out, vals_out, cap, n_out, reserve_out, stats);
-}
-
-// pprhip_fora_topk from a seed set: the push session starts from p (the live seeds parked, as {s} is for one source)
-int pprhip_fora_topk_seeds(pprhip_graph_t* g, const int32_t* seeds, const double* weights, int n_seeds, double eps,
-                           const pprhip_fora_conf_t* conf, uint64_t seed, int32_t* ids_out, double* vals_out, int cap,
-                           int* n_out, double* reserve_out, pprhip_stats_t* stats) {
-  static const char* fn = "pprhip_fora_topk_seeds";
-  PPRHIP_TRY(check_graph(g, fn));
-  if (!fora_topk_args_ok(conf, eps, cap, ids_out, vals_out, fn)) return PPRHIP_ERR_INVALID;
-  SeedTable plan;
-  PPRHIP_TRY(seed_plan(g, seeds, weights, n_seeds, conf->alpha, fn, plan));
-  PPRHIP_TRY(reset_query_state(g, true, plan.max_id));
-  PPRHIP_TRY(seed_upload(g, plan));
-  g->topk_active = true;
-  g->topk_first = true;
-  g->topk_src = -1;
-  g->topk_seeded = true;
-  g->topk_alpha = conf->alpha;
-  g->topk_rsum = 1.0;
-  const int rc = fora_topk_run(g, -1, eps, conf, seed, ids_out, vals_out, cap, n_out, reserve_out, stats);
-  g->topk_active = false;  // (no public round continues a seed-set session)
-  return rc;
 }
 
 // ------------------------------------------------------------------ pure Monte-Carlo

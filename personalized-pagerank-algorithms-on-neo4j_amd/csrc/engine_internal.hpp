@@ -439,5 +439,14 @@ struct SeedScope {
   }
 };
 
+// ---- the top-k push session (Forward_Push.forward_push_topk, resumed round after round by Fora_Topk)
+// a new session from one source (internal id src; Q = {s} parked) or from a seed table (plan; src is ignored), its
+// residue sum rsum until a round has measured one
+int topk_session_reset(pprhip_graph* g, int32_t src, SeedTable* plan, double alpha, double rsum);
+// a round's push at rmax up to its levels: the dead-source rule (Forward_Push.java:149-153; *pushing false, nothing
+// to run), the session's first residue, and the scan of the start set into a / L; run_levels(g, a, L, ...) follows.
+// A seed-set session runs it and its levels under SeedScope.
+int topk_push_start(pprhip_graph* g, double min_rmax, double rmax, PushArgs& a, LevelCtx& L, bool* pushing);
+
 }  // namespace detail
 }  // namespace pprhip

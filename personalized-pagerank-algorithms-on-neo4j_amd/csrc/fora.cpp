@@ -21,6 +21,21 @@ using namespace pprhip::detail;
 // ------------------------------------------------------------------ FORA whole graph (a5)
 namespace pprhip {
 
+// Fora_Topk.java's schedule on delta: the push's floor (:113), a round's thresholds (:124-125) and the push's
+// threshold (:133), the end of the loop (:175-176) and the next delta (:178)
+struct TopkSchedule {
+  double eps = 0, min_delta = 0, m = 0, lg = 0, min_rmax = 0;
+  TopkSchedule() = default;
+  TopkSchedule(double eps_half, const pprhip_fora_conf_t* conf)
+      : eps(eps_half), min_delta(conf->min_delta), m((double)conf->m), lg(std::log(2.0 / conf->pfail)),
+        min_rmax(rmax(min_delta)) {}
+  double rmax(double delta) const { return eps * std::sqrt(delta / 3.0 / m / lg); }
+  double omega(double delta) const { return (eps + 2.0) * lg / eps / eps / delta; }
+  double push_rmax(double rmax) const { return rmax * (std::sqrt(m * rmax) * 3.0); }
+  bool last(double kth, double delta) const { return kth >= (1 + eps) * delta || delta <= min_delta; }
+  double next(double delta) const { return std::max(min_delta, delta / 4.0); }
+};
+
 // One FORA query as a resumable run: step() advances it until it is finished or (yield_dense)
 // until its next level is dense, so that the batch driver can run that level for many queries
 // in one sweep.  pprhip_fora_single_source drives the same code without yielding.
@@ -39,7 +54,8 @@ struct ForaRun {
   LevelCtx L;
   PushArgs a;
   RoundCut cut;
-  enum Phase { kRoundStart, kLevels, kWalks, kWalkWait, kTopkRoundStart, kTopkLevels, kTopkFinal, kBwdLevels, kBwdFinal, kDone } phase = kDone;
+  enum Phase { kRoundStart, kLevels, kWalks, kWalkWait, kTopkRoundStart, kTopkLevels, kTopkRoundEnd, kTopkFinal, kBwdLevels,
+               kBwdFinal, kDone } phase = kDone;
   hipStream_t side = nullptr;  // batch driver: the walk phase goes to this stream and the run yields until it has ended
   int query = -1;  // batch driver: index of the query this run serves
   detail::BatchJob* job = nullptr;  // ... and the call (or stream submission) that query belongs to
@@ -47,11 +63,22 @@ struct ForaRun {
   bool in_push = false;  // between a push phase's start and its end (BatchSync: may hold sweeps off)
   // top-k runs (Fora_Topk.computeTopKPPR, kind 1): the trial-and-error loop on delta
   int kind = 0;
-  double eps_half = 0, delta_local = 0, min_delta = 0, min_rmax = 0;
+  TopkSchedule sched;
+  double delta_local = 0, kth_prev = -1.0;  // (kth_prev: the k-th estimate of the round before; -1: none yet)
   uint32_t round = 0;
   int cap = 0, nsel = 0;
   int32_t* ids_out = nullptr;
   double* vals_out = nullptr;
+  // ... options of the single-query driver (pprhip_fora_topk): the next round's push runs ahead on the handle's second
+  // stream (ahead), the walks run at walk_waves waves per CU (0: the handle's width), each phase is marked by an event
+  // and timed (marks: push_ms / mc_ms / sel_ms)
+  bool ahead = false, marks = false;
+  uint32_t walk_waves = 0;
+  double push_ms = 0, mc_ms = 0, sel_ms = 0;
+  bool pushed_ahead = false;     // this round's push, residue sum and walk plan have already run (second stream)
+  bool ahead_pending = false;    // a push ahead is queued and the compute stream has not joined it yet
+  bool ahead_discarded = false;  // the last push ahead was not needed
+  unsigned long long dead_before_ahead = 0;
   // backward searches of All-Pair (kind 2): entries >= threshold of the finished search
   int32_t target_orig = -1;
   std::vector<Triple> triples;
@@ -250,109 +277,254 @@ int fora_step(ForaRun& r, bool yield_dense) {
   }
 }
 
-// Fora_Topk.computeTopKPPR (Fora_Topk.java:102-184) as a resumable run; the same sequence as
-// pprhip_fora_topk, which keeps the per-phase timing of a single call.
-int topk_begin(ForaRun& r, pprhip_graph* g, int32_t src_internal, double eps, const pprhip_fora_conf_t* conf,
-               uint64_t seed, int32_t* ids_out, double* vals_out, int cap) {
+// Fora_Topk.computeTopKPPR (Fora_Topk.java:102-184) as a resumable run: the one loop of every top-k entry point
+// (pprhip_fora_topk, pprhip_fora_topk_seeds, the batched calls and streams).  src_internal -1: from the seed table
+// (plan), whose largest id bounds the reset.
+static int topk_begin_at(ForaRun& r, pprhip_graph* g, int32_t src_internal, SeedTable* plan, double eps,
+                         const pprhip_fora_conf_t* conf, uint64_t seed, int32_t* ids_out, double* vals_out, int cap) {
+  r = ForaRun();  // (every field of the loop at its start value)
   r.g = g;
   r.kind = 1;
   r.src = src_internal;
+  r.seeded = plan != nullptr;
   r.conf = conf;
   r.seed = seed;
-  std::memset(&r.st, 0, sizeof r.st);
-  PPRHIP_TRY(reset_query_state(g, true, src_internal));
-  PPRHIP_CHECK_HIP(hipMemsetAsync(g->flags + src_internal, 1, 1, g->stream));  // Q = {s} (:117-118)
-  g->topk_active = true;
-  g->topk_first = true;
-  g->topk_src = src_internal;
-  g->topk_seeded = false;
-  g->topk_alpha = conf->alpha;
-  g->topk_rsum = conf->rsum;
+  PPRHIP_TRY(topk_session_reset(g, src_internal, plan, conf->alpha, conf->rsum));
   r.alpha = conf->alpha;
-  r.eps_half = eps * 0.5;  // :109-110
+  r.sched = TopkSchedule(eps * 0.5, conf);  // :109-110, :113
   r.delta_local = conf->delta;
-  r.min_delta = conf->min_delta;
-  r.min_rmax = r.eps_half * std::sqrt(r.min_delta / 3 / (double)conf->m / std::log(2 / conf->pfail));  // :113
   r.rsum_local = conf->rsum;
-  r.omega_local = r.rmax_local = 0.0;
-  r.round = 0;
-  r.dead_src = false;
   r.ids_out = ids_out;
   r.vals_out = vals_out;
   r.cap = cap;
-  r.nsel = 0;
   r.phase = ForaRun::kTopkRoundStart;
-  r.waiting = false;
-  r.in_push = false;
+  return PPRHIP_OK;
+}
+
+int topk_begin(ForaRun& r, pprhip_graph* g, int32_t src_internal, double eps, const pprhip_fora_conf_t* conf,
+               uint64_t seed, int32_t* ids_out, double* vals_out, int cap) {
+  return topk_begin_at(r, g, src_internal, nullptr, eps, conf, seed, ids_out, vals_out, cap);
+}
+
+// the same query from a seed set: the push session starts from p (the live seeds parked, as {s} is for one source)
+int topk_begin_seeds(ForaRun& r, pprhip_graph* g, SeedTable& plan, double eps, const pprhip_fora_conf_t* conf,
+                     uint64_t seed, int32_t* ids_out, double* vals_out, int cap) {
+  return topk_begin_at(r, g, -1, &plan, eps, conf, seed, ids_out, vals_out, cap);
+}
+
+// the counters of a push that ran ahead, once its round is taken
+void add_push_stats(pprhip_stats_t& sum, const pprhip_stats_t& st) {
+  sum.pops += st.pops; sum.edge_pushes += st.edge_pushes; sum.enqueues += st.enqueues;
+  sum.dense_nodes += st.dense_nodes; sum.dense_edges += st.dense_edges;
+  sum.levels += st.levels; sum.dense_levels += st.dense_levels;
+  sum.sweep_min_bytes += st.sweep_min_bytes; sum.push_bytes += st.push_bytes;
+}
+
+// The second stream of pprhip_fora_topk (make_side_stream picks one that runs beside the compute stream), its host
+// mail, its plan record buffer and its events.
+static int ensure_spec(pprhip_graph* g) {
+  if (g->spec_stream) return PPRHIP_OK;
+  if (g->spec_failed) return PPRHIP_ERR_STATE;
+  int prio_lo = 0, prio_hi = 0;
+  (void)hipDeviceGetStreamPriorityRange(&prio_lo, &prio_hi);
+  if (prio_lo == prio_hi) return PPRHIP_ERR_STATE;  // no second queue to be had: the rounds run one after another
+  if (!g->spec_mail) {
+    if (hipHostMalloc((void**)&g->spec_mail, sizeof(HostMail), hipHostMallocMapped) != hipSuccess) {
+      (void)hipGetLastError();
+      g->spec_mail = nullptr;
+      return PPRHIP_ERR_OOM;
+    }
+    std::memset(g->spec_mail, 0, sizeof(HostMail));
+  }
+  if (hipHostGetDevicePointer((void**)&g->spec_mail_dev, g->spec_mail, 0) != hipSuccess) return PPRHIP_ERR_HIP;
+  if (!g->mc_plan_rec2 && alloc_dev((void**)&g->mc_plan_rec2, sizeof(WalkPlanRec) * (size_t)g->n) != PPRHIP_OK) {
+    g->mc_plan_rec2 = nullptr;
+    return PPRHIP_ERR_OOM;
+  }
+  for (auto& e : g->spec_ev)
+    if (!e && hipEventCreateWithFlags(&e, hipEventDisableTiming) != hipSuccess) {
+      e = nullptr;
+      return PPRHIP_ERR_HIP;
+    }
+  PPRHIP_TRY(make_side_stream(g, &g->spec_stream));
+  if (!g->spec_stream) {
+    g->spec_failed = true;  // no stream of this process runs beside the compute stream: the rounds run in order
+    return PPRHIP_ERR_STATE;
+  }
+  return PPRHIP_OK;
+}
+
+// While it lives, the handle launches on its second stream, reads back through that stream's mail and the calling
+// thread times with that stream's timer.
+struct SpecContext {
+  pprhip_graph* g;
+  hipStream_t stream;
+  HostMail *mail, *mail_dev;
+  unsigned long long seq;
+  KernelTimer* timer;
+  explicit SpecContext(pprhip_graph* g_) : g(g_), stream(g_->stream), mail(g_->mail), mail_dev(g_->mail_dev), seq(g_->mail_seq), timer(g_timer_cur) {
+    g->stream = g->spec_stream;
+    g->mail = g->spec_mail;
+    g->mail_dev = g->spec_mail_dev;
+    g->mail_seq = g->spec_mail_seq;
+    g->spec_timer.stream = g->spec_stream;
+    g->spec_timer.off = true;  // (its kernels run beside the compute stream's: their time is not the query's)
+    g_timer_cur = &g->spec_timer;
+  }
+  ~SpecContext() {
+    g->spec_mail_seq = g->mail_seq;
+    g->stream = stream;
+    g->mail = mail;
+    g->mail_dev = mail_dev;
+    g->mail_seq = seq;
+    g_timer_cur = timer;
+  }
+};
+
+// The next round's push, residue sum and walk plan (at delta_next), queued on the second stream behind the point where
+// this round's walks have read the residues and the reserve (spec_ev[0]); spec_ev[1] marks its end.
+int push_ahead(ForaRun& r, double delta_next, pprhip_stats_t& st_ahead) {
+  pprhip_graph* g = r.g;
+  SpecContext ctx(g);  // g->stream, the mail and the calling thread's timer are the second stream's until it ends
+  PPRHIP_CHECK_HIP(hipStreamWaitEvent(g->stream, g->spec_ev[0], 0));
+  r.ahead_pending = true;  // (from the first launch on the second stream on)
+  PPRHIP_TRY(fetch_small(g, &g->ctr->dead_pops, &r.dead_before_ahead, sizeof r.dead_before_ahead));
+  PushArgs a;
+  LevelCtx L;
+  bool pushing = false;  // (always: a query whose source is a dead end ends before its first round)
+  PPRHIP_TRY(topk_push_start(g, r.sched.min_rmax, r.sched.push_rmax(r.sched.rmax(delta_next)), a, L, &pushing));
+  PPRHIP_TRY(run_levels(g, a, L, st_ahead, nullptr));
+  PPRHIP_TRY(launch_sum_partial(g, g->residue, act_n(g)));
+  PPRHIP_TRY(launch_walk_plan(g, 1, r.alpha, 0.0, 0, g->est, r.sched.omega(delta_next)));
+  PPRHIP_CHECK_HIP(hipEventRecord(g->spec_ev[1], g->stream));
   return PPRHIP_OK;
 }
 
 int topk_step(ForaRun& r, bool yield_dense) {
   pprhip_graph* g = r.g;
   const pprhip_fora_conf_t* conf = r.conf;
+  const TopkSchedule& sc = r.sched;
   const size_t nd = sizeof(double) * (size_t)act_n(g);  // (est beyond the query's scan bound is zero and stays so)
   for (;;) {
     if (r.phase == ForaRun::kTopkRoundStart) {
-      if (!(r.delta_local >= r.min_delta)) {  // :123
+      if (!(r.delta_local >= sc.min_delta)) {  // :123
         r.phase = ForaRun::kTopkFinal;
         continue;
       }
-      r.rmax_local = r.eps_half * std::sqrt(r.delta_local / 3.0 / (double)conf->m / std::log(2.0 / conf->pfail));  // :124
-      r.omega_local = (r.eps_half + 2.0) * std::log(2.0 / conf->pfail) / r.eps_half / r.eps_half / r.delta_local;  // :125
-      if (hdeg_out(g, r.src) == 0) {  // :126-132
+      r.rmax_local = sc.rmax(r.delta_local);    // :124
+      r.omega_local = sc.omega(r.delta_local);  // :125
+      // :126-132; a seed set whose seeds are all dead ends: the estimate is p (the reserve its start writes)
+      if (r.seeded ? g->seeds->n_live == 0 : hdeg_out(g, r.src) == 0) {
         PPRHIP_CHECK_HIP(hipMemsetAsync(g->est, 0, nd, g->stream));
-        PPRHIP_TRY(launch_set_f64(g, g->est, (uint32_t)r.src, 1.0));
+        if (!r.seeded) {
+          PPRHIP_TRY(launch_set_f64(g, g->est, (uint32_t)r.src, 1.0));
+        } else {
+          PPRHIP_TRY(launch_seed_init(g, 0, true));
+          PPRHIP_CHECK_HIP(hipMemcpyAsync(g->est, g->reserve, nd, hipMemcpyDeviceToDevice, g->stream));
+        }
         r.rsum_local = 0.0;
         r.dead_src = true;
         r.phase = ForaRun::kTopkFinal;
         continue;
       }
-      r.rmax_local *= std::sqrt((double)conf->m * r.rmax_local) * 3.0;  // :133
-      // forward_push_topk (:137; Forward_Push.java:144-250)
-      if (g->topk_first) PPRHIP_TRY(launch_set_f64(g, g->residue, (uint32_t)r.src, 1.0));
-      r.a = PushArgs{r.alpha, r.rmax_local, r.min_rmax, r.src, kFwdTopk};
-      r.L = LevelCtx();
-      r.in_push = true;
-      PPRHIP_TRY(seed_scan(g, r.a, 1, r.L));
-      r.phase = ForaRun::kTopkLevels;
+      r.rmax_local = sc.push_rmax(r.rmax_local);  // :133
+      if (r.marks) (void)hipEventRecord(g->ev[1], g->stream);
+      if (r.pushed_ahead) {
+        PPRHIP_CHECK_HIP(hipStreamWaitEvent(g->stream, g->spec_ev[1], 0));
+        r.ahead_pending = false;
+        r.phase = ForaRun::kTopkRoundEnd;
+      } else {
+        // forward_push_topk (:137; Forward_Push.java:144-250)
+        bool pushing = false;  // (always: the dead-source case has ended the loop above)
+        r.in_push = true;
+        PPRHIP_TRY(topk_push_start(g, sc.min_rmax, r.rmax_local, r.a, r.L, &pushing));
+        r.phase = ForaRun::kTopkLevels;
+      }
     }
     if (r.phase == ForaRun::kTopkLevels) {
       const int rc = run_levels(g, r.a, r.L, r.st, nullptr, yield_dense);
       if (rc != PPRHIP_OK) return rc;  // kYield or an error
       leave_push(r);
-      // :142-168 without a host round trip: the residue sum stays on the device, where the walk plan derives rsum and
-      // the walk budget from it (:148,151) and the walk kernel reads the plan's counts; the sum reaches the host with
-      // the selection's read-back
+      // :142-151 without a host round trip: the residue sum stays on the device, where the walk plan derives rsum and
+      // the walk budget from it (:148,151); the sum reaches the host with the selection's read-back.  :143 the
+      // estimate := copy of the push reserve (walk increments of earlier rounds are dropped), taken in the plan's pass
       PPRHIP_TRY(launch_sum_partial(g, g->residue, act_n(g)));  // (the plan adds the partial sums up)
-      g->topk_first = false;
-      // :143 the estimate := copy of the push reserve (walk increments of earlier rounds are dropped), taken in the
-      // plan's pass over the same range; :155-168 the walks
       PPRHIP_TRY(launch_walk_plan(g, 1, r.alpha, 0.0, 0, g->est, r.omega_local, g->reserve, g->est));
-      PPRHIP_TRY(launch_walk_run(g, 1, r.alpha, r.seed, r.round, g->est));
+      r.phase = ForaRun::kTopkRoundEnd;
+    }
+    if (r.phase == ForaRun::kTopkRoundEnd) {
+      if (r.marks) (void)hipEventRecord(g->ev[2], g->stream);
+      // a plan that ran ahead could not touch the estimate (the round before was still reading it): :143 here
+      if (r.pushed_ahead) PPRHIP_CHECK_HIP(hipMemcpyAsync(g->est, g->reserve, nd, hipMemcpyDeviceToDevice, g->stream));
+      r.pushed_ahead = false;
+      if (r.ahead) PPRHIP_CHECK_HIP(hipEventRecord(g->spec_ev[0], g->stream));  // residues and reserve have been read
+      // :155-168: the walk kernel reads the plan's counts on the device: no host round trip between push and selection
+      const uint32_t waves = g->walk_waves;
+      if (r.walk_waves) g->walk_waves = r.walk_waves;
+      const int wrc = launch_walk_run(g, 1, r.alpha, r.seed, r.round, g->est);
+      g->walk_waves = waves;
+      PPRHIP_TRY(wrc);
+      if (r.marks) (void)hipEventRecord(g->ev[3], g->stream);
       r.round++;
+      unsigned long long sel_seq = 0;
+      PPRHIP_TRY(select_launch(g, g->est, conf->k, &sel_seq, true));  // :173; the round's residue sum comes back with it
+      // The next round's push, residue sum and walk plan run ahead of the decision whether there is a next round - but
+      // not when this round is expected to be the last: at min_delta the loop ends whatever the selection says
+      // (:175-176), and the k-th estimate hardly moves from round to round, so a round whose threshold the last k-th
+      // value already meets is (almost always) final - its push ahead would be the largest of the query, and unused.
+      const double delta_next = sc.next(r.delta_local);  // :178
+      const bool likely_final = r.kth_prev >= 0.0 ? sc.last(r.kth_prev, r.delta_local) : r.delta_local <= sc.min_delta;
+      pprhip_stats_t st_ahead;
+      std::memset(&st_ahead, 0, sizeof st_ahead);
+      const bool ahead = r.ahead && !likely_final;
+      if (ahead) PPRHIP_TRY(push_ahead(r, delta_next, st_ahead));
       double kth = 0.0;
       bool have = false;
-      int nsel = 0;
-      PPRHIP_TRY(select_topk(g, g->est, conf->k, nullptr, nullptr, 0, &nsel, &kth, &have, r.st, true));  // :173
-      g->topk_rsum = g->sel_plan_sum;  // (the sum the round's plan was derived from, in the selection's header)
-      r.rsum_local = g->topk_rsum;       // :142
-      if (!have) kth = 0.0;                                                                          // :174
-      r.st.kth_value = kth;
-      if (kth >= (1 + r.eps_half) * r.delta_local || r.delta_local <= r.min_delta) {  // :175-176
-        r.phase = ForaRun::kTopkFinal;
-      } else {
-        r.delta_local = std::max(r.min_delta, r.delta_local / 4.0);  // :178
-        r.phase = ForaRun::kTopkRoundStart;
+      PPRHIP_TRY(select_finish(g, sel_seq, g->est, conf->k, r.ids_out, r.vals_out, r.cap, &r.nsel, &kth, &have, r.st));
+      g->topk_rsum = g->sel_plan_sum;  // (the sum this round's plan was derived from, in the selection's header)
+      r.rsum_local = g->topk_rsum;     // :142
+      if (!have) kth = 0.0;            // :174
+      if (r.marks) {
+        (void)hipEventRecord(g->ev[4], g->stream);
+        PPRHIP_CHECK_HIP(hipStreamSynchronize(g->stream));
+        r.push_ms += CallTimer::ms(g->ev[1], g->ev[2]);
+        r.mc_ms += CallTimer::ms(g->ev[2], g->ev[3]);
+        r.sel_ms += CallTimer::ms(g->ev[3], g->ev[4]);
       }
+      r.st.kth_value = kth;
+      r.kth_prev = kth;
+      if (sc.last(kth, r.delta_local)) {  // :175-176
+        r.ahead_discarded = ahead;
+        r.phase = ForaRun::kTopkFinal;
+        continue;
+      }
+      if (ahead) {  // the push ahead was this round's: its counters join the query's
+        add_push_stats(r.st, st_ahead);
+        r.pushed_ahead = true;
+      }
+      r.delta_local = delta_next;
+      r.phase = ForaRun::kTopkRoundStart;
       continue;
     }
     if (r.phase == ForaRun::kTopkFinal) {
-      if (r.round == 0 && !r.dead_src) PPRHIP_CHECK_HIP(hipMemsetAsync(g->est, 0, nd, g->stream));
+      if (r.round == 0 && !r.dead_src) PPRHIP_CHECK_HIP(hipMemsetAsync(g->est, 0, nd, g->stream));  // nothing ran
       g->result_in_est = true;
+      if (r.ahead_discarded) {  // before the next query clears
+        PPRHIP_CHECK_HIP(hipStreamWaitEvent(g->stream, g->spec_ev[1], 0));
+        r.ahead_pending = false;
+      }
       PPRHIP_TRY(read_dead_pops(g, r.st));
-      bool have = false;
-      double kth = 0.0;
-      PPRHIP_TRY(select_topk(g, g->est, conf->k, r.ids_out, r.vals_out, r.cap, &r.nsel, &kth, &have, r.st));
+      if (r.ahead_discarded && r.st.dead_end_pops >= r.dead_before_ahead) {  // the unused push's dead-end pops are not the query's
+        r.st.push_bytes -= 16ull * (r.st.dead_end_pops - r.dead_before_ahead);
+        r.st.dead_end_pops = r.dead_before_ahead;
+      }
+      if (r.marks) (void)hipEventRecord(g->ev[3], g->stream);
+      if (r.round == 0) {  // no round selected anything (the last round's selection is the result otherwise)
+        bool have = false;
+        double kth = 0.0;
+        PPRHIP_TRY(select_topk(g, g->est, conf->k, r.ids_out, r.vals_out, r.cap, &r.nsel, &kth, &have, r.st));
+      }
+      if (r.marks) (void)hipEventRecord(g->ev[4], g->stream);
       r.st.rounds = r.round;
       r.st.rsum = r.rsum_local;
       r.st.rmax_final = r.rmax_local;
@@ -492,6 +664,92 @@ int pprhip_fora_seeds(pprhip_graph_t* g, const int32_t* seeds, const double* wei
   PPRHIP_TRY(copy_out(g, g->reserve, reserve_out));
   if (stats) *stats = r.st;
   return PPRHIP_OK;
+}
+
+// ------------------------------------------------------------------ FORA top-k (a6)
+static bool fora_topk_args_ok(const pprhip_fora_conf_t* conf, double eps, int cap, const int32_t* ids_out,
+                              const double* vals_out, const char* fn) {
+  if (!conf || conf->k < 1 || !(eps > 0.0) || cap < 0 || (cap > 0 && (!ids_out || !vals_out))) {
+    set_error("%s: bad arguments", fn);
+    return false;
+  }
+  return true;
+}
+
+// Fora_Topk.computeTopKPPR for one query, without yielding, on the run topk_begin* has just started.  A round's walks
+// and selection do not touch what the next round's push works on (residue, reserve, frontier lists, parked flags: the
+// plan has read the residues and the estimate is a copy of the reserve by then), and the next threshold is known
+// beforehand (:178).  So while this round's walk kernel - bound by its longest walk, with most of the chip idle
+//  - and selection run on the compute stream, the next round's push runs on a second stream, with
+// counters of its own that only join the query's when the round turns out to be needed.  The one push that was not
+// (after the last round) costs no time: it ends before that round's walks do.  PPRHIP_TOPK_AHEAD=0: the rounds run
+// one after another, their phases timed by events.
+static int fora_topk_drive(ForaRun& r, int* n_out, double* reserve_out, pprhip_stats_t* stats) {
+  pprhip_graph* g = r.g;
+  CallTimer tm(g);
+  const char* spec_env = hook_env("PPRHIP_TOPK_AHEAD");
+  r.ahead = !(spec_env && spec_env[0] == '0') && ensure_spec(g) == PPRHIP_OK;
+  r.marks = !r.ahead;
+  static const uint32_t topk_waves = [] {  // PPRHIP_TOPK_WALK_WAVES: measurement switch
+    const char* e = hook_env("PPRHIP_TOPK_WALK_WAVES");
+    return e && atoi(e) > 0 ? (uint32_t)atoi(e) : 8u;
+  }();
+  r.walk_waves = r.ahead ? topk_waves : 0u;  // (the next round's push runs beside these walks: leave it room)
+  // A push queued ahead on the second stream works on this handle's residues, reserve and lists: whatever way this
+  // function is left - an error return from any call below included - nothing may follow on the compute stream (the
+  // next query's reset first of all) before that push has ended.  Joined: the compute stream waits for spec_ev[1]
+  // (the round is taken, or the unused push is waited for at the end); otherwise the guard drains the second stream.
+  struct SpecJoin {
+    ForaRun& r;
+    ~SpecJoin() {
+      if (r.ahead_pending && r.g->spec_stream) (void)hipStreamSynchronize(r.g->spec_stream);
+    }
+  } spec_join{r};
+  {
+    SeedScope scope(g, r.seeded);
+    PPRHIP_TRY(topk_step(r, false));
+  }
+  tm.finish(r.st);
+  if (r.ahead) {  // phases of different rounds run side by side: the per-class kernel times stand for the phases
+    r.st.push_ms = r.st.class_ms[PPRHIP_KERNEL_SPARSE_PUSH] + r.st.class_ms[PPRHIP_KERNEL_DENSE_PULL];
+    r.st.mc_ms = r.st.class_ms[PPRHIP_KERNEL_WALK];
+    r.st.select_ms = r.st.class_ms[PPRHIP_KERNEL_QUERY_SETUP];
+  } else {
+    r.st.push_ms = r.push_ms;
+    r.st.mc_ms = r.mc_ms;
+    r.st.select_ms = r.sel_ms + CallTimer::ms(g->ev[3], g->ev[4]);
+  }
+  if (n_out) *n_out = r.nsel;
+  PPRHIP_TRY(copy_out(g, g->est, reserve_out));
+  if (stats) *stats = r.st;
+  return PPRHIP_OK;
+}
+
+int pprhip_fora_topk(pprhip_graph_t* g, int32_t src, double eps, const pprhip_fora_conf_t* conf, uint64_t seed,
+                     int32_t* ids_out, double* vals_out, int cap, int* n_out, double* reserve_out,
+                     pprhip_stats_t* stats) {
+  PPRHIP_TRY(check_graph(g, "pprhip_fora_topk"));
+  PPRHIP_TRY(check_node(g, src, "pprhip_fora_topk"));
+  if (!fora_topk_args_ok(conf, eps, cap, ids_out, vals_out, "pprhip_fora_topk")) return PPRHIP_ERR_INVALID;
+  ForaRun r;
+  PPRHIP_TRY(topk_begin(r, g, g->h_old2new[src], eps, conf, seed, ids_out, vals_out, cap));
+  return fora_topk_drive(r, n_out, reserve_out, stats);
+}
+
+// pprhip_fora_topk from a seed set (seeds.cpp): the push session starts from p
+int pprhip_fora_topk_seeds(pprhip_graph_t* g, const int32_t* seeds, const double* weights, int n_seeds, double eps,
+                           const pprhip_fora_conf_t* conf, uint64_t seed, int32_t* ids_out, double* vals_out, int cap,
+                           int* n_out, double* reserve_out, pprhip_stats_t* stats) {
+  static const char* fn = "pprhip_fora_topk_seeds";
+  PPRHIP_TRY(check_graph(g, fn));
+  if (!fora_topk_args_ok(conf, eps, cap, ids_out, vals_out, fn)) return PPRHIP_ERR_INVALID;
+  SeedTable plan;
+  PPRHIP_TRY(seed_plan(g, seeds, weights, n_seeds, conf->alpha, fn, plan));
+  ForaRun r;
+  PPRHIP_TRY(topk_begin_seeds(r, g, plan, eps, conf, seed, ids_out, vals_out, cap));
+  const int rc = fora_topk_drive(r, n_out, reserve_out, stats);
+  g->topk_active = false;  // (no public round continues a seed-set session)
+  return rc;
 }
 
 namespace {

@@ -456,7 +456,8 @@ def test_fora_batch_topk(pkg, orc, got, dev_got, rmat12, dev_rmat12, threads, mo
 @pytest.mark.parametrize("ahead", ["1", "0"])
 def test_fora_topk_rmat12(pkg, orc, rmat12, dev_rmat12, ahead, monkeypatch):
     """ahead = 1 (default): the next round's push, sum and plan run on a second stream beside this round's walks and
-    join the query only when the round is needed (engine.cpp: pprhip_fora_topk); 0: the rounds run one after another.
+    join the query only when the round is needed (fora.cpp: topk_step, driven by pprhip_fora_topk); 0: the rounds run
+    one after another.
     Same rounds, walks, level counters and lists either way."""
     monkeypatch.setenv("PPRHIP_TOPK_AHEAD", ahead)
     og = to_oracle(orc, rmat12)
