@@ -154,6 +154,19 @@ typedef struct pprhip_fora_conf {
   uint64_t m;        /* rel_amount */
 } pprhip_fora_conf_t;
 
+/* Parameter ranges.  Every entry point checks its numeric parameters before it looks at its handle and refuses a value
+ * outside its range with PPRHIP_ERR_INVALID (pprhip_last_error names the function and the parameter); nothing reaches a
+ * device.
+ *   alpha (argument or conf->alpha)        finite, 0 < alpha < 1
+ *   eps                                    finite, > 0
+ *   rmax, min_rmax, the All-Pair threshold finite, >= 0 (0 is legal: a push at threshold 0 ends by underflow;
+ *                                          pprhip_shard_target_cuts keeps its own threshold > 0)
+ *   conf->delta                            finite, > 0
+ *   conf->pfail                            whole-graph calls: finite, > 0; top-k calls: > 0 or the values
+ *                                          pprhip_conf_fora_topk derives at n div k = 1 (+inf) and k > n (-0)
+ *   conf->min_delta (top-k calls)          finite, > 0
+ *   iters (pprhip_power_method)            >= 0 */
+
 /* ---------------------------------------------------------------- errors / build info */
 const char* pprhip_last_error(void);
 int pprhip_version(void);

@@ -860,6 +860,8 @@ extern "C" {
 
 int pprhip_all_pair_backward(pprhip_graph_t* g, double alpha, double threshold, int k, uint32_t t_begin, uint32_t t_end,
                              pprhip_index_t** index_out, pprhip_stats_t* stats) {
+  PPRHIP_TRY(check_alpha(alpha, "pprhip_all_pair_backward"));
+  PPRHIP_TRY(check_threshold(threshold, "pprhip_all_pair_backward", "threshold"));
   PPRHIP_TRY(check_graph(g, "pprhip_all_pair_backward"));
   if (!index_out || t_begin > t_end || t_end > g->n) {
     set_error("pprhip_all_pair_backward: bad target range [%u, %u) for n=%u", t_begin, t_end, g->n);

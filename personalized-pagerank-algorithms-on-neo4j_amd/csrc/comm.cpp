@@ -838,6 +838,8 @@ int pprhip_shard_target_range(int rank, int world, uint32_t n, uint32_t* begin, 
 
 int pprhip_shard_target_cuts(pprhip_graph_t* g, int world, double alpha, double threshold, int mode, uint32_t* cuts_out,
                              double* skew_out) {
+  PPRHIP_TRY(check_alpha(alpha, "pprhip_shard_target_cuts"));
+  PPRHIP_TRY(check_threshold(threshold, "pprhip_shard_target_cuts", "threshold"));
   PPRHIP_TRY(check_graph(g, "pprhip_shard_target_cuts"));
   if (world < 1 || !cuts_out || mode < 0 || mode > 2 || !(threshold > 0.0)) {
     set_error("pprhip_shard_target_cuts: bad arguments (world %d, mode %d)", world, mode);
@@ -862,6 +864,8 @@ int pprhip_shard_target_cuts(pprhip_graph_t* g, int world, double alpha, double 
 
 int pprhip_all_pair_backward_sharded(pprhip_comm_t* c, double alpha, double threshold, int k, pprhip_index_t** own_out,
                                      pprhip_stats_t* stats) {
+  PPRHIP_TRY(check_alpha(alpha, "pprhip_all_pair_backward_sharded"));
+  PPRHIP_TRY(check_threshold(threshold, "pprhip_all_pair_backward_sharded", "threshold"));
   if (!c || !own_out) {
     set_error("pprhip_all_pair_backward_sharded: null argument");
     return PPRHIP_ERR_INVALID;
@@ -1045,6 +1049,8 @@ extern "C" {
 int pprhip_fora_batch(pprhip_graph_t* const* per_gpu, int n_gpu, const int32_t* srcs, int q, int k, double eps,
                       const pprhip_fora_conf_t* conf, uint64_t seed, int n_rounds, int32_t* ids_out, double* vals_out,
                       int* n_out, pprhip_stats_t* stats_per_gpu) {
+  PPRHIP_TRY(check_positive(eps, "pprhip_fora_batch", "eps"));
+  PPRHIP_TRY(check_conf(conf, "pprhip_fora_batch", false));
   RankSetup S;
   PPRHIP_TRY(setup_ranks(per_gpu, n_gpu, S, "pprhip_fora_batch"));
   if (q < 0 || k < 1 || !conf || !(eps > 0.0) || (q && (!srcs || !ids_out || !vals_out))) {
@@ -1088,6 +1094,8 @@ int pprhip_fora_batch(pprhip_graph_t* const* per_gpu, int n_gpu, const int32_t* 
 
 int pprhip_all_pair_backward_multi(pprhip_graph_t* const* per_gpu, int n_gpu, double alpha, double threshold, int k,
                                    pprhip_index_t** index_out, pprhip_stats_t* stats_per_gpu) {
+  PPRHIP_TRY(check_alpha(alpha, "pprhip_all_pair_backward_multi"));
+  PPRHIP_TRY(check_threshold(threshold, "pprhip_all_pair_backward_multi", "threshold"));
   RankSetup S;
   PPRHIP_TRY(setup_ranks(per_gpu, n_gpu, S, "pprhip_all_pair_backward_multi"));
   if (!index_out) {

@@ -1132,6 +1132,47 @@ int check_node(const pprhip_graph* g, int32_t v, const char* fn) {
   return PPRHIP_OK;
 }
 
+// Range checks of the numeric parameters (include/pprhip.h, "Parameter ranges").  Every entry point runs them before
+// check_graph, so an out-of-range value is refused without a device and never reaches a kernel: at alpha <= 0 a walk
+// never stops and a push on a cycle never ends, at alpha = 1 rmax0 divides by zero, at eps <= 0 the walk count omega
+// is infinite.  NaN fails every test below.
+int check_alpha(double alpha, const char* fn, const char* name) {
+  if (!(alpha > 0.0 && alpha < 1.0)) {
+    set_error("%s: %s = %g outside (0, 1)", fn, name, alpha);
+    return PPRHIP_ERR_INVALID;
+  }
+  return PPRHIP_OK;
+}
+
+int check_positive(double v, const char* fn, const char* name) {
+  if (!(v > 0.0 && std::isfinite(v))) {
+    set_error("%s: %s = %g must be finite and > 0", fn, name, v);
+    return PPRHIP_ERR_INVALID;
+  }
+  return PPRHIP_OK;
+}
+
+int check_threshold(double v, const char* fn, const char* name) {
+  if (!(v >= 0.0 && std::isfinite(v))) {
+    set_error("%s: %s = %g must be finite and >= 0", fn, name, v);
+    return PPRHIP_ERR_INVALID;
+  }
+  return PPRHIP_OK;
+}
+
+int check_conf(const pprhip_fora_conf_t* c, const char* fn, bool topk) {
+  if (!c) return PPRHIP_OK;  // (the entry point's own null check reports it)
+  PPRHIP_TRY(check_alpha(c->alpha, fn, "conf->alpha"));
+  PPRHIP_TRY(check_positive(c->delta, fn, "conf->delta"));
+  if (!topk) return check_positive(c->pfail, fn, "conf->pfail");
+  // pprhip_conf_fora_topk's own degenerate values pass: pfail = +inf at n div k = 1 and -0 at k > n
+  if (std::isnan(c->pfail) || c->pfail < 0.0) {
+    set_error("%s: conf->pfail = %g must be > 0", fn, c->pfail);
+    return PPRHIP_ERR_INVALID;
+  }
+  return check_positive(c->min_delta, fn, "conf->min_delta");
+}
+
 // host-side CSR facts live on the graph handle; batch slots borrow them
 const pprhip_graph* host_of(const pprhip_graph* g) { return g->parent ? g->parent : g; }
 uint32_t hdeg_out(const pprhip_graph* g, int32_t v) { return host_of(g)->h_out_rp[v + 1] - host_of(g)->h_out_rp[v]; }
@@ -1503,6 +1544,7 @@ void pprhip_tuning_batch_for(int q, pprhip_tuning_t* t) {
 }
 
 int pprhip_conf_fora_whole_graph(uint32_t n, uint64_t m, double alpha, pprhip_fora_conf_t* c) {
+  PPRHIP_TRY(check_alpha(alpha, "pprhip_conf_fora_whole_graph"));
   if (!c || n == 0) {
     set_error("pprhip_conf_fora_whole_graph: bad arguments");
     return PPRHIP_ERR_INVALID;
@@ -1518,6 +1560,7 @@ int pprhip_conf_fora_whole_graph(uint32_t n, uint64_t m, double alpha, pprhip_fo
 }
 
 int pprhip_conf_fora_topk(uint32_t n, uint64_t m, int k, double alpha, pprhip_fora_conf_t* c) {
+  PPRHIP_TRY(check_alpha(alpha, "pprhip_conf_fora_topk"));
   if (!c || n == 0 || k < 1) {
     set_error("pprhip_conf_fora_topk: bad arguments (n=%u k=%d)", n, k);
     return PPRHIP_ERR_INVALID;
@@ -1535,6 +1578,8 @@ int pprhip_conf_fora_topk(uint32_t n, uint64_t m, int k, double alpha, pprhip_fo
 }
 
 int pprhip_fora_whole_params(const pprhip_fora_conf_t* c, double eps, double* rmax0, double* omega) {
+  PPRHIP_TRY(check_positive(eps, "pprhip_fora_whole_params", "eps"));
+  PPRHIP_TRY(check_conf(c, "pprhip_fora_whole_params", false));
   if (!c || !rmax0 || !omega) {
     set_error("pprhip_fora_whole_params: null argument");
     return PPRHIP_ERR_INVALID;
@@ -1546,6 +1591,9 @@ int pprhip_fora_whole_params(const pprhip_fora_conf_t* c, double eps, double* rm
 
 int pprhip_fora_topk_params(const pprhip_fora_conf_t* c, double eps, double delta, double* min_rmax,
                             double* rmax_scaled, double* omega) {
+  PPRHIP_TRY(check_positive(eps, "pprhip_fora_topk_params", "eps"));
+  PPRHIP_TRY(check_positive(delta, "pprhip_fora_topk_params", "delta"));
+  PPRHIP_TRY(check_conf(c, "pprhip_fora_topk_params", true));
   if (!c || !min_rmax || !rmax_scaled || !omega) {
     set_error("pprhip_fora_topk_params: null argument");
     return PPRHIP_ERR_INVALID;
@@ -1801,6 +1849,8 @@ int pprhip_get_residue(pprhip_graph_t* g, double* out) {
 // ------------------------------------------------------------------ forward push (a1)
 int pprhip_forward_push(pprhip_graph_t* g, int32_t src, double alpha, double rmax, double* reserve_out,
                         double* residue_out, double* rsum_out, pprhip_stats_t* stats) {
+  PPRHIP_TRY(check_alpha(alpha, "pprhip_forward_push"));
+  PPRHIP_TRY(check_threshold(rmax, "pprhip_forward_push", "rmax"));
   PPRHIP_TRY(check_graph(g, "pprhip_forward_push"));
   PPRHIP_TRY(check_node(g, src, "pprhip_forward_push"));
   src = g->h_old2new[src];  // internal (degree-sorted) id
@@ -1836,6 +1886,7 @@ int pprhip_forward_push(pprhip_graph_t* g, int32_t src, double alpha, double rma
 
 // ------------------------------------------------------------------ resumable top-k push (a2)
 int pprhip_fwdpush_topk_reset(pprhip_graph_t* g, int32_t src, double alpha) {
+  PPRHIP_TRY(check_alpha(alpha, "pprhip_fwdpush_topk_reset"));
   PPRHIP_TRY(check_graph(g, "pprhip_fwdpush_topk_reset"));
   PPRHIP_TRY(check_node(g, src, "pprhip_fwdpush_topk_reset"));
   return topk_session_reset(g, g->h_old2new[src], nullptr, alpha, 1.0);
@@ -1843,6 +1894,8 @@ int pprhip_fwdpush_topk_reset(pprhip_graph_t* g, int32_t src, double alpha) {
 
 int pprhip_fwdpush_topk_round(pprhip_graph_t* g, double min_rmax, double rmax, double* rsum_out,
                               pprhip_stats_t* stats) {
+  PPRHIP_TRY(check_threshold(min_rmax, "pprhip_fwdpush_topk_round", "min_rmax"));
+  PPRHIP_TRY(check_threshold(rmax, "pprhip_fwdpush_topk_round", "rmax"));
   PPRHIP_TRY(check_graph(g, "pprhip_fwdpush_topk_round"));
   if (!g->topk_active) {
     set_error("pprhip_fwdpush_topk_round: call pprhip_fwdpush_topk_reset first");
@@ -1878,6 +1931,7 @@ int pprhip_fwdpush_topk_round(pprhip_graph_t* g, double min_rmax, double rmax, d
 int pprhip_random_walk_batch(pprhip_graph_t* g, const int32_t* starts, const uint64_t* walk_idx, uint64_t count,
                              double alpha, uint64_t seed, uint32_t stream, int no_zero_hop, int32_t* terminals_out,
                              uint32_t* steps_out) {
+  PPRHIP_TRY(check_alpha(alpha, "pprhip_random_walk_batch"));
   PPRHIP_TRY(check_graph(g, "pprhip_random_walk_batch"));
   if ((!starts || !walk_idx || !terminals_out) && count) {
     set_error("pprhip_random_walk_batch: null argument");
@@ -1946,6 +2000,8 @@ int pprhip_topk_select(pprhip_graph_t* g, int k, int32_t* ids_out, double* vals_
 // ------------------------------------------------------------------ pure Monte-Carlo
 int pprhip_monte_carlo(pprhip_graph_t* g, int32_t src, double eps, const pprhip_fora_conf_t* conf, uint64_t seed,
                        double* ppr_out, pprhip_stats_t* stats) {
+  PPRHIP_TRY(check_positive(eps, "pprhip_monte_carlo", "eps"));
+  PPRHIP_TRY(check_conf(conf, "pprhip_monte_carlo", false));
   PPRHIP_TRY(check_graph(g, "pprhip_monte_carlo"));
   PPRHIP_TRY(check_node(g, src, "pprhip_monte_carlo"));
   src = g->h_old2new[src];  // internal (degree-sorted) id
@@ -2000,6 +2056,8 @@ static int backward_push_impl(pprhip_graph_t* g, int32_t target, double alpha, d
 
 int pprhip_backward_push(pprhip_graph_t* g, int32_t target, double alpha, double rmax, double* reserve_out,
                          double* residue_out, pprhip_stats_t* stats) {
+  PPRHIP_TRY(check_alpha(alpha, "pprhip_backward_push"));
+  PPRHIP_TRY(check_threshold(rmax, "pprhip_backward_push", "rmax"));
   PPRHIP_TRY(check_graph(g, "pprhip_backward_push"));
   PPRHIP_TRY(check_node(g, target, "pprhip_backward_push"));
   target = g->h_old2new[target];  // internal (degree-sorted) id
@@ -2022,13 +2080,14 @@ int pprhip_backward_push(pprhip_graph_t* g, int32_t target, double alpha, double
 // ------------------------------------------------------------------ ground truth (a12)
 int pprhip_power_method(pprhip_graph_t* g, int32_t src, double alpha, int iters, double* reserve_out,
                         pprhip_stats_t* stats) {
+  PPRHIP_TRY(check_alpha(alpha, "pprhip_power_method"));
+  if (iters < 0) {
+    set_error("pprhip_power_method: iters = %d must be >= 0", iters);
+    return PPRHIP_ERR_INVALID;
+  }
   PPRHIP_TRY(check_graph(g, "pprhip_power_method"));
   PPRHIP_TRY(check_node(g, src, "pprhip_power_method"));
   src = g->h_old2new[src];  // internal (degree-sorted) id
-  if (iters < 0) {
-    set_error("pprhip_power_method: iters must be >= 0");
-    return PPRHIP_ERR_INVALID;
-  }
   pprhip_stats_t st;
   std::memset(&st, 0, sizeof st);
   g->topk_active = false;

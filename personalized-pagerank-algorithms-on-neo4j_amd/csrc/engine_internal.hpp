@@ -276,6 +276,11 @@ int launch_walk_run(pprhip_graph* g, int variant, double alpha, uint64_t seed, u
 int copy_out(pprhip_graph* g, const double* dev, double* host);
 int check_graph(const pprhip_graph* g, const char* fn);
 int check_node(const pprhip_graph* g, int32_t v, const char* fn);
+// parameter ranges (include/pprhip.h): alpha in (0, 1); eps, delta, pfail finite and > 0; thresholds finite and >= 0
+int check_alpha(double alpha, const char* fn, const char* name = "alpha");
+int check_positive(double v, const char* fn, const char* name);
+int check_threshold(double v, const char* fn, const char* name);
+int check_conf(const pprhip_fora_conf_t* c, const char* fn, bool topk);
 const pprhip_graph* host_of(const pprhip_graph* g);
 uint32_t hdeg_out(const pprhip_graph* g, int32_t v);
 uint32_t hdeg_in(const pprhip_graph* g, int32_t v);

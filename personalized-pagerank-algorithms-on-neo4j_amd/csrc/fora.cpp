@@ -617,6 +617,8 @@ void add_stats(pprhip_stats_t& sum, const pprhip_stats_t& st) {
 
 int pprhip_fora_single_source(pprhip_graph_t* g, int32_t src, double eps, const pprhip_fora_conf_t* conf,
                               uint64_t seed, int n_rounds, double* reserve_out, pprhip_stats_t* stats) {
+  PPRHIP_TRY(check_positive(eps, "pprhip_fora_single_source", "eps"));
+  PPRHIP_TRY(check_conf(conf, "pprhip_fora_single_source", false));
   PPRHIP_TRY(check_graph(g, "pprhip_fora_single_source"));
   PPRHIP_TRY(check_node(g, src, "pprhip_fora_single_source"));
   src = g->h_old2new[src];  // internal (degree-sorted) id
@@ -643,6 +645,8 @@ int pprhip_fora_seeds(pprhip_graph_t* g, const int32_t* seeds, const double* wei
                       const pprhip_fora_conf_t* conf, uint64_t seed, int n_rounds, double* reserve_out,
                       pprhip_stats_t* stats) {
   static const char* fn = "pprhip_fora_seeds";
+  PPRHIP_TRY(check_positive(eps, fn, "eps"));
+  PPRHIP_TRY(check_conf(conf, fn, false));
   PPRHIP_TRY(check_graph(g, fn));
   if (!conf || !(eps > 0.0) || n_rounds < 0) {
     set_error("%s: bad arguments (eps=%g n_rounds=%d)", fn, eps, n_rounds);
@@ -728,6 +732,8 @@ static int fora_topk_drive(ForaRun& r, int* n_out, double* reserve_out, pprhip_s
 int pprhip_fora_topk(pprhip_graph_t* g, int32_t src, double eps, const pprhip_fora_conf_t* conf, uint64_t seed,
                      int32_t* ids_out, double* vals_out, int cap, int* n_out, double* reserve_out,
                      pprhip_stats_t* stats) {
+  PPRHIP_TRY(check_positive(eps, "pprhip_fora_topk", "eps"));
+  PPRHIP_TRY(check_conf(conf, "pprhip_fora_topk", true));
   PPRHIP_TRY(check_graph(g, "pprhip_fora_topk"));
   PPRHIP_TRY(check_node(g, src, "pprhip_fora_topk"));
   if (!fora_topk_args_ok(conf, eps, cap, ids_out, vals_out, "pprhip_fora_topk")) return PPRHIP_ERR_INVALID;
@@ -741,6 +747,8 @@ int pprhip_fora_topk_seeds(pprhip_graph_t* g, const int32_t* seeds, const double
                            const pprhip_fora_conf_t* conf, uint64_t seed, int32_t* ids_out, double* vals_out, int cap,
                            int* n_out, double* reserve_out, pprhip_stats_t* stats) {
   static const char* fn = "pprhip_fora_topk_seeds";
+  PPRHIP_TRY(check_positive(eps, fn, "eps"));
+  PPRHIP_TRY(check_conf(conf, fn, true));
   PPRHIP_TRY(check_graph(g, fn));
   if (!fora_topk_args_ok(conf, eps, cap, ids_out, vals_out, fn)) return PPRHIP_ERR_INVALID;
   SeedTable plan;
@@ -1789,6 +1797,8 @@ int pprhip_fora_batch_single_source_resident(pprhip_graph_t* g, const int32_t* s
                                              pprhip_results_t* keep, double* reserve_out, int k, int32_t* ids_out,
                                              double* vals_out, int* n_out, pprhip_stats_t* per_query,
                                              pprhip_stats_t* stats_sum) {
+  PPRHIP_TRY(check_positive(eps, "pprhip_fora_batch_single_source", "eps"));
+  PPRHIP_TRY(check_conf(conf, "pprhip_fora_batch_single_source", false));
   PPRHIP_TRY(check_graph(g, "pprhip_fora_batch_single_source"));
   if (q < 0 || !conf || !(eps > 0.0) || n_rounds < 0 || (q > 0 && !srcs) || k < 0 ||
       (k > 0 && q > 0 && (!ids_out || !vals_out))) {
@@ -1897,6 +1907,8 @@ int pprhip_results_sum(pprhip_results_t* r, int i, double* sum_out) {
 
 int pprhip_fora_batch_topk(pprhip_graph_t* g, const int32_t* srcs, int q, int k, double eps, double alpha,
                            uint64_t seed, int32_t* ids_out, double* vals_out, pprhip_stats_t* stats_sum) {
+  PPRHIP_TRY(check_positive(eps, "pprhip_fora_batch_topk", "eps"));
+  PPRHIP_TRY(check_alpha(alpha, "pprhip_fora_batch_topk"));
   PPRHIP_TRY(check_graph(g, "pprhip_fora_batch_topk"));
   if (q < 0 || k < 1 || !(eps > 0.0) || (q > 0 && (!srcs || !ids_out || !vals_out))) {
     set_error("pprhip_fora_batch_topk: bad arguments");
@@ -2068,6 +2080,8 @@ int stream_error(pprhip_stream* s, const char* fn) {  // (s->mu held)
 
 int pprhip_fora_stream_open(pprhip_graph_t* g, double eps, const pprhip_fora_conf_t* conf, int k,
                             pprhip_stream_t** stream_out) {
+  PPRHIP_TRY(check_positive(eps, "pprhip_fora_stream_open", "eps"));
+  PPRHIP_TRY(check_conf(conf, "pprhip_fora_stream_open", false));
   PPRHIP_TRY(check_graph(g, "pprhip_fora_stream_open"));
   if (!stream_out || !conf || !(eps > 0.0) || k < 0) {
     set_error("pprhip_fora_stream_open: bad arguments (eps=%g k=%d)", eps, k);

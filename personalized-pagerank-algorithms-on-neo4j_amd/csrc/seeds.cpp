@@ -190,6 +190,8 @@ int pprhip_forward_push_seeds(pprhip_graph_t* g, const int32_t* seeds, const dou
                               double alpha, double rmax, double* reserve_out, double* residue_out, double* rsum_out,
                               pprhip_stats_t* stats) {
   static const char* fn = "pprhip_forward_push_seeds";
+  PPRHIP_TRY(check_alpha(alpha, fn));
+  PPRHIP_TRY(check_threshold(rmax, fn, "rmax"));
   PPRHIP_TRY(check_graph(g, fn));
   SeedTable plan;
   PPRHIP_TRY(seed_plan(g, seeds, weights, n_seeds, alpha, fn, plan));

@@ -11,6 +11,7 @@
 // relationship type, as PPR.setupAdjMatrix does (PPR.java:141-147).
 #include <dirent.h>
 
+#include <cmath>
 #include <cstdlib>
 #include <cstring>
 #include <iostream>
@@ -71,6 +72,16 @@ int main(int argc, char** argv) {
       else if (a == "seed") seed = std::stoull(v);
       else if (a == "single") single = std::stol(v);
       else throw PprError(PPRHIP_ERR_INVALID, "Unrecognized option: -" + a);
+    }
+    // Refused before the store or a device is opened: at alpha <= 0 no walk stops, at alpha >= 1 rmax0 divides by zero,
+    // at eps <= 0 the walk count is infinite (include/pprhip.h, "Parameter ranges").
+    if (!(alpha > 0.0 && alpha < 1.0)) {
+      std::cerr << "-alpha " << alpha << " is outside (0, 1)" << std::endl;
+      return 2;
+    }
+    if (!(eps > 0.0 && std::isfinite(eps))) {
+      std::cerr << "-eps " << eps << " must be finite and > 0" << std::endl;
+      return 2;
     }
     std::string dir_db = db;  // createDb keeps the directory's base name (PPR.java:52-60)
     while (dir_db.size() > 1 && dir_db.back() == '/') dir_db.pop_back();

@@ -19,6 +19,17 @@ def test_help_lists_reference_flags():
         assert flag in out  # PPR.java:157-166
 
 
+@pytest.mark.parametrize("flag,value", [("-alpha", "0"), ("-alpha", "1"), ("-alpha", "nan"), ("-eps", "0"),
+                                        ("-eps", "-1")])
+def test_out_of_range_flags_are_refused_before_loading(tmp_path, flag, value):
+    """-alpha outside (0, 1) and a non-positive -eps end the run right after the flags are read: non-zero exit, the
+    flag named, no store opened and no device touched (at alpha = 0 no walk would stop)."""
+    r = subprocess.run([PPR, flag, value, "-db", GOT_DIR], capture_output=True, text=True, timeout=60, cwd=tmp_path)
+    assert r.returncode != 0
+    assert flag in r.stderr, r.stderr
+    assert "Loading graph" not in r.stdout and not os.listdir(tmp_path)
+
+
 def test_batch_report_on_got(tmp_path):
     r = subprocess.run([PPR, "-alpha", "0.15", "-eps", "0.5", "-query", "6", "-k", "10", "-db", GOT_DIR],
                        capture_output=True, text=True, timeout=600, cwd=tmp_path)

@@ -146,6 +146,11 @@ def test_index_merge_and_files(pkg, orc, got, tmp_path):
 def test_conf_validation(pkg):
     with pytest.raises(pkg.PprhipError):
         pkg.conf_topk(100, 1000, 0, 0.15)
+    for bad in (0.0, -0.1, 1.0, 1.5, float("nan"), float("inf")):  # alpha must lie in (0, 1)
+        with pytest.raises(pkg.PprhipError, match="alpha"):
+            pkg.conf_whole_graph(100, 1000, bad)
+        with pytest.raises(pkg.PprhipError, match="alpha"):
+            pkg.conf_topk(100, 1000, 10, bad)
     c = pkg.conf_whole_graph(100, 1000, 0.2)
     assert (c.alpha, c.delta, c.pfail, c.rsum, c.n, c.m) == (0.2, 0.01, 0.01, 1.0, 100, 1000)
     t = pkg.tuning_default()
