@@ -235,7 +235,7 @@ int all_pair_collect(pprhip_graph_t* g, double alpha, double threshold, uint32_t
   // was sized for 65 536 entries, the hubs' searches were repeated a thousand times (44 G edge pushes) and then
   // dropped without an error.  Four entries per node also keeps a range of hubs from running pass after pass.
   B.out_cap = std::min<unsigned long long>(
-      1ull << 27, std::max<unsigned long long>(std::max<unsigned long long>(1ull << 16, 16ull * n_targets), 4ull * g->n + 1024));
+      1ull << 27, std::max<unsigned long long>(std::max<unsigned long long>(1ull << 16, 16ull * n_targets), 4ull * g->gr->n + 1024));
   if ((rc = alloc_dev((void**)&cells, sizeof(unsigned long long) * 16)) ||
       (rc = alloc_dev((void**)&B.out_rec, sizeof(TripleRec) * B.out_cap)) ||
       (rc = alloc_dev((void**)&B.overflow, sizeof(int32_t) * std::max<uint32_t>(1, n_targets))) ||
@@ -325,7 +325,7 @@ int all_pair_collect(pprhip_graph_t* g, double alpha, double threshold, uint32_t
   // in-edge records for both tiers' edge loops (8 B per edge; stays with the handle)
   if (!g->in_rec) {
     void* rec = nullptr;
-    if ((rc = alloc_dev(&rec, sizeof(unsigned long long) * std::max<uint64_t>(1, g->m))) == PPRHIP_OK &&
+    if ((rc = alloc_dev(&rec, sizeof(unsigned long long) * std::max<uint64_t>(1, g->gr->m))) == PPRHIP_OK &&
         (rc = launch_build_in_rec(g, rec)) == PPRHIP_OK)
       g->in_rec = rec;
     else if (rec)
@@ -361,11 +361,11 @@ int all_pair_collect(pprhip_graph_t* g, double alpha, double threshold, uint32_t
       const char* e_f = hook_env("PPRHIP_APBS_CAP_F");
       const char* e_c = hook_env("PPRHIP_APBS_CHUNK");
       const uint32_t chunk = e_c ? (uint32_t)std::max(16, atoi(e_c)) : apbs_default_chunk();
-      const uint32_t cap_t = e_t ? (uint32_t)std::max(1, atoi(e_t)) : std::min<uint32_t>(g->n, 1u << 20) + 4096u;
-      const uint32_t cap_f = e_f ? (uint32_t)std::max(1, atoi(e_f)) : std::min<uint32_t>(g->n, 1u << 20) + 64u;
+      const uint32_t cap_t = e_t ? (uint32_t)std::max(1, atoi(e_t)) : std::min<uint32_t>(g->gr->n, 1u << 20) + 4096u;
+      const uint32_t cap_f = e_f ? (uint32_t)std::max(1, atoi(e_f)) : std::min<uint32_t>(g->gr->n, 1u << 20) + 64u;
       const char* per_cu = hook_env("PPRHIP_APBS_WGS_PER_CU");
-      uint32_t want = (uint32_t)g->n_cus * (uint32_t)std::max(1, std::min(2, per_cu ? atoi(per_cu) : 1));
-      const size_t per = apbs_dense_bytes(g->n, g->m, cap_t, cap_f, chunk);
+      uint32_t want = (uint32_t)g->gr->n_cus * (uint32_t)std::max(1, std::min(2, per_cu ? atoi(per_cu) : 1));
+      const size_t per = apbs_dense_bytes(g->gr->n, g->gr->m, cap_t, cap_f, chunk);
       int arc = PPRHIP_ERR_OOM;
       // a device that cannot spare them all runs the tier with fewer workgroups in flight
       for (; want >= 8; want /= 2) {
@@ -406,14 +406,14 @@ int all_pair_collect(pprhip_graph_t* g, double alpha, double threshold, uint32_t
       // (a stable counting sort by in-degree, degrees from 65535 up in one bucket that is sorted on its own: a
       // comparison sort of half a million ids with two indirections per comparison was 15-40 ms of every pass)
       {
-        const std::vector<uint32_t>& irp = g->h_in_rp;
-        const std::vector<int32_t>& o2n = g->h_old2new;
+        const std::vector<uint32_t>& irp = g->gr->h_in_rp;
+        const std::vector<int32_t>& o2n = g->gr->h_old2new;
         constexpr uint32_t kCapDeg = 65535;
         const size_t L = list.size();
         std::vector<uint32_t> deg(L);
         std::vector<uint32_t> at((size_t)kCapDeg + 2, 0);
         for (size_t i = 0; i < L; ++i) {
-          const int32_t a = g->relabeled ? o2n[list[i]] : list[i];
+          const int32_t a = g->gr->relabeled ? o2n[list[i]] : list[i];
           deg[i] = irp[a + 1] - irp[a];
           at[kCapDeg - std::min(deg[i], kCapDeg) + 1]++;  // bucket 0: the largest degrees
         }
@@ -525,17 +525,17 @@ int all_pair_collect(pprhip_graph_t* g, double alpha, double threshold, uint32_t
     if (rc == PPRHIP_OK && !to_tier3.empty() && to_tier3.size() <= whole_max) {
       TripleRec* d_rec = nullptr;
       unsigned long long* d_cnt = nullptr;
-      const unsigned long long cap = std::max<uint32_t>(act_n(g), g->n);
+      const unsigned long long cap = std::max<uint32_t>(act_n(g), g->gr->n);
       auto whole = [&]() -> int {
         PPRHIP_TRY(alloc_dev((void**)&d_rec, sizeof(TripleRec) * cap));
         PPRHIP_TRY(alloc_dev((void**)&d_cnt, sizeof(unsigned long long)));
-        const std::vector<int32_t>& o2n = g->h_old2new;
+        const std::vector<int32_t>& o2n = g->gr->h_old2new;
         for (int32_t t_old : to_tier3) {
           pprhip_stats_t s1;
           std::memset(&s1, 0, sizeof s1);
-          PPRHIP_TRY(backward_search_whole(g, g->relabeled ? o2n[t_old] : t_old, alpha, threshold, s1));
+          PPRHIP_TRY(backward_search_whole(g, g->gr->relabeled ? o2n[t_old] : t_old, alpha, threshold, s1));
           PPRHIP_CHECK_HIP(hipMemsetAsync(d_cnt, 0, sizeof(unsigned long long), g->stream));
-          PPRHIP_TRY(launch_emit_reserve(g, g->reserve, g->n, threshold, t_old, d_rec, cap, d_cnt));
+          PPRHIP_TRY(launch_emit_reserve(g, g->reserve, g->gr->n, threshold, t_old, d_rec, cap, d_cnt));
           unsigned long long cnt = 0;
           PPRHIP_CHECK_HIP(hipMemcpyAsync(&cnt, d_cnt, sizeof cnt, hipMemcpyDeviceToHost, g->stream));
           PPRHIP_CHECK_HIP(hipStreamSynchronize(g->stream));
@@ -561,16 +561,16 @@ int all_pair_collect(pprhip_graph_t* g, double alpha, double threshold, uint32_t
     if (rc == PPRHIP_OK && g->apbs_blocks && !to_tier3.empty() && to_tier3.size() < to_tier2.size() &&
         !hook_env("PPRHIP_APBS_NO_XL")) {
       if (!g->apbs_xl_ws) {
-        const uint32_t xl_t = g->n + 4096u, xl_f = g->n + 64u;
+        const uint32_t xl_t = g->gr->n + 4096u, xl_f = g->gr->n + 64u;
         uint32_t want = 4;
         int arc = PPRHIP_ERR_OOM;
         for (; want >= 1; want /= 2) {
-          arc = alloc_dev((void**)&g->apbs_xl_ws, (size_t)want * apbs_dense_bytes(g->n, g->m, xl_t, xl_f, g->apbs_chunk));
+          arc = alloc_dev((void**)&g->apbs_xl_ws, (size_t)want * apbs_dense_bytes(g->gr->n, g->gr->m, xl_t, xl_f, g->apbs_chunk));
           if (arc != PPRHIP_ERR_OOM) break;
           (void)hipGetLastError();
         }
         if (arc == PPRHIP_OK &&
-            hipMemsetAsync(g->apbs_xl_ws, 0, (size_t)want * apbs_dense_bytes(g->n, g->m, xl_t, xl_f, g->apbs_chunk), g->stream) !=
+            hipMemsetAsync(g->apbs_xl_ws, 0, (size_t)want * apbs_dense_bytes(g->gr->n, g->gr->m, xl_t, xl_f, g->apbs_chunk), g->stream) !=
                 hipSuccess) {
           (void)hipFree(g->apbs_xl_ws);
           g->apbs_xl_ws = nullptr;
@@ -704,7 +704,7 @@ int ring_download(pprhip_graph* g, const void* d_src, void* h_dst, size_t bytes)
   size_t taken = 0;                  // next chunk a copier takes
   size_t freed[kIxSlots] = {};       // per slot: chunks of that slot moved on so far
   int err = PPRHIP_OK;
-  const int device = g->device;
+  const int device = g->gr->device;
   auto copier = [&] {
     (void)hipSetDevice(device);
     for (;;) {
@@ -777,8 +777,8 @@ int ring_download(pprhip_graph* g, const void* d_src, void* h_dst, size_t bytes)
 // over all n rows cost a rank of a sharded job the same whatever its share of the entries.
 int index_from_device(pprhip_graph* g, const TripleRec* rec, unsigned long long count, int k, uint32_t v_lo, uint32_t v_hi,
                       pprhip_index_t** out) {
-  if (v_lo > v_hi || v_hi > g->n) {
-    set_error("index: source range [%u, %u) outside [0, %u)", v_lo, v_hi, g->n);
+  if (v_lo > v_hi || v_hi > g->gr->n) {
+    set_error("index: source range [%u, %u) outside [0, %u)", v_lo, v_hi, g->gr->n);
     return PPRHIP_ERR_INVALID;
   }
   const bool dbg = hook_env("PPRHIP_APBS_DEBUG") != nullptr;
@@ -786,17 +786,17 @@ int index_from_device(pprhip_graph* g, const TripleRec* rec, unsigned long long 
   auto ms = [&] { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count(); };
   std::unique_ptr<pprhip_index> ix(new (std::nothrow) pprhip_index());
   if (!ix) return PPRHIP_ERR_OOM;
-  ix->n = g->n;
+  ix->n = g->gr->n;
   DeviceRows R;
   PPRHIP_TRY(finalize_rows_device(g, rec, count, k, v_lo, v_hi, &R));
   if (dbg) fprintf(stderr, "[index] rows finished on the device at %.1f ms (%llu of %llu entries kept)\n", ms(), R.entries, count);
   if (!R.offsets) {  // no entries: every row is empty
-    ix->offsets.assign((size_t)g->n + 1, 0);
+    ix->offsets.assign((size_t)g->gr->n + 1, 0);
     *out = ix.release();
     return PPRHIP_OK;
   }
   try {
-    ix->offsets.resize((size_t)g->n + 1);
+    ix->offsets.resize((size_t)g->gr->n + 1);
     ix->targets.resize(R.entries);
     ix->values.resize(R.entries);
   } catch (const std::bad_alloc&) {  // (up to 12 bytes of HBM per entry must not stay behind)
@@ -804,7 +804,7 @@ int index_from_device(pprhip_graph* g, const TripleRec* rec, unsigned long long 
     device_rows_free(&R);
     return PPRHIP_ERR_OOM;
   }
-  int rc = ring_download(g, R.offsets, ix->offsets.data(), 8 * ((size_t)g->n + 1));
+  int rc = ring_download(g, R.offsets, ix->offsets.data(), 8 * ((size_t)g->gr->n + 1));
   if (rc == PPRHIP_OK) rc = ring_download(g, R.values, ix->values.data(), 8 * (size_t)R.entries);
   if (rc == PPRHIP_OK) rc = ring_download(g, R.targets, ix->targets.data(), 4 * (size_t)R.entries);
   device_rows_free(&R);
@@ -863,8 +863,8 @@ int pprhip_all_pair_backward(pprhip_graph_t* g, double alpha, double threshold, 
   PPRHIP_TRY(check_alpha(alpha, "pprhip_all_pair_backward"));
   PPRHIP_TRY(check_threshold(threshold, "pprhip_all_pair_backward", "threshold"));
   PPRHIP_TRY(check_graph(g, "pprhip_all_pair_backward"));
-  if (!index_out || t_begin > t_end || t_end > g->n) {
-    set_error("pprhip_all_pair_backward: bad target range [%u, %u) for n=%u", t_begin, t_end, g->n);
+  if (!index_out || t_begin > t_end || t_end > g->gr->n) {
+    set_error("pprhip_all_pair_backward: bad target range [%u, %u) for n=%u", t_begin, t_end, g->gr->n);
     return PPRHIP_ERR_INVALID;
   }
   pprhip_stats_t st;
@@ -877,7 +877,7 @@ int pprhip_all_pair_backward(pprhip_graph_t* g, double alpha, double threshold, 
   if (!g->ix_stage) {
     try {
       pin = std::thread([g] {
-        if (hipSetDevice(g->device) == hipSuccess) (void)ensure_ring(g);
+        if (hipSetDevice(g->gr->device) == hipSuccess) (void)ensure_ring(g);
       });
     } catch (const std::system_error&) {  // (no helper thread: the download pins its ring when it gets there)
     }
@@ -890,7 +890,7 @@ int pprhip_all_pair_backward(pprhip_graph_t* g, double alpha, double threshold, 
   PPRHIP_TRY(crc);
   const auto t1 = std::chrono::steady_clock::now();
   try {  // (the index arrays are host allocations of hundreds of megabytes: no exception leaves the C ABI)
-    PPRHIP_TRY(index_from_device(g, sink.rec, sink.count, k, 0u, g->n, index_out));
+    PPRHIP_TRY(index_from_device(g, sink.rec, sink.count, k, 0u, g->gr->n, index_out));
   } catch (const std::exception& e) {
     set_error("pprhip_all_pair_backward: index finalisation: %s", e.what());
     return PPRHIP_ERR_OOM;

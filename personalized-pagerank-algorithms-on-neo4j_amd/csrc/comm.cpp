@@ -421,7 +421,7 @@ constexpr int kPilotTop = 16, kPilotRanks = 48;
 double equal_count_skew(const pprhip_graph* g, int W) {
   // (every 8th id of a range stands for the range: the test only has to tell a degree-sorted store from a scrambled one,
   // and rank 0 runs it while its peers wait - 3 ms instead of 20 for R-MAT 22)
-  const uint32_t n = g->n;
+  const uint32_t n = g->gr->n;
   const double d_star = std::max(64.0, (double)n / 256.0);
   std::vector<double> share((size_t)W, 0.0);
   double total = 0.0;
@@ -431,7 +431,7 @@ double equal_count_skew(const pprhip_graph* g, int W) {
     double s = 0.0;
     const uint32_t step = hi - lo >= 4096 ? 8u : 1u;
     for (uint32_t t = lo; t < hi; t += step) {
-      const double d = (double)hdeg_in(g, g->h_old2new[t]);
+      const double d = (double)hdeg_in(g, g->gr->h_old2new[t]);
       s += 1.0 + d * (1.0 + d / d_star);
     }
     s *= (double)step;
@@ -444,11 +444,11 @@ double equal_count_skew(const pprhip_graph* g, int W) {
 }
 
 int weighted_target_cuts(pprhip_graph* g, int W, double alpha, double threshold, std::vector<uint32_t>& cuts) {
-  const uint32_t n = g->n;
+  const uint32_t n = g->gr->n;
   cuts.assign((size_t)W + 1, n);
   cuts[0] = 0;
   std::vector<uint32_t> deg(n);
-  for (uint32_t t = 0; t < n; ++t) deg[t] = hdeg_in(g, g->h_old2new[t]);
+  for (uint32_t t = 0; t < n; ++t) deg[t] = hdeg_in(g, g->gr->h_old2new[t]);
   std::vector<uint32_t> order(n);
   for (uint32_t t = 0; t < n; ++t) order[t] = t;
   std::stable_sort(order.begin(), order.end(), [&](uint32_t a, uint32_t b) { return deg[a] > deg[b]; });
@@ -471,7 +471,7 @@ int weighted_target_cuts(pprhip_graph* g, int W, double alpha, double threshold,
       pprhip_stats_t st;
       std::memset(&st, 0, sizeof st);
       const uint32_t t = order[ranks[i]];
-      PPRHIP_TRY(backward_search_whole(g, g->h_old2new[t], alpha, threshold, st));
+      PPRHIP_TRY(backward_search_whole(g, g->gr->h_old2new[t], alpha, threshold, st));
       cost[i] = 1.0 + (double)(st.edge_pushes + st.dense_edges) + 4.0 * (double)(st.pops + st.dense_nodes);
     }
     PPRHIP_CHECK_HIP(hipStreamSynchronize(g->stream));
@@ -538,7 +538,7 @@ int decide_target_cuts(pprhip_comm* c, double alpha, double threshold, std::vect
       if (by_work) {
         rc = weighted_target_cuts(g, W, alpha, threshold, cuts);
       } else {
-        for (int r = 0; r < W; ++r) target_range(r, W, g->n, &cuts[(size_t)r], &cuts[(size_t)r + 1]);
+        for (int r = 0; r < W; ++r) target_range(r, W, g->gr->n, &cuts[(size_t)r], &cuts[(size_t)r + 1]);
       }
       if (rc == PPRHIP_OK) {
         std::vector<uint32_t> all((size_t)W * (W + 1));
@@ -564,10 +564,10 @@ int decide_target_cuts(pprhip_comm* c, double alpha, double threshold, std::vect
       set_error("sharded All-Pair: download of the target cuts failed");
       rc = PPRHIP_ERR_HIP;
     } else {
-      bool ok = cuts[0] == 0 && cuts[(size_t)W] == g->n;
+      bool ok = cuts[0] == 0 && cuts[(size_t)W] == g->gr->n;
       for (int r = 0; r < W; ++r) ok = ok && cuts[(size_t)r] <= cuts[(size_t)r + 1];
       if (!ok) {
-        set_error("sharded All-Pair: rank %d received target cuts that do not tile [0, %u)", c->rank, g->n);
+        set_error("sharded All-Pair: rank %d received target cuts that do not tile [0, %u)", c->rank, g->gr->n);
         rc = PPRHIP_ERR_STATE;
       }
     }
@@ -585,18 +585,18 @@ int all_pair_sharded(pprhip_comm* c, double alpha, double threshold, int k, pprh
   pprhip_graph* g = c->g;
   const int W = c->world;
   int rc = pre_rc;
-  if (g->n < (uint32_t)W) {
+  if (g->gr->n < (uint32_t)W) {
     // every rank sees the same n (replicas of one graph): ALL of them return here, a rank that came in with an error
     // of its own included - nobody goes on to an exchange the others have left
     if (rc == PPRHIP_OK) {
-      set_error("sharded All-Pair: fewer nodes (%u) than ranks (%d)", g->n, W);
+      set_error("sharded All-Pair: fewer nodes (%u) than ranks (%d)", g->gr->n, W);
       rc = PPRHIP_ERR_INVALID;
     }
     return rc;
   }
   // the sources this rank owns: equal counts; the targets it searches: rank 0's cut (equal counts, or by modelled work)
   uint32_t lo = 0, hi = 0, t_lo = 0, t_hi = 0;
-  target_range(c->rank, W, g->n, &lo, &hi);
+  target_range(c->rank, W, g->gr->n, &lo, &hi);
   {
     std::vector<uint32_t> cuts;
     rc = decide_target_cuts(c, alpha, threshold, cuts, rc);
@@ -765,7 +765,7 @@ int pprhip_comm_create(pprhip_graph_t* g, const void* id, int rank, int world, p
   std::unique_ptr<pprhip_comm> c(new (std::nothrow) pprhip_comm());
   if (!c) return PPRHIP_ERR_OOM;
   c->g = g;
-  c->device = g->device;
+  c->device = g->gr->device;
   c->rank = rank;
   c->world = world;
   // ncclCommInitRank is a rendezvous: it returns when all `world` ranks have called it.  It runs on a helper thread
@@ -781,7 +781,7 @@ int pprhip_comm_create(pprhip_graph_t* g, const void* id, int rank, int world, p
   auto st = std::make_shared<Init>();
   ncclUniqueId uid;
   std::memcpy(&uid, id, sizeof uid);
-  const int device = g->device;
+  const int device = g->gr->device;
   std::thread([st, R, uid, rank, world, device] {
     ncclComm_t cm = nullptr;
     int r = hipSetDevice(device) == hipSuccess ? R->CommInitRank(&cm, world, uid, rank) : 2 /* ncclSystemError */;
@@ -852,7 +852,7 @@ int pprhip_shard_target_cuts(pprhip_graph_t* g, int world, double alpha, double 
     if (mode == 1 || (mode == 2 && skew > 1.15)) {
       PPRHIP_TRY(weighted_target_cuts(g, world, alpha, threshold, cuts));
     } else {
-      for (int r = 0; r < world; ++r) target_range(r, world, g->n, &cuts[(size_t)r], &cuts[(size_t)r + 1]);
+      for (int r = 0; r < world; ++r) target_range(r, world, g->gr->n, &cuts[(size_t)r], &cuts[(size_t)r + 1]);
     }
     std::copy(cuts.begin(), cuts.end(), cuts_out);
   } catch (const std::bad_alloc&) {
@@ -937,7 +937,7 @@ int setup_ranks(pprhip_graph_t* const* per_gpu, int n_gpu, RankSetup& S, const c
     return PPRHIP_ERR_INVALID;
   }
   for (int r = 0; r < n_gpu; ++r) {
-    if (!per_gpu[r] || per_gpu[r]->n != per_gpu[0]->n || per_gpu[r]->m != per_gpu[0]->m) {
+    if (!per_gpu[r] || per_gpu[r]->gr->n != per_gpu[0]->gr->n || per_gpu[r]->gr->m != per_gpu[0]->gr->m) {
       set_error("%s: handle %d is null or holds another graph (every GPU needs a replica of the same CSR)", fn, r);
       return PPRHIP_ERR_INVALID;
     }
@@ -949,7 +949,7 @@ int setup_ranks(pprhip_graph_t* const* per_gpu, int n_gpu, RankSetup& S, const c
   }
   bool distinct = true;
   for (int r = 0; r < n_gpu; ++r)
-    for (int s = 0; s < r; ++s) distinct = distinct && per_gpu[r]->device != per_gpu[s]->device;
+    for (int s = 0; s < r; ++s) distinct = distinct && per_gpu[r]->gr->device != per_gpu[s]->gr->device;
   S.comms.assign((size_t)n_gpu, pprhip_comm());
   S.errs.assign((size_t)n_gpu, "");
   S.rcs.assign((size_t)n_gpu, PPRHIP_OK);
@@ -980,8 +980,8 @@ int run_ranks(RankSetup& S, F fn) {
   int dev0 = 0;
   (void)hipGetDevice(&dev0);
   for (int r = 0; r < W; ++r)
-    if (hipSetDevice(S.comms[r].g->device) != hipSuccess) {
-      set_error("GPU %d: hipSetDevice(%d) failed", r, S.comms[r].g->device);
+    if (hipSetDevice(S.comms[r].g->gr->device) != hipSuccess) {
+      set_error("GPU %d: hipSetDevice(%d) failed", r, S.comms[r].g->gr->device);
       (void)hipSetDevice(dev0);
       return PPRHIP_ERR_NO_DEVICE;
     }
@@ -994,7 +994,7 @@ int run_ranks(RankSetup& S, F fn) {
     }
     std::vector<ncclComm_t> cs((size_t)W, nullptr);
     std::vector<int> devs((size_t)W);
-    for (int r = 0; r < W; ++r) devs[r] = S.comms[r].g->device;
+    for (int r = 0; r < W; ++r) devs[r] = S.comms[r].g->gr->device;
     PPRHIP_CHECK_RCCL(R->CommInitAll(cs.data(), W, devs.data()));
     for (int r = 0; r < W; ++r) S.comms[r].nccl = cs[r];
     (void)hipSetDevice(dev0);
@@ -1003,8 +1003,8 @@ int run_ranks(RankSetup& S, F fn) {
   for (int r = 0; r < W; ++r)
     th.emplace_back([&, r] {
       int pre = PPRHIP_OK;
-      if (hipSetDevice(S.comms[r].g->device) != hipSuccess) {
-        set_error("hipSetDevice(%d) failed on rank %d's thread", S.comms[r].g->device, r);
+      if (hipSetDevice(S.comms[r].g->gr->device) != hipSuccess) {
+        set_error("hipSetDevice(%d) failed on rank %d's thread", S.comms[r].g->gr->device, r);
         pre = PPRHIP_ERR_NO_DEVICE;
       }
       int rc;
@@ -1024,7 +1024,7 @@ int run_ranks(RankSetup& S, F fn) {
   for (auto& t : th) t.join();
   for (int r = 0; r < W; ++r)
     if (S.comms[r].nccl) {
-      (void)hipSetDevice(S.comms[r].g->device);
+      (void)hipSetDevice(S.comms[r].g->gr->device);
       (void)rccl()->CommDestroy(S.comms[r].nccl);
       S.comms[r].nccl = nullptr;
     }
@@ -1036,7 +1036,7 @@ int run_ranks(RankSetup& S, F fn) {
                                                S.errs[r].find("failed before the exchange") == std::string::npos)))
       first = r;
   if (first >= 0) {
-    set_error("GPU %d (device %d): %s", first, S.comms[first].g->device, S.errs[first].c_str());
+    set_error("GPU %d (device %d): %s", first, S.comms[first].g->gr->device, S.errs[first].c_str());
     return S.rcs[first];
   }
   return PPRHIP_OK;

@@ -93,7 +93,7 @@ C8Scope::C8Scope(pprhip_graph* g_, bool back_) : g(g_), back(back_) {
   }
   own = g->stream;
   g->stream = g->parent->stream;
-  g->parent->in_c8++;
+  g->parent->batch->in_c8++;
   on = true;
 }
 
@@ -101,7 +101,7 @@ int C8Scope::leave() {
   if (!on) return rc;
   on = false;
   g->stream = own;
-  g->parent->in_c8--;
+  g->parent->batch->in_c8--;
   if (back && (hipEventRecord(g->c8_ev[1], g->parent->stream) != hipSuccess ||
                hipStreamWaitEvent(own, g->c8_ev[1], 0) != hipSuccess)) {
     set_error("slot %d: the sweeps' stream could not be joined to its stream", g->slot_index);
@@ -153,7 +153,8 @@ int fetch_end(pprhip_graph* g, unsigned long long seq, const void* dev, void* ho
   // called between looks at the mailbox, so that the sweep's end is noticed - and the next sweep launched - at once
   // instead of after this slot's step (kernel trace: the compute stream waited 97 us per sweep for the host).
   pprhip_graph* const H = g->parent;
-  const bool hooked = H && H->idle_hook;
+  const BatchState* bs = H ? H->batch : nullptr;
+  const bool hooked = bs && bs->idle_hook;
   const double kSpinUs = hooked ? 2e6 : 60.0;
   const auto t0 = std::chrono::steady_clock::now();
   bool arrived = false;
@@ -163,7 +164,7 @@ int fetch_end(pprhip_graph* g, unsigned long long seq, const void* dev, void* ho
       break;
     }
     __builtin_ia32_pause();
-    if (hooked && (spins & 7u) == 7u) H->idle_hook(H->idle_arg);
+    if (hooked && (spins & 7u) == 7u) bs->idle_hook(bs->idle_arg);
     if ((spins & 63u) == 63u &&
         std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now() - t0).count() > kSpinUs)
       break;
@@ -210,30 +211,31 @@ int write_packed(pprhip_graph* g, int slot, uint32_t nf, uint64_t ef) {
 // level cost model; the test twin evaluates the same expression
 double level_cost(const pprhip_graph* g, uint64_t nf, uint64_t ef, bool* dense) {
   const pprhip_tuning_t& t = g->tun;
-  const bool d = (double)(ef + nf) >= t.dense_frac * (double)g->m;
+  const bool d = (double)(ef + nf) >= t.dense_frac * (double)g->gr->m;
   *dense = d;
-  if (d) return t.c_level_ns + t.c_dense_edge_ns * (double)g->m + t.c_dense_node_ns * (double)g->n;
+  if (d) return t.c_level_ns + t.c_dense_edge_ns * (double)g->gr->m + t.c_dense_node_ns * (double)g->gr->n;
   return t.c_level_ns + t.c_edge_ns * (double)ef + t.c_pop_ns * (double)nf;
 }
 
 // SURVEY 8(d) sweep model, 12 m + 36 n + 4, with n = the rows the sweep carries: rows without in-edges receive
 // nothing and are not touched by the single-query sweep (the power method counts the same rows)
-uint64_t dense_level_bytes(const pprhip_graph* g) { return 12ull * g->m + 36ull * host_of(g)->n_nz + 4ull; }
+uint64_t dense_level_bytes(const pprhip_graph* g) { return 12ull * g->gr->m + 36ull * g->gr->n_nz + 4ull; }
 
 // Compulsory bytes of one sweep: what it has to move when every byte is counted once (pprhip_stats_t.sweep_min_bytes).
 // Single query: column indices + row-start bits, every gatherable contribution once (8 B per node with out-edges),
 // per row with in-edges the row sum out and in (16 B), the next contribution (8 B) and the residue read and written
 // (16 B).  The reserve is touched by crossing rows only and is left out: a lower bound.
 uint64_t dense_level_min_bytes(const pprhip_graph* g) {
-  const pprhip_graph* H = host_of(g);
-  return 4ull * H->m + H->m / 8 + 8ull * H->n_src_live + 40ull * H->n_nz;
+  const GraphData* D = g->gr;
+  return 4ull * D->m + D->m / 8 + 8ull * D->n_src_live + 40ull * D->n_nz;
 }
 // Batched: the index stream once, every gatherable line c8[v][0..15] once (128 B), per carried row the 128-byte row-sum
 // line out and in and the next-contribution line out, and per busy query the residue of every row with in-edges.
 uint64_t batch_sweep_min_bytes(const pprhip_graph* P, bool backward, int n_active) {
-  const uint64_t rows_nz = backward ? P->n_nz_o : P->n_nz, rows_all = rows_nz + (backward ? P->n_z_o : P->n_zin);
-  const uint64_t gather = backward ? (uint64_t)P->n_nz : (uint64_t)P->n_src_live;
-  return 4ull * P->m + P->m / 8 + 128ull * gather + 256ull * rows_nz + 128ull * rows_all +
+  const GraphData* D = P->gr;
+  const uint64_t rows_nz = backward ? D->n_nz_o : D->n_nz, rows_all = rows_nz + (backward ? D->n_z_o : D->n_zin);
+  const uint64_t gather = backward ? (uint64_t)D->n_nz : (uint64_t)D->n_src_live;
+  return 4ull * D->m + D->m / 8 + 128ull * gather + 256ull * rows_nz + 128ull * rows_all +
          16ull * rows_nz * (uint64_t)n_active;
 }
 
@@ -241,14 +243,13 @@ uint64_t batch_sweep_min_bytes(const pprhip_graph* P, bool backward, int n_activ
 // contribution array has to be flushed
 double dense_sweep_cost(const pprhip_graph* g) {
   const pprhip_tuning_t& t = g->tun;
-  return t.c_level_ns + t.c_dense_edge_ns * (double)g->m + t.c_dense_node_ns * (double)g->n;
+  return t.c_level_ns + t.c_dense_edge_ns * (double)g->gr->m + t.c_dense_node_ns * (double)g->gr->n;
 }
 
 // smallest frontier (nodes + edges) that runs as Gauss-Seidel sweeps; ~0 when they are switched off
 unsigned long long gs_thresh_of(const pprhip_graph* g) {
-  const pprhip_graph* H = host_of(g);
-  if (g->tun.gs_blocks <= 1 || !H->relabeled) return ~0ull;
-  return (unsigned long long)std::ceil(g->tun.gs_frac * (double)g->m);
+  if (g->tun.gs_blocks <= 1 || !g->gr->relabeled) return ~0ull;
+  return (unsigned long long)std::ceil(g->tun.gs_frac * (double)g->gr->m);
 }
 
 // Blocks of the forward sweep (rows = nodes with in-edges in internal order): block b holds the row ordinals
@@ -256,17 +257,17 @@ unsigned long long gs_thresh_of(const pprhip_graph* g) {
 // 256 (whole apply tiles), and the in-edges of those rows.  The test twin builds the same blocks
 // (oracle/ppr_oracle.c: build_blocks).
 const GsBlock* gs_blocks_of(pprhip_graph* g, int* n_blocks) {
-  pprhip_graph* H = g->parent ? g->parent : g;
+  GraphData* D = g->gr;
   const int B = g->tun.gs_blocks;
   *n_blocks = 1;
-  if (B <= 1 || !H->relabeled || H->n_nz == 0) return nullptr;
-  if (H->gs_plan_B != B) {
-    const std::vector<uint32_t>& irp = H->h_in_rp;
-    const std::vector<int32_t>& rows = H->h_nz_rows;
-    const uint32_t n_nz = H->n_nz;
+  if (B <= 1 || !D->relabeled || D->n_nz == 0) return nullptr;
+  if (D->gs_plan_B != B) {
+    const std::vector<uint32_t>& irp = D->h_in_rp;
+    const std::vector<int32_t>& rows = D->h_nz_rows;
+    const uint32_t n_nz = D->n_nz;
     std::vector<uint32_t> jb((size_t)B + 1, 0);
     for (int b = 1; b < B; ++b) {
-      const uint64_t target = (uint64_t)b * H->m / (uint64_t)B;
+      const uint64_t target = (uint64_t)b * D->m / (uint64_t)B;
       uint32_t lo = 0, hi = n_nz;  // first ordinal whose in-edge prefix (= row start) reaches the target
       while (lo < hi) {
         const uint32_t mid = (lo + hi) >> 1;
@@ -276,18 +277,18 @@ const GsBlock* gs_blocks_of(pprhip_graph* g, int* n_blocks) {
       jb[b] = std::max(jb[b - 1], j);
     }
     jb[B] = n_nz;
-    H->gs_plan.assign((size_t)B, GsBlock{0, 0, 0, 0});
+    D->gs_plan.assign((size_t)B, GsBlock{0, 0, 0, 0});
     for (int b = 0; b < B; ++b) {
-      GsBlock& K = H->gs_plan[b];
+      GsBlock& K = D->gs_plan[b];
       K.j_lo = jb[b];
       K.j_hi = jb[b + 1];
-      K.e_lo = K.j_lo < n_nz ? irp[rows[K.j_lo]] : H->m;
-      K.e_hi = K.j_hi < n_nz ? irp[rows[K.j_hi]] : H->m;
+      K.e_lo = K.j_lo < n_nz ? irp[rows[K.j_lo]] : D->m;
+      K.e_hi = K.j_hi < n_nz ? irp[rows[K.j_hi]] : D->m;
     }
-    H->gs_plan_B = B;
+    D->gs_plan_B = B;
   }
   *n_blocks = B;
-  return H->gs_plan.data();
+  return D->gs_plan.data();
 }
 
 // Windows of the sliced layout (engine.hpp: SlicedLayout) for a sweep cut into the row blocks `blocks` (nullptr: one
@@ -295,11 +296,11 @@ const GsBlock* gs_blocks_of(pprhip_graph* g, int* n_blocks) {
 // joined.  Cached per block count (the blocks of a count are always the same, gs_blocks_of).
 static std::mutex g_sl_plan_mu;
 const EdgeWindows* sliced_windows_of(pprhip_graph* g, const GsBlock* blocks, int nb) {
-  pprhip_graph* H = g->parent ? g->parent : g;
-  SlicedLayout* L = H->sl;
+  GraphData* D = g->gr;
+  SlicedLayout* L = D->sl;
   std::lock_guard<std::mutex> lock(g_sl_plan_mu);
   if (L->plan_B == nb) return L->plan.data();
-  const GsBlock whole{0u, H->n_nz, 0ull, (unsigned long long)H->m};
+  const GsBlock whole{0u, D->n_nz, 0ull, (unsigned long long)D->m};
   if (!blocks || nb <= 1) {
     blocks = &whole;
     nb = 1;
@@ -335,9 +336,16 @@ const EdgeWindows* sliced_windows_of(pprhip_graph* g, const GsBlock* blocks, int
   return L->plan.data();
 }
 
+// a host array copied to a device allocation of its own
+static int upload(void** dst, const void* src, size_t bytes) {
+  PPRHIP_TRY(alloc_dev(dst, bytes));
+  if (bytes) PPRHIP_CHECK_HIP(hipMemcpy(*dst, src, bytes, hipMemcpyHostToDevice));
+  return PPRHIP_OK;
+}
+
 // Uploads the sliced copy of the (internal-order) in-CSR the host half of the lift built (lift.cpp); no layout when
 // the source ids fit one slice.
-static int upload_sliced_layout(pprhip_graph* G, HostLift& H) {
+static int upload_sliced_layout(GraphData* D, HostLift& H) {
   if (H.S < 2) return PPRHIP_OK;
   std::unique_ptr<SlicedLayout> L(new (std::nothrow) SlicedLayout());
   if (!L) return PPRHIP_ERR_OOM;
@@ -348,20 +356,15 @@ static int upload_sliced_layout(pprhip_graph* G, HostLift& H) {
   L->seg_base = std::move(H.seg_base);
   L->h_seg_row = std::move(H.seg_row);
   L->h_seg_off = std::move(H.seg_off);
-  auto up = [&](void** dst, const void* src, size_t bytes) -> int {
-    PPRHIP_TRY(alloc_dev(dst, bytes));
-    if (bytes) PPRHIP_CHECK_HIP(hipMemcpy(*dst, src, bytes, hipMemcpyHostToDevice));
-    return PPRHIP_OK;
-  };
-  G->sl = L.release();  // from here on pprhip_graph_destroy frees what has been allocated
-  PPRHIP_TRY(up((void**)&G->sl->ci, H.sl_ci.data(), sizeof(int32_t) * H.sl_ci.size()));
-  PPRHIP_TRY(up((void**)&G->sl->flags, H.sl_flags.data(), H.sl_flags.size()));
-  PPRHIP_TRY(up((void**)&G->sl->chunk_starts, H.sl_chunk_starts.data(), sizeof(uint32_t) * H.sl_chunk_starts.size()));
-  PPRHIP_TRY(up((void**)&G->sl->seg_row, G->sl->h_seg_row.data(), sizeof(uint32_t) * G->sl->h_seg_row.size()));
+  D->sl = L.release();  // from here on free_graph_data frees what has been allocated
+  PPRHIP_TRY(upload((void**)&D->sl->ci, H.sl_ci.data(), sizeof(int32_t) * H.sl_ci.size()));
+  PPRHIP_TRY(upload((void**)&D->sl->flags, H.sl_flags.data(), H.sl_flags.size()));
+  PPRHIP_TRY(upload((void**)&D->sl->chunk_starts, H.sl_chunk_starts.data(), sizeof(uint32_t) * H.sl_chunk_starts.size()));
+  PPRHIP_TRY(upload((void**)&D->sl->seg_row, D->sl->h_seg_row.data(), sizeof(uint32_t) * D->sl->h_seg_row.size()));
   return PPRHIP_OK;
 }
 
-static int upload_panel_layout(pprhip_graph* G, HostLift& H) {
+static int upload_panel_layout(GraphData* D, HostLift& H) {
   if (!H.pn.n_items) return PPRHIP_OK;
   std::unique_ptr<PanelLayout> L(new (std::nothrow) PanelLayout());
   if (!L) return PPRHIP_ERR_OOM;
@@ -369,26 +372,22 @@ static int upload_panel_layout(pprhip_graph* G, HostLift& H) {
   L->n_items = H.pn.n_items;
   L->n_part = H.pn.n_part;
   L->h_panel_item0 = std::move(H.pn.panel_item0);
-  auto up = [&](void** dst, const void* src, size_t bytes) -> int {
-    PPRHIP_TRY(alloc_dev(dst, bytes));
-    if (bytes) PPRHIP_CHECK_HIP(hipMemcpy(*dst, src, bytes, hipMemcpyHostToDevice));
-    return PPRHIP_OK;
-  };
-  G->pn = L.release();  // from here on pprhip_graph_destroy frees what has been allocated
-  PPRHIP_TRY(up((void**)&G->pn->src, H.pn.src.data(), sizeof(int32_t) * H.pn.src.size()));
-  PPRHIP_TRY(up((void**)&G->pn->rloc, H.pn.rloc.data(), sizeof(uint16_t) * H.pn.rloc.size()));
-  PPRHIP_TRY(up((void**)&G->pn->items, H.pn.items.data(), sizeof(PanelItem) * H.pn.items.size()));
-  PPRHIP_TRY(up((void**)&G->pn->panels, H.pn.panels.data(), sizeof(PanelDesc) * H.pn.panels.size()));
+  D->pn = L.release();  // from here on free_graph_data frees what has been allocated
+  PPRHIP_TRY(upload((void**)&D->pn->src, H.pn.src.data(), sizeof(int32_t) * H.pn.src.size()));
+  PPRHIP_TRY(upload((void**)&D->pn->rloc, H.pn.rloc.data(), sizeof(uint16_t) * H.pn.rloc.size()));
+  PPRHIP_TRY(upload((void**)&D->pn->items, H.pn.items.data(), sizeof(PanelItem) * H.pn.items.size()));
+  PPRHIP_TRY(upload((void**)&D->pn->panels, H.pn.panels.data(), sizeof(PanelDesc) * H.pn.panels.size()));
   return PPRHIP_OK;
 }
 
-// the buffer the items of a panel sweep leave their sums in: per handle, on its first forward dense level
+// the buffer the items of a panel sweep leave their sums in: per handle, on its first forward dense level (a slot runs
+// no single-query dense level and has none)
 int ensure_panel_part(pprhip_graph* g) {
-  if (!g->pn || g->pn_part) return PPRHIP_OK;
+  if (g->parent || !g->gr->pn || g->pn_part) return PPRHIP_OK;
   // (pn_part last: its presence means both exist; a failed second allocation leaves neither behind)
   PPRHIP_TRY(alloc_dev((void**)&g->pn_ctr, kPanelQueues * sizeof(uint32_t)));
   PPRHIP_CHECK_HIP(hipMemsetAsync(g->pn_ctr, 0, kPanelQueues * sizeof(uint32_t), g->stream));
-  const int rc = alloc_dev((void**)&g->pn_part, sizeof(double) * (size_t)g->pn->n_part);
+  const int rc = alloc_dev((void**)&g->pn_part, sizeof(double) * (size_t)g->gr->pn->n_part);
   if (rc != PPRHIP_OK) {
     (void)hipFree(g->pn_ctr);
     g->pn_ctr = nullptr;
@@ -432,7 +431,7 @@ int run_levels(pprhip_graph* g, const PushArgs& a, LevelCtx& L, pprhip_stats_t& 
   // smallest integer x with (double)x >= dense_frac * m: the device-side form of level_cost()'s test
   const bool sparse_only = false;  // every push direction has both level shapes
   const unsigned long long dense_thresh =
-      sparse_only ? ~0ull : (unsigned long long)std::ceil(g->tun.dense_frac * (double)g->m);
+      sparse_only ? ~0ull : (unsigned long long)std::ceil(g->tun.dense_frac * (double)g->gr->m);
   const unsigned long long gs_thresh = bwd ? ~0ull : gs_thresh_of(g);
   int n_gs = 1;
   const GsBlock* gs_blocks = gs_thresh != ~0ull ? gs_blocks_of(g, &n_gs) : nullptr;
@@ -449,9 +448,9 @@ int run_levels(pprhip_graph* g, const PushArgs& a, LevelCtx& L, pprhip_stats_t& 
         // workspace pool: the level needs a column of c8 (nothing has been decided or queued yet: the driver calls
         // again when one is free)
         int c = 0;
-        while (c < kBatch && g->parent->col_owner[c] >= 0) ++c;
+        while (c < kBatch && g->parent->batch->col_owner[c] >= 0) ++c;
         if (c == kBatch) return kYieldColumn;
-        g->parent->col_owner[c] = g->ws_index;
+        g->parent->batch->col_owner[c] = g->ws_index;
         g->slot_index = c;
         g->has_col = true;
       }
@@ -464,9 +463,9 @@ int run_levels(pprhip_graph* g, const PushArgs& a, LevelCtx& L, pprhip_stats_t& 
         PPRHIP_TRY(c8.rc);
         if (slot) {
           if (g->sync) g->sync->c8_enter(g->slot_index);
-          L.ccur = g->parent->c8cur;  // the slot's column of the shared array is all-zero here
+          L.ccur = g->parent->batch->c8cur;  // the slot's column of the shared array is all-zero here
         } else
-          PPRHIP_CHECK_HIP(hipMemsetAsync(g->cdense[L.ccur], 0, sizeof(double) * g->n, g->stream));
+          PPRHIP_CHECK_HIP(hipMemsetAsync(g->cdense[L.ccur], 0, sizeof(double) * g->gr->n, g->stream));
         PPRHIP_TRY(launch_sparse_prepare(g, a, L.fcur, 0, L.nf, dense_thresh, true, L.ccur, L.dslot,
                                          ((unsigned long long)L.nf << kPackShift) | L.ef));
         PPRHIP_TRY(c8.leave());
@@ -493,7 +492,7 @@ int run_levels(pprhip_graph* g, const PushArgs& a, LevelCtx& L, pprhip_stats_t& 
         // and the seeded buffer right after its first level has consumed it.
         const bool first_of_phase = j == 0 && L.dense_run == 0;
         if (first_of_phase)
-          PPRHIP_CHECK_HIP(hipMemsetAsync(g->cdense[cc ^ 1], 0, sizeof(double) * g->n, g->stream));
+          PPRHIP_CHECK_HIP(hipMemsetAsync(g->cdense[cc ^ 1], 0, sizeof(double) * g->gr->n, g->stream));
         ktimer().begin(PPRHIP_KERNEL_DENSE_PULL, dense_level_bytes(g));
         rec0[j] = ktimer().recs.size() - 1;
         DenseLaunch dl;
@@ -508,7 +507,7 @@ int run_levels(pprhip_graph* g, const PushArgs& a, LevelCtx& L, pprhip_stats_t& 
         PPRHIP_TRY(launch_dense_level(g, a, cc, out, ds, dl));
         ktimer().end();
         if (first_of_phase)
-          PPRHIP_CHECK_HIP(hipMemsetAsync(g->cdense[cc], 0, sizeof(double) * g->n, g->stream));
+          PPRHIP_CHECK_HIP(hipMemsetAsync(g->cdense[cc], 0, sizeof(double) * g->gr->n, g->stream));
       }
       PPRHIP_TRY(fetch_small(g, &g->ctr->dhist[0], &g->h_ctr->dhist[0], sizeof(unsigned long long) * 8 + sizeof(int) * 8));
       int state = L.gs_state;
@@ -652,9 +651,9 @@ int run_levels(pprhip_graph* g, const PushArgs& a, LevelCtx& L, pprhip_stats_t& 
 int reset_query_state(pprhip_graph* g, bool clear_flags, int32_t node) {
   poll_idle(g);
   // the entries the query before could have written are cleared; the new query's passes cover n_act entries
-  const uint32_t n_live = host_of(g)->n_live;
-  g->n_act = (n_live && node >= 0 && (uint32_t)node < n_live) ? n_live : g->n;
-  const uint32_t clr = std::max(g->n_act, g->n_dirty ? g->n_dirty : g->n);
+  const uint32_t n_live = g->gr->n_live;
+  g->n_act = (n_live && node >= 0 && (uint32_t)node < n_live) ? n_live : g->gr->n;
+  const uint32_t clr = std::max(g->n_act, g->n_dirty ? g->n_dirty : g->gr->n);
   g->n_dirty = g->n_act;
   ClearList cl{};  // one launch for all of them (five fill commands before: the device idled between them)
   auto add = [&](void* p, size_t bytes) {
@@ -681,7 +680,7 @@ int reset_query_state(pprhip_graph* g, bool clear_flags, int32_t node) {
 
 // per-query workspace of a handle (the graph's own, or a batch slot's)
 int alloc_workspace(pprhip_graph* G) {
-  const uint32_t n = G->n;
+  const uint32_t n = G->gr->n;
   const size_t nd = sizeof(double) * (size_t)n;
   void** dbl[] = {(void**)&G->residue, (void**)&G->reserve, (void**)&G->est, (void**)&G->cF};
   for (void** p : dbl) PPRHIP_TRY(alloc_dev(p, nd));
@@ -765,42 +764,21 @@ void free_workspace(pprhip_graph* g) {
 }
 
 void free_batch(pprhip_graph* P);
-static int build_part_layout_device(pprhip_graph* P);
 
 // one batch workspace: slots[w] works on column w % kBatch of the interleaved arrays
 static int make_slot(pprhip_graph* P, int w) {
   pprhip_graph* S = new (std::nothrow) pprhip_graph();
   if (!S) return PPRHIP_ERR_OOM;
-  P->slots.push_back(S);
+  P->batch->slots.push_back(S);
   S->parent = P;
   S->slot_index = w % kBatch;
   S->ws_index = w;
-  S->device = P->device;
-  S->n_cus = P->n_cus;
-  S->n = P->n;
-  S->m = P->m;
-  S->n_live = P->n_live;
   if (hipStreamCreateWithFlags(&S->own_stream, hipStreamNonBlocking) != hipSuccess) {
     set_error("hipStreamCreate failed");
     return PPRHIP_ERR_HIP;
   }
+  S->gr = P->gr;  // (the handle's graph itself: a slot holds no copy of any of it)
   S->stream = P->stream;
-  S->out_rp = P->out_rp;
-  S->in_rp = P->in_rp;
-  S->out_ext = P->out_ext;
-  S->out_ci = P->out_ci;
-  S->in_ci = P->in_ci;
-  S->walk_rec = P->walk_rec;
-  S->relabeled = P->relabeled;
-  S->new2old = P->new2old;
-  S->old2new = P->old2new;
-  S->start_flags = P->start_flags;
-  S->chunk_starts = P->chunk_starts;
-  S->n_chunks = P->n_chunks;
-  S->nz_rows = P->nz_rows;
-  S->n_nz = P->n_nz;
-  S->sl = P->sl;
-  S->pn = nullptr;  // (slots run no dense levels of their own: the parent's shared sweeps serve them)
   S->tun = P->tun;
   PPRHIP_TRY(alloc_workspace(S));
   return PPRHIP_OK;
@@ -824,15 +802,16 @@ static void drop_slot(pprhip_graph* S) {
 }
 
 int ensure_workspaces(pprhip_graph* P, int count) {
-  while ((int)P->slots.size() < count) {
-    const size_t before = P->slots.size();
+  std::vector<pprhip_graph*>& slots = P->batch->slots;
+  while ((int)slots.size() < count) {
+    const size_t before = slots.size();
     const int rc = make_slot(P, (int)before);
     if (rc != PPRHIP_OK) {
       // a workspace that could not be completed (out of memory, mostly) must not stay in the list: the driver falls
       // back to the workspaces there are, and a later call tries again from a clean state
-      if (P->slots.size() > before) {
-        drop_slot(P->slots.back());
-        P->slots.pop_back();
+      if (slots.size() > before) {
+        drop_slot(slots.back());
+        slots.pop_back();
       }
       return rc;
     }
@@ -842,33 +821,33 @@ int ensure_workspaces(pprhip_graph* P, int count) {
 }
 
 // Batch slots and the interleaved dense-level arrays, created on the first batched call.
-int build_batch(pprhip_graph* P) {
-  const size_t n = P->n;
+static int build_batch(pprhip_graph* P) {
+  BatchState* B = P->batch;
+  const size_t n = P->gr->n;
   for (int i = 0; i < 2; ++i) {
-    PPRHIP_TRY(alloc_dev((void**)&P->c8[i], sizeof(double) * n * kBatch));
-    PPRHIP_CHECK_HIP(hipMemsetAsync(P->c8[i], 0, sizeof(double) * n * kBatch, P->stream));
+    PPRHIP_TRY(alloc_dev((void**)&B->c8[i], sizeof(double) * n * kBatch));
+    PPRHIP_CHECK_HIP(hipMemsetAsync(B->c8[i], 0, sizeof(double) * n * kBatch, P->stream));
   }
-  PPRHIP_TRY(alloc_dev((void**)&P->acc8, sizeof(double) * (n + 1) * kBatch));
-  PPRHIP_CHECK_HIP(hipMemsetAsync(P->acc8, 0, sizeof(double) * (n + 1) * kBatch, P->stream));
-  PPRHIP_TRY(alloc_dev((void**)&P->prep_bits, sizeof(unsigned long long) * kBatch * (n / 64 + 2)));
-  PPRHIP_CHECK_HIP(hipMemsetAsync(P->prep_bits, 0, sizeof(unsigned long long) * kBatch * (n / 64 + 2), P->stream));
-  PPRHIP_TRY(alloc_dev((void**)&P->d_slot_args, sizeof(SlotArgs) * kBatch));
-  if (hipHostMalloc((void**)&P->h_slot_args, sizeof(SlotArgs) * kBatch, hipHostMallocDefault) != hipSuccess) {
+  PPRHIP_TRY(alloc_dev((void**)&B->acc8, sizeof(double) * (n + 1) * kBatch));
+  PPRHIP_CHECK_HIP(hipMemsetAsync(B->acc8, 0, sizeof(double) * (n + 1) * kBatch, P->stream));
+  PPRHIP_TRY(alloc_dev((void**)&B->prep_bits, sizeof(unsigned long long) * kBatch * (n / 64 + 2)));
+  PPRHIP_CHECK_HIP(hipMemsetAsync(B->prep_bits, 0, sizeof(unsigned long long) * kBatch * (n / 64 + 2), P->stream));
+  PPRHIP_TRY(alloc_dev((void**)&B->d_slot_args, sizeof(SlotArgs) * kBatch));
+  if (hipHostMalloc((void**)&B->h_slot_args, sizeof(SlotArgs) * kBatch, hipHostMallocDefault) != hipSuccess) {
     set_error("hipHostMalloc failed");
     return PPRHIP_ERR_OOM;
   }
-  std::memset(P->h_slot_args, 0, sizeof(SlotArgs) * kBatch);
-  PPRHIP_TRY(alloc_dev((void**)&P->sweep_out, sizeof(unsigned long long) * kBatch));
-  if (hipHostMalloc((void**)&P->h_sweep_out, sizeof(unsigned long long) * kBatch, hipHostMallocDefault) != hipSuccess) {
+  std::memset(B->h_slot_args, 0, sizeof(SlotArgs) * kBatch);
+  PPRHIP_TRY(alloc_dev((void**)&B->sweep_out, sizeof(unsigned long long) * kBatch));
+  if (hipHostMalloc((void**)&B->h_sweep_out, sizeof(unsigned long long) * kBatch, hipHostMallocDefault) != hipSuccess) {
     set_error("hipHostMalloc failed");
     return PPRHIP_ERR_OOM;
   }
-  PPRHIP_TRY(alloc_dev((void**)&P->blk_pack8, sizeof(unsigned long long) * kBatch * kApplyBlocks8));
-  PPRHIP_TRY(alloc_dev((void**)&P->blk_dead8, sizeof(double) * kBatch * kApplyBlocks8));
-  PPRHIP_TRY(alloc_dev((void**)&P->blk_ndead8, sizeof(uint32_t) * kBatch * kApplyBlocks8));
-  P->c8cur = 0;
+  PPRHIP_TRY(alloc_dev((void**)&B->blk_pack8, sizeof(unsigned long long) * kBatch * kApplyBlocks8));
+  PPRHIP_TRY(alloc_dev((void**)&B->blk_dead8, sizeof(double) * kBatch * kApplyBlocks8));
+  PPRHIP_TRY(alloc_dev((void**)&B->blk_ndead8, sizeof(uint32_t) * kBatch * kApplyBlocks8));
   for (int s = 0; s < kBatch; ++s) {
-    P->col_owner[s] = -1;
+    B->col_owner[s] = -1;
     PPRHIP_TRY(make_slot(P, s));
   }
   PPRHIP_CHECK_HIP(hipStreamSynchronize(P->stream));
@@ -876,49 +855,42 @@ int build_batch(pprhip_graph* P) {
 }
 
 int ensure_batch(pprhip_graph* P) {
-  if (!P->slots.empty()) return PPRHIP_OK;
+  if (P->batch) return PPRHIP_OK;
+  P->batch = new (std::nothrow) BatchState();
+  if (!P->batch) return PPRHIP_ERR_OOM;
   const int rc = build_batch(P);
   if (rc != PPRHIP_OK) free_batch(P);  // e.g. out of memory half-way: leave no partial batch state behind
   return rc;
 }
 
 void free_batch(pprhip_graph* P) {
-  if (P->fetch) {
-    P->fetch->destroy();
-    delete P->fetch;
-    P->fetch = nullptr;
+  P->ktimer.destroy();  // (the batched sweeps' timer)
+  BatchState* B = P->batch;
+  if (!B) return;
+  if (B->fetch) {
+    B->fetch->destroy();
+    delete B->fetch;
   }
-  if (P->walk_stream) (void)hipStreamDestroy(P->walk_stream);
-  P->walk_stream = nullptr;
-  P->walk_stream_tried = false;
-  if (P->slot_stream) (void)hipStreamDestroy(P->slot_stream);
-  P->slot_stream = nullptr;
-  P->slot_stream_tried = false;
-  for (pprhip_graph* S : P->slots) drop_slot(S);
-  P->ktimer.destroy();
-  P->slots.clear();
-  void* ptrs[] = {P->c8[0], P->c8[1], P->acc8, P->prep_bits, P->d_slot_args, P->sweep_out, P->blk_pack8, P->blk_dead8,
-                  P->blk_ndead8};
-  if (P->h_sweep_out) (void)hipHostFree(P->h_sweep_out);
-  P->sweep_out = P->h_sweep_out = nullptr;
-  P->prep_bits = nullptr;
-  for (void* p : ptrs)
+  if (B->walk_stream) (void)hipStreamDestroy(B->walk_stream);
+  if (B->slot_stream) (void)hipStreamDestroy(B->slot_stream);
+  for (pprhip_graph* S : B->slots) drop_slot(S);
+  void* dev[] = {B->c8[0], B->c8[1], B->acc8, B->prep_bits, B->d_slot_args, B->sweep_out, B->blk_pack8, B->blk_dead8,
+                 B->blk_ndead8};
+  for (void* p : dev)
     if (p) (void)hipFree(p);
-  if (P->h_slot_args) (void)hipHostFree(P->h_slot_args);
-  P->c8[0] = P->c8[1] = P->acc8 = nullptr;
-  P->acc8_dir = 0;
-  P->d_slot_args = P->h_slot_args = nullptr;
-  P->blk_pack8 = nullptr;
-  P->blk_dead8 = nullptr;
-  P->blk_ndead8 = nullptr;
+  if (B->h_slot_args) (void)hipHostFree(B->h_slot_args);
+  if (B->h_sweep_out) (void)hipHostFree(B->h_sweep_out);
+  delete B;
+  P->batch = nullptr;
 }
 
 // sweep layout over the out-CSR for batched backward searches (the forward one is built at graph lift)
 int ensure_bwd_layout(pprhip_graph* P) {
-  if (P->start_flags_o) return PPRHIP_OK;
-  const uint32_t n = P->n;
-  const uint64_t m = P->m;
-  const std::vector<uint32_t>& rp = P->h_out_rp;
+  GraphData* D = P->gr;
+  if (D->start_flags_o) return PPRHIP_OK;
+  const uint32_t n = D->n;
+  const uint64_t m = D->m;
+  const std::vector<uint32_t>& rp = D->h_out_rp;
   const size_t n_chunks = ((size_t)m + kChunkPad - 1) / kChunkPad;
   std::vector<uint8_t> flags((n_chunks + 1) * (kChunkPad / 8), 0);
   std::vector<uint32_t> chunk_starts(n_chunks + 1, 0);
@@ -927,7 +899,7 @@ int ensure_bwd_layout(pprhip_graph* P) {
     if (rp[v + 1] == rp[v]) {
       // a row that never receives; it can still hold a contribution of its own when it is a search's target, which
       // only matters to rows that pull from it - so rows that nobody points to are left out of the sweep altogether
-      if (P->h_in_rp[v + 1] > P->h_in_rp[v]) zr.push_back((int32_t)v);
+      if (D->h_in_rp[v + 1] > D->h_in_rp[v]) zr.push_back((int32_t)v);
       continue;
     }
     nz.push_back((int32_t)v);
@@ -943,18 +915,13 @@ int ensure_bwd_layout(pprhip_graph* P) {
     if (rp[v] / kChunkPad != last / kChunkPad || (last + 1) % kChunkPad == 0 || (uint64_t)last + 1 == m)
       cross[j >> 6] |= 1ull << (j & 63);
   }
-  auto up = [&](void** dst, const void* src, size_t bytes) -> int {
-    PPRHIP_TRY(alloc_dev(dst, bytes));
-    if (bytes) PPRHIP_CHECK_HIP(hipMemcpy(*dst, src, bytes, hipMemcpyHostToDevice));
-    return PPRHIP_OK;
-  };
-  P->n_nz_o = (uint32_t)nz.size();
-  P->n_z_o = (uint32_t)zr.size();
-  PPRHIP_TRY(up((void**)&P->chunk_starts_o, chunk_starts.data(), sizeof(uint32_t) * chunk_starts.size()));
-  PPRHIP_TRY(up((void**)&P->nz_rows_o, nz.data(), sizeof(int32_t) * nz.size()));
-  PPRHIP_TRY(up((void**)&P->z_rows_o, zr.data(), sizeof(int32_t) * zr.size()));
-  PPRHIP_TRY(up((void**)&P->cross_bits_o, cross.data(), sizeof(unsigned long long) * cross.size()));
-  PPRHIP_TRY(up((void**)&P->start_flags_o, flags.data(), flags.size()));
+  D->n_nz_o = (uint32_t)nz.size();
+  D->n_z_o = (uint32_t)zr.size();
+  PPRHIP_TRY(upload((void**)&D->chunk_starts_o, chunk_starts.data(), sizeof(uint32_t) * chunk_starts.size()));
+  PPRHIP_TRY(upload((void**)&D->nz_rows_o, nz.data(), sizeof(int32_t) * nz.size()));
+  PPRHIP_TRY(upload((void**)&D->z_rows_o, zr.data(), sizeof(int32_t) * zr.size()));
+  PPRHIP_TRY(upload((void**)&D->cross_bits_o, cross.data(), sizeof(unsigned long long) * cross.size()));
+  PPRHIP_TRY(upload((void**)&D->start_flags_o, flags.data(), flags.size()));
   return PPRHIP_OK;
 }
 
@@ -1002,7 +969,7 @@ int seed_scan(pprhip_graph* g, const PushArgs& a, int kind, LevelCtx& L) {
     PPRHIP_TRY(c8.rc);
     if (g->parent) {
       if (g->sync) g->sync->c8_enter(g->slot_index);
-      L.ccur = g->parent->c8cur;
+      L.ccur = g->parent->batch->c8cur;
     }
     {
       SetupScope setup(g);
@@ -1071,7 +1038,7 @@ int launch_walk_plan(pprhip_graph* g, int variant, double alpha, double rsum, lo
   // walk to it), or - with the budget derived on the device - nothing
   g->walk_hint = omega_dev > 0.0 ? 0ull : (unsigned long long)nrw + act_n(g);
   const double bound = omega_dev > 0.0 ? omega_dev : (double)nrw;
-  if (bound + (double)g->n >= (double)(1ull << kPackShift)) {
+  if (bound + (double)g->gr->n >= (double)(1ull << kPackShift)) {
     set_error("walk budget %.0f exceeds the engine's 2^36 walk limit", bound);
     return PPRHIP_ERR_INVALID;
   }
@@ -1098,11 +1065,11 @@ int run_walk_phase(pprhip_graph* g, int variant, double alpha, double rsum, long
 int copy_out(pprhip_graph* g, const double* dev, double* host) {
   if (!host) return PPRHIP_OK;
   const double* srcp = dev;
-  if (g->relabeled) {  // back to the caller's ids: out[old] = x[old2new[old]]
+  if (g->gr->relabeled) {  // back to the caller's ids: out[old] = x[old2new[old]]
     PPRHIP_TRY(launch_permute_out(g, dev, g->cF));
     srcp = g->cF;
   }
-  PPRHIP_CHECK_HIP(hipMemcpyAsync(host, srcp, sizeof(double) * g->n, hipMemcpyDeviceToHost, g->stream));
+  PPRHIP_CHECK_HIP(hipMemcpyAsync(host, srcp, sizeof(double) * g->gr->n, hipMemcpyDeviceToHost, g->stream));
   PPRHIP_CHECK_HIP(hipStreamSynchronize(g->stream));
   return PPRHIP_OK;
 }
@@ -1116,17 +1083,17 @@ int check_graph(const pprhip_graph* g, const char* fn) {
     set_error("%s: a query stream is open on this handle (pprhip_fora_stream_close first)", fn);
     return PPRHIP_ERR_STATE;
   }
-  hipError_t e = hipSetDevice(g->device);
+  hipError_t e = hipSetDevice(g->gr->device);
   if (e != hipSuccess) {
-    set_error("%s: hipSetDevice(%d) failed: %s", fn, g->device, hipGetErrorString(e));
+    set_error("%s: hipSetDevice(%d) failed: %s", fn, g->gr->device, hipGetErrorString(e));
     return PPRHIP_ERR_NO_DEVICE;
   }
   return PPRHIP_OK;
 }
 
 int check_node(const pprhip_graph* g, int32_t v, const char* fn) {
-  if (v < 0 || (uint32_t)v >= g->n) {
-    set_error("%s: node id %d outside [0, %u)", fn, v, g->n);
+  if (v < 0 || (uint32_t)v >= g->gr->n) {
+    set_error("%s: node id %d outside [0, %u)", fn, v, g->gr->n);
     return PPRHIP_ERR_INVALID;
   }
   return PPRHIP_OK;
@@ -1173,10 +1140,8 @@ int check_conf(const pprhip_fora_conf_t* c, const char* fn, bool topk) {
   return check_positive(c->min_delta, fn, "conf->min_delta");
 }
 
-// host-side CSR facts live on the graph handle; batch slots borrow them
-const pprhip_graph* host_of(const pprhip_graph* g) { return g->parent ? g->parent : g; }
-uint32_t hdeg_out(const pprhip_graph* g, int32_t v) { return host_of(g)->h_out_rp[v + 1] - host_of(g)->h_out_rp[v]; }
-uint32_t hdeg_in(const pprhip_graph* g, int32_t v) { return host_of(g)->h_in_rp[v + 1] - host_of(g)->h_in_rp[v]; }
+uint32_t hdeg_out(const pprhip_graph* g, int32_t v) { return g->gr->h_out_rp[v + 1] - g->gr->h_out_rp[v]; }
+uint32_t hdeg_in(const pprhip_graph* g, int32_t v) { return g->gr->h_in_rp[v + 1] - g->gr->h_in_rp[v]; }
 
 // ------------------------------------------------------------------ top-k selection driver
 struct IdVal {
@@ -1228,7 +1193,7 @@ static int select_topk_passes(pprhip_graph* g, const double* x, int k, int32_t* 
                                     g->stream));
     PPRHIP_CHECK_HIP(hipStreamSynchronize(g->stream));
     st.select_passes++;
-    st.select_bytes += 8ull * g->n;
+    st.select_bytes += 8ull * g->gr->n;
     if (pass == 0) {
       for (uint32_t b = 0; b < (1u << dbits); ++b) total += hist[b];
       if (total == 0) {
@@ -1271,14 +1236,14 @@ static int select_topk_passes(pprhip_graph* g, const double* x, int k, int32_t* 
   const size_t want = prefetched ? (size_t)expected : 0;
   std::vector<char> blob(kSelHeader + sizeof(SelRec) * want);
   PPRHIP_TRY(fetch_small(g, g->sel_blob, blob.data(), blob.size()));
-  st.select_bytes += 8ull * g->n;
+  st.select_bytes += 8ull * g->gr->n;
   uint64_t cnt = 0;
   std::memcpy(&cnt, blob.data(), 8);
   std::vector<IdVal> cand;
   auto take_recs = [&](const char* p, uint64_t c) {
     cand.resize(c);
     const SelRec* r = reinterpret_cast<const SelRec*>(p);
-    for (uint64_t i = 0; i < c; ++i) cand[i] = {host_of(g)->h_new2old[r[i].id], r[i].val};
+    for (uint64_t i = 0; i < c; ++i) cand[i] = {g->gr->h_new2old[r[i].id], r[i].val};
   };
   if (prefetched && cnt == expected) {
     take_recs(blob.data() + kSelHeader, cnt);
@@ -1291,12 +1256,12 @@ static int select_topk_passes(pprhip_graph* g, const double* x, int k, int32_t* 
     take_recs(more.data(), cnt);
   } else {
     // more ties at the k-th value than the candidate buffer holds: finish on the whole vector
-    std::vector<double> all(g->n);
-    PPRHIP_CHECK_HIP(hipMemcpyAsync(all.data(), x, sizeof(double) * g->n, hipMemcpyDeviceToHost, g->stream));
+    std::vector<double> all(g->gr->n);
+    PPRHIP_CHECK_HIP(hipMemcpyAsync(all.data(), x, sizeof(double) * g->gr->n, hipMemcpyDeviceToHost, g->stream));
     PPRHIP_CHECK_HIP(hipStreamSynchronize(g->stream));
     const double lb = [&] { double d; std::memcpy(&d, &lower_bits, 8); return d; }();
-    for (uint32_t i = 0; i < g->n; ++i)
-      if (all[i] > 0.0 && (!have || all[i] >= lb)) cand.push_back({host_of(g)->h_new2old[i], all[i]});
+    for (uint32_t i = 0; i < g->gr->n; ++i)
+      if (all[i] > 0.0 && (!have || all[i] >= lb)) cand.push_back({g->gr->h_new2old[i], all[i]});
   }
   finish_select(cand, have, k, ids_out, vals_out, cap, n_out, kth_out, have_kth, st);
   return PPRHIP_OK;
@@ -1349,7 +1314,7 @@ int select_finish(pprhip_graph* g, unsigned long long seq, const double* x, int 
   if (expected > g->sel_cap || cnt != expected)  // too many share the leading bits (or the header is not what it should be)
     return select_topk_passes(g, x, k, ids_out, vals_out, cap, n_out, kth_out, have_kth, st);
   std::vector<IdVal> cand(cnt);
-  const std::vector<int32_t>& n2o = host_of(g)->h_new2old;
+  const std::vector<int32_t>& n2o = g->gr->h_new2old;
   if (cnt <= kPre) {
     const SelRec* r = reinterpret_cast<const SelRec*>(blob.data() + kSelHeader);
     for (uint64_t i = 0; i < cnt; ++i) cand[i] = {n2o[r[i].id], r[i].val};
@@ -1647,63 +1612,60 @@ int pprhip_graph_create(uint32_t n, uint64_t m, const uint32_t* out_rp, const in
   const auto t_lift1 = std::chrono::steady_clock::now();
   std::unique_ptr<pprhip_graph> g(new (std::nothrow) pprhip_graph());
   if (!g) return PPRHIP_ERR_OOM;
-  g->device = device;
-  g->n = n;
-  g->m = m;
+  GraphData* D = g->gr = new (std::nothrow) GraphData();
+  if (!D) return PPRHIP_ERR_OOM;
+  D->device = device;
+  D->n = n;
+  D->m = m;
   pprhip_tuning_default(&g->tun);
   {
     hipDeviceProp_t prop;
     if (hipGetDeviceProperties(&prop, device) == hipSuccess && prop.multiProcessorCount > 0)
-      g->n_cus = prop.multiProcessorCount;
+      D->n_cus = prop.multiProcessorCount;
   }
-  g->relabeled = H.relabeled;
-  g->h_new2old = std::move(H.new2old);
-  g->h_old2new = std::move(H.old2new);
-  g->h_out_rp = std::move(H.out_rp);
-  g->h_in_rp = std::move(H.in_rp);
-  g->h_nz_rows = std::move(H.nz_rows);
-  g->n_chunks = H.n_chunks;
-  g->n_nz = (uint32_t)g->h_nz_rows.size();
-  g->n_zin = (uint32_t)H.zin_rows.size();
-  g->n_live = g->relabeled ? g->n_nz + g->n_zin : 0u;  // (ids are the caller's without the relabeling: no bound)
-  g->n_src_live = H.n_src_live;
+  D->relabeled = H.relabeled;
+  D->h_new2old = std::move(H.new2old);
+  D->h_old2new = std::move(H.old2new);
+  D->h_out_rp = std::move(H.out_rp);
+  D->h_in_rp = std::move(H.in_rp);
+  D->h_nz_rows = std::move(H.nz_rows);
+  D->n_chunks = H.n_chunks;
+  D->n_nz = (uint32_t)D->h_nz_rows.size();
+  D->n_zin = (uint32_t)H.zin_rows.size();
+  D->n_live = D->relabeled ? D->n_nz + D->n_zin : 0u;  // (ids are the caller's without the relabeling: no bound)
+  D->n_src_live = H.n_src_live;
 
   pprhip_graph* G = g.get();
-  auto up = [&](void** dst, const void* src, size_t bytes) -> int {
-    PPRHIP_TRY(alloc_dev(dst, bytes));
-    if (bytes) PPRHIP_CHECK_HIP(hipMemcpy(*dst, src, bytes, hipMemcpyHostToDevice));
-    return PPRHIP_OK;
-  };
   int rc = PPRHIP_OK;
   auto fail = [&](int code) {
     pprhip_graph_destroy(g.release());
     return code;
   };
-  if ((rc = up((void**)&G->out_rp, G->h_out_rp.data(), sizeof(uint32_t) * ((size_t)n + 1)))) return fail(rc);
-  if ((rc = up((void**)&G->out_ci, H.out_ci.data(), sizeof(int32_t) * H.out_ci.size()))) return fail(rc);
-  if ((rc = up((void**)&G->out_ext, H.ext.data(), sizeof(unsigned long long) * (size_t)n))) return fail(rc);
-  if ((rc = up((void**)&G->in_rp, G->h_in_rp.data(), sizeof(uint32_t) * ((size_t)n + 1)))) return fail(rc);
-  if ((rc = up((void**)&G->in_ci, H.in_ci.data(), sizeof(int32_t) * H.in_ci.size()))) return fail(rc);
-  if ((rc = up((void**)&G->new2old, G->h_new2old.data(), sizeof(int32_t) * (size_t)n))) return fail(rc);
-  if ((rc = up((void**)&G->old2new, G->h_old2new.data(), sizeof(int32_t) * (size_t)n))) return fail(rc);
-  if ((rc = up((void**)&G->start_flags, H.flags.data(), H.flags.size()))) return fail(rc);
-  if ((rc = up((void**)&G->chunk_starts, H.chunk_starts.data(), sizeof(uint32_t) * H.chunk_starts.size()))) return fail(rc);
-  if ((rc = up((void**)&G->nz_rows, G->h_nz_rows.data(), sizeof(int32_t) * G->h_nz_rows.size()))) return fail(rc);
-  if ((rc = upload_sliced_layout(G, H))) return fail(rc);
-  if ((rc = upload_panel_layout(G, H))) return fail(rc);
+  if ((rc = upload((void**)&D->out_rp, D->h_out_rp.data(), sizeof(uint32_t) * ((size_t)n + 1)))) return fail(rc);
+  if ((rc = upload((void**)&D->out_ci, H.out_ci.data(), sizeof(int32_t) * H.out_ci.size()))) return fail(rc);
+  if ((rc = upload((void**)&D->out_ext, H.ext.data(), sizeof(unsigned long long) * (size_t)n))) return fail(rc);
+  if ((rc = upload((void**)&D->in_rp, D->h_in_rp.data(), sizeof(uint32_t) * ((size_t)n + 1)))) return fail(rc);
+  if ((rc = upload((void**)&D->in_ci, H.in_ci.data(), sizeof(int32_t) * H.in_ci.size()))) return fail(rc);
+  if ((rc = upload((void**)&D->new2old, D->h_new2old.data(), sizeof(int32_t) * (size_t)n))) return fail(rc);
+  if ((rc = upload((void**)&D->old2new, D->h_old2new.data(), sizeof(int32_t) * (size_t)n))) return fail(rc);
+  if ((rc = upload((void**)&D->start_flags, H.flags.data(), H.flags.size()))) return fail(rc);
+  if ((rc = upload((void**)&D->chunk_starts, H.chunk_starts.data(), sizeof(uint32_t) * H.chunk_starts.size()))) return fail(rc);
+  if ((rc = upload((void**)&D->nz_rows, D->h_nz_rows.data(), sizeof(int32_t) * D->h_nz_rows.size()))) return fail(rc);
+  if ((rc = upload_sliced_layout(D, H))) return fail(rc);
+  if ((rc = upload_panel_layout(D, H))) return fail(rc);
   if (hipStreamCreateWithFlags(&G->stream, hipStreamNonBlocking) != hipSuccess) {
     set_error("hipStreamCreate failed");
     return fail(PPRHIP_ERR_HIP);
   }
-  if ((rc = up((void**)&G->zin_rows, H.zin_rows.data(), sizeof(int32_t) * H.zin_rows.size()))) return fail(rc);
-  if ((rc = up((void**)&G->cross_bits, H.cross.data(), sizeof(unsigned long long) * H.cross.size()))) return fail(rc);
+  if ((rc = upload((void**)&D->zin_rows, H.zin_rows.data(), sizeof(int32_t) * H.zin_rows.size()))) return fail(rc);
+  if ((rc = upload((void**)&D->cross_bits, H.cross.data(), sizeof(unsigned long long) * H.cross.size()))) return fail(rc);
   if (hook_env("PPRHIP_LIFT_DEBUG")) {
     const auto t_up = std::chrono::steady_clock::now();
     fprintf(stderr, "[pprhip lift] host half %.1f ms, uploads %.1f ms\n",
             std::chrono::duration<double, std::milli>(t_lift1 - t_lift0).count(),
             std::chrono::duration<double, std::milli>(t_up - t_lift1).count());
   }
-  if ((rc = alloc_dev((void**)&G->walk_rec, sizeof(uint4) * (size_t)m))) return fail(rc);
+  if ((rc = alloc_dev((void**)&D->walk_rec, sizeof(uint4) * (size_t)m))) return fail(rc);
   if ((rc = launch_build_walk_rec(G))) return fail(rc);
   if ((rc = alloc_workspace(G))) return fail(rc);
   if (hipStreamSynchronize(G->stream) != hipSuccess) {
@@ -1712,6 +1674,28 @@ int pprhip_graph_create(uint32_t n, uint64_t m, const uint32_t* out_rp, const in
   }
   *graph_out = g.release();
   return PPRHIP_OK;
+}
+
+// the lifted graph and every layout built from it (pprhip_graph_destroy, after everything that uses it)
+static void free_graph_data(GraphData* D) {
+  void* ptrs[] = {D->walk_rec, D->out_ext, D->out_rp, D->out_ci, D->in_rp, D->in_ci, D->new2old, D->old2new, D->start_flags,
+                  D->chunk_starts, D->nz_rows, D->zin_rows, D->cross_bits, D->start_flags_o, D->chunk_starts_o,
+                  D->nz_rows_o, D->z_rows_o, D->cross_bits_o};
+  for (void* p : ptrs)
+    if (p) (void)hipFree(p);
+  if (D->sl) {
+    void* sp[] = {D->sl->ci, D->sl->flags, D->sl->chunk_starts, D->sl->seg_row};
+    for (void* p : sp)
+      if (p) (void)hipFree(p);
+    delete D->sl;
+  }
+  if (D->pn) {
+    void* pp[] = {D->pn->src, D->pn->rloc, D->pn->items, D->pn->panels};
+    for (void* p : pp)
+      if (p) (void)hipFree(p);
+    delete D->pn;
+  }
+  delete D;
 }
 
 static void free_all_pair(pprhip_graph* g) {
@@ -1741,32 +1725,14 @@ int pprhip_graph_release(pprhip_graph_t* g, unsigned what) {
 void pprhip_graph_destroy(pprhip_graph_t* g) {
   if (!g) return;
   if (g->stream_obj) stream_detach(g->stream_obj);  // (its driver thread uses the handle; the stream object stays its owner's)
-  (void)hipSetDevice(g->device);
+  (void)hipSetDevice(g->gr->device);
   if (g->stream) (void)hipStreamSynchronize(g->stream);
   free_batch(g);
-  void* ptrs[] = {g->walk_rec, g->out_ext, g->out_rp, g->out_ci, g->in_rp, g->in_ci, g->new2old, g->old2new, g->start_flags,
-                  g->chunk_starts, g->nz_rows, g->zin_rows, g->cross_bits, g->start_flags_o, g->chunk_starts_o,
-                  g->nz_rows_o, g->z_rows_o, g->cross_bits_o};
-  for (void* p : ptrs)
-    if (p) (void)hipFree(p);
   free_all_pair(g);
-  if (g->sl) {
-    void* sp[] = {g->sl->ci, g->sl->flags, g->sl->chunk_starts, g->sl->seg_row};
-    for (void* p : sp)
-      if (p) (void)hipFree(p);
-    delete g->sl;
-    g->sl = nullptr;
-  }
-  if (g->pn) {
-    void* pp[] = {g->pn->src, g->pn->rloc, g->pn->items, g->pn->panels};
-    for (void* p : pp)
-      if (p) (void)hipFree(p);
-    delete g->pn;
-    g->pn = nullptr;
-  }
   seed_free(g);
   free_workspace(g);
   if (g->stream) (void)hipStreamDestroy(g->stream);
+  free_graph_data(g->gr);
   delete g;
 }
 
@@ -1775,7 +1741,7 @@ int pprhip_device_memory(const pprhip_graph_t* g, uint64_t* free_bytes, uint64_t
     set_error("pprhip_device_memory: null handle");
     return PPRHIP_ERR_INVALID;
   }
-  PPRHIP_CHECK_HIP(hipSetDevice(g->device));
+  PPRHIP_CHECK_HIP(hipSetDevice(g->gr->device));
   size_t f = 0, t = 0;
   PPRHIP_CHECK_HIP(hipMemGetInfo(&f, &t));
   if (free_bytes) *free_bytes = (uint64_t)f;
@@ -1788,9 +1754,9 @@ int pprhip_graph_info(const pprhip_graph_t* g, uint32_t* n, uint64_t* m, int* de
     set_error("pprhip_graph_info: null graph handle");
     return PPRHIP_ERR_INVALID;
   }
-  if (n) *n = g->n;
-  if (m) *m = g->m;
-  if (device) *device = g->device;
+  if (n) *n = g->gr->n;
+  if (m) *m = g->gr->m;
+  if (device) *device = g->gr->device;
   return PPRHIP_OK;
 }
 
@@ -1853,7 +1819,7 @@ int pprhip_forward_push(pprhip_graph_t* g, int32_t src, double alpha, double rma
   PPRHIP_TRY(check_threshold(rmax, "pprhip_forward_push", "rmax"));
   PPRHIP_TRY(check_graph(g, "pprhip_forward_push"));
   PPRHIP_TRY(check_node(g, src, "pprhip_forward_push"));
-  src = g->h_old2new[src];  // internal (degree-sorted) id
+  src = g->gr->h_old2new[src];  // internal (degree-sorted) id
   pprhip_stats_t st;
   std::memset(&st, 0, sizeof st);
   g->topk_active = false;
@@ -1889,7 +1855,7 @@ int pprhip_fwdpush_topk_reset(pprhip_graph_t* g, int32_t src, double alpha) {
   PPRHIP_TRY(check_alpha(alpha, "pprhip_fwdpush_topk_reset"));
   PPRHIP_TRY(check_graph(g, "pprhip_fwdpush_topk_reset"));
   PPRHIP_TRY(check_node(g, src, "pprhip_fwdpush_topk_reset"));
-  return topk_session_reset(g, g->h_old2new[src], nullptr, alpha, 1.0);
+  return topk_session_reset(g, g->gr->h_old2new[src], nullptr, alpha, 1.0);
 }
 
 int pprhip_fwdpush_topk_round(pprhip_graph_t* g, double min_rmax, double rmax, double* rsum_out,
@@ -1957,7 +1923,7 @@ int pprhip_random_walk_batch(pprhip_graph_t* g, const int32_t* starts, const uin
     return code;
   };
   std::vector<int32_t> mapped(count);
-  for (uint64_t i = 0; i < count; ++i) mapped[i] = g->h_old2new[starts[i]];
+  for (uint64_t i = 0; i < count; ++i) mapped[i] = g->gr->h_old2new[starts[i]];
   if (hipMemcpy(d_s, mapped.data(), sizeof(int32_t) * count, hipMemcpyHostToDevice) != hipSuccess ||
       hipMemcpyAsync(d_i, walk_idx, sizeof(uint64_t) * count, hipMemcpyHostToDevice, g->stream) != hipSuccess) {
     set_error("pprhip_random_walk_batch: upload failed");
@@ -1972,7 +1938,7 @@ int pprhip_random_walk_batch(pprhip_graph_t* g, const int32_t* starts, const uin
     set_error("pprhip_random_walk_batch: download failed: %s", hipGetErrorString(hipGetLastError()));
     return done(PPRHIP_ERR_HIP);
   }
-  for (uint64_t i = 0; i < count; ++i) terminals_out[i] = g->h_new2old[terminals_out[i]];
+  for (uint64_t i = 0; i < count; ++i) terminals_out[i] = g->gr->h_new2old[terminals_out[i]];
   return done(PPRHIP_OK);
 }
 
@@ -2004,7 +1970,7 @@ int pprhip_monte_carlo(pprhip_graph_t* g, int32_t src, double eps, const pprhip_
   PPRHIP_TRY(check_conf(conf, "pprhip_monte_carlo", false));
   PPRHIP_TRY(check_graph(g, "pprhip_monte_carlo"));
   PPRHIP_TRY(check_node(g, src, "pprhip_monte_carlo"));
-  src = g->h_old2new[src];  // internal (degree-sorted) id
+  src = g->gr->h_old2new[src];  // internal (degree-sorted) id
   if (!conf || !(eps > 0.0)) {
     set_error("pprhip_monte_carlo: bad arguments");
     return PPRHIP_ERR_INVALID;
@@ -2060,7 +2026,7 @@ int pprhip_backward_push(pprhip_graph_t* g, int32_t target, double alpha, double
   PPRHIP_TRY(check_threshold(rmax, "pprhip_backward_push", "rmax"));
   PPRHIP_TRY(check_graph(g, "pprhip_backward_push"));
   PPRHIP_TRY(check_node(g, target, "pprhip_backward_push"));
-  target = g->h_old2new[target];  // internal (degree-sorted) id
+  target = g->gr->h_old2new[target];  // internal (degree-sorted) id
   pprhip_stats_t st;
   std::memset(&st, 0, sizeof st);
   g->topk_active = false;
@@ -2087,7 +2053,7 @@ int pprhip_power_method(pprhip_graph_t* g, int32_t src, double alpha, int iters,
   }
   PPRHIP_TRY(check_graph(g, "pprhip_power_method"));
   PPRHIP_TRY(check_node(g, src, "pprhip_power_method"));
-  src = g->h_old2new[src];  // internal (degree-sorted) id
+  src = g->gr->h_old2new[src];  // internal (degree-sorted) id
   pprhip_stats_t st;
   std::memset(&st, 0, sizeof st);
   g->topk_active = false;
@@ -2098,7 +2064,7 @@ int pprhip_power_method(pprhip_graph_t* g, int32_t src, double alpha, int iters,
     PPRHIP_TRY(ensure_panel_part(g));
     LevelCtx L;
     PushArgs a{alpha, 0.0, 0.0, src, kPower};
-    PPRHIP_CHECK_HIP(hipMemsetAsync(g->cdense[L.ccur], 0, sizeof(double) * g->n, g->stream));
+    PPRHIP_CHECK_HIP(hipMemsetAsync(g->cdense[L.ccur], 0, sizeof(double) * g->gr->n, g->stream));
     PPRHIP_TRY(launch_set_f64(g, g->reserve, (uint32_t)src, 1.0 * alpha));
     const uint32_t d = hdeg_out(g, src);
     const double remain = 1.0 * (1 - alpha);
@@ -2108,11 +2074,11 @@ int pprhip_power_method(pprhip_graph_t* g, int32_t src, double alpha, int iters,
       PPRHIP_TRY(launch_set_f64(g, g->cdense[L.ccur], (uint32_t)src, remain / (double)d));
     for (int it = 1; it < iters; ++it) {
       const int out = L.pslot ^ 1;
-      if (it == 1) PPRHIP_CHECK_HIP(hipMemsetAsync(g->cdense[L.ccur ^ 1], 0, sizeof(double) * g->n, g->stream));
+      if (it == 1) PPRHIP_CHECK_HIP(hipMemsetAsync(g->cdense[L.ccur ^ 1], 0, sizeof(double) * g->gr->n, g->stream));
       ktimer().begin(PPRHIP_KERNEL_DENSE_PULL, dense_level_bytes(g));
       PPRHIP_TRY(launch_dense_level(g, a, L.ccur, out, L.dslot));
       ktimer().end();
-      if (it == 1) PPRHIP_CHECK_HIP(hipMemsetAsync(g->cdense[L.ccur], 0, sizeof(double) * g->n, g->stream));
+      if (it == 1) PPRHIP_CHECK_HIP(hipMemsetAsync(g->cdense[L.ccur], 0, sizeof(double) * g->gr->n, g->stream));
       L.ccur ^= 1;
       L.dslot ^= 1;
       L.pslot = out;
@@ -2139,15 +2105,15 @@ int pprhip_hook_time_sweep_edges(pprhip_graph_t* g, int block, int n_blocks, int
     set_error("pprhip_hook_time_sweep_edges: bad arguments");
     return PPRHIP_ERR_INVALID;
   }
-  PPRHIP_CHECK_HIP(hipSetDevice(g->device));
+  PPRHIP_CHECK_HIP(hipSetDevice(g->gr->device));
   PPRHIP_TRY(ensure_batch(g));
-  GsBlock B{0u, g->n_nz, 0ull, (unsigned long long)g->m};
+  GsBlock B{0u, g->gr->n_nz, 0ull, (unsigned long long)g->gr->m};
   if (n_blocks > 1) {
-    pprhip_tuning_t keep = g->slots[0]->tun;
-    g->slots[0]->tun.gs_blocks = n_blocks;
+    pprhip_tuning_t keep = g->batch->slots[0]->tun;
+    g->batch->slots[0]->tun.gs_blocks = n_blocks;
     int nb = 1;
-    const GsBlock* blocks = gs_blocks_of(g->slots[0], &nb);
-    g->slots[0]->tun = keep;
+    const GsBlock* blocks = gs_blocks_of(g->batch->slots[0], &nb);
+    g->batch->slots[0]->tun = keep;
     if (!blocks || block < 0 || block >= nb) {
       set_error("pprhip_hook_time_sweep_edges: no block %d of %d", block, n_blocks);
       return PPRHIP_ERR_INVALID;
@@ -2168,7 +2134,7 @@ int pprhip_hook_time_sweep_edges(pprhip_graph_t* g, int block, int n_blocks, int
   (void)hipEventDestroy(e1);
   *us_out = (double)ms * 1e3 / reps;
   // (the row-major kernel adds into acc8 with atomics where rows cross chunks: start the next sweep clean)
-  PPRHIP_CHECK_HIP(hipMemsetAsync(g->acc8, 0, sizeof(double) * ((size_t)g->n + 1) * kBatch, g->stream));
+  PPRHIP_CHECK_HIP(hipMemsetAsync(g->batch->acc8, 0, sizeof(double) * ((size_t)g->gr->n + 1) * kBatch, g->stream));
   PPRHIP_CHECK_HIP(hipStreamSynchronize(g->stream));
   return PPRHIP_OK;
 }

@@ -323,14 +323,17 @@ namespace pprhip {
 namespace detail {
 struct FetchPipe;
 }
-}  // namespace pprhip
 
-struct pprhip_graph {
+// The lifted graph (pprhip_graph_create): the CSR pair, the internal vertex order and the sweep layouts derived from
+// them.  One per handle; the handle and its batch slots reach it through the same pointer (pprhip_graph::gr).  Only the
+// lift fills it, plus the builders of the layouts made on first use (gs_blocks_of, sliced_windows_of under a lock,
+// ensure_bwd_layout before a batched call's workers start): during a batched call it is read-only.  free_graph_data
+// frees it, last of what a handle holds.
+struct GraphData {
   int device = 0;
   int n_cus = 256;  // compute units of the device (persistent-kernel grid sizing)
   uint32_t n = 0;
   uint64_t m = 0;
-  hipStream_t stream = nullptr;
   // CSR pair in HBM: uint32 row pointers, int32 column indices
   uint32_t *out_rp = nullptr, *in_rp = nullptr;
   unsigned long long* out_ext = nullptr;  // per vertex: out row begin | out-degree << 32 (one gather instead of two)
@@ -348,51 +351,97 @@ struct pprhip_graph {
   uint32_t n_chunks = 0;
   int32_t* nz_rows = nullptr;  // rows with in-degree > 0, ascending
   uint32_t n_nz = 0;
-  std::vector<int32_t> h_nz_rows;         // host copy (block boundaries of the Gauss-Seidel sweeps)
-  std::vector<pprhip::GsBlock> gs_plan;   // blocks of the forward sweep for gs_plan_B blocks (built on demand)
+  std::vector<int32_t> h_nz_rows;  // host copy (block boundaries of the Gauss-Seidel sweeps)
+  int32_t* zin_rows = nullptr;     // rows without in-edges
+  uint32_t n_zin = 0;
+  unsigned long long* cross_bits = nullptr;  // per row ordinal (non-empty rows first): row spans two 512-edge chunks
+  uint32_t n_src_live = 0;  // nodes with out-edges: the contributions a forward sweep can gather
+  // Internal ids [0, n_live) are the nodes with at least one edge (the vertex order puts nodes with in-edges first, then
+  // the others by out-degree: isolated nodes - 43 % of an R-MAT 22 - come last).  A query whose source / target is
+  // one of them can only ever hold residue, reserve or walk terminals below n_live, so the passes over "all nodes"
+  // (seeding, sums, walk plan, selection, resets) run over n_act = n_live entries; a query on an isolated node uses n.
+  uint32_t n_live = 0;
+  std::vector<GsBlock> gs_plan;  // blocks of the forward sweep for gs_plan_B blocks (built on demand)
   int gs_plan_B = 0;
-  double* acc_nz = nullptr;  // per non-empty row: sum of this level's contributions
-  pprhip::SlicedLayout* sl = nullptr;
-  pprhip::PanelLayout* pn = nullptr;   // row-panel copy of the in-CSR (shared with the batch slots), or none
-  double* pn_part = nullptr;           // [pn->n_part] the items' sums of this handle's sweep (first forward dense level)
-  uint32_t* pn_ctr = nullptr;          // [kPanelQueues] item queues of a level's edge launches (one per Gauss-Seidel block); k_dense_reduce and reset_query_state zero them  // single-query sweep layout (owned by the lifted graph, borrowed by slots)
-  // batched queries: kBatch workspaces ("slots") borrow this handle's CSR and stream; their dense
-  // levels run as one sweep over the interleaved contribution array c8[v][slot]
+  SlicedLayout* sl = nullptr;  // sliced copy of the in-CSR, or none
+  PanelLayout* pn = nullptr;   // row-panel copy of the in-CSR, or none
+  // the same sweep layout over the out-CSR (backward search: a row pulls from its out-neighbours), built on the first
+  // batched backward call
+  uint8_t* start_flags_o = nullptr;
+  uint32_t* chunk_starts_o = nullptr;
+  int32_t *nz_rows_o = nullptr, *z_rows_o = nullptr;  // rows with / without out-edges
+  uint32_t n_nz_o = 0, n_z_o = 0;
+  unsigned long long* cross_bits_o = nullptr;
+};
+
+// The handle's batched-call state: the workspaces ("slots") of its batched queries and the arrays their dense levels
+// share - one sweep over the interleaved contribution array c8[v][column] serves every slot waiting at a dense level.
+// Built by ensure_batch on the first batched call, destroyed whole by free_batch.
+struct BatchState {
+  std::vector<pprhip_graph*> slots;
+  double* c8[2] = {nullptr, nullptr};
+  int c8cur = 0;
+  double* acc8 = nullptr;  // [row ordinal][kBatch] row sums
+  int acc8_dir = 0;        // layout the row sums were last written in (0 forward, 1 backward)
+  unsigned long long* prep_bits = nullptr;  // [kBatch][tiles]: rows holding a contribution after the last sweep
+  SlotArgs* d_slot_args = nullptr;
+  SlotArgs* h_slot_args = nullptr;  // pinned
+  unsigned long long* sweep_out = nullptr;    // [kBatch] frontier counters a sweep produced
+  unsigned long long* h_sweep_out = nullptr;  // pinned
+  unsigned long long* blk_pack8 = nullptr;  // [kBatch][kApplyBlocks8]
+  double* blk_dead8 = nullptr;
+  uint32_t* blk_ndead8 = nullptr;
+  // Workspace pool (fora.cpp: SlotDriver; more workspaces than columns of c8): who holds each column (-1: nobody; an
+  // index into `slots`)
+  int col_owner[kBatch];
+  // Sequential batch driver (SlotDriver): the one stream all slots work on beside the sweeps (sparse levels, seeds,
+  // sums, selections), and a stream for the slots' walk phases while sweeps go on (make_side_stream, both)
+  hipStream_t slot_stream = nullptr;
+  bool slot_stream_tried = false;
+  hipStream_t walk_stream = nullptr;
+  bool walk_stream_tried = false;
+  // called by a slot's small read-backs while they wait (fetch_end): the driver looks after the sweep in flight
+  void (*idle_hook)(void*) = nullptr;
+  void* idle_arg = nullptr;
+  int in_c8 = 0;  // C8Scopes open on the slots (poll_idle: the hook stays out while a slot borrows the sweeps' stream)
+  detail::FetchPipe* fetch = nullptr;  // delivery of batched queries' vectors to host memory (engine_internal.hpp)
+};
+
+}  // namespace pprhip
+
+// A graph handle or one of its batch slots: the per-query workspace, the stream it runs on, and the lifted graph it
+// borrows.
+struct pprhip_graph {
+  pprhip::GraphData* gr = nullptr;      // the lifted graph: the handle's own, a slot's parent's
+  pprhip::BatchState* batch = nullptr;  // the handle's batched-call state (null until the first batched call and on slots)
+  hipStream_t stream = nullptr;
+  // single-query dense levels (not on a slot: its dense levels run in the parent's batched sweeps)
+  double* acc_nz = nullptr;    // per non-empty row: sum of this level's contributions
+  double* pn_part = nullptr;   // [gr->pn->n_part] the items' sums of this handle's panel sweep (first forward dense level)
+  uint32_t* pn_ctr = nullptr;  // [kPanelQueues] item queues of a level's edge launches (one per Gauss-Seidel block); k_dense_reduce and reset_query_state zero them
+  // batched queries: kBatch workspaces ("slots") borrow this handle's graph and stream; their dense levels run as one
+  // sweep over the interleaved contribution array BatchState::c8[v][slot]
   pprhip_graph* parent = nullptr;  // set on a slot
   int slot_index = -1;
   pprhip::BatchSync* sync = nullptr;  // set on a slot while a batched call is running
   hipStream_t own_stream = nullptr;   // slot: the stream its worker thread uses
-  // Sequential batch driver (fora.cpp: SlotDriver): graph: the one stream all slots work on beside the sweeps
-  // (sparse levels, seeds, sums, selections; make_side_stream); slot: its c8-touching kernels go to the parent's stream
-  // (engine_internal.hpp: C8Scope) and the events that order them
-  hipStream_t slot_stream = nullptr;
-  bool slot_stream_tried = false;
+  // Sequential batch driver (fora.cpp: SlotDriver): a slot's c8-touching kernels go to the parent's stream
+  // (engine_internal.hpp: C8Scope), and the events that order them
   bool c8_via_parent = false;
   bool c8_settled = false;  // nothing of this slot is pending on its stream: C8Scope need not wait for that stream
   hipEvent_t c8_ev[2] = {nullptr, nullptr};
   hipEvent_t col_ev = nullptr;  // recorded on the slot's stream when it began to wait for its column
-  // Workspace pool (SlotDriver): more workspaces than columns of c8.  graph: who holds each column (-1: nobody; an
-  // index into `slots`); slot: its own index there; pooled: it has to win a free column - which becomes its
-  // slot_index - before it prepares a dense level, and the driver takes the column back when it leaves the sweeps
-  // (not pooled: column ws_index % kBatch is its own, as in the threaded driver)
-  int col_owner[pprhip::kBatch];
+  // Workspace pool (SlotDriver): the slot's index in BatchState::slots; pooled: it has to win a free column - which
+  // becomes its slot_index - before it prepares a dense level, and the driver takes the column back when it leaves the
+  // sweeps (not pooled: column ws_index % kBatch is its own, as in the threaded driver)
   int ws_index = -1;
   bool pooled = false;
   bool has_col = false;
-  // graph: called by a slot's small read-backs while they wait (fetch_end): the driver looks after the sweep in flight
-  void (*idle_hook)(void*) = nullptr;
-  int in_c8 = 0;  // C8Scopes open on this handle's slots (poll_idle: the hook stays out while a slot borrows the sweeps' stream)
-  void* idle_arg = nullptr;
-  // graph: a stream that runs beside the compute stream (make_side_stream) for the slots' walk phases while sweeps
-  // go on (sequential batch driver); slot: the events around its walk phase on that stream
   uint32_t walk_waves = 0;  // waves per CU of the next walk kernels (0: the default)
-  hipStream_t walk_stream = nullptr;
-  bool walk_stream_tried = false;
   bool stream_open = false;  // a query stream's driver thread owns the handle (fora.cpp: pprhip_stream)
   void* stream_obj = nullptr;  // ... that stream (pprhip_graph_destroy closes a stream its owner forgot)
-  hipEvent_t walk_ev[3] = {nullptr, nullptr, nullptr};
-  pprhip::KernelTimer ktimer;         // slot: its worker's kernel-class timer; graph: the sweeps' timer
-  std::vector<pprhip_graph*> slots;
+  hipEvent_t walk_ev[3] = {nullptr, nullptr, nullptr};  // slot: the events around its walk phase on the walk stream
+  pprhip::KernelTimer ktimer;  // kernel-class timer of this workspace's work (a slot's worker; a handle's batched sweeps)
   // All-Pair: in-edge records {source, its out-degree} (8 B per edge, built on first use), and tier 2's dense
   // workspaces of apbs_blocks workgroups (16n bytes + lists each, all-zero between searches), kept between calls
   void* in_rec = nullptr;
@@ -403,37 +452,8 @@ struct pprhip_graph {
   char* apbs_xl_ws = nullptr;  // a few workspaces whose lists hold every node, for the searches that outgrow the others
   uint32_t apbs_xl_blocks = 0, apbs_xl_cap_t = 0, apbs_xl_cap_f = 0;
   uint32_t apbs_blocks = 0, apbs_cap_t = 0, apbs_cap_f = 0, apbs_chunk = 0;
-  pprhip::detail::FetchPipe* fetch = nullptr;  // delivery of batched queries' vectors to host memory (engine_internal.hpp)
-  double* c8[2] = {nullptr, nullptr};
-  int c8cur = 0;
-  double* acc8 = nullptr;      // [row ordinal][kBatch] row sums
-  int acc8_dir = 0;            // layout the row sums were last written in (0 forward, 1 backward)
-  int32_t* zin_rows = nullptr;  // rows without in-edges
-  // the same sweep layout over the out-CSR (backward search: a row pulls from its out-neighbours), built on
-  // the first batched backward call
-  uint8_t* start_flags_o = nullptr;
-  uint32_t* chunk_starts_o = nullptr;
-  int32_t *nz_rows_o = nullptr, *z_rows_o = nullptr;  // rows with / without out-edges
-  uint32_t n_nz_o = 0, n_z_o = 0;
-  unsigned long long* cross_bits_o = nullptr;
-  unsigned long long* cross_bits = nullptr;  // per row ordinal (non-empty rows first): row spans two 512-edge chunks
-  unsigned long long* prep_bits = nullptr;   // [kBatch][tiles]: rows holding a contribution after the last sweep
-  uint32_t n_zin = 0;
-  uint32_t n_src_live = 0;  // nodes with out-edges: the contributions a forward sweep can gather
-  // Internal ids [0, n_live) are the nodes with at least one edge (the vertex order puts nodes with in-edges first, then
-  // the others by out-degree: isolated nodes - 43 % of an R-MAT 22 - come last).  A query whose source / target is
-  // one of them can only ever hold residue, reserve or walk terminals below n_live, so the passes over "all nodes"
-  // (seeding, sums, walk plan, selection, resets) run over n_act = n_live entries; a query on an isolated node uses n.
-  uint32_t n_live = 0;
-  uint32_t n_act = 0;    // scan bound of the query this workspace is running (0: n)
+  uint32_t n_act = 0;    // scan bound of the query this workspace is running (0: n; GraphData::n_live)
   uint32_t n_dirty = 0;  // ... of the query before it (what the reset has to clear)
-  pprhip::SlotArgs* d_slot_args = nullptr;
-  pprhip::SlotArgs* h_slot_args = nullptr;  // pinned
-  unsigned long long* sweep_out = nullptr;    // [kBatch] frontier counters a sweep produced
-  unsigned long long* h_sweep_out = nullptr;  // pinned
-  unsigned long long* blk_pack8 = nullptr;  // [kBatch][kApplyBlocks8]
-  double* blk_dead8 = nullptr;
-  uint32_t* blk_ndead8 = nullptr;
   // per-query state
   double *residue = nullptr, *reserve = nullptr, *est = nullptr;
   double* cdense[2] = {nullptr, nullptr};
@@ -526,7 +546,7 @@ namespace detail {
 const EdgeWindows* sliced_windows_of(pprhip_graph* g, const GsBlock* blocks, int nb);
 }
 constexpr uint32_t kApplyBlocks8 = 2048;  // workgroups of the batched apply kernel (per-slot partials each)
-// slot arguments already staged in parent->h_slot_args; blocks: Gauss-Seidel blocks (nullptr / 1: one launch)
+// slot arguments already staged in parent->batch->h_slot_args; blocks: Gauss-Seidel blocks (nullptr / 1: one launch)
 int launch_dense_level_b8(pprhip_graph* parent, bool backward, const pprhip::GsBlock* blocks = nullptr, int n_blocks = 1);
 #ifdef PPRHIP_TEST_HOOKS
 int launch_sweep_edges_only(pprhip_graph* parent, const pprhip::GsBlock& B);
@@ -540,7 +560,7 @@ int launch_seed_dense(pprhip_graph* g, const PushArgs& a, int seed_kind, int cbu
 int launch_sum(pprhip_graph* g, const double* x, uint32_t n);  // result -> ctr->sum_out
 int launch_sum_partial(pprhip_graph* g, const double* x, uint32_t n);  // partial sums -> g->partial, for the plan that follows
 bool old_small_kernels();
-inline uint32_t act_n(const pprhip_graph* g) { return g->n_act ? g->n_act : g->n; }  // entries a query's passes cover
+inline uint32_t act_n(const pprhip_graph* g) { return g->n_act ? g->n_act : g->gr->n; }  // entries a query's passes cover
 int launch_set_f64(pprhip_graph* g, double* p, uint32_t idx, double value);
 int launch_permute_out(pprhip_graph* g, const double* x, double* out);  // out[old] = x[old2new[old]]
 // seed sets (g->seeds): the query's start from p (residue, dead-end reserves, landing weights, and the frontier list

@@ -126,15 +126,16 @@ struct C8Scope {
   int leave();
 };
 
-// A slot of the sequential batch driver gives the driver a look at the sweep in flight (pprhip_graph::idle_hook) -
+// A slot of the sequential batch driver gives the driver a look at the sweep in flight (BatchState::idle_hook) -
 // called between the launches of the slot's longer sequences, which keep the host busy for 100 us and more.
 // The hook runs a whole driver turn (collect the sweep, other workspaces' deferred steps, the next sweep) on the
 // caller's thread, so it must never be entered while a slot has its stream swapped for the sweeps' (C8Scope): what the
 // turn queues for that slot would land on the wrong stream.  No caller does; the counter makes that an invariant the
 // code checks instead of one it relies on (SlotDriver::on_idle also refuses to nest, and keeps the sweeps' own timer).
 inline void poll_idle(pprhip_graph* g) {
-  pprhip_graph* const H = g->parent;
-  if (H && H->idle_hook && H->in_c8 == 0) H->idle_hook(H->idle_arg);
+  if (!g->parent) return;
+  const BatchState* bs = g->parent->batch;
+  if (bs->idle_hook && bs->in_c8 == 0) bs->idle_hook(bs->idle_arg);
 }
 
 struct SetupScope {
@@ -281,7 +282,6 @@ int check_alpha(double alpha, const char* fn, const char* name = "alpha");
 int check_positive(double v, const char* fn, const char* name);
 int check_threshold(double v, const char* fn, const char* name);
 int check_conf(const pprhip_fora_conf_t* c, const char* fn, bool topk);
-const pprhip_graph* host_of(const pprhip_graph* g);
 uint32_t hdeg_out(const pprhip_graph* g, int32_t v);
 uint32_t hdeg_in(const pprhip_graph* g, int32_t v);
 int select_topk(pprhip_graph* g, const double* x, int k, int32_t* ids_out, double* vals_out, int cap, int* n_out,

@@ -126,9 +126,9 @@ static int fora_begin_at(ForaRun& r, pprhip_graph* g, int32_t src_internal, int3
     // rsum <= rmax * m and the walks cost at most c_walk * omega * (1 - alpha) * rmax * m; while that bound still
     // covers prior_levels dense levels the turn would be repeated at half the threshold anyway (twin: same rule).
     const pprhip_tuning_t& t = g->tun;
-    double walk_bound = t.c_walk_ns * r.omega_local * (1 - r.alpha) * r.rmax_local * (double)g->m;
+    double walk_bound = t.c_walk_ns * r.omega_local * (1 - r.alpha) * r.rmax_local * (double)g->gr->m;
     const double push_est =
-        (double)t.prior_levels * (t.c_level_ns + t.c_dense_edge_ns * (double)g->m + t.c_dense_node_ns * (double)g->n);
+        (double)t.prior_levels * (t.c_level_ns + t.c_dense_edge_ns * (double)g->gr->m + t.c_dense_node_ns * (double)g->gr->n);
     for (int h = 0; h < t.max_halvings && walk_bound >= push_est; ++h) {
       walk_bound /= 2.0;
       r.rmax_local /= 2.0;
@@ -337,7 +337,7 @@ static int ensure_spec(pprhip_graph* g) {
     std::memset(g->spec_mail, 0, sizeof(HostMail));
   }
   if (hipHostGetDevicePointer((void**)&g->spec_mail_dev, g->spec_mail, 0) != hipSuccess) return PPRHIP_ERR_HIP;
-  if (!g->mc_plan_rec2 && alloc_dev((void**)&g->mc_plan_rec2, sizeof(WalkPlanRec) * (size_t)g->n) != PPRHIP_OK) {
+  if (!g->mc_plan_rec2 && alloc_dev((void**)&g->mc_plan_rec2, sizeof(WalkPlanRec) * (size_t)g->gr->n) != PPRHIP_OK) {
     g->mc_plan_rec2 = nullptr;
     return PPRHIP_ERR_OOM;
   }
@@ -579,11 +579,11 @@ int bwd_step(ForaRun& r, bool yield_dense) {
     PPRHIP_TRY(launch_select_gather(g, g->reserve, act_n(g), thr_bits, true));  // Base_Whole_Graph.java:83 pi >= threshold
     unsigned long long cnt = 0;
     PPRHIP_TRY(fetch_small(g, g->sel_blob, &cnt, sizeof cnt));
-    const std::vector<int32_t>& n2o = host_of(g)->h_new2old;
+    const std::vector<int32_t>& n2o = g->gr->h_new2old;
     if (cnt > g->sel_cap) {
-      std::vector<double> all(g->n);
+      std::vector<double> all(g->gr->n);
       PPRHIP_TRY(copy_out(g, g->reserve, all.data()));
-      for (uint32_t v = 0; v < g->n; ++v)  // copy_out already returned original ids
+      for (uint32_t v = 0; v < g->gr->n; ++v)  // copy_out already returned original ids
         if (all[v] > 0.0 && all[v] >= threshold) r.triples.push_back({(int32_t)v, r.target_orig, all[v]});
     } else if (cnt) {
       std::vector<SelRec> recs(cnt);
@@ -621,7 +621,7 @@ int pprhip_fora_single_source(pprhip_graph_t* g, int32_t src, double eps, const 
   PPRHIP_TRY(check_conf(conf, "pprhip_fora_single_source", false));
   PPRHIP_TRY(check_graph(g, "pprhip_fora_single_source"));
   PPRHIP_TRY(check_node(g, src, "pprhip_fora_single_source"));
-  src = g->h_old2new[src];  // internal (degree-sorted) id
+  src = g->gr->h_old2new[src];  // internal (degree-sorted) id
   if (!conf || !(eps > 0.0) || n_rounds < 0) {
     set_error("pprhip_fora_single_source: bad arguments (eps=%g n_rounds=%d)", eps, n_rounds);
     return PPRHIP_ERR_INVALID;
@@ -738,7 +738,7 @@ int pprhip_fora_topk(pprhip_graph_t* g, int32_t src, double eps, const pprhip_fo
   PPRHIP_TRY(check_node(g, src, "pprhip_fora_topk"));
   if (!fora_topk_args_ok(conf, eps, cap, ids_out, vals_out, "pprhip_fora_topk")) return PPRHIP_ERR_INVALID;
   ForaRun r;
-  PPRHIP_TRY(topk_begin(r, g, g->h_old2new[src], eps, conf, seed, ids_out, vals_out, cap));
+  PPRHIP_TRY(topk_begin(r, g, g->gr->h_old2new[src], eps, conf, seed, ids_out, vals_out, cap));
   return fora_topk_drive(r, n_out, reserve_out, stats);
 }
 
@@ -778,13 +778,15 @@ struct SweepTicket {
   unsigned long long seq = 0;
 };
 
-// ws: the workspace (index into P->slots and `runs`) that stands at each active column; nullptr: column c = slots[c]
+// ws: the workspace (index into P->batch->slots and `runs`) that stands at each active column; nullptr: column c = slots[c]
 int launch_sweep(pprhip_graph* P, ForaRun* runs, const bool* active, int n_active, SweepTicket* T, const int* ws = nullptr) {
+  BatchState* bs = P->batch;
+  const GraphData* D = P->gr;
   T->n_active = n_active;
   for (int s = 0; s < kBatch; ++s) {
     T->ws[s] = (ws && active[s]) ? ws[s] : s;
-    pprhip_graph* S = P->slots[T->ws[s]];
-    SlotArgs& sa = P->h_slot_args[s];
+    pprhip_graph* S = bs->slots[T->ws[s]];
+    SlotArgs& sa = bs->h_slot_args[s];
     T->active[s] = active[s];
     sa.res = S->residue;
     sa.reserve = S->reserve;
@@ -813,16 +815,16 @@ int launch_sweep(pprhip_graph* P, ForaRun* runs, const bool* active, int n_activ
     if (active[s] && runs[T->ws[s]].a.mode == kBackward) backward = true;  // a job's runs all push the same way
   T->backward = backward;
   // SURVEY 8(d) sweep model with n = the rows the sweep carries (launch_dense_level_b8: isolated nodes are left out)
-  const uint64_t rows = backward ? (uint64_t)P->n_nz_o + P->n_z_o : (uint64_t)P->n_nz + P->n_zin;
+  const uint64_t rows = backward ? (uint64_t)D->n_nz_o + D->n_z_o : (uint64_t)D->n_nz + D->n_zin;
   T->rows = rows;
-  const uint64_t sweep_bytes = 4ull * P->m + (uint64_t)n_active * (8ull * P->m + 36ull * rows + 4ull);
-  if ((int)backward != P->acc8_dir) {
+  const uint64_t sweep_bytes = 4ull * D->m + (uint64_t)n_active * (8ull * D->m + 36ull * rows + 4ull);
+  if ((int)backward != bs->acc8_dir) {
     // rows summed with atomics are cleared by the apply kernel of their own layout only: start clean
-    PPRHIP_CHECK_HIP(hipMemsetAsync(P->acc8, 0, sizeof(double) * ((size_t)P->n + 1) * kBatch, P->stream));
-    P->acc8_dir = (int)backward;
+    PPRHIP_CHECK_HIP(hipMemsetAsync(bs->acc8, 0, sizeof(double) * ((size_t)D->n + 1) * kBatch, P->stream));
+    bs->acc8_dir = (int)backward;
   }
   int n_gs = 1;
-  const GsBlock* gs_blocks = backward ? nullptr : gs_blocks_of(P->slots[0], &n_gs);  // slots carry the call's tuning
+  const GsBlock* gs_blocks = backward ? nullptr : gs_blocks_of(bs->slots[0], &n_gs);  // slots carry the call's tuning
   // (Tried against the ~30 us between two sweeps, round 5: the slots' arguments passed to the kernels by value instead
   // of through a copy command, and the reduce kernel writing the counters into the mailbox itself instead of a
   // k_publish behind it - the sweep took 20-35 us longer either way (1 636-1 651 against 1 613-1 618 us on one box:
@@ -843,7 +845,7 @@ int launch_sweep(pprhip_graph* P, ForaRun* runs, const bool* active, int n_activ
         unsigned long long h[2];
         PPRHIP_CHECK_HIP(hipMemcpy(h, d_cnt, 16, hipMemcpyDeviceToHost));
         fprintf(stderr, "[pprhip live lines] %llu sweeps: gathers of live lines %.3f of m, live lines %.3f of the sources, busy columns now %d\n",
-                sweeps, (double)h[0] / (double)sweeps / (double)P->m, (double)h[1] / (double)sweeps / (double)P->n_src_live, n_active);
+                sweeps, (double)h[0] / (double)sweeps / (double)D->m, (double)h[1] / (double)sweeps / (double)D->n_src_live, n_active);
       }
     }
   }
@@ -851,8 +853,8 @@ int launch_sweep(pprhip_graph* P, ForaRun* runs, const bool* active, int n_activ
   P->ktimer.begin(PPRHIP_KERNEL_DENSE_PULL_BATCH, sweep_bytes);
   PPRHIP_TRY(launch_dense_level_b8(P, backward, gs_blocks, n_gs));
   P->ktimer.end();
-  P->c8cur ^= 1;
-  return fetch_begin(P, P->sweep_out, sizeof(unsigned long long) * kBatch, &T->seq);
+  bs->c8cur ^= 1;
+  return fetch_begin(P, bs->sweep_out, sizeof(unsigned long long) * kBatch, &T->seq);
 }
 
 // true when the counters of a sweep in flight have arrived (collect_sweep would not wait)
@@ -861,13 +863,13 @@ bool sweep_arrived(const pprhip_graph* P, const SweepTicket& T) {
 }
 
 int collect_sweep(pprhip_graph* P, ForaRun* runs, const SweepTicket& T) {
-  PPRHIP_TRY(fetch_end(P, T.seq, P->sweep_out, P->h_sweep_out, sizeof(unsigned long long) * kBatch));
+  PPRHIP_TRY(fetch_end(P, T.seq, P->batch->sweep_out, P->batch->h_sweep_out, sizeof(unsigned long long) * kBatch));
   for (int s = 0; s < kBatch; ++s)
     if (T.active[s]) {
       ForaRun& r = runs[T.ws[s]];
-      const unsigned long long pk = P->h_sweep_out[s];
+      const unsigned long long pk = P->batch->h_sweep_out[s];
       // the sweep's index stream is shared: each query is charged its own gathers and row work
-      finish_dense(r.L, r.st, 8ull * P->m + 36ull * T.rows + 4ull + 4ull * P->m / (uint64_t)T.n_active,
+      finish_dense(r.L, r.st, 8ull * P->gr->m + 36ull * T.rows + 4ull + 4ull * P->gr->m / (uint64_t)T.n_active,
                    batch_sweep_min_bytes(P, T.backward, T.n_active) / (uint64_t)T.n_active, (uint32_t)(pk >> kPackShift),
                    pk & kPackMask);
     }
@@ -902,12 +904,12 @@ int finish_query(BatchJob& J, ForaRun& r) {
   if (J.keep) {  // the vector stays in HBM after the slot moves on (internal order; pprhip_results_fetch permutes)
     {
       SetupScope setup(S);
-      PPRHIP_TRY(launch_copy_f64(S, r.kind == 1 ? S->est : S->reserve, J.keep->buf + (size_t)(J.keep_first + i) * J.P->n,
-                                 (size_t)J.P->n));
+      PPRHIP_TRY(launch_copy_f64(S, r.kind == 1 ? S->est : S->reserve, J.keep->buf + (size_t)(J.keep_first + i) * J.P->gr->n,
+                                 (size_t)J.P->gr->n));
     }
   }
   if (J.reserve_out) {
-    double* dst = J.reserve_out + (size_t)i * J.P->n;
+    double* dst = J.reserve_out + (size_t)i * J.P->gr->n;
     if (J.pipe) PPRHIP_TRY(J.pipe->submit(S, r.kind == 1 ? S->est : S->reserve, dst));
     else PPRHIP_TRY(copy_out(S, r.kind == 1 ? S->est : S->reserve, dst));
   }
@@ -941,7 +943,7 @@ int finish_query(BatchJob& J, ForaRun& r) {
 
 int begin_query(BatchJob& J, ForaRun& r, pprhip_graph* S, int i) {
   S->tun = J.P->tun;
-  const int32_t src = J.P->h_old2new[J.srcs[i]];
+  const int32_t src = J.P->gr->h_old2new[J.srcs[i]];
   if (J.kind == 2) {
     pprhip_tuning_batch(&S->tun);  // level shapes only: a backward search has no cost-model decisions
     PPRHIP_TRY(bwd_begin(r, S, src, J.srcs[i], J.alpha, J.threshold));
@@ -963,35 +965,37 @@ int begin_query(BatchJob& J, ForaRun& r, pprhip_graph* S, int i) {
 // tools/micro/chain_rate.hip), so that the compute stream's kernels find room beside it: 292 -> 327 queries/s on
 // R-MAT 22 (16 waves per CU beside: 307; 2: 300).
 static hipStream_t side_stream_for_walks(pprhip_graph* P) {
-  if (!P->walk_stream_tried) {
-    P->walk_stream_tried = true;
+  BatchState* bs = P->batch;
+  if (!bs->walk_stream_tried) {
+    bs->walk_stream_tried = true;
     const char* e = hook_env("PPRHIP_BATCH_WALKS_BESIDE");
-    if (!(e && e[0] == '0') && make_side_stream(P, &P->walk_stream) != PPRHIP_OK) P->walk_stream = nullptr;
+    if (!(e && e[0] == '0') && make_side_stream(P, &bs->walk_stream) != PPRHIP_OK) bs->walk_stream = nullptr;
   }
-  if (P->walk_stream)  // (every call: workspaces may have joined since)
-    for (pprhip_graph* S : P->slots)
+  if (bs->walk_stream)  // (every call: workspaces may have joined since)
+    for (pprhip_graph* S : bs->slots)
       for (auto& ev : S->walk_ev)
         if (!ev && hipEventCreate(&ev) != hipSuccess) {
           ev = nullptr;
-          (void)hipStreamDestroy(P->walk_stream);
-          P->walk_stream = nullptr;
+          (void)hipStreamDestroy(bs->walk_stream);
+          bs->walk_stream = nullptr;
           return nullptr;
         }
-  return P->walk_stream;
+  return bs->walk_stream;
 }
 
 // The stream the slots of the sequential driver work on: it has to run beside the compute stream (the sweeps) and
 // beside the walk stream.  PPRHIP_BATCH_SLOTS_BESIDE=0: the slots stay on the compute stream (the driver of rounds 1-4).
 static hipStream_t stream_for_slots(pprhip_graph* P) {
-  if (!P->slot_stream_tried) {
-    P->slot_stream_tried = true;
+  BatchState* bs = P->batch;
+  if (!bs->slot_stream_tried) {
+    bs->slot_stream_tried = true;
     const char* e = hook_env("PPRHIP_BATCH_SLOTS_BESIDE");
     if (!(e && e[0] == '0')) {
-      if (make_side_stream(P, &P->slot_stream, P->walk_stream) != PPRHIP_OK) P->slot_stream = nullptr;
-      if (!P->slot_stream && P->walk_stream && make_side_stream(P, &P->slot_stream) != PPRHIP_OK) P->slot_stream = nullptr;
+      if (make_side_stream(P, &bs->slot_stream, bs->walk_stream) != PPRHIP_OK) bs->slot_stream = nullptr;
+      if (!bs->slot_stream && bs->walk_stream && make_side_stream(P, &bs->slot_stream) != PPRHIP_OK) bs->slot_stream = nullptr;
     }
   }
-  return P->slot_stream;
+  return bs->slot_stream;
 }
 
 // The sequential batch driver: kBatch resumable runs on one host thread, their dense levels served by batched sweeps on
@@ -1050,9 +1054,9 @@ struct SlotDriver {
       }
       n_ws = want;
     }
-    for (int c = 0; c < kBatch; ++c) P->col_owner[c] = -1;
-    for (size_t w = 0; w < P->slots.size(); ++w) {
-      pprhip_graph* S = P->slots[w];
+    for (int c = 0; c < kBatch; ++c) P->batch->col_owner[c] = -1;
+    for (size_t w = 0; w < P->batch->slots.size(); ++w) {
+      pprhip_graph* S = P->batch->slots[w];
       S->stream = slots_on ? slots_on : P->stream;
       S->c8_via_parent = S->stream != P->stream;
       S->sync = nullptr;
@@ -1062,19 +1066,19 @@ struct SlotDriver {
     // the workspaces' read-backs look after the sweep in flight while they wait (only worth it when they wait on
     // another stream than the sweep's)
     if (slots_on && slots_on != P->stream && !hook_env("PPRHIP_BATCH_NO_HOOK")) {
-      P->idle_hook = &SlotDriver::on_idle;
-      P->idle_arg = this;
+      P->batch->idle_hook = &SlotDriver::on_idle;
+      P->batch->idle_arg = this;
     }
     return PPRHIP_OK;
   }
   void teardown() {
     prof.print();
-    P->idle_hook = nullptr;
-    P->idle_arg = nullptr;
-    if (P->slot_stream) (void)hipStreamSynchronize(P->slot_stream);
-    for (size_t w = 0; w < P->slots.size(); ++w) {  // (as the other drivers expect them)
-      P->slots[w]->pooled = P->slots[w]->has_col = false;
-      P->slots[w]->slot_index = (int)(w % kBatch);
+    P->batch->idle_hook = nullptr;
+    P->batch->idle_arg = nullptr;
+    if (P->batch->slot_stream) (void)hipStreamSynchronize(P->batch->slot_stream);
+    for (size_t w = 0; w < P->batch->slots.size(); ++w) {  // (as the other drivers expect them)
+      P->batch->slots[w]->pooled = P->batch->slots[w]->has_col = false;
+      P->batch->slots[w]->slot_index = (int)(w % kBatch);
     }
   }
   static void on_idle(void* self) {
@@ -1105,9 +1109,9 @@ struct SlotDriver {
   // a workspace that holds its column without standing at a dense level lets it go (its column is all-zero, or the
   // compaction that makes it so is queued on the compute stream)
   void release_if_idle(int w) {
-    pprhip_graph* S = P->slots[w];
+    pprhip_graph* S = P->batch->slots[w];
     if (S->has_col && !(runs[w].query >= 0 && runs[w].waiting)) {
-      P->col_owner[S->slot_index] = -1;
+      P->batch->col_owner[S->slot_index] = -1;
       S->has_col = false;
     }
   }
@@ -1128,7 +1132,7 @@ struct SlotDriver {
         BatchJob* J = nullptr;
         int i = -1;
         if (!next(&J, &i)) break;
-        if ((rc = begin_query(*J, r, P->slots[w], i)) != PPRHIP_OK) break;
+        if ((rc = begin_query(*J, r, P->batch->slots[w], i)) != PPRHIP_OK) break;
         r.side = side;
       }
       if (r.waiting) break;
@@ -1145,9 +1149,9 @@ struct SlotDriver {
         }
         r.L.defer_compact = true;
       }
-      P->slots[w]->c8_settled = defer;
+      P->batch->slots[w]->c8_settled = defer;
       rc = run_step(r, true);
-      P->slots[w]->c8_settled = false;
+      P->batch->slots[w]->c8_settled = false;
       r.L.defer_compact = false;
       if (rc != kYieldColumn) col_marked[w] = false;  // (it no longer stands ready for a column)
       if (rc == kYield) {
@@ -1157,7 +1161,7 @@ struct SlotDriver {
       }
       if (rc == kYieldColumn && !defer) {
         // what it has queued so far must have ended before it may take the column without waiting for the stream
-        pprhip_graph* S = P->slots[w];
+        pprhip_graph* S = P->batch->slots[w];
         if (!S->col_ev && hipEventCreateWithFlags(&S->col_ev, hipEventDisableTiming) != hipSuccess) S->col_ev = nullptr;
         col_marked[w] = S->col_ev && hipEventRecord(S->col_ev, S->stream) == hipSuccess;
       }
@@ -1230,11 +1234,11 @@ struct SlotDriver {
         }
       // columns have been let go: workspaces that stand ready prepare their levels behind the compactions
       int n_free = 0;
-      for (int c = 0; c < kBatch; ++c) n_free += P->col_owner[c] < 0 ? 1 : 0;
+      for (int c = 0; c < kBatch; ++c) n_free += P->batch->col_owner[c] < 0 ? 1 : 0;
       for (int t = 0; t < n_ws && n_free > 0; ++t) {
         const int w = (ready_rr + t) % n_ws;
         if (w == cur_ws || runs[w].query < 0 || walking[w] || runs[w].waiting || !col_marked[w] ||
-            hipEventQuery(P->slots[w]->col_ev) != hipSuccess)
+            hipEventQuery(P->batch->slots[w]->col_ev) != hipSuccess)
           continue;
         PPRHIP_TRY(step_ws(w, true));
         prof.lap(3);
@@ -1253,7 +1257,7 @@ struct SlotDriver {
     int ws[kBatch];
     int n_wait = 0;
     for (int c = 0; c < kBatch; ++c) {
-      const int w = P->col_owner[c];
+      const int w = P->batch->col_owner[c];
       active[c] = w >= 0 && runs[w].query >= 0 && runs[w].waiting;
       ws[c] = active[c] ? w : c;
       n_wait += active[c] ? 1 : 0;
@@ -1288,12 +1292,12 @@ struct SlotDriver {
         break;
       }
       if (walking[w]) {
-        if (hipEventQuery(P->slots[w]->walk_ev[2]) == hipErrorNotReady) continue;
+        if (hipEventQuery(P->batch->slots[w]->walk_ev[2]) == hipErrorNotReady) continue;
         walking[w] = false;
       }
       if (col_marked[w]) {  // it stands ready for a column: nothing to do for it while none is free
         bool any_free = false;
-        for (int c = 0; c < kBatch && !any_free; ++c) any_free = P->col_owner[c] < 0;
+        for (int c = 0; c < kBatch && !any_free; ++c) any_free = P->batch->col_owner[c] < 0;
         if (!any_free) continue;
       }
       PPRHIP_TRY(step_ws(w, false));
@@ -1314,7 +1318,7 @@ struct SlotDriver {
         set_error("batch driver: %d queries in flight, none waiting", *busy);
         return PPRHIP_ERR_STATE;
       }
-      PPRHIP_CHECK_HIP(hipEventSynchronize(P->slots[first_walk]->walk_ev[2]));
+      PPRHIP_CHECK_HIP(hipEventSynchronize(P->batch->slots[first_walk]->walk_ev[2]));
     }
     return PPRHIP_OK;
   }
@@ -1352,7 +1356,7 @@ int batch_sequential(BatchJob& J) {
   PPRHIP_TRY(D.setup(P, J.kind == 0 && J.q > kBatch, stream_for_slots(P)));
   if (D.side) D.side = side_stream_for_walks(P);  // (the new workspaces' events)
   KernelTimer& tm = ktimer();  // (the call's timer watches the stream the workspaces' kernels run on ...)
-  tm.stream = P->slots[0]->stream;
+  tm.stream = P->batch->slots[0]->stream;
   // queries the workspaces run (the leftover rule is for one workspace per column: with the pool there are no rounds
   // of 16 whose last one would be nearly empty - 50 / 51 / 35 sources per call: 306 / 302 / 281 queries/s without
   // the rule, 306 / 292 / 270 with it).
@@ -1402,11 +1406,11 @@ int batch_sequential(BatchJob& J) {
 // one worker thread per slot
 void batch_worker(BatchJob* J, BatchSync* B, ForaRun* runs, int s) {
   pprhip_graph* P = J->P;
-  pprhip_graph* S = P->slots[s];
+  pprhip_graph* S = P->batch->slots[s];
   ForaRun& r = runs[s];
   int rc = PPRHIP_OK;
-  if (hipSetDevice(P->device) != hipSuccess) {
-    set_error("hipSetDevice(%d) failed in a batch worker", P->device);
+  if (hipSetDevice(P->gr->device) != hipSuccess) {
+    set_error("hipSetDevice(%d) failed in a batch worker", P->gr->device);
     rc = PPRHIP_ERR_HIP;
   }
   KernelTimer* const own_timer = g_timer_cur;
@@ -1494,7 +1498,7 @@ int BatchSync::arrive(int s) {
 
 // the sweeper thread: one batched sweep whenever somebody waits and nobody holds
 void BatchSync::sweeper() {
-  (void)hipSetDevice(P->device);
+  (void)hipSetDevice(P->gr->device);
   std::unique_lock<std::mutex> lk(mu);
   for (;;) {
     cv.wait(lk, [&] { return n_workers == 0 || err != 0 || (n_wait > 0 && n_hold == 0); });
@@ -1538,7 +1542,7 @@ void BatchSync::sweeper() {
 int pprhip::detail::FetchPipe::ensure(pprhip_graph* parent) {
   if (cs) return PPRHIP_OK;
   P = parent;
-  n = parent->n;
+  n = parent->gr->n;
   for (int e = 0; e < kRing; ++e) {
     PPRHIP_TRY(alloc_dev((void**)&dev[e], sizeof(double) * n));
     PPRHIP_CHECK_HIP(hipHostMalloc((void**)&pin[e], sizeof(double) * std::max<size_t>(n, 1), hipHostMallocDefault));
@@ -1565,7 +1569,7 @@ void pprhip::detail::FetchPipe::start() {
 }
 
 void pprhip::detail::FetchPipe::copier() {
-  (void)hipSetDevice(P->device);
+  (void)hipSetDevice(P->gr->device);
   for (;;) {
     Item it;
     {
@@ -1620,7 +1624,7 @@ int pprhip::detail::FetchPipe::submit(pprhip_graph* S, const double* dev_vec, do
     return rc;
   };
   int rc = PPRHIP_OK;
-  if (S->relabeled) {  // back to the caller's ids: out[old] = x[old2new[old]]
+  if (S->gr->relabeled) {  // back to the caller's ids: out[old] = x[old2new[old]]
     rc = launch_permute_out(S, dev_vec, dev[e]);
   } else if (hipMemcpyAsync(dev[e], dev_vec, sizeof(double) * n, hipMemcpyDeviceToDevice, S->stream) != hipSuccess) {
     set_error("delivery of a result vector failed (staging copy)");
@@ -1701,17 +1705,17 @@ int pprhip::detail::batch_run(pprhip_graph_t* g, BatchJob& J, pprhip_stats_t* st
   // vectors go to the caller's memory behind the queries' backs (a synchronous copy of 8n bytes to pageable memory per
   // query would stall the one stream everything runs on: 170 instead of 270 queries/s on R-MAT 22)
   if (J.reserve_out && J.kind != 2 && q > 1) {
-    if (!g->fetch) g->fetch = new (std::nothrow) FetchPipe();
-    if (!g->fetch) return PPRHIP_ERR_OOM;
-    const int prc = g->fetch->ensure(g);
+    if (!g->batch->fetch) g->batch->fetch = new (std::nothrow) FetchPipe();
+    if (!g->batch->fetch) return PPRHIP_ERR_OOM;
+    const int prc = g->batch->fetch->ensure(g);
     if (prc != PPRHIP_OK) {
-      g->fetch->destroy();
-      delete g->fetch;
-      g->fetch = nullptr;
+      g->batch->fetch->destroy();
+      delete g->batch->fetch;
+      g->batch->fetch = nullptr;
       return prc;
     }
-    g->fetch->start();
-    J.pipe = g->fetch;
+    g->batch->fetch->start();
+    J.pipe = g->batch->fetch;
   }
   ForaRun runs[kBatch];
   g->ktimer.stream = g->stream;
@@ -1725,7 +1729,7 @@ int pprhip::detail::batch_run(pprhip_graph_t* g, BatchJob& J, pprhip_stats_t* st
     BatchSync B;
     B.P = g;
     B.runs = runs;
-    for (pprhip_graph* S : g->slots) {
+    for (pprhip_graph* S : g->batch->slots) {
       S->stream = S->own_stream;
       S->c8_via_parent = false;
       S->sync = &B;
@@ -1736,7 +1740,7 @@ int pprhip::detail::batch_run(pprhip_graph_t* g, BatchJob& J, pprhip_stats_t* st
     for (int s = 0; s < kBatch; ++s) workers.emplace_back(batch_worker, &J, &B, runs, s);
     for (auto& w : workers) w.join();
     sweeper.join();
-    for (pprhip_graph* S : g->slots) {
+    for (pprhip_graph* S : g->batch->slots) {
       S->sync = nullptr;
       S->ktimer.resolve(tot, bytes, cnt);
     }
@@ -1745,7 +1749,7 @@ int pprhip::detail::batch_run(pprhip_graph_t* g, BatchJob& J, pprhip_stats_t* st
       rc = B.err;
     }
   } else {
-    for (pprhip_graph* S : g->slots) {
+    for (pprhip_graph* S : g->batch->slots) {
       S->stream = g->stream;
       S->c8_via_parent = false;
       S->sync = nullptr;
@@ -1850,9 +1854,9 @@ int pprhip_results_create(pprhip_graph_t* g, int capacity, pprhip_results_t** re
   pprhip_results* r = new (std::nothrow) pprhip_results();
   if (!r) return PPRHIP_ERR_OOM;
   r->g = g;
-  r->device = g->device;
+  r->device = g->gr->device;
   r->capacity = capacity;
-  const int rc = alloc_dev((void**)&r->buf, sizeof(double) * (size_t)capacity * g->n);
+  const int rc = alloc_dev((void**)&r->buf, sizeof(double) * (size_t)capacity * g->gr->n);
   if (rc != PPRHIP_OK) {
     delete r;
     return rc;
@@ -1875,7 +1879,7 @@ int pprhip_results_info(const pprhip_results_t* r, int* capacity, int* count, ui
   }
   if (capacity) *capacity = r->capacity;
   if (count) *count = r->count;
-  if (n) *n = r->g->n;
+  if (n) *n = r->g->gr->n;
   return PPRHIP_OK;
 }
 
@@ -1893,7 +1897,7 @@ int pprhip_results_fetch(pprhip_results_t* r, int i, double* reserve_out) {
     set_error("pprhip_results_fetch: null output");
     return PPRHIP_ERR_INVALID;
   }
-  return copy_out(r->g, r->buf + (size_t)i * r->g->n, reserve_out);
+  return copy_out(r->g, r->buf + (size_t)i * r->g->gr->n, reserve_out);
 }
 
 int pprhip_results_sum(pprhip_results_t* r, int i, double* sum_out) {
@@ -1902,7 +1906,7 @@ int pprhip_results_sum(pprhip_results_t* r, int i, double* sum_out) {
     set_error("pprhip_results_sum: null output");
     return PPRHIP_ERR_INVALID;
   }
-  return device_sum(r->g, r->buf + (size_t)i * r->g->n, sum_out, r->g->n);
+  return device_sum(r->g, r->buf + (size_t)i * r->g->gr->n, sum_out, r->g->gr->n);
 }
 
 int pprhip_fora_batch_topk(pprhip_graph_t* g, const int32_t* srcs, int q, int k, double eps, double alpha,
@@ -1916,7 +1920,7 @@ int pprhip_fora_batch_topk(pprhip_graph_t* g, const int32_t* srcs, int q, int k,
   }
   for (int i = 0; i < q; ++i) PPRHIP_TRY(check_node(g, srcs[i], "pprhip_fora_batch_topk"));
   pprhip_fora_conf_t conf;
-  PPRHIP_TRY(pprhip_conf_fora_topk(g->n, g->m, k, alpha, &conf));
+  PPRHIP_TRY(pprhip_conf_fora_topk(g->gr->n, g->gr->m, k, alpha, &conf));
   BatchJob J;
   J.P = g;
   J.kind = 1;
@@ -1991,8 +1995,8 @@ void stream_fail(pprhip_stream* s, int rc) {
 
 void stream_driver(pprhip_stream* s) {
   pprhip_graph* P = s->g;
-  if (hipSetDevice(P->device) != hipSuccess) {
-    set_error("hipSetDevice(%d) failed in the stream driver", P->device);
+  if (hipSetDevice(P->gr->device) != hipSuccess) {
+    set_error("hipSetDevice(%d) failed in the stream driver", P->gr->device);
     stream_fail(s, PPRHIP_ERR_HIP);
     return;
   }
@@ -2065,8 +2069,8 @@ void stream_driver(pprhip_stream* s) {
   // once, and copies or selections of other slots' queries can still be queued against those buffers.
   (void)hipStreamSynchronize(P->stream);
   D.teardown();
-  if (P->walk_stream) (void)hipStreamSynchronize(P->walk_stream);
-  if (side && side != P->stream && side != P->walk_stream) (void)hipStreamSynchronize(side);
+  if (P->batch->walk_stream) (void)hipStreamSynchronize(P->batch->walk_stream);
+  if (side && side != P->stream && side != P->batch->walk_stream) (void)hipStreamSynchronize(side);
   if (rc != PPRHIP_OK) stream_fail(s, rc);
   g_timer_cur = saved;
 }
@@ -2204,7 +2208,7 @@ static int stream_shutdown(pprhip_stream* s) {
   g->stream_obj = nullptr;
   s->g = nullptr;
   if (s->err != PPRHIP_OK) {
-    (void)hipSetDevice(g->device);
+    (void)hipSetDevice(g->gr->device);
     free_batch(g);  // slots may hold half-pushed levels: the next batched call builds clean ones
   }
   return s->err;

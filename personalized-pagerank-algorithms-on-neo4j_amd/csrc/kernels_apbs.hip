@@ -1294,7 +1294,7 @@ int launch_owner_partition(pprhip_graph* g, const TripleRec* rec, unsigned long 
     return PPRHIP_ERR_INVALID;
   }
   const uint32_t grid = (uint32_t)std::min<unsigned long long>((count + kPartTile - 1) / kPartTile, 2048ull);
-  k_owner_partition<<<dim3(grid), dim3(256), 0, g->stream>>>(rec, count, g->n / (uint32_t)world, g->n % (uint32_t)world,
+  k_owner_partition<<<dim3(grid), dim3(256), 0, g->stream>>>(rec, count, g->gr->n / (uint32_t)world, g->gr->n % (uint32_t)world,
                                                              world, cursors, out);
   PPRHIP_CHECK_HIP(hipGetLastError());
   return PPRHIP_OK;
@@ -1330,7 +1330,7 @@ int launch_emit_reserve(pprhip_graph* g, const double* reserve, uint32_t n, doub
                         unsigned long long cap, unsigned long long* count) {
   if (!n) return PPRHIP_OK;
   const uint32_t grid = (uint32_t)std::min<uint64_t>(((uint64_t)n + 255) / 256, 4096);
-  k_emit_reserve<<<dim3(grid), dim3(256), 0, g->stream>>>(reserve, n, rmax, g->relabeled ? g->new2old : nullptr, t_old, out, cap,
+  k_emit_reserve<<<dim3(grid), dim3(256), 0, g->stream>>>(reserve, n, rmax, g->gr->relabeled ? g->gr->new2old : nullptr, t_old, out, cap,
                                                           count);
   PPRHIP_CHECK_HIP(hipGetLastError());
   return PPRHIP_OK;
@@ -1348,9 +1348,9 @@ int init_kernels_apbs() {  // loads this file's code object on the current devic
 }
 
 int launch_build_in_rec(pprhip_graph* g, void* rec) {
-  if (!g->m) return PPRHIP_OK;
-  const uint32_t grid = (uint32_t)std::min<unsigned long long>((g->m + 255) / 256, 8192ull);
-  k_build_in_rec<<<dim3(grid), dim3(256), 0, g->stream>>>(g->in_ci, g->out_ext, (unsigned long long)g->m, (InRec*)rec);
+  if (!g->gr->m) return PPRHIP_OK;
+  const uint32_t grid = (uint32_t)std::min<unsigned long long>((g->gr->m + 255) / 256, 8192ull);
+  k_build_in_rec<<<dim3(grid), dim3(256), 0, g->stream>>>(g->gr->in_ci, g->gr->out_ext, (unsigned long long)g->gr->m, (InRec*)rec);
   PPRHIP_CHECK_HIP(hipGetLastError());
   return PPRHIP_OK;
 }
@@ -1374,7 +1374,7 @@ int launch_apbs(pprhip_graph* g, bool dense_tier, const int32_t* d_targets, uint
     // of the graph so that small graphs still run both paths (PPRHIP_APBS_HOT: developer / test switch, 0 = none)
     const char* he = hook_env("PPRHIP_APBS_HOT");
     uint32_t hot_n = he ? (uint32_t)std::max(0, atoi(he)) : (uint32_t)kDnHotDefault;
-    hot_n = std::min<uint32_t>(std::min<uint32_t>(hot_n, (uint32_t)kDnHotMax), g->n / 4);
+    hot_n = std::min<uint32_t>(std::min<uint32_t>(hot_n, (uint32_t)kDnHotMax), g->gr->n / 4);
     // Workgroups also help between two searches of their own when the pass is short (below 2^17 targets): there the
     // largest searches are what the launch ends with, and help that comes early shortens the end - R-MAT 22, tier 2 of
     // 2^18 / 2^19 targets of the range: 49.5 -> 44.3 ms / 79.1 -> 74.9 ms.  A long pass has no idle end to shorten
@@ -1383,8 +1383,8 @@ int launch_apbs(pprhip_graph* g, bool dense_tier, const int32_t* d_targets, uint
     const char* hb = hook_env("PPRHIP_APBS_HELP_BETWEEN");
     const int help_between = hb ? (hb[0] != '0') : (n_targets < (1u << 17));
     k_apbs_dense<<<dim3(grid), dim3(kDnThreads), 2 * sizeof(double) * (size_t)hot_n, g->stream>>>(
-        d_targets, n_targets, b.next_target, g->in_rp, rec, g->old2new, g->new2old, alpha, rmax, O, b.ws, (DnBoard*)b.board,
-        b.done_targets, b.done_targets + 1, b.done_targets + 2, dims_of(g->n, (unsigned long long)g->m, b.cap_t, b.cap_f, b.chunk), share,
+        d_targets, n_targets, b.next_target, g->gr->in_rp, rec, g->gr->old2new, g->gr->new2old, alpha, rmax, O, b.ws, (DnBoard*)b.board,
+        b.done_targets, b.done_targets + 1, b.done_targets + 2, dims_of(g->gr->n, (unsigned long long)g->gr->m, b.cap_t, b.cap_f, b.chunk), share,
         owners, hot_n, help_between, b.dbg);
   } else if (!d_targets && b.list0 && b.list1) {
     // a range, in three steps on the device: trivial targets and the list of the others; the small table; the large
@@ -1404,23 +1404,23 @@ int launch_apbs(pprhip_graph* g, bool dense_tier, const int32_t* d_targets, uint
         deg_dense = c ? std::max(c, a) : 0xFFFFFFFFu;
       }
     }
-    k_apbs_split<<<dim3(sgrid), dim3(256), 0, g->stream>>>(t_begin, n_targets, g->in_rp, g->old2new, rmax, O, b.list0, cells + 6,
+    k_apbs_split<<<dim3(sgrid), dim3(256), 0, g->stream>>>(t_begin, n_targets, g->gr->in_rp, g->gr->old2new, rmax, O, b.list0, cells + 6,
                                                            b.list1, cells + 11, deg_big, deg_dense);
     PPRHIP_CHECK_HIP(hipGetLastError());
     ApOut O0 = O;  // the small table's give-ups (and retries) go to the second list
     O0.overflow_list = b.list1;
     O0.overflow_count = cells + 11;
-    const uint32_t grid0 = std::min<uint32_t>((uint32_t)g->n_cus * 8u, std::max(1u, n_targets));
+    const uint32_t grid0 = std::min<uint32_t>((uint32_t)g->gr->n_cus * 8u, std::max(1u, n_targets));
     k_apbs_lds<kApSmallCap, kApSmallFront, kApSmallThreads><<<dim3(grid0), dim3(kApSmallThreads), 0, g->stream>>>(
-        b.list0, 0u, 0u, cells + 6, cells + 7, g->in_rp, rec, g->old2new, g->new2old, alpha, rmax, O0);
+        b.list0, 0u, 0u, cells + 6, cells + 7, g->gr->in_rp, rec, g->gr->old2new, g->gr->new2old, alpha, rmax, O0);
     PPRHIP_CHECK_HIP(hipGetLastError());
-    const uint32_t grid1 = std::min<uint32_t>((uint32_t)g->n_cus * 2u, std::max(1u, n_targets));
+    const uint32_t grid1 = std::min<uint32_t>((uint32_t)g->gr->n_cus * 2u, std::max(1u, n_targets));
     k_apbs_lds<kApLdsCap, kApFront, 256><<<dim3(grid1), dim3(256), 0, g->stream>>>(
-        b.list1, 0u, 0u, cells + 11, b.next_target, g->in_rp, rec, g->old2new, g->new2old, alpha, rmax, O);
+        b.list1, 0u, 0u, cells + 11, b.next_target, g->gr->in_rp, rec, g->gr->old2new, g->gr->new2old, alpha, rmax, O);
   } else {
-    const uint32_t grid = std::min<uint32_t>((uint32_t)g->n_cus * 2u, std::max(1u, n_targets));
+    const uint32_t grid = std::min<uint32_t>((uint32_t)g->gr->n_cus * 2u, std::max(1u, n_targets));
     k_apbs_lds<kApLdsCap, kApFront, 256><<<dim3(grid), dim3(256), 0, g->stream>>>(d_targets, t_begin, n_targets, nullptr, b.next_target,
-                                                                             g->in_rp, rec, g->old2new, g->new2old, alpha, rmax, O);
+                                                                             g->gr->in_rp, rec, g->gr->old2new, g->gr->new2old, alpha, rmax, O);
   }
   PPRHIP_CHECK_HIP(hipGetLastError());
   return PPRHIP_OK;

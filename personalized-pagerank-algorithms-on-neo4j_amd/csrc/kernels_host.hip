@@ -55,7 +55,7 @@ __global__ void k_seed_one(int32_t* __restrict__ F, uint32_t* __restrict__ eoff,
 
 int launch_copy_f64(pprhip_graph* g, const double* src, double* dst, size_t n) {
   if (!n) return PPRHIP_OK;
-  const uint32_t grid = (uint32_t)std::min<size_t>((n + 256 * 8 - 1) / (256 * 8), (size_t)g->n_cus * 8);
+  const uint32_t grid = (uint32_t)std::min<size_t>((n + 256 * 8 - 1) / (256 * 8), (size_t)g->gr->n_cus * 8);
   hipLaunchKernelGGL(k_copy_f64, dim3(grid), dim3(256), 0, g->stream, src, dst, n);
   PPRHIP_CHECK_HIP(hipGetLastError());
   return PPRHIP_OK;
@@ -100,7 +100,7 @@ int launch_clear(pprhip_graph* g, const ClearList& L) {
   for (int r = 0; r < L.n; ++r) total += L.bytes[r];
   if (total == 0) return PPRHIP_OK;
   const size_t blocks = (total / 8 + 256 * 16 - 1) / (256 * 16);
-  const uint32_t grid = (uint32_t)std::min<size_t>(std::max<size_t>(blocks, 1), (size_t)g->n_cus * 8);
+  const uint32_t grid = (uint32_t)std::min<size_t>(std::max<size_t>(blocks, 1), (size_t)g->gr->n_cus * 8);
   hipLaunchKernelGGL(k_clear, dim3(grid), dim3(256), 0, g->stream, L);
   PPRHIP_CHECK_HIP(hipGetLastError());
   return PPRHIP_OK;

@@ -830,7 +830,7 @@ __global__ __launch_bounds__(1024) void k_dense_edges_b(const int32_t* __restric
 // ------------------------------------------------------------------------------------------------
 // k_dense_edges_panel (round 6): the single-query forward edge kernel over the row-panel copy (engine_internal.hpp:
 // HostPanelLayout).  A workgroup takes an ITEM - at most kItemEdges edges of one panel of kPanelRows rows, sorted by
-// source - and sums it into acc[row] in LDS (128 KB).  A wave takes 512 consecutive edges per turn, lane l the edges l,
+// source - and sums it into acc[row] in LDS (kPanelLdsBytes, 64 KB).  A wave takes 512 consecutive edges per turn, lane l the edges l,
 // l + 64, ... of them (stored as the lane's 32 bytes), the workgroup 8 192: neighbouring lanes gather neighbouring sources, so the sixteen contributions of a 128-byte line are
 // one request to the L1 (which keeps ~256 lines in flight per CU - what bounds the row-major and the sliced kernel:
 // TCP_PENDING_STALL_CYCLES 0.69 of their cycles), and every workgroup walks the contribution array front to back.  Sums
@@ -1765,7 +1765,7 @@ static inline uint32_t grid_for(uint64_t work, uint32_t per_block, uint32_t cap)
 
 // contribution buffer `cbuf` of a handle: its own array, or its column of the parent's c8 array
 static inline CView cview(pprhip_graph* g, int cbuf) {
-  if (g->parent) return CView{g->parent->c8[cbuf], (uint32_t)kBatch, (uint32_t)g->slot_index};
+  if (g->parent) return CView{g->parent->batch->c8[cbuf], (uint32_t)kBatch, (uint32_t)g->slot_index};
   return CView{g->cdense[cbuf], 1u, 0u};
 }
 
@@ -1783,7 +1783,7 @@ int launch_sparse_prepare(pprhip_graph* g, const PushArgs& a, int fbuf, int leve
   const uint32_t grid = grid_for(nf_upper, 256, 512);
   const CView cd = scatter_dense ? cview(g, cbuf) : CView{nullptr, 1, 0};
   DISPATCH_MODE(a.mode, k_sparse_prepare<M><<<dim3(grid), dim3(256), 0, g->stream>>>(
-                            g->F[fbuf], g->out_rp, g->residue, g->reserve, g->cF, cd, g->ctr, level, dense_thresh,
+                            g->F[fbuf], g->gr->out_rp, g->residue, g->reserve, g->cF, cd, g->ctr, level, dense_thresh,
                             dead_slot, pk0, a));
   PPRHIP_CHECK_HIP(hipGetLastError());
   return PPRHIP_OK;
@@ -1793,13 +1793,13 @@ int launch_sparse_push(pprhip_graph* g, const PushArgs& a, int fbuf, int level, 
                        unsigned long long dense_thresh, int dead_slot, unsigned long long pk0) {
   const uint32_t grid = grid_for(ef_upper, kPushTile, 2048);
   const bool bwd = a.mode == kBackward;
-  const uint32_t* trp = bwd ? g->in_rp : g->out_rp;
-  const int32_t* tci = bwd ? g->in_ci : g->out_ci;
+  const uint32_t* trp = bwd ? g->gr->in_rp : g->gr->out_rp;
+  const int32_t* tci = bwd ? g->gr->in_ci : g->gr->out_ci;
   // (the override exists for the tests, which run the table on graphs far below the default switch-over)
   const char* comb_env = hook_env("PPRHIP_COMB_MIN_EDGES");
   const unsigned long long comb_min = comb_env ? strtoull(comb_env, nullptr, 10) : (unsigned long long)kCombMinEdges;
   DISPATCH_MODE(a.mode, k_sparse_push<M><<<dim3(grid), dim3(256), 0, g->stream>>>(
-                            g->F[fbuf], g->cF, g->eoff[fbuf], trp, tci, g->out_ext, g->in_rp, g->residue, g->flags,
+                            g->F[fbuf], g->cF, g->eoff[fbuf], trp, tci, g->gr->out_ext, g->gr->in_rp, g->residue, g->flags,
                             g->armed, g->F[fbuf ^ 1], g->eoff[fbuf ^ 1], g->ctr, level, dense_thresh, dead_slot,
                             comb_min, pk0, a));
   PPRHIP_CHECK_HIP(hipGetLastError());
@@ -1810,13 +1810,13 @@ int launch_sparse_levels_wg(pprhip_graph* g, const PushArgs& a, int fbuf0, int f
                             unsigned long long dense_thresh, unsigned long long wg_cap, int dead_slot,
                             unsigned long long pk0) {
   const bool bwd = a.mode == kBackward;
-  const uint32_t* trp = bwd ? g->in_rp : g->out_rp;
-  const int32_t* tci = bwd ? g->in_ci : g->out_ci;
+  const uint32_t* trp = bwd ? g->gr->in_rp : g->gr->out_rp;
+  const int32_t* tci = bwd ? g->gr->in_ci : g->gr->out_ci;
   const char* comb_env = hook_env("PPRHIP_COMB_MIN_EDGES");
   const unsigned long long comb_min = comb_env ? strtoull(comb_env, nullptr, 10) : (unsigned long long)kCombMinEdges;
   DISPATCH_MODE(a.mode, k_sparse_levels_wg<M><<<dim3(1), dim3(256), 0, g->stream>>>(
-                            g->F[0], g->F[1], g->eoff[0], g->eoff[1], g->out_rp, g->residue, g->reserve, g->cF, trp, tci,
-                            g->out_ext, g->in_rp, g->flags, g->armed, g->ctr, fbuf0, first, last, dense_thresh, wg_cap,
+                            g->F[0], g->F[1], g->eoff[0], g->eoff[1], g->gr->out_rp, g->residue, g->reserve, g->cF, trp, tci,
+                            g->gr->out_ext, g->gr->in_rp, g->flags, g->armed, g->ctr, fbuf0, first, last, dense_thresh, wg_cap,
                             dead_slot, comb_min, pk0, a));
   PPRHIP_CHECK_HIP(hipGetLastError());
   return PPRHIP_OK;
@@ -1826,25 +1826,26 @@ int launch_dense_level(pprhip_graph* g, const PushArgs& a, int cbuf, int out_slo
                        const DenseLaunch& dl) {
   // forward levels pull over the in-CSR, backward levels over the out-CSR (layout built by the caller)
   const bool bwd = a.mode == kBackward;
-  const int32_t* ci = bwd ? g->out_ci : g->in_ci;
-  const uint8_t* flags = bwd ? g->start_flags_o : g->start_flags;
-  const uint32_t* cstarts = bwd ? g->chunk_starts_o : g->chunk_starts;
-  const int32_t* nz = bwd ? g->nz_rows_o : g->nz_rows;
-  const uint32_t n_nz = bwd ? g->n_nz_o : g->n_nz;
+  const int32_t* ci = bwd ? g->gr->out_ci : g->gr->in_ci;
+  const uint8_t* flags = bwd ? g->gr->start_flags_o : g->gr->start_flags;
+  const uint32_t* cstarts = bwd ? g->gr->chunk_starts_o : g->gr->chunk_starts;
+  const int32_t* nz = bwd ? g->gr->nz_rows_o : g->gr->nz_rows;
+  const uint32_t n_nz = bwd ? g->gr->n_nz_o : g->gr->n_nz;
   // a source without in-edges still receives returned dead-end mass: one extra apply thread, behind the last block
   // (a seed set: one per live seed without in-edges; the live seeds' landing weights go to the apply kernel)
   const SeedTable* sd = (!bwd && g->seed_on) ? g->seeds : nullptr;
-  const int src_extra = sd ? (int)sd->n_zin : (!bwd && a.src >= 0 && g->h_in_rp[a.src + 1] == g->h_in_rp[a.src]) ? 1 : 0;
+  const int src_extra = sd ? (int)sd->n_zin : (!bwd && a.src >= 0 && g->gr->h_in_rp[a.src + 1] == g->gr->h_in_rp[a.src]) ? 1 : 0;
   const double* seed_w = sd ? sd->w_node : nullptr;
   const int32_t* extra_rows = sd ? sd->zin : nullptr;
-  const GsBlock whole{0u, n_nz, 0ull, (unsigned long long)g->m};
+  const GsBlock whole{0u, n_nz, 0ull, (unsigned long long)g->gr->m};
   const GsBlock* blocks = (dl.blocks && dl.n_blocks > 1 && !bwd) ? dl.blocks : &whole;
   const int nb = blocks == &whole ? 1 : dl.n_blocks;
-  const uint32_t n_hot = g->relabeled ? std::min<uint32_t>(g->n, (uint32_t)kHotMax) : 0u;
-  // forward sweeps walk the row-panel copy of the in-CSR where the graph has one (from 2^20 edges on), else - a graph
-  // whose sources span several slices - the sliced copy
-  const PanelLayout* pn = (!bwd && g->pn && g->pn_part) ? g->pn : nullptr;
-  const SlicedLayout* sl = (bwd || pn) ? nullptr : g->sl;
+  const uint32_t n_hot = g->gr->relabeled ? std::min<uint32_t>(g->gr->n, (uint32_t)kHotMax) : 0u;
+  // forward sweeps walk the row-panel copy of the in-CSR where the graph has one (from 2^26 edges on) and the handle
+  // has the buffer of its parts' sums (ensure_panel_part), else - a graph whose sources span several slices - the sliced
+  // copy
+  const PanelLayout* pn = (!bwd && g->gr->pn && g->pn_part) ? g->gr->pn : nullptr;
+  const SlicedLayout* sl = (bwd || pn) ? nullptr : g->gr->sl;
   const EdgeWindows* wins = sl ? detail::sliced_windows_of(g, blocks == &whole ? nullptr : blocks, nb) : nullptr;
   if (sl) {
     ci = sl->ci;
@@ -1870,7 +1871,7 @@ int launch_dense_level(pprhip_graph* g, const PushArgs& a, int cbuf, int out_slo
       const uint32_t p_lo = B.j_lo / kPanelRows, p_hi = std::min<uint32_t>(pn->n_panels, (B.j_hi + kPanelRows - 1) / kPanelRows);
       const uint32_t i_lo = p_hi > p_lo ? pn->h_panel_item0[p_lo] : 0u, i_hi = p_hi > p_lo ? pn->h_panel_item0[p_hi] : 0u;
       if (i_hi > i_lo) {
-        const uint32_t grid = std::min<uint32_t>(i_hi - i_lo, (uint32_t)g->n_cus * (uint32_t)(160 * 1024 / (kPanelLdsBytes + 1024)));
+        const uint32_t grid = std::min<uint32_t>(i_hi - i_lo, (uint32_t)g->gr->n_cus * (uint32_t)(160 * 1024 / (kPanelLdsBytes + 1024)));
         k_dense_edges_panel<<<dim3(grid), dim3(kPanelThreads), kPanelLdsBytes, g->stream>>>(
             pn->src, pn->rloc, pn->items, i_lo, i_hi, g->cdense[cbuf], g->pn_part, B.j_lo, B.j_hi, n_nz, dl.state_in,
             g->pn_ctr + std::min(b, kPanelQueues - 1));
@@ -1890,10 +1891,10 @@ int launch_dense_level(pprhip_graph* g, const PushArgs& a, int cbuf, int out_slo
           PPRHIP_CHECK_HIP(hipGetLastError());
         }
       }
-    } else if (g->n_chunks && n_ch) {
+    } else if (g->gr->n_chunks && n_ch) {
       // persistent workgroups: one 1024-thread workgroup per CU when the LDS hot table is in use
       const uint32_t want = (n_ch + 15) / 16;
-      const uint32_t grid = std::min<uint32_t>(want, (uint32_t)g->n_cus * (n_hot ? 1u : 2u));
+      const uint32_t grid = std::min<uint32_t>(want, (uint32_t)g->gr->n_cus * (n_hot ? 1u : 2u));
       const size_t lds = n_hot ? sizeof(double) * n_hot : 0;  // (above 64 KB: opted in by init_kernels_push)
       if (n_hot && sl)
         k_dense_edges<true, true><<<dim3(grid), dim3(1024), lds, g->stream>>>(
@@ -1915,13 +1916,13 @@ int launch_dense_level(pprhip_graph* g, const PushArgs& a, int cbuf, int out_slo
     if (grid) {
       if (pn) {
         DISPATCH_MODE(a.mode, (k_dense_apply<M, true><<<dim3(grid), dim3(256), 0, g->stream>>>(
-                                  nz, B.j_lo, B.j_hi, g->pn_part, pn->panels, g->out_rp, g->in_rp, g->cdense[cbuf],
+                                  nz, B.j_lo, B.j_hi, g->pn_part, pn->panels, g->gr->out_rp, g->gr->in_rp, g->cdense[cbuf],
                                   g->cdense[cbuf ^ 1], g->residue, g->reserve, g->flags, g->armed, g->ctr,
                                   g->blk_pack + part_base, g->blk_dead + part_base, g->blk_ndead + part_base, dead_slot,
                                   extra, a, dl.state_in, dl.state0, b == nb - 1 ? 1 : 0, seed_w, extra_rows)));
       } else {
         DISPATCH_MODE(a.mode, (k_dense_apply<M, false><<<dim3(grid), dim3(256), 0, g->stream>>>(
-                                  nz, B.j_lo, B.j_hi, g->acc_nz, nullptr, g->out_rp, g->in_rp, g->cdense[cbuf],
+                                  nz, B.j_lo, B.j_hi, g->acc_nz, nullptr, g->gr->out_rp, g->gr->in_rp, g->cdense[cbuf],
                                   g->cdense[cbuf ^ 1], g->residue, g->reserve, g->flags, g->armed, g->ctr,
                                   g->blk_pack + part_base, g->blk_dead + part_base, g->blk_ndead + part_base, dead_slot,
                                   extra, a, dl.state_in, dl.state0, b == nb - 1 ? 1 : 0, seed_w, extra_rows)));
@@ -1955,21 +1956,21 @@ static uint32_t sweep_hot_bytes() {
 template <int G>
 static int launch_dense_edges_bG(pprhip_graph* g, const int32_t* ci, const uint8_t* start_flags,
                                  const uint32_t* chunk_starts, const double* cB, double* accB, const GsBlock& B) {
-  if (!g->n_chunks || B.e_hi <= B.e_lo) return PPRHIP_OK;
+  if (!g->gr->n_chunks || B.e_hi <= B.e_lo) return PPRHIP_OK;
   const uint32_t hot_max = sweep_hot_bytes() / (8 * G);
-  const uint32_t n_hot = g->relabeled ? std::min<uint32_t>(g->n, hot_max) : 0u;
+  const uint32_t n_hot = g->gr->relabeled ? std::min<uint32_t>(g->gr->n, hot_max) : 0u;
   const uint32_t c_lo = (uint32_t)(B.e_lo / kChunkEdges);
   const uint32_t c_hi = (uint32_t)((B.e_hi + kChunkEdges - 1) / kChunkEdges);
   const uint32_t want = (c_hi - c_lo + 15) / 16;
   const unsigned long long* flags64 = reinterpret_cast<const unsigned long long*>(start_flags);
   if (n_hot) {
-    const uint32_t grid = std::min<uint32_t>(want, (uint32_t)g->n_cus);
+    const uint32_t grid = std::min<uint32_t>(want, (uint32_t)g->gr->n_cus);
     k_dense_edges_b<true, G><<<dim3(grid), dim3(1024), sizeof(double) * n_hot * G, g->stream>>>(
-        ci, flags64, chunk_starts, c_hi, (unsigned long long)g->m, cB, accB, n_hot, c_lo, B.e_lo, B.e_hi, g->n);
+        ci, flags64, chunk_starts, c_hi, (unsigned long long)g->gr->m, cB, accB, n_hot, c_lo, B.e_lo, B.e_hi, g->gr->n);
   } else {
-    const uint32_t grid = std::min<uint32_t>(want, (uint32_t)g->n_cus * 2u);
+    const uint32_t grid = std::min<uint32_t>(want, (uint32_t)g->gr->n_cus * 2u);
     k_dense_edges_b<false, G><<<dim3(grid), dim3(1024), 0, g->stream>>>(
-        ci, flags64, chunk_starts, c_hi, (unsigned long long)g->m, cB, accB, 0u, c_lo, B.e_lo, B.e_hi, g->n);
+        ci, flags64, chunk_starts, c_hi, (unsigned long long)g->gr->m, cB, accB, 0u, c_lo, B.e_lo, B.e_hi, g->gr->n);
   }
   PPRHIP_CHECK_HIP(hipGetLastError());
   return PPRHIP_OK;
@@ -1998,7 +1999,9 @@ __global__ __launch_bounds__(256) void k_count_live_lines(const double* __restri
   }
 }
 int launch_count_live_lines(pprhip_graph* P, unsigned long long* d_out) {
-  k_count_live_lines<<<dim3((P->n + 255) / 256), dim3(256), 0, P->stream>>>(P->c8[P->c8cur], P->out_rp, P->n, d_out);
+  const BatchState* bs = P->batch;
+  k_count_live_lines<<<dim3((P->gr->n + 255) / 256), dim3(256), 0, P->stream>>>(bs->c8[bs->c8cur], P->gr->out_rp, P->gr->n,
+                                                                              d_out);
   PPRHIP_CHECK_HIP(hipGetLastError());
   return PPRHIP_OK;
 }
@@ -2007,40 +2010,44 @@ int launch_count_live_lines(pprhip_graph* P, unsigned long long* d_out) {
 #ifdef PPRHIP_TEST_HOOKS
 // the edge kernel of one block of a batched forward sweep alone (pprhip_hook_time_sweep_edges)
 int launch_sweep_edges_only(pprhip_graph* P, const GsBlock& B) {
-  return launch_dense_edges_bG<kBatch>(P, P->in_ci, P->start_flags, P->chunk_starts, P->c8[P->c8cur], P->acc8, B);
+  const GraphData* D = P->gr;
+  const BatchState* bs = P->batch;
+  return launch_dense_edges_bG<kBatch>(P, D->in_ci, D->start_flags, D->chunk_starts, bs->c8[bs->c8cur], bs->acc8, B);
 }
 #endif
 
 int launch_dense_level_b8(pprhip_graph* P, bool backward, const GsBlock* gs_blocks, int n_gs_blocks) {
-  PPRHIP_CHECK_HIP(hipMemcpyAsync(P->d_slot_args, P->h_slot_args, sizeof(SlotArgs) * kBatch, hipMemcpyHostToDevice,
+  const GraphData* D = P->gr;
+  const BatchState* bs = P->batch;
+  PPRHIP_CHECK_HIP(hipMemcpyAsync(bs->d_slot_args, bs->h_slot_args, sizeof(SlotArgs) * kBatch, hipMemcpyHostToDevice,
                                   P->stream));
   // forward levels pull over the in-CSR, backward levels over the out-CSR
-  const int32_t* ci = backward ? P->out_ci : P->in_ci;
-  const uint8_t* flags = backward ? P->start_flags_o : P->start_flags;
-  const uint32_t* cstarts = backward ? P->chunk_starts_o : P->chunk_starts;
-  const int32_t* nz = backward ? P->nz_rows_o : P->nz_rows;
-  const int32_t* zr = backward ? P->z_rows_o : P->zin_rows;
-  const uint32_t n_nz = backward ? P->n_nz_o : P->n_nz, n_z = backward ? P->n_z_o : P->n_zin;
-  const unsigned long long* cross = backward ? P->cross_bits_o : P->cross_bits;
+  const int32_t* ci = backward ? D->out_ci : D->in_ci;
+  const uint8_t* flags = backward ? D->start_flags_o : D->start_flags;
+  const uint32_t* cstarts = backward ? D->chunk_starts_o : D->chunk_starts;
+  const int32_t* nz = backward ? D->nz_rows_o : D->nz_rows;
+  const int32_t* zr = backward ? D->z_rows_o : D->zin_rows;
+  const uint32_t n_nz = backward ? D->n_nz_o : D->n_nz, n_z = backward ? D->n_z_o : D->n_zin;
+  const unsigned long long* cross = backward ? D->cross_bits_o : D->cross_bits;
   // slots whose sweep state writes the current contribution array in place; without any, one launch serves the
   // whole sweep (Jacobi rows do not care in which order the blocks run)
   uint32_t gs_mask = 0, entry_mask = 0;
   for (int s = 0; s < kBatch; ++s)
-    if (P->h_slot_args[s].active) {
-      const int st = P->h_slot_args[s].gs_state;
+    if (bs->h_slot_args[s].active) {
+      const int st = bs->h_slot_args[s].gs_state;
       if (st == kGsEntry || st == kGsInPlace || st == kGsFlush) gs_mask |= 1u << s;
       if (st == kGsEntry) entry_mask |= 1u << s;
     }
   const uint32_t n_rows = n_nz + n_z;
   const uint32_t n_tiles = (n_rows + kApplyRows - 1) / kApplyRows;
-  const GsBlock whole{0u, n_nz, 0ull, (unsigned long long)P->m};
+  const GsBlock whole{0u, n_nz, 0ull, (unsigned long long)D->m};
   const bool cut = gs_mask && gs_blocks && n_gs_blocks > 1 && !backward;
   const GsBlock* blocks = cut ? gs_blocks : &whole;
   const int nb = cut ? n_gs_blocks : 1;
   uint32_t part_base = 0;
   for (int b = 0; b < nb; ++b) {
     const GsBlock& B = blocks[b];
-    PPRHIP_TRY(launch_dense_edges_bG<kBatch>(P, ci, flags, cstarts, P->c8[P->c8cur], P->acc8, B));
+    PPRHIP_TRY(launch_dense_edges_bG<kBatch>(P, ci, flags, cstarts, bs->c8[bs->c8cur], bs->acc8, B));
     // block boundaries are multiples of 256 row ordinals, so tiles never straddle; the rows without in-edges
     // follow the last block.  The last block's rows are read by nobody again in this sweep (the next sweep reads the
     // other array), so only the blocks before it write the current array in place.
@@ -2050,32 +2057,32 @@ int launch_dense_level_b8(pprhip_graph* P, bool backward, const GsBlock* gs_bloc
     const uint32_t quota = kApplyBlocks8 / (uint32_t)nb;
     const uint32_t grid = std::max(1u, std::min((t_hi - t_lo + kApplyGroups - 1) / kApplyGroups, quota));
     k_dense_apply_batch<<<dim3(grid), dim3(kApplyThreads), 0, P->stream>>>(
-          nz, n_nz, zr, n_z, P->acc8, P->out_rp, backward ? P->in_rp : nullptr, P->c8[P->c8cur], P->c8[P->c8cur ^ 1], t_lo,
-          t_hi, b == nb - 1 ? 0u : gs_mask, b == nb - 1 ? 0u : entry_mask, P->d_slot_args, cross, P->prep_bits,
-          P->blk_pack8, P->blk_dead8, P->blk_ndead8, part_base, kApplyBlocks8);
+          nz, n_nz, zr, n_z, bs->acc8, D->out_rp, backward ? D->in_rp : nullptr, bs->c8[bs->c8cur], bs->c8[bs->c8cur ^ 1], t_lo,
+          t_hi, b == nb - 1 ? 0u : gs_mask, b == nb - 1 ? 0u : entry_mask, bs->d_slot_args, cross, bs->prep_bits,
+          bs->blk_pack8, bs->blk_dead8, bs->blk_ndead8, part_base, kApplyBlocks8);
     PPRHIP_CHECK_HIP(hipGetLastError());
     part_base += grid;
   }
-  k_dense_reduce_batch<<<dim3(kBatch), dim3(1024), 0, P->stream>>>(P->blk_pack8, P->blk_dead8, P->blk_ndead8, part_base,
-                                                                   kApplyBlocks8, P->d_slot_args, P->sweep_out);
+  k_dense_reduce_batch<<<dim3(kBatch), dim3(1024), 0, P->stream>>>(bs->blk_pack8, bs->blk_dead8, bs->blk_ndead8, part_base,
+                                                                   kApplyBlocks8, bs->d_slot_args, bs->sweep_out);
   PPRHIP_CHECK_HIP(hipGetLastError());
   return PPRHIP_OK;
 }
 
 int launch_compact_prepared(pprhip_graph* g, int cbuf, int out_fbuf, unsigned long long* d_counter, bool backward) {
-  const uint32_t grid = grid_for(g->n, 1024, 1024);
+  const uint32_t grid = grid_for(g->gr->n, 1024, 1024);
   if (g->parent) {
-    pprhip_graph* P = g->parent;
+    const GraphData* D = g->gr;
     // the rows the batched sweep carries (launch_dense_level_b8): one bit each, per slot
-    const uint32_t n_rows = backward ? P->n_nz_o + P->n_z_o : P->n_nz + P->n_zin;
+    const uint32_t n_rows = backward ? D->n_nz_o + D->n_z_o : D->n_nz + D->n_zin;
     const uint32_t n_tiles = (n_rows + kApplyRows - 1) / kApplyRows;
     k_compact_bits<<<dim3(grid), dim3(256), 0, g->stream>>>(
-        n_rows, backward ? P->n_nz_o : P->n_nz, P->prep_bits + (size_t)g->slot_index * n_tiles,
-        backward ? P->nz_rows_o : P->nz_rows, backward ? P->z_rows_o : P->zin_rows, cview(g, cbuf),
-        backward ? g->in_rp : g->out_rp, g->F[out_fbuf], g->eoff[out_fbuf], g->cF, d_counter);
+        n_rows, backward ? D->n_nz_o : D->n_nz, g->parent->batch->prep_bits + (size_t)g->slot_index * n_tiles,
+        backward ? D->nz_rows_o : D->nz_rows, backward ? D->z_rows_o : D->zin_rows, cview(g, cbuf),
+        backward ? D->in_rp : D->out_rp, g->F[out_fbuf], g->eoff[out_fbuf], g->cF, d_counter);
   } else {
     k_compact_prepared<<<dim3(grid), dim3(256), 0, g->stream>>>(act_n(g), cview(g, cbuf), false,
-                                                                backward ? g->in_rp : g->out_rp, g->F[out_fbuf],
+                                                                backward ? g->gr->in_rp : g->gr->out_rp, g->F[out_fbuf],
                                                                 g->eoff[out_fbuf], g->cF, d_counter);
   }
   PPRHIP_CHECK_HIP(hipGetLastError());
@@ -2094,10 +2101,10 @@ static int reduce_partials(pprhip_graph* g, uint32_t n_blocks, int out_slot, int
 int launch_count_active(pprhip_graph* g, const PushArgs& a, int seed_kind, int out_slot) {
   const uint32_t grid = grid_for(act_n(g), 256 * 8, 1024);
   if (seed_kind == 0)
-    k_count_active<0><<<dim3(grid), dim3(256), 0, g->stream>>>(act_n(g), g->residue, g->out_rp, g->flags, g->armed,
+    k_count_active<0><<<dim3(grid), dim3(256), 0, g->stream>>>(act_n(g), g->residue, g->gr->out_rp, g->flags, g->armed,
                                                                g->blk_pack, &g->ctr->hist[kMaxBatch + 2], a);
   else
-    k_count_active<1><<<dim3(grid), dim3(256), 0, g->stream>>>(act_n(g), g->residue, g->out_rp, g->flags, g->armed,
+    k_count_active<1><<<dim3(grid), dim3(256), 0, g->stream>>>(act_n(g), g->residue, g->gr->out_rp, g->flags, g->armed,
                                                                g->blk_pack, &g->ctr->hist[kMaxBatch + 2], a);
   PPRHIP_CHECK_HIP(hipGetLastError());
   return reduce_partials(g, grid, out_slot, 0, false);
@@ -2114,16 +2121,16 @@ int launch_seed_list(pprhip_graph* g, const PushArgs& a, int seed_kind, int out_
   // workgroups: with sixteen queries on the chip, smaller launches do better (1 018 vs 946-977 queries/s)
   const uint32_t grid = grid_for(act_n(g), 1024, g->sync ? 1024 : 16384);
   if (seed_kind == 0)
-    k_seed_list<0><<<dim3(grid), dim3(256), 0, g->stream>>>(act_n(g), g->residue, g->out_rp, g->flags, g->F[out_fbuf],
+    k_seed_list<0><<<dim3(grid), dim3(256), 0, g->stream>>>(act_n(g), g->residue, g->gr->out_rp, g->flags, g->F[out_fbuf],
                                                             g->eoff[out_fbuf], d_counter, nullptr, a);
   else if (write_armed && !old_small_kernels()) {
     // (the one-pass form always rewrites the flags and the armed bits of every node: the round-start call)
     const uint32_t tiles = (act_n(g) + 256u * kSeedItems - 1) / (256u * kSeedItems);
-    k_seed_list_topk<<<dim3(std::max(1u, tiles)), dim3(256), 0, g->stream>>>(act_n(g), g->residue, g->out_rp, g->flags,
+    k_seed_list_topk<<<dim3(std::max(1u, tiles)), dim3(256), 0, g->stream>>>(act_n(g), g->residue, g->gr->out_rp, g->flags,
                                                                             g->F[out_fbuf], g->eoff[out_fbuf], d_counter,
                                                                             g->armed, a);
   } else
-    k_seed_list<1><<<dim3(grid), dim3(256), 0, g->stream>>>(act_n(g), g->residue, g->out_rp, g->flags, g->F[out_fbuf],
+    k_seed_list<1><<<dim3(grid), dim3(256), 0, g->stream>>>(act_n(g), g->residue, g->gr->out_rp, g->flags, g->F[out_fbuf],
                                                             g->eoff[out_fbuf], d_counter, write_armed ? g->armed : nullptr, a);
   PPRHIP_CHECK_HIP(hipGetLastError());
   return PPRHIP_OK;
@@ -2132,11 +2139,11 @@ int launch_seed_list(pprhip_graph* g, const PushArgs& a, int seed_kind, int out_
 int launch_seed_dense(pprhip_graph* g, const PushArgs& a, int seed_kind, int cbuf, int out_slot, int dead_slot) {
   const uint32_t grid = grid_for(act_n(g), 256 * 8, 1024);
   if (seed_kind == 0)
-    k_seed_dense<0><<<dim3(grid), dim3(256), 0, g->stream>>>(act_n(g), g->residue, g->reserve, g->out_rp, g->flags,
+    k_seed_dense<0><<<dim3(grid), dim3(256), 0, g->stream>>>(act_n(g), g->residue, g->reserve, g->gr->out_rp, g->flags,
                                                              cview(g, cbuf), g->blk_pack, g->blk_dead,
                                                              g->blk_ndead, a);
   else
-    k_seed_dense<1><<<dim3(grid), dim3(256), 0, g->stream>>>(act_n(g), g->residue, g->reserve, g->out_rp, g->flags,
+    k_seed_dense<1><<<dim3(grid), dim3(256), 0, g->stream>>>(act_n(g), g->residue, g->reserve, g->gr->out_rp, g->flags,
                                                              cview(g, cbuf), g->blk_pack, g->blk_dead,
                                                              g->blk_ndead, a);
   PPRHIP_CHECK_HIP(hipGetLastError());
@@ -2164,7 +2171,7 @@ int launch_sum_partial(pprhip_graph* g, const double* x, uint32_t n) {
 }
 
 int launch_permute_out(pprhip_graph* g, const double* x, double* out) {
-  k_permute_out<<<dim3(grid_for(g->n, 256, 4096)), dim3(256), 0, g->stream>>>(x, g->old2new, out, g->n);
+  k_permute_out<<<dim3(grid_for(g->gr->n, 256, 4096)), dim3(256), 0, g->stream>>>(x, g->gr->old2new, out, g->gr->n);
   PPRHIP_CHECK_HIP(hipGetLastError());
   return PPRHIP_OK;
 }
@@ -2210,7 +2217,7 @@ int launch_seed_land_sparse(pprhip_graph* g, const PushArgs& a, int fbuf, int le
   const uint32_t n_all = sd->n_live + sd->n_dead;
   const uint32_t grid = grid_for(n_all, 256, 1024);
   DISPATCH_MODE(a.mode, k_seed_land_sparse<M><<<dim3(grid), dim3(256), 0, g->stream>>>(
-                            sd->id, sd->w, sd->n_live, n_all, sd->done, g->out_ext, g->in_rp, g->residue, g->reserve,
+                            sd->id, sd->w, sd->n_live, n_all, sd->done, g->gr->out_ext, g->gr->in_rp, g->residue, g->reserve,
                             g->flags, g->armed, g->F[fbuf ^ 1], g->eoff[fbuf ^ 1], g->ctr, level, dense_thresh, dead_slot,
                             pk0, a));
   PPRHIP_CHECK_HIP(hipGetLastError());

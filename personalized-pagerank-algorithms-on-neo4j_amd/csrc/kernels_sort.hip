@@ -106,7 +106,7 @@ int finalize_rows_device(pprhip_graph* g, const TripleRec* rec, u64 count, int k
                          DeviceRows* out) {
   *out = DeviceRows();
   if (count == 0) return PPRHIP_OK;
-  const uint32_t n = g->n;
+  const uint32_t n = g->gr->n;
   if (count >= (1ull << 31)) {
     set_error("index: %llu entries exceed the 2^31 the device sort takes", count);
     return PPRHIP_ERR_INVALID;

@@ -504,9 +504,9 @@ int init_kernels_walk() {  // loads this file's code object on the current devic
 }
 
 int launch_build_walk_rec(pprhip_graph* g) {
-  if (g->m == 0) return PPRHIP_OK;
-  hipLaunchKernelGGL(k_build_walk_rec, dim3(4096), dim3(256), 0, g->stream, (unsigned long long)g->m, g->out_ci,
-                     g->out_ext, reinterpret_cast<uint4*>(g->walk_rec));
+  if (g->gr->m == 0) return PPRHIP_OK;
+  hipLaunchKernelGGL(k_build_walk_rec, dim3(4096), dim3(256), 0, g->stream, (unsigned long long)g->gr->m, g->gr->out_ci,
+                     g->gr->out_ext, reinterpret_cast<uint4*>(g->gr->walk_rec));
   PPRHIP_CHECK_HIP(hipGetLastError());
   return PPRHIP_OK;
 }
@@ -530,14 +530,14 @@ int launch_mc_plan(pprhip_graph* g, int variant, double alpha, double rsum, doub
   if (variant == 1 && omega_dev > 0.0 && np > 0) {
     const uint32_t tiles = (n + 256u * kPlanItems - 1) / (256u * kPlanItems);
     hipLaunchKernelGGL(k_mc_plan_topk, dim3(std::max(1u, tiles)), dim3(256), 0, g->stream, n, g->residue, alpha, omega_dev,
-                       g->partial, np, g->out_ext, g->new2old, plan_rec_of(g, phase), g->ctr, cell, next_cell, copy_src,
+                       g->partial, np, g->gr->out_ext, g->gr->new2old, plan_rec_of(g, phase), g->ctr, cell, next_cell, copy_src,
                        copy_dst);
   } else if (variant == 0)
     hipLaunchKernelGGL(k_mc_plan<0>, dim3(grid), dim3(256), 0, g->stream, n, g->residue, target, alpha, rsum, nrw,
-                       omega_dev, g->out_ext, g->new2old, plan_rec_of(g, phase), g->ctr, cell, next_cell, copy_src, copy_dst);
+                       omega_dev, g->gr->out_ext, g->gr->new2old, plan_rec_of(g, phase), g->ctr, cell, next_cell, copy_src, copy_dst);
   else
     hipLaunchKernelGGL(k_mc_plan<1>, dim3(grid), dim3(256), 0, g->stream, n, g->residue, target, alpha, rsum, nrw,
-                       omega_dev, g->out_ext, g->new2old, plan_rec_of(g, phase), g->ctr, cell, next_cell, copy_src, copy_dst);
+                       omega_dev, g->gr->out_ext, g->gr->new2old, plan_rec_of(g, phase), g->ctr, cell, next_cell, copy_src, copy_dst);
   PPRHIP_CHECK_HIP(hipGetLastError());
   return PPRHIP_OK;
 }
@@ -549,13 +549,13 @@ int launch_mc_walk(pprhip_graph* g, double alpha, uint64_t seed, uint32_t stream
   // system from a few waves per CU on, tools/micro/chain_rate.hip)
   // a slot of a threaded batch shares the chip with fifteen others: few waves per CU, like a walk phase beside sweeps
   // (batched top-k on R-MAT 22: 851 queries/s at 16 waves per CU, 961 / 1 026 / 905 at 2 / 4 / 8)
-  uint32_t grid = (uint32_t)g->n_cus * (g->walk_waves ? g->walk_waves
+  uint32_t grid = (uint32_t)g->gr->n_cus * (g->walk_waves ? g->walk_waves
                                         : g->sync   ? kWalkWavesBeside
                                                     : kWalkWavesPerCu);
   if (g->walk_hint) grid = (uint32_t)std::min<unsigned long long>(grid, std::max<unsigned long long>((g->walk_hint + 63) / 64, 1ull));
   g->walk_hint = 0;
   hipLaunchKernelGGL(k_mc_walk, dim3(grid), dim3(64), 0, g->stream, plan_rec_of(g, g->mc_last_plan),
-                     reinterpret_cast<const uint4*>(g->walk_rec), target, alpha, (uint32_t)seed, (uint32_t)(seed >> 32), stream,
+                     reinterpret_cast<const uint4*>(g->gr->walk_rec), target, alpha, (uint32_t)seed, (uint32_t)(seed >> 32), stream,
                      no_zero_hop, g->ctr, (int)(g->mc_last_plan % 3u));
   PPRHIP_CHECK_HIP(hipGetLastError());
   return PPRHIP_OK;
@@ -567,7 +567,7 @@ int launch_walk_batch(pprhip_graph* g, const int32_t* d_starts, const uint64_t* 
   uint64_t b = (count + 255) / 256;
   const uint32_t grid = (uint32_t)(b > 4096 ? 4096 : b);
   hipLaunchKernelGGL(k_walk_batch, dim3(grid), dim3(256), 0, g->stream, d_starts,
-                     (const unsigned long long*)d_idx, (unsigned long long)count, g->out_ext, g->walk_rec, g->new2old, alpha,
+                     (const unsigned long long*)d_idx, (unsigned long long)count, g->gr->out_ext, g->gr->walk_rec, g->gr->new2old, alpha,
                      (uint32_t)seed, (uint32_t)(seed >> 32), stream, no_zero_hop, d_term, d_steps);
   PPRHIP_CHECK_HIP(hipGetLastError());
   return PPRHIP_OK;
@@ -577,8 +577,8 @@ int launch_mc_pure(pprhip_graph* g, int32_t src, uint64_t n_walks, double alpha,
                    double* target) {
   const uint32_t phase = g->mc_phase++;
   g->mc_last_plan = phase;
-  hipLaunchKernelGGL(k_plan_single, dim3(1), dim3(1), 0, g->stream, src, inc, (unsigned long long)n_walks, g->out_ext,
-                     g->new2old, plan_rec_of(g, phase), g->ctr, (int)(phase % 3u), (int)((phase + 1u) % 3u));
+  hipLaunchKernelGGL(k_plan_single, dim3(1), dim3(1), 0, g->stream, src, inc, (unsigned long long)n_walks, g->gr->out_ext,
+                     g->gr->new2old, plan_rec_of(g, phase), g->ctr, (int)(phase % 3u), (int)((phase + 1u) % 3u));
   PPRHIP_CHECK_HIP(hipGetLastError());
   return launch_mc_walk(g, alpha, seed, 0, 0, target);
 }

@@ -59,7 +59,7 @@ int seed_plan(pprhip_graph* g, const int32_t* seeds, const double* weights, int 
               SeedTable& t) {
   std::vector<int32_t> ids;
   std::vector<double> p;
-  PPRHIP_TRY(seed_normalize(g->n, seeds, weights, k, fn, ids, p));
+  PPRHIP_TRY(seed_normalize(g->gr->n, seeds, weights, k, fn, ids, p));
   struct E {
     int32_t v;
     double p;
@@ -67,7 +67,7 @@ int seed_plan(pprhip_graph* g, const int32_t* seeds, const double* weights, int 
   std::vector<E> live, dead;
   double D = 0.0;
   for (size_t i = 0; i < ids.size(); ++i) {
-    const int32_t v = g->h_old2new[ids[i]];
+    const int32_t v = g->gr->h_old2new[ids[i]];
     if (hdeg_out(g, v) == 0) {
       dead.push_back({v, p[i]});
       D += p[i];
@@ -114,9 +114,9 @@ int seed_upload(pprhip_graph* g, SeedTable& plan) {
   SeedTable& t = *g->seeds;
   const uint32_t count = plan.n_live + plan.n_dead;
   if (!t.w_node) {  // (all-zero from here on: each upload clears the entries of the set before)
-    PPRHIP_TRY(alloc_dev((void**)&t.w_node, sizeof(double) * (size_t)g->n));
+    PPRHIP_TRY(alloc_dev((void**)&t.w_node, sizeof(double) * (size_t)g->gr->n));
     PPRHIP_TRY(alloc_dev((void**)&t.done, sizeof(unsigned int)));
-    PPRHIP_CHECK_HIP(hipMemsetAsync(t.w_node, 0, sizeof(double) * (size_t)g->n, g->stream));
+    PPRHIP_CHECK_HIP(hipMemsetAsync(t.w_node, 0, sizeof(double) * (size_t)g->gr->n, g->stream));
     PPRHIP_CHECK_HIP(hipMemsetAsync(t.done, 0, sizeof(unsigned int), g->stream));
   }
   PPRHIP_TRY(launch_seed_clear(g, t.n_live));  // the set before's landing weights, while its ids are still in the table
