@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py — single-source FORA queries/sec on a synthetic R-MAT graph (BASELINE.json metric).
 
-    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR]
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
 
 Workload (N = 1): R-MAT scale 22 (n = 4 194 304, m = 67 108 864, generator seed 1), single-source FORA with
 alpha = 0.15, eps = 0.5.  A *step* is one batch of `--queries-per-step` sources drawn uniformly (seed 2) from the
@@ -10,8 +10,15 @@ computations, 16 of them in flight, every query's whole-graph vector kept in a d
 (what getWholeGraphPPR() serves, Gen_Util.java:309) and its top-32 selected on the device.  Dead-end sources are
 NOT drawn: they return at once in the reference (Forward_Push.java:72-76) and here, and counting them (the
 reference's harness does, Gen_Util.java:99-107; 52 % of this graph's nodes) would inflate the rate 2.1x; the rate
-with them in the mix is reported beside the headline as `value_uniform_sources`.  The graph is lifted into HBM
-once before the timed region.  `value` = queries / second over all ranks.
+with them in the mix is reported beside the headline as `value_uniform_sources` (--full).  The graph is lifted into
+HBM once before the timed region.  `value` = queries / second over all ranks.
+
+A plain run does what the headline needs and nothing else: it generates and lifts the graph, runs the warm-up and
+timed steps, writes --dump-outputs, checks the results and prints the line - the headline, what the timed region
+counted, and a `roofline` on compulsory bytes.  `--full` adds everything else described below: the per-class kernel
+times of one more step, the samples of the other workloads, the counter, trace and A/B child passes, the CPU baselines
+and, at N > 1, config #4's strong scaling and `all_pair_scaling`; `--no-extras`, `--no-pmc`, `--no-rmat24` and
+`--no-cpu-baseline` leave parts of it out.
 
 Before the line is printed the results of the last timed step are checked on every rank: every vector's mass is
 1 +- 1e-9 (device-side sum), every top-32 is sorted and consistent with the fetched vector.  A run that fails the
@@ -22,12 +29,12 @@ batch per step (weak scaling, no data-path collective) and the per-step top-k bl
 library's own entry point (pprhip_comm_create + pprhip_topk_gather: grouped ncclSend / ncclRecv inside libpprhip.so,
 the exchange Gen_Util.java:208-232's loop needs when it is sharded); torch.distributed only carries the barrier and
 the max-over-ranks of the clock.  The library's gather is probed once before the warm-up; should it fail on any
-rank, all ranks agree to gather with torch.distributed instead and the line's `config.sharding` says why.  `all_pair_scaling` reports the path's other workload, All-Pair-Backward-Search over
+rank, all ranks agree to gather with torch.distributed instead and the line's `config.sharding` says why.  `all_pair_scaling` (--full) reports the path's other workload, All-Pair-Backward-Search over
 all n targets, at the same N (strong scaling; the exchange by owner of the source runs inside the library over RCCL;
 every rank's share runs in a watched child process, so a collective that hangs or faults costs that sample, not the
 line).
 
-Extra objects on the JSON line:
+Extra objects on the JSON line of a --full run:
   `roofline`  dominant kernel class (HIP-event time on the engine's stream).  `achieved` / `frac`: the bytes the
               memory-side counters saw per launch over the launch's duration, against the 8 TB/s HBM peak - measured
               in this run by `rocprofv3 --pmc` child passes of this build (FETCH_SIZE, WRITE_SIZE, TCC hit / miss; one
@@ -36,7 +43,7 @@ Extra objects on the JSON line:
               `frac_compulsory`: the same with every byte the sweep has to move counted once (a lower bound of its
               traffic: <= 1 by construction; traffic / compulsory = how often bytes are re-moved); `frac_model`:
               SURVEY 8(d)'s per-query gather model (counts gathers L2 / LDS serve; can exceed 1; kept for comparison
-              with rounds 1-2).  Without counters (`--no-pmc`) `frac` falls back to the compulsory figure.
+              with rounds 1-2).  Without counters (a plain run, `--no-pmc`) `frac` is the compulsory figure.
   `cpu_baseline`  the reference's algorithm on the host cores (rank 0, N = 1), in a background process: while the GPU
               measurements go on, the hash-map-shaped faithful port run to the end of two queries (one thread each,
               both times printed) and the dense-array port on two sources; after them, the array port on every core this job may use (its cgroup
@@ -45,11 +52,12 @@ Extra objects on the JSON line:
 blocks it gathered from every rank) as DIR/<name>.npy in float64, 64 MB at most (dump_outputs):
 with the same arguments the graph, the sources and the seeds are the same from run to run, so two builds can be
 compared output for output.  `ms_per_step` is the wall time of one timed step.
-After the timed region, at N = 1: `one_query_at_a_time` (the drop-in path, pprhip_fora_single_source), `topk_sample`
+After the timed region, at N = 1 with --full: `one_query_at_a_time` (the drop-in path, pprhip_fora_single_source), `topk_sample`
 (FORA top-32), `all_pair_sample` (All-Pair-Backward-Search on 2^18 targets) and `all_pair_rmat24` (config #5's graph
 on one GPU, in a child process), each with its own `roofline` incl. counter traffic.
 """
 import argparse
+import atexit
 import csv
 import glob
 import importlib
@@ -84,10 +92,17 @@ RANDOM_ATOMIC_ROOF_G = 20.0   # random fp64 read-modify-writes per second, any f
                               # (tools/micro/atomic_rate.hip, profiles/r03_atomic_rate.txt)
 
 
+GRAPH_DIR_ENV = "PPRHIP_BENCH_GRAPH_DIR"
+
+
 def load_host(pkg, scale):
-    """The R-MAT host CSR (generator seed 1); cached in /tmp so that the child processes of one run (counter passes,
-    All-Pair children, CPU baseline) do not generate it again."""
-    path = "/tmp/pprhip_rmat%d_seed1.npz" % scale
+    """The R-MAT host CSR (generator seed 1).  A --full run keeps it in a directory of its own (named to its child
+    processes in PPRHIP_BENCH_GRAPH_DIR, removed when the run ends) so that its counter passes, All-Pair children and
+    CPU baseline do not generate it again; no run reads a graph an earlier run wrote."""
+    graph_dir = os.environ.get(GRAPH_DIR_ENV)
+    if not graph_dir:
+        return pkg.HostCsr.rmat(scale, 16, seed=1)
+    path = os.path.join(graph_dir, "rmat%d_seed1.npz" % scale)
     if os.path.exists(path):
         try:
             z = np.load(path)
@@ -145,10 +160,17 @@ def main():
     ap.add_argument("--queries-per-step", type=int, default=128)
     ap.add_argument("--mode", choices=["batch", "single"], default="batch")
     ap.add_argument("--rounds", type=int, default=0, help="FORA threshold rounds (0 = cost model)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-extras", action="store_true", help="skip the one-query-at-a-time, top-k and All-Pair samples")
-    ap.add_argument("--no-pmc", action="store_true", help="skip the rocprofv3 --pmc child passes (roofline traffic)")
-    ap.add_argument("--no-rmat24", action="store_true", help="skip the R-MAT 24 All-Pair child sample")
+    ap.add_argument("--full", action="store_true",
+                    help="measure everything beyond the headline too: per-class kernel times, the samples of the other "
+                         "workloads, counter and trace passes, the CPU baselines and, at N > 1, config #4's strong "
+                         "scaling and All-Pair scaling (the --no-* options below leave parts of it out)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baselines")
+    ap.add_argument("--no-extras", action="store_true",
+                    help="with --full: skip the one-query-at-a-time, top-k and All-Pair samples")
+    ap.add_argument("--no-pmc", action="store_true",
+                    help="with --full: skip the counter, kernel-trace and A/B child passes (roofline traffic, "
+                         "stream occupancy, sweeps alone)")
+    ap.add_argument("--no-rmat24", action="store_true", help="with --full: skip the R-MAT 24 All-Pair child sample")
     ap.add_argument("--rmat24-targets", type=int, default=1 << 24)
     ap.add_argument("--pmc-child", action="store_true", help=argparse.SUPPRESS)
     ap.add_argument("--trace-child", action="store_true", help=argparse.SUPPRESS)
@@ -185,6 +207,10 @@ def main():
     world = int(os.environ.get("WORLD_SIZE", "1"))
     if world != args.gpus and world > 1:
         raise SystemExit("WORLD_SIZE=%d does not match --gpus %d" % (world, args.gpus))
+    samples = args.full and not args.no_extras
+    if args.full:  # one copy of each graph for this run and its child processes
+        os.environ[GRAPH_DIR_ENV] = tempfile.mkdtemp(prefix="pprhip_bench_graphs_")
+        atexit.register(shutil.rmtree, os.environ[GRAPH_DIR_ENV], True)
 
     import torch  # first: libpprhip.so then binds to the HIP runtime torch already loaded
     import torch.distributed as dist
@@ -209,8 +235,8 @@ def main():
     # and top-k samples take their rates without them (as a caller gets them by default) and their class times in a
     # second pass.
     # Round 5: the timed region times the dense sweeps only (level 2: two records per sweep of 1.6 ms - the roofline's
-    # class) and counts every other class; one more step outside the timed region runs with every class timed and
-    # gives the per-class breakdown (kernel_ms_per_query, other_kernels).  The batch driver is one host thread that
+    # class) and counts every other class; with --full, one more step outside the timed region runs with every class
+    # timed and gives the per-class breakdown (kernel_ms_per_query, other_kernels).  The batch driver is one host thread that
     # feeds three streams: ~60 records per query on the small kernels' stream cost it 1.5 % (347-348 -> 353).
     # PPRHIP_BENCH_TIMING=0 / 1: developer A/B (no records at all / every class in the timed region, as until round 4).
     bench_timing = os.environ.get("PPRHIP_BENCH_TIMING", "2")
@@ -225,7 +251,7 @@ def main():
     live_frac_graph = live_ids.size / host.n
     q = args.queries_per_step
     total_steps = args.warmup + args.steps
-    extra_step = 1 if args.mode == "batch" else 0  # (the step with every class timed, behind the timed region)
+    extra_step = 1 if args.mode == "batch" else 0  # (the step with every class timed, behind the timed region; --full)
     rng = np.random.default_rng(2 + 7919 * rank)
     srcs = live_draw(rng, live_ids, (total_steps + extra_step, q))
 
@@ -236,7 +262,7 @@ def main():
     # host-only work that runs beside the GPU measurements: the CPU baselines (a process of their own: they take
     # minutes of CPU time and use every core for a while) and the generation of config #5's graph
     cpu_child = None
-    if solo and not args.no_cpu_baseline:
+    if solo and args.full and not args.no_cpu_baseline:
         cpu_child = start_cpu_baseline(args, srcs[args.warmup:].ravel())
     r24_child = None  # (started behind the timed region: its graph generation uses every core for a few seconds)
     if rank == 0:
@@ -371,18 +397,19 @@ def main():
         dumped = dump_outputs(args.dump_outputs, srcs[last["step"]], last, store, host.n,
                               gathered=(gathered or gathered_dump) if world > 1 else None)
     acc_timed = acc
+    acc_classes = acc
     if extra_step and bench_timing == "2":
-        # per-class times of the same workload: one more step, every class timed, outside the timed region
-        acc = {k: (list(v) if isinstance(v, list) else v) for k, v in acc.items()}
-        for k in acc:
-            acc[k] = [type(x)(0) for x in acc[k]] if isinstance(acc[k], list) else type(acc[k])(0)
-        was_t = pkg.set_kernel_timing(True)
-        run_step(total_steps, True)  # (the self-check below then looks at this step's results: they are what the store holds)
-        pkg.set_kernel_timing(was_t)
-        acc_classes, acc = acc, acc_timed
-    else:
-        acc_classes = acc
-    if solo and not args.no_extras and not args.no_rmat24:
+        acc_classes = None  # (the timed region times the sweeps only: the other classes' times need the step below)
+        if args.full:
+            # per-class times of the same workload: one more step, every class timed, outside the timed region
+            acc = {k: (list(v) if isinstance(v, list) else v) for k, v in acc.items()}
+            for k in acc:
+                acc[k] = [type(x)(0) for x in acc[k]] if isinstance(acc[k], list) else type(acc[k])(0)
+            was_t = pkg.set_kernel_timing(True)
+            run_step(total_steps, True)  # (the self-check below then looks at this step's results: they are what the store holds)
+            pkg.set_kernel_timing(was_t)
+            acc_classes, acc = acc, acc_timed
+    if solo and samples and not args.no_rmat24:
         r24_child = start_rmat24(args)
     check = None
     if args.mode == "batch" and last:
@@ -395,7 +422,7 @@ def main():
     # takes the sources i mod N = g), every rank under pprhip_tuning_batch_for(its share), the 50 x 32 pairs gathered on
     # rank 0 through the library when its communicator stands; beside the weak-scaling `value`, outside the timed region
     config4_strong = None
-    if world > 1 and args.mode == "batch" and not args.no_extras:
+    if world > 1 and args.mode == "batch" and samples:
         try:
             all50 = live_draw(np.random.default_rng(50), live_ids, 50)          # the same 50 sources on every rank
             mine = np.ascontiguousarray(all50[rank::world], dtype=np.int32)
@@ -424,7 +451,7 @@ def main():
         comm.close()
 
     all_pair_scaling = None
-    if not args.no_extras and args.mode == "batch":
+    if samples and args.mode == "batch":
         all_pair_scaling = all_pair_scaling_sample(pkg, args, dist, torch, rank, world, local_rank, xdev)
         if rank == 0:
             note("All-Pair scaling sample done")
@@ -442,8 +469,25 @@ def main():
         is_sweep = dom in (1, 5)
         comp_bytes = acc["sweep_min_bytes"] / max(1, dom_n) if is_sweep else dom_bytes / max(1, dom_n)
         comp = comp_bytes / 1e9 / (avg_us / 1e6) if avg_us > 0 else 0.0
-        nq_c = max(1, acc_classes["queries"])
-        kernel_ms = sum(acc_classes["class_ms"][c] for c in range(1, 8)) * (nq / nq_c)  # (scaled to the timed region's queries)
+        class_fields, class_roofline = {}, {}
+        if acc_classes is not None:
+            nq_c = max(1, acc_classes["queries"])
+            kernel_ms = sum(acc_classes["class_ms"][c] for c in range(1, 8)) * (nq / nq_c)  # (scaled to the timed region's queries)
+            class_fields = {
+                "kernel_ms_per_query": {pkg.KERNEL_NAMES[c]: round(acc_classes["class_ms"][c] / nq_c, 3)
+                                        for c in (1, 2, 3, 5, 6) if acc_classes["class_launches"][c]},
+                "kernel_class_time": host_gap(1e3 * elapsed / (args.steps * q), kernel_ms / nq),
+                "walk_steps_G_per_s": round(acc_classes["walk_steps"] / (acc_classes["class_ms"][3] / 1e3) / 1e9, 2)
+                if acc_classes["class_ms"][3] > 0 else None}
+            class_roofline = {
+                "other_kernels": {
+                    pkg.KERNEL_NAMES[c]: {
+                        "ms": round(acc_classes["class_ms"][c], 3), "launches": acc_classes["class_launches"][c],
+                        "achieved_GBps": round((acc_classes["class_bytes"][c] / 1e9) / (acc_classes["class_ms"][c] / 1e3), 1)
+                        if acc_classes["class_ms"][c] > 0 else 0.0}
+                    for c in (1, 2, 3, 5) if c != dom and acc_classes["class_launches"][c]},
+                "other_kernels_note": "class times of one more step of the same workload with every class timed, outside "
+                                      "the timed region (which times the sweeps only)" if acc_classes is not acc else None}
         roofline = {
             "bound": "hbm", "kernel": pkg.KERNEL_NAMES[dom], "achieved": round(comp, 1), "peak": HBM_PEAK_GBS,
             "unit": "GB/s", "frac": round(comp / HBM_PEAK_GBS, 4), "frac_basis": "compulsory bytes (no counters in this run)",
@@ -466,14 +510,7 @@ def main():
             "useful_edge_fraction": round(useful, 4),
             "useful_note": "frontier edges of the levels run as sweeps / (sweeps x m): the share of a sweep's edge "
                            "gathers that carry a pushed residue",
-            "other_kernels": {
-                pkg.KERNEL_NAMES[c]: {
-                    "ms": round(acc_classes["class_ms"][c], 3), "launches": acc_classes["class_launches"][c],
-                    "achieved_GBps": round((acc_classes["class_bytes"][c] / 1e9) / (acc_classes["class_ms"][c] / 1e3), 1)
-                    if acc_classes["class_ms"][c] > 0 else 0.0}
-                for c in (1, 2, 3, 5) if c != dom and acc_classes["class_launches"][c]},
-            "other_kernels_note": "class times of one more step of the same workload with every class timed, outside the "
-                                  "timed region (which times the sweeps only)" if acc_classes is not acc else None,
+            **class_roofline,
         }
         out = {
             "metric": "single-source PPR queries/sec (FORA, alpha=0.15, eps=0.5)", "value": round(value, 3),
@@ -494,14 +531,10 @@ def main():
             "live_node_fraction_of_graph": round(live_frac_graph, 4),
             "value_vectors_resident": round(value, 3),
             "avg_rounds": round(acc["rounds"] / nq, 2),
-            "kernel_ms_per_query": {pkg.KERNEL_NAMES[c]: round(acc_classes["class_ms"][c] / nq_c, 3)
-                                    for c in (1, 2, 3, 5, 6) if acc_classes["class_launches"][c]},
-            "kernel_class_time": host_gap(1e3 * elapsed / (args.steps * q), kernel_ms / nq),
+            **class_fields,
             "dense_levels_per_query": round(acc["dense_levels"] / nq, 1),
             "levels_per_query": round(acc["levels"] / nq, 1),
             "walks_per_query": int(acc["walks"] / nq),
-            "walk_steps_G_per_s": round(acc_classes["walk_steps"] / (acc_classes["class_ms"][3] / 1e3) / 1e9, 2)
-            if acc_classes["class_ms"][3] > 0 else None,
             "walk_lanes_per_load": round(acc["walk_load_lanes"] / max(1, acc["walk_loads"]), 2),
             "graph_lift_s": {"generate_and_csr": round(t_gen, 2), "upload_and_tile": round(t_lift, 2)},
             "self_check": check,
@@ -513,7 +546,7 @@ def main():
             out["config4_strong_scaling"] = config4_strong
         if dumped is not None:
             out["dumped_outputs"] = dumped
-        extras = solo and not args.no_extras
+        extras = solo and samples
         if extras:
             out.update(q50_sample(pkg, g, store, rng, live_ids, conf, value))
             out["config4_share_rates"] = config4_share_sample(pkg, g, store, rng, live_ids, conf)
@@ -533,7 +566,7 @@ def main():
         if r24_child is not None:
             out["all_pair_rmat24"] = finish_rmat24(r24_child)
             note("R-MAT 24 All-Pair child done")
-        if solo and not args.no_pmc:
+        if solo and args.full and not args.no_pmc:
             apply_counters(out, pmc_traffic(args, host), avg_us, extras)
             note("counter passes done")
             if r24_child is not None and "error" not in out["all_pair_rmat24"]:
@@ -1546,7 +1579,7 @@ def sweeps_alone(args, roofline):
     if roofline.get("kernel") != "dense_pull_batch":
         return
     cmd = [sys.executable, os.path.abspath(__file__), "--steps", "2", "--warmup", "1", "--scale", str(args.scale),
-           "--queries-per-step", str(args.queries_per_step), "--no-cpu-baseline", "--no-pmc", "--no-extras", "--no-rmat24"]
+           "--queries-per-step", str(args.queries_per_step)]
     if args.tuning:
         cmd += ["--tuning", args.tuning]
     # (the two switches are measurement switches: read by libpprhip_hooks.so only - the same sources with the test hooks)

@@ -6,7 +6,7 @@ tag=$1; shift
 root=${GRAFT_REPO_ROOT:-$(pwd)}; out=$root/gpurun_out
 : > $out/${tag}_tune.txt
 for t in "$@"; do
-  timeout -k 10 300 python3 $root/bench.py --steps 4 --warmup 1 --no-cpu-baseline --no-pmc --no-extras --no-rmat24 ${t:+--tuning $t} > /tmp/tune.log 2>&1
+  timeout -k 10 300 python3 $root/bench.py --steps 4 --warmup 1 --full --no-cpu-baseline --no-pmc --no-extras --no-rmat24 ${t:+--tuning $t} > /tmp/tune.log 2>&1
   python3 - "$t" >> $out/${tag}_tune.txt <<'PY'
 import json, sys
 line = [l for l in open("/tmp/tune.log") if l.startswith("{")]
