@@ -414,9 +414,9 @@ int pprhip_fora_batch_topk(pprhip_graph_t* g, const int32_t* srcs, int q, int k,
  * (DESIGN.md §2 "Seed sets").  The walks of FORA are the single-source path's: they start at residue nodes with the
  * same counters and restart at their start node at a dead end (Monte_Carlo.java:87-90; the same walk quirk as the
  * single-source path).  A set of one seed reduces to the single-source call (same levels, rounds and walks, reserve
- * up to fp64 addition order).  One query at a time per handle; pprhip_get_reserve / _get_residue / pprhip_topk_select
- * work on the result as after the single-source calls.  Generalized calls: pprhip_forward_push, pprhip_fora_single_source,
- * pprhip_fora_topk. */
+ * up to fp64 addition order).  One query at a time per handle (many per call: the batched calls below);
+ * pprhip_get_reserve / _get_residue / pprhip_topk_select work on the result as after the single-source calls.
+ * Generalized calls: pprhip_forward_push, pprhip_fora_single_source, pprhip_fora_topk. */
 /* pprhip_forward_push from p; outputs as there. */
 int pprhip_forward_push_seeds(pprhip_graph_t* g, const int32_t* seeds, const double* weights, int n_seeds,
                               double alpha, double rmax, double* reserve_out, double* residue_out,
@@ -431,6 +431,25 @@ int pprhip_fora_seeds(pprhip_graph_t* g, const int32_t* seeds, const double* wei
 int pprhip_fora_topk_seeds(pprhip_graph_t* g, const int32_t* seeds, const double* weights, int n_seeds,
                            double eps, const pprhip_fora_conf_t* conf, uint64_t seed, int32_t* ids_out,
                            double* vals_out, int cap, int* n_out, double* reserve_out, pprhip_stats_t* stats);
+/* Batched seed sets: q sets in one call, kBatch (16) of them in flight on the handle's batch workspaces, their dense
+ * levels sharing the batched sweeps as the single-source batched calls' do.  The sets are described like a CSR:
+ * offsets holds q + 1 entries, offsets[0] == 0, non-decreasing; set i is seeds[offsets[i] .. offsets[i + 1]) with the
+ * same slice of weights (weights NULL: every set uniform).  Every set is checked by the rules above before any device
+ * work - the message names the set (", set i: ") - and so are the offsets; a failed check or q < 0 is
+ * PPRHIP_ERR_INVALID with the handle untouched; q == 0 is an empty call.  While a query stream is open on the handle:
+ * PPRHIP_ERR_STATE, as for every call. */
+/* Query i is pprhip_fora_seeds(set i, eps, conf, seed, n_rounds): the same rounds, levels, dense levels and walks, the
+ * vector equal up to fp64 addition order.  keep / reserve_out / k / ids_out / vals_out / n_out / per_query /
+ * stats_sum as in pprhip_fora_batch_single_source_resident. */
+int pprhip_fora_batch_seeds(pprhip_graph_t* g, const int32_t* seeds, const double* weights, const uint64_t* offsets,
+                            int q, double eps, const pprhip_fora_conf_t* conf, uint64_t seed, int n_rounds,
+                            pprhip_results_t* keep, double* reserve_out, int k, int32_t* ids_out, double* vals_out,
+                            int* n_out, pprhip_stats_t* per_query, pprhip_stats_t* stats_sum);
+/* Query i is pprhip_fora_topk_seeds(set i, eps, conf, seed + i) under the conf pprhip_fora_batch_topk builds
+ * (pprhip_conf_fora_topk(n, m, k, alpha)); ids_out / vals_out (q*k) and stats_sum as in pprhip_fora_batch_topk. */
+int pprhip_fora_batch_topk_seeds(pprhip_graph_t* g, const int32_t* seeds, const double* weights,
+                                 const uint64_t* offsets, int q, int k, double eps, double alpha, uint64_t seed,
+                                 int32_t* ids_out, double* vals_out, pprhip_stats_t* stats_sum);
 
 /* ---------------------------------------------------------------- backward search (a8, a9) */
 /* Backward_Search.backward_search_whole_graph(Long t) (Backward_Search.java:38-100). */

@@ -84,7 +84,7 @@ EXPORTS = [
     "pprhip_device_memory", "pprhip_graph_lift_host", "pprhip_lift_array", "pprhip_lift_destroy",
     "pprhip_fora_stream_open", "pprhip_fora_stream_submit", "pprhip_fora_stream_wait", "pprhip_fora_stream_close",
     "pprhip_set_kernel_timing", "pprhip_shard_target_cuts", "pprhip_forward_push_seeds", "pprhip_fora_seeds",
-    "pprhip_fora_topk_seeds",
+    "pprhip_fora_topk_seeds", "pprhip_fora_batch_seeds", "pprhip_fora_batch_topk_seeds",
 ]
 COMM_ID_BYTES = 128
 
@@ -144,6 +144,9 @@ def lib():
     L.pprhip_forward_push_seeds.argtypes = [vp, vp, vp, ci, dbl, dbl, vp, vp, P(dbl), P(Stats)]
     L.pprhip_fora_seeds.argtypes = [vp, vp, vp, ci, dbl, P(ForaConf), u64, ci, vp, P(Stats)]
     L.pprhip_fora_topk_seeds.argtypes = [vp, vp, vp, ci, dbl, P(ForaConf), u64, vp, vp, ci, P(ci), vp, P(Stats)]
+    L.pprhip_fora_batch_seeds.argtypes = [vp, vp, vp, vp, ci, dbl, P(ForaConf), u64, ci, vp, vp, ci, vp, vp, vp, vp,
+                                          P(Stats)]
+    L.pprhip_fora_batch_topk_seeds.argtypes = [vp, vp, vp, vp, ci, ci, dbl, dbl, u64, vp, vp, P(Stats)]
     L.pprhip_fora_topk.argtypes = [vp, i32, dbl, P(ForaConf), u64, vp, vp, ci, P(ci), vp, P(Stats)]
     L.pprhip_topk_select.argtypes = [vp, ci, vp, vp, ci, P(ci), P(dbl), P(Stats)]
     L.pprhip_monte_carlo.argtypes = [vp, i32, dbl, P(ForaConf), u64, vp, P(Stats)]
@@ -215,6 +218,30 @@ def _seed_arrays(seeds, weights):
     if w is not None and w.size != s.size:
         raise ValueError("weights: %d entries for %d seeds" % (w.size, s.size))
     return s, w
+
+
+def _seed_set_arrays(sets, weights):
+    """q seed sets as the batched C calls take them: (seeds int32, weights float64 | None, offsets uint64 [q + 1]).
+    weights: None (every set uniform) or one entry per set, each None (that set uniform: ones) or as long as its set."""
+    sets = [np.ascontiguousarray(np.atleast_1d(s), dtype=np.int32).ravel() for s in sets]
+    if weights is not None:
+        weights = list(weights)
+        if len(weights) != len(sets):
+            raise ValueError("weights: %d entries for %d seed sets" % (len(weights), len(sets)))
+    offsets = np.zeros(len(sets) + 1, dtype=np.uint64)
+    if sets:
+        offsets[1:] = np.cumsum([s.size for s in sets], dtype=np.uint64)
+    seeds = np.concatenate(sets).astype(np.int32, copy=False) if sets else np.zeros(0, dtype=np.int32)
+    if weights is None:
+        return np.ascontiguousarray(seeds), None, offsets
+    ws = []
+    for i, (s, w) in enumerate(zip(sets, weights)):
+        w = np.ones(s.size) if w is None else np.ascontiguousarray(np.atleast_1d(w), dtype=np.float64).ravel()
+        if w.size != s.size:
+            raise ValueError("weights of set %d: %d entries for %d seeds" % (i, w.size, s.size))
+        ws.append(w)
+    wv = np.concatenate(ws).astype(np.float64, copy=False) if ws else np.zeros(0)
+    return np.ascontiguousarray(seeds), np.ascontiguousarray(wv), offsets
 
 
 def set_kernel_timing(on):
@@ -829,6 +856,42 @@ class Graph:
             self.h, _ptr(srcs), q, eps, C.byref(conf), seed, n_rounds, keep.h if keep is not None else None, _ptr(out),
             k, _ptr(ids), _ptr(vals), _ptr(nsel), C.cast(pq, C.c_void_p) if pq is not None else None, C.byref(st)))
         return out, ids, vals, nsel, (list(pq) if pq is not None else None), st
+
+    def fora_batch_seeds(self, sets, eps, alpha, seed, weights=None, n_rounds=0, k=0, conf=None, fetch=False,
+                         per_query=False, keep=None, out=None):
+        """fora_batch_single_source over seed sets: query i is fora_seeds(sets[i], ..., weights[i]); the same return
+        tuple.  sets: a sequence of array-likes of node ids; weights: None or one entry per set (None: uniform)."""
+        s, w, offsets = _seed_set_arrays(sets, weights)
+        q = int(offsets.size - 1)
+        conf = conf or conf_whole_graph(self.n, self.m, alpha)
+        if fetch and out is not None:
+            assert out.dtype == np.float64 and out.flags["C_CONTIGUOUS"] and out.shape == (q, self.n)
+        elif fetch:
+            out = np.empty((q, self.n))
+        else:
+            out = None
+        ids = np.empty((q, k), dtype=np.int32) if k > 0 else None
+        vals = np.empty((q, k)) if k > 0 else None
+        nsel = np.zeros(q, dtype=np.int32) if k > 0 else None
+        pq = (Stats * q)() if per_query and q else None
+        st = Stats()
+        _check(lib().pprhip_fora_batch_seeds(
+            self.h, _ptr(s), _ptr(w), _ptr(offsets), q, eps, C.byref(conf), seed, n_rounds,
+            keep.h if keep is not None else None, _ptr(out), k, _ptr(ids), _ptr(vals), _ptr(nsel),
+            C.cast(pq, C.c_void_p) if pq is not None else None, C.byref(st)))
+        return out, ids, vals, nsel, (list(pq) if pq is not None else None), st
+
+    def fora_batch_topk_seeds(self, sets, k, eps, alpha, seed, weights=None):
+        """fora_batch_topk over seed sets: query i is fora_topk_seeds(sets[i], ..., seed + i); returns (ids, vals,
+        summed Stats)."""
+        s, w, offsets = _seed_set_arrays(sets, weights)
+        q = int(offsets.size - 1)
+        ids = np.empty((q, k), dtype=np.int32)
+        vals = np.empty((q, k))
+        st = Stats()
+        _check(lib().pprhip_fora_batch_topk_seeds(self.h, _ptr(s), _ptr(w), _ptr(offsets), q, k, eps, alpha, seed,
+                                                  _ptr(ids), _ptr(vals), C.byref(st)))
+        return ids, vals, st
 
     def fora_batch_topk(self, srcs, k, eps, alpha, seed):
         srcs = np.ascontiguousarray(srcs, dtype=np.int32)

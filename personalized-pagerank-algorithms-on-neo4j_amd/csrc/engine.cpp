@@ -795,6 +795,7 @@ static void drop_slot(pprhip_graph* S) {
   }
   if (S->col_ev) (void)hipEventDestroy(S->col_ev);
   S->col_ev = nullptr;
+  seed_free(S);  // (a workspace's seed table: made by its first seed-set query)
   free_workspace(S);
   S->ktimer.destroy();
   if (S->own_stream) (void)hipStreamDestroy(S->own_stream);

@@ -294,6 +294,14 @@ struct SlotArgs {
   int32_t mode;
   int32_t dead_slot, out_slot;
   int32_t gs_state;  // GsState of this slot in this sweep
+  // a seed-set query (SeedTable of the slot's workspace; seed_w nullptr: not seeded): the live seeds' landing weights
+  // per node for the apply kernel, the dead-end seeds (seed_id / seed_e [seed_n_live, seed_n_all)) and the done counter
+  // for k_seed_land_dense_batch
+  const double* seed_w;
+  const int32_t* seed_id;
+  const double* seed_e;
+  unsigned int* seed_done;
+  uint32_t seed_n_live, seed_n_all;
 };
 
 // Small results the host waits for (kernels_host.hip): mapped pinned memory a kernel writes and the host reads.

@@ -363,7 +363,7 @@ struct FetchPipe {
 
 struct BatchJob {
   pprhip_graph* P;
-  const int32_t* srcs;
+  const int32_t* srcs;  // nullptr: a job of seed sets (sets)
   int q;
   double eps;
   const pprhip_fora_conf_t* conf;
@@ -381,6 +381,9 @@ struct BatchJob {
   pprhip_results* keep = nullptr;          // kind 0: device-resident store of the queries' vectors
   int keep_first = 0;                      // ... query i goes to slot keep_first + i of it
   FetchPipe* pipe = nullptr;               // reserve_out given: asynchronous delivery (batch_run opens / closes it)
+  // kinds 0 and 1 without srcs: query i runs from seed set i, its host plan (seed_plan) made before anything runs; the
+  // query's workspace takes it over (seed_upload) when the query begins
+  std::vector<SeedTable> sets;
   pprhip_stats_t sum;
   std::mutex sum_mu;
   std::atomic<int> next_query{0};
@@ -429,6 +432,11 @@ int seed_normalize(uint32_t n, const int32_t* seeds, const double* weights, int 
 // ... resolved for the dead-end seeds under alpha into the host half of a seed table (h_* arrays and counts)
 int seed_plan(pprhip_graph* g, const int32_t* seeds, const double* weights, int k, double alpha, const char* fn,
               SeedTable& plan);
+// q seed sets described like a CSR (set i = seeds / weights [offsets[i], offsets[i + 1])) as q plans: the checks of
+// seed_normalize for every set (the message names the set); bad offsets and q < 0 are PPRHIP_ERR_INVALID as well.
+// Host only.
+int seed_plan_sets(pprhip_graph* g, const int32_t* seeds, const double* weights, const uint64_t* offsets, int q,
+                   double alpha, const char* fn, std::vector<SeedTable>& plans);
 int seed_upload(pprhip_graph* g, SeedTable& plan);  // plan -> g->seeds (HBM; allocated on first use, grown)
 int seed_start(pprhip_graph* g, LevelCtx& L);       // r = p resolved, the live seeds as L's frontier
 void seed_free(pprhip_graph* g);

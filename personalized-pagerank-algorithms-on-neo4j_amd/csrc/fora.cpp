@@ -783,6 +783,7 @@ int launch_sweep(pprhip_graph* P, ForaRun* runs, const bool* active, int n_activ
   BatchState* bs = P->batch;
   const GraphData* D = P->gr;
   T->n_active = n_active;
+  int n_seeded = 0;
   for (int s = 0; s < kBatch; ++s) {
     T->ws[s] = (ws && active[s]) ? ws[s] : s;
     pprhip_graph* S = bs->slots[T->ws[s]];
@@ -794,6 +795,15 @@ int launch_sweep(pprhip_graph* P, ForaRun* runs, const bool* active, int n_activ
     sa.armed = S->armed;
     sa.ctr = S->ctr;
     sa.active = active[s] ? 1 : 0;
+    // a seeded query lands its dead-end mass in the sweep (k_dense_apply_batch, k_seed_land_dense_batch)
+    const SeedTable* sd = (active[s] && S->seed_on) ? S->seeds : nullptr;
+    sa.seed_w = sd ? sd->w_node : nullptr;
+    sa.seed_id = sd ? sd->id : nullptr;
+    sa.seed_e = sd ? sd->w : nullptr;
+    sa.seed_done = sd ? sd->done : nullptr;
+    sa.seed_n_live = sd ? sd->n_live : 0u;
+    sa.seed_n_all = sd ? sd->n_live + sd->n_dead : 0u;
+    n_seeded += sd ? 1 : 0;
     if (!active[s]) continue;
     const ForaRun& r = runs[T->ws[s]];
     sa.alpha = r.a.alpha;
@@ -817,7 +827,9 @@ int launch_sweep(pprhip_graph* P, ForaRun* runs, const bool* active, int n_activ
   // SURVEY 8(d) sweep model with n = the rows the sweep carries (launch_dense_level_b8: isolated nodes are left out)
   const uint64_t rows = backward ? (uint64_t)D->n_nz_o + D->n_z_o : (uint64_t)D->n_nz + D->n_zin;
   T->rows = rows;
-  const uint64_t sweep_bytes = 4ull * D->m + (uint64_t)n_active * (8ull * D->m + 36ull * rows + 4ull);
+  // (+ 8 B per row for each seeded column: its landing weights)
+  const uint64_t sweep_bytes =
+      4ull * D->m + (uint64_t)n_active * (8ull * D->m + 36ull * rows + 4ull) + (uint64_t)n_seeded * 8ull * rows;
   if ((int)backward != bs->acc8_dir) {
     // rows summed with atomics are cleared by the apply kernel of their own layout only: start clean
     PPRHIP_CHECK_HIP(hipMemsetAsync(bs->acc8, 0, sizeof(double) * ((size_t)D->n + 1) * kBatch, P->stream));
@@ -891,6 +903,7 @@ int run_step(ForaRun& r, bool yield_dense) {
 int finish_query(BatchJob& J, ForaRun& r) {
   pprhip_graph* S = r.g;
   const int i = r.query;
+  S->seed_on = false;  // (the query's pushes are over: a later query of the workspace must not land on its table)
   if (r.kind == 2) {
     std::lock_guard<std::mutex> lk(J.sum_mu);
     J.triples->insert(J.triples->end(), r.triples.begin(), r.triples.end());
@@ -941,19 +954,28 @@ int finish_query(BatchJob& J, ForaRun& r) {
   return PPRHIP_OK;
 }
 
+// A query of a job of seed sets begins as pprhip_fora_seeds / pprhip_fora_topk_seeds begin theirs: its plan goes to the
+// workspace's seed table, and the workspace lands dead-end mass on that table until finish_query.
 int begin_query(BatchJob& J, ForaRun& r, pprhip_graph* S, int i) {
   S->tun = J.P->tun;
-  const int32_t src = J.P->gr->h_old2new[J.srcs[i]];
+  S->seed_on = false;
+  const bool seeded = !J.srcs && J.kind != 2;
+  const int32_t src = seeded ? -1 : J.P->gr->h_old2new[J.srcs[i]];
   if (J.kind == 2) {
     pprhip_tuning_batch(&S->tun);  // level shapes only: a backward search has no cost-model decisions
     PPRHIP_TRY(bwd_begin(r, S, src, J.srcs[i], J.alpha, J.threshold));
   } else if (J.kind == 1) {
-    PPRHIP_TRY(topk_begin(r, S, src, J.eps, J.conf, J.seed + (uint64_t)i, J.ids_out + (size_t)i * J.k,
-                          J.vals_out + (size_t)i * J.k, J.k));
+    int32_t* const ids = J.ids_out + (size_t)i * J.k;
+    double* const vals = J.vals_out + (size_t)i * J.k;
+    const uint64_t seed = J.seed + (uint64_t)i;
+    if (seeded) PPRHIP_TRY(topk_begin_seeds(r, S, J.sets[(size_t)i], J.eps, J.conf, seed, ids, vals, J.k));
+    else PPRHIP_TRY(topk_begin(r, S, src, J.eps, J.conf, seed, ids, vals, J.k));
   } else {
     r.kind = 0;
-    PPRHIP_TRY(fora_begin(r, S, src, J.eps, J.conf, J.seed, J.n_rounds));
+    if (seeded) PPRHIP_TRY(fora_begin_seeds(r, S, J.sets[(size_t)i], J.eps, J.conf, J.seed, J.n_rounds));
+    else PPRHIP_TRY(fora_begin(r, S, src, J.eps, J.conf, J.seed, J.n_rounds));
   }
+  S->seed_on = seeded;
   r.query = i;
   r.job = &J;
   return PPRHIP_OK;
@@ -1335,13 +1357,17 @@ int tail_queries(const BatchJob& J) {
 int run_tail(BatchJob& J, int q_slots) {
   for (int i = q_slots; i < J.q; ++i) {  // the stragglers, one at a time on the handle's own vectors
     ForaRun r;
-    PPRHIP_TRY(begin_query(J, r, J.P, i));
-    r.side = nullptr;
-    int rc;
-    while ((rc = run_step(r, false)) == kYield) {
+    int rc = begin_query(J, r, J.P, i);  // (a seed set: the single-query seeded path, on the handle's own table)
+    if (rc == PPRHIP_OK) {
+      r.side = nullptr;
+      while ((rc = run_step(r, false)) == kYield) {
+      }
     }
-    if (rc != PPRHIP_OK) return rc;
-    PPRHIP_TRY(finish_query(J, r));
+    if (rc == PPRHIP_OK) rc = finish_query(J, r);
+    if (rc != PPRHIP_OK) {
+      J.P->seed_on = false;
+      return rc;
+    }
   }
   return PPRHIP_OK;
 }
@@ -1434,6 +1460,7 @@ void batch_worker(BatchJob* J, BatchSync* B, ForaRun* runs, int s) {
   }
   if (rc != PPRHIP_OK) {
     leave_push(r);
+    S->seed_on = false;
     B->fail(rc);
   }
   (void)hipStreamSynchronize(S->stream);
@@ -1774,7 +1801,8 @@ int pprhip::detail::batch_run(pprhip_graph_t* g, BatchJob& J, pprhip_stats_t* st
   }
   if (rc != PPRHIP_OK) {
     const std::string msg = get_error();
-    free_batch(g);  // slots may hold half-pushed levels: the next batched call builds clean ones
+    g->seed_on = false;  // (the leftover rule runs seed sets on the handle's own workspace)
+    free_batch(g);  // slots may hold half-pushed levels (and seed tables): the next batched call builds clean ones
     set_error("%s", msg.c_str());
     return rc;
   }
@@ -1929,6 +1957,80 @@ int pprhip_fora_batch_topk(pprhip_graph_t* g, const int32_t* srcs, int q, int k,
   J.eps = eps;
   J.conf = &conf;
   J.seed = seed;  // query i runs with seed + i, as pprhip_fora_topk(srcs[i], ..., seed + i) would
+  J.n_rounds = 0;
+  J.reserve_out = nullptr;
+  J.k = k;
+  J.ids_out = ids_out;
+  J.vals_out = vals_out;
+  J.n_out = nullptr;
+  J.per_query = nullptr;
+  return batch_run(g, J, stats_sum);
+}
+
+
+// ------------------------------------------------------------------ batched seed sets
+// pprhip_fora_batch_single_source_resident / pprhip_fora_batch_topk over seed sets: query i runs as pprhip_fora_seeds
+// (seed) / pprhip_fora_topk_seeds (seed + i) would run set i; every set is checked before anything runs
+int pprhip_fora_batch_seeds(pprhip_graph_t* g, const int32_t* seeds, const double* weights, const uint64_t* offsets,
+                            int q, double eps, const pprhip_fora_conf_t* conf, uint64_t seed, int n_rounds,
+                            pprhip_results_t* keep, double* reserve_out, int k, int32_t* ids_out, double* vals_out,
+                            int* n_out, pprhip_stats_t* per_query, pprhip_stats_t* stats_sum) {
+  static const char* fn = "pprhip_fora_batch_seeds";
+  PPRHIP_TRY(check_positive(eps, fn, "eps"));
+  PPRHIP_TRY(check_conf(conf, fn, false));
+  PPRHIP_TRY(check_graph(g, fn));
+  if (q < 0 || !conf || n_rounds < 0 || k < 0 || (k > 0 && q > 0 && (!ids_out || !vals_out))) {
+    set_error("%s: bad arguments (q=%d eps=%g n_rounds=%d k=%d)", fn, q, eps, n_rounds, k);
+    return PPRHIP_ERR_INVALID;
+  }
+  if (keep && (keep->g != g || q > keep->capacity)) {
+    set_error("%s: the result store belongs to another graph or holds %d < %d queries", fn, keep->capacity, q);
+    return PPRHIP_ERR_INVALID;
+  }
+  BatchJob J;
+  PPRHIP_TRY(seed_plan_sets(g, seeds, weights, offsets, q, conf->alpha, fn, J.sets));
+  J.P = g;
+  J.srcs = nullptr;
+  J.q = q;
+  J.eps = eps;
+  J.conf = conf;
+  J.seed = seed;
+  J.n_rounds = n_rounds;
+  J.reserve_out = reserve_out;
+  J.k = k;
+  J.ids_out = ids_out;
+  J.vals_out = vals_out;
+  J.n_out = n_out;
+  J.per_query = per_query;
+  J.keep = keep;
+  if (keep) keep->count = 0;
+  PPRHIP_TRY(batch_run(g, J, stats_sum));
+  if (keep) keep->count = q;
+  return PPRHIP_OK;
+}
+
+int pprhip_fora_batch_topk_seeds(pprhip_graph_t* g, const int32_t* seeds, const double* weights,
+                                 const uint64_t* offsets, int q, int k, double eps, double alpha, uint64_t seed,
+                                 int32_t* ids_out, double* vals_out, pprhip_stats_t* stats_sum) {
+  static const char* fn = "pprhip_fora_batch_topk_seeds";
+  PPRHIP_TRY(check_positive(eps, fn, "eps"));
+  PPRHIP_TRY(check_alpha(alpha, fn));
+  PPRHIP_TRY(check_graph(g, fn));
+  if (q < 0 || k < 1 || (q > 0 && (!ids_out || !vals_out))) {
+    set_error("%s: bad arguments (q=%d k=%d)", fn, q, k);
+    return PPRHIP_ERR_INVALID;
+  }
+  pprhip_fora_conf_t conf;
+  PPRHIP_TRY(pprhip_conf_fora_topk(g->gr->n, g->gr->m, k, alpha, &conf));
+  BatchJob J;
+  PPRHIP_TRY(seed_plan_sets(g, seeds, weights, offsets, q, conf.alpha, fn, J.sets));
+  J.P = g;
+  J.kind = 1;
+  J.srcs = nullptr;
+  J.q = q;
+  J.eps = eps;
+  J.conf = &conf;
+  J.seed = seed;  // query i runs with seed + i, as pprhip_fora_topk_seeds(set i, ..., seed + i) would
   J.n_rounds = 0;
   J.reserve_out = nullptr;
   J.k = k;

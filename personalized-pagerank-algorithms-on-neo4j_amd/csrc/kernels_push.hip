@@ -1197,6 +1197,17 @@ __global__ __launch_bounds__(kApplyThreads) void k_dense_apply_batch(const int32
             acc += dd;
             a[i].ctr->dead[a[i].dead_slot] = 0.0;
           }
+        } else if (a[i].seed_w && a[i].mode != kBackward) {
+          // seed set (k_dense_apply's rule): the level's dead-end mass x lands on row u as x * seed_w[u].  The branch
+          // is wave-uniform: a column that is not seeded loads nothing more.  x is one scalar load per wave, slot and
+          // tile trip (held across the loop it cost more SGPR spills); the cell stays as it is - every block of a
+          // Gauss-Seidel sweep reads it, k_seed_land_dense_batch clears it behind the last one.  A live seed without
+          // in-edges needs no extra row: the sweep carries every row without in-edges that has out-edges (zin_rows).
+          const double x = a[i].ctr->dead[a[i].dead_slot];
+          if (x > 0.0 && on) {
+            const double sw = a[i].seed_w[u[g]];
+            if (sw != 0.0) acc += x * sw;
+          }
         }
         accv[g][i] = acc;
         live[g][i] = on && acc > 0.0;
@@ -1753,6 +1764,20 @@ __global__ __launch_bounds__(256) void k_seed_land_dense(const int32_t* __restri
   seed_land_done(done, ctr, dead_slot);
 }
 
+// The same for the seeded columns of a batched sweep, all in one launch (blockIdx.y = column), between the last apply
+// block and k_dense_reduce_batch: column c's dead-end seeds take x e_j and its cell is cleared (the workspace's own
+// SeedTable::done counts the column's workgroups).  Columns that are not seeded or not in the sweep return at once.
+__global__ __launch_bounds__(256) void k_seed_land_dense_batch(const SlotArgs* __restrict__ slots) {
+  const SlotArgs& a = slots[blockIdx.y];
+  if (!a.active || !a.seed_w || a.mode == kBackward) return;
+  const double x = a.ctr->dead[a.dead_slot];
+  if (!(x > 0.0)) return;
+  const uint32_t stride = gridDim.x * blockDim.x;
+  for (uint32_t i = a.seed_n_live + blockIdx.x * blockDim.x + threadIdx.x; i < a.seed_n_all; i += stride)
+    a.reserve[a.seed_id[i]] = a.reserve[a.seed_id[i]] + x * a.seed_e[i];
+  seed_land_done(a.seed_done, a.ctr, a.dead_slot);
+}
+
 // ------------------------------------------------------------------------------------------------
 // launchers
 // ------------------------------------------------------------------------------------------------
@@ -2062,6 +2087,21 @@ int launch_dense_level_b8(pprhip_graph* P, bool backward, const GsBlock* gs_bloc
           bs->blk_pack8, bs->blk_dead8, bs->blk_ndead8, part_base, kApplyBlocks8);
     PPRHIP_CHECK_HIP(hipGetLastError());
     part_base += grid;
+  }
+  // seed sets: the dead-end seeds of every seeded column, and their dead-mass cells cleared
+  uint32_t seed_dead_max = 0;
+  bool seeded = false;
+  for (int s = 0; s < kBatch; ++s) {
+    const SlotArgs& sa = bs->h_slot_args[s];
+    if (sa.active && sa.seed_w && !backward) {
+      seeded = true;
+      seed_dead_max = std::max(seed_dead_max, sa.seed_n_all - sa.seed_n_live);
+    }
+  }
+  if (seeded) {
+    k_seed_land_dense_batch<<<dim3(grid_for(seed_dead_max, 256, 1024), kBatch), dim3(256), 0, P->stream>>>(
+        bs->d_slot_args);
+    PPRHIP_CHECK_HIP(hipGetLastError());
   }
   k_dense_reduce_batch<<<dim3(kBatch), dim3(1024), 0, P->stream>>>(bs->blk_pack8, bs->blk_dead8, bs->blk_ndead8, part_base,
                                                                    kApplyBlocks8, bs->d_slot_args, bs->sweep_out);

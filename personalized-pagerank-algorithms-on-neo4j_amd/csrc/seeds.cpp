@@ -4,7 +4,10 @@
 // states the rule.
 #include <algorithm>
 #include <cmath>
+#include <climits>
+#include <cstdint>
 #include <cstring>
+#include <string>
 
 #include "engine_internal.hpp"
 
@@ -103,6 +106,49 @@ int seed_plan(pprhip_graph* g, const int32_t* seeds, const double* weights, int 
   t.n_live = (uint32_t)live.size();
   t.n_dead = (uint32_t)dead.size();
   t.n_zin = (uint32_t)t.h_zin.size();
+  return PPRHIP_OK;
+}
+
+int seed_plan_sets(pprhip_graph* g, const int32_t* seeds, const double* weights, const uint64_t* offsets, int q,
+                   double alpha, const char* fn, std::vector<SeedTable>& plans) {
+  plans.clear();
+  if (q < 0 || (q > 0 && !offsets)) {
+    set_error("%s: bad arguments (q=%d, offsets %s)", fn, q, offsets ? "given" : "NULL");
+    return PPRHIP_ERR_INVALID;
+  }
+  if (q == 0) return PPRHIP_OK;
+  if (offsets[0] != 0) {
+    set_error("%s: offsets[0] = %llu, not 0", fn, (unsigned long long)offsets[0]);
+    return PPRHIP_ERR_INVALID;
+  }
+  for (int i = 0; i < q; ++i)
+    if (offsets[i + 1] < offsets[i] || offsets[i + 1] - offsets[i] > (uint64_t)INT32_MAX) {
+      set_error("%s: set %d: offsets %llu .. %llu do not describe a set", fn, i, (unsigned long long)offsets[i],
+                (unsigned long long)offsets[i + 1]);
+      return PPRHIP_ERR_INVALID;
+    }
+  if (offsets[q] > 0 && !seeds) {
+    set_error("%s: seeds is NULL for %llu entries", fn, (unsigned long long)offsets[q]);
+    return PPRHIP_ERR_INVALID;
+  }
+  try {
+    plans.resize((size_t)q);
+    std::string where;
+    for (int i = 0; i < q; ++i) {
+      where = std::string(fn) + ": set " + std::to_string(i);
+      const size_t o = (size_t)offsets[i];
+      const int rc = seed_plan(g, seeds ? seeds + o : nullptr, weights ? weights + o : nullptr,
+                               (int)(offsets[i + 1] - offsets[i]), alpha, where.c_str(), plans[(size_t)i]);
+      if (rc != PPRHIP_OK) {
+        plans.clear();
+        return rc;
+      }
+    }
+  } catch (const std::bad_alloc&) {
+    plans.clear();
+    set_error("%s: out of host memory for the plans of %d seed sets", fn, q);
+    return PPRHIP_ERR_OOM;
+  }
   return PPRHIP_OK;
 }
 
