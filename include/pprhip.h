@@ -545,6 +545,40 @@ int pprhip_owner_partition(uint32_t n, int world, const int32_t* sources, uint64
 int pprhip_index_from_entries(uint32_t n, const int32_t* sources, const int32_t* targets, const double* values,
                               uint64_t count, int k, pprhip_index_t** index_out);
 
+/* ---------------------------------------------------------------- single pairs (beyond the reference)
+ * pi(s, t) for many pairs at once: the bidirectional estimator (BiPPR) built from a backward push from t and walks from
+ * s.  pi is the vector pprhip_power_method(s, alpha, inf) and FORA estimate (a walk stops at a dead end with probability
+ * alpha and otherwise restarts at s).  The push estimates the leaking PPR pi' (a dead end's (1 - alpha) mass is lost),
+ * and pi(s, .) = pi'(s, .) / S(s) with S(u) the survival of a leaking walk from u (DESIGN.md §2 "Single pairs"), so
+ *     value(s, t) = p_t(s) / S(s) + (1 / w) * sum_{i < w} r_t(V_i)
+ * with p_t / r_t the reserve / residue of a backward push from t at r_max that starts r(t) = 1 and pops t (also when t
+ * has no in-edges: p_t(t) = alpha, no residue - not Backward_Search.java:46-49's reserve(t) = 1), V_i the terminal of
+ * walk i = (seed, PPRHIP_PAIR_WALK_STREAM, s, i) of pprhip_random_walk_batch (no_zero_hop = 0), and
+ * w = ceil(omega * r_max), omega = 3 ln(2 / pfail) / (eps^2 delta): |value - pi| <= eps * max(pi, delta) with
+ * probability >= 1 - pfail (delta, pfail from conf).  A pair's value depends on the seed and the pair only.
+ * The push of a pair call runs under the handle's tuning (pprhip_graph_set_tuning): pprhip_backward_push under the
+ * same tuning yields the same p_t and r_t up to fp64 addition order (when t has in-edges).  alpha, eps and rmax are
+ * checked first (header "Parameter ranges"; rmax: 0 = the default below, else finite and 0 < rmax <= 1), then every
+ * id before any device work (PPRHIP_ERR_INVALID, the handle untouched); q == 0 is an empty call; while a query stream
+ * is open: PPRHIP_ERR_STATE.  After a pair call pprhip_get_reserve / _get_residue are undefined. */
+#define PPRHIP_PAIR_WALK_STREAM 0xFFFFu /* the walk stream of every pair walk; no other path uses it */
+/* Pure: r_max (rmax_in = 0: the balanced default eps * sqrt(dbar * delta / (3 ln(2 / pfail))), dbar = m / n, clamped
+ * to (0, 1]) and the walks per pair w = ceil(omega * r_max) (at most 2^48). */
+int pprhip_pair_params(const pprhip_fora_conf_t* conf, double eps, double rmax_in, double* rmax_out, uint64_t* walks_out);
+/* S of the leaking walk at alpha, n doubles in original id order: S(u) = alpha + (1 - alpha) / d(u) * sum_{u->v} S(v)
+ * for d(u) > 0, alpha at dead ends (1 on a graph without dead ends).  Jacobi iterations on the device until
+ * (1 - alpha) / alpha * max|dS| <= 1e-14; computed once per (handle, alpha) and kept on the handle (8n bytes).
+ * survival_out may be NULL (computes and keeps it). */
+int pprhip_walk_survival(pprhip_graph_t* g, double alpha, double* survival_out);
+/* q pairs (sources[i], targets[i]); values_out[i] = the estimate of pair i.  The pairs are grouped by target; every
+ * distinct target is one backward push of a batched call (up to PPRHIP_BATCH in flight, their dense levels sharing
+ * the batched sweeps), followed by the walks of its sources.  stats_sum: rmax_final = r_max, omega = omega,
+ * walks / walk_steps / pops / edge_pushes / levels summed; push_ms / mc_ms: HIP-event times of the targets' push and
+ * walk phases, summed over targets (they overlap); total_ms: the call. */
+int pprhip_ppr_pairs(pprhip_graph_t* g, const int32_t* sources, const int32_t* targets, int q, double eps,
+                     const pprhip_fora_conf_t* conf, double rmax, uint64_t seed, double* values_out,
+                     pprhip_stats_t* stats_sum);
+
 /* ---------------------------------------------------------------- ground truth (a12) */
 /* Power_Method.computeWholeGraphPPR (Power_Method.java:44-101): `iters` synchronous sweeps. */
 int pprhip_power_method(pprhip_graph_t* g, int32_t src, double alpha, int iters, double* reserve_out,

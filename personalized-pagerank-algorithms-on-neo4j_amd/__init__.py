@@ -85,7 +85,9 @@ EXPORTS = [
     "pprhip_fora_stream_open", "pprhip_fora_stream_submit", "pprhip_fora_stream_wait", "pprhip_fora_stream_close",
     "pprhip_set_kernel_timing", "pprhip_shard_target_cuts", "pprhip_forward_push_seeds", "pprhip_fora_seeds",
     "pprhip_fora_topk_seeds", "pprhip_fora_batch_seeds", "pprhip_fora_batch_topk_seeds",
+    "pprhip_pair_params", "pprhip_walk_survival", "pprhip_ppr_pairs",
 ]
+PAIR_WALK_STREAM = 0xFFFF  # PPRHIP_PAIR_WALK_STREAM: the walk stream of every single-pair walk
 COMM_ID_BYTES = 128
 
 _lib = None
@@ -194,6 +196,9 @@ def lib():
     L.pprhip_fora_stream_wait.argtypes = [vp, u64, P(Stats)]
     L.pprhip_fora_stream_close.argtypes = [vp]
     L.pprhip_set_kernel_timing.argtypes = [ci]
+    L.pprhip_pair_params.argtypes = [P(ForaConf), dbl, dbl, P(dbl), P(u64)]
+    L.pprhip_walk_survival.argtypes = [vp, dbl, vp]
+    L.pprhip_ppr_pairs.argtypes = [vp, vp, vp, ci, dbl, P(ForaConf), dbl, u64, vp, P(Stats)]
     _lib = L
     # the destroy entry points, reachable from destructors that run while the interpreter shuts down (the name `lib`
     # may already be None then: "TypeError: 'NoneType' object is not callable" out of Index.__del__, round 3)
@@ -391,6 +396,13 @@ def fora_whole_params(conf, eps):
     a, b = C.c_double(), C.c_double()
     _check(lib().pprhip_fora_whole_params(C.byref(conf), eps, C.byref(a), C.byref(b)))
     return a.value, b.value
+
+
+def pair_params(conf, eps, rmax=0.0):
+    """Single pairs (pprhip_pair_params): (r_max, walks per pair); rmax 0 picks the balanced default."""
+    r, w = C.c_double(), C.c_uint64()
+    _check(lib().pprhip_pair_params(C.byref(conf), eps, rmax, C.byref(r), C.byref(w)))
+    return r.value, w.value
 
 
 def fora_topk_params(conf, eps, delta):
@@ -901,6 +913,26 @@ class Graph:
         _check(lib().pprhip_fora_batch_topk(self.h, _ptr(srcs), srcs.size, k, eps, alpha, seed, _ptr(ids), _ptr(vals),
                                             C.byref(st)))
         return ids, vals, st
+
+    def walk_survival(self, alpha):
+        """S of the leaking walk at alpha (pprhip_walk_survival), n doubles by node id."""
+        out = np.empty(self.n)
+        _check(lib().pprhip_walk_survival(self.h, alpha, _ptr(out)))
+        return out
+
+    def ppr_pairs(self, sources, targets, eps, alpha, seed, rmax=0.0, conf=None):
+        """pi(sources[i], targets[i]) for every i by the bidirectional estimator (pprhip_ppr_pairs); conf defaults to
+        conf_whole_graph(n, m, alpha) (its alpha is the one used).  Returns (values, summed Stats)."""
+        conf = conf or conf_whole_graph(self.n, self.m, alpha)
+        s = np.ascontiguousarray(np.atleast_1d(sources), dtype=np.int32).ravel()
+        t = np.ascontiguousarray(np.atleast_1d(targets), dtype=np.int32).ravel()
+        if s.size != t.size:
+            raise ValueError("%d sources for %d targets" % (s.size, t.size))
+        out = np.empty(s.size)
+        st = Stats()
+        _check(lib().pprhip_ppr_pairs(self.h, _ptr(s), _ptr(t), s.size, eps, C.byref(conf), rmax, seed, _ptr(out),
+                                      C.byref(st)))
+        return out, st
 
     def backward_push(self, target, alpha, rmax):
         reserve = np.empty(self.n)

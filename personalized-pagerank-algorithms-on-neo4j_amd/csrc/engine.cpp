@@ -1681,7 +1681,7 @@ int pprhip_graph_create(uint32_t n, uint64_t m, const uint32_t* out_rp, const in
 static void free_graph_data(GraphData* D) {
   void* ptrs[] = {D->walk_rec, D->out_ext, D->out_rp, D->out_ci, D->in_rp, D->in_ci, D->new2old, D->old2new, D->start_flags,
                   D->chunk_starts, D->nz_rows, D->zin_rows, D->cross_bits, D->start_flags_o, D->chunk_starts_o,
-                  D->nz_rows_o, D->z_rows_o, D->cross_bits_o};
+                  D->nz_rows_o, D->z_rows_o, D->cross_bits_o, D->survival};
   for (void* p : ptrs)
     if (p) (void)hipFree(p);
   if (D->sl) {

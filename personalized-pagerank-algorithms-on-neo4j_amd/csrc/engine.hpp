@@ -380,6 +380,10 @@ struct GraphData {
   int32_t *nz_rows_o = nullptr, *z_rows_o = nullptr;  // rows with / without out-edges
   uint32_t n_nz_o = 0, n_z_o = 0;
   unsigned long long* cross_bits_o = nullptr;
+  // survival S of the leaking walk at survival_alpha (single pairs, pprhip_walk_survival): internal ids, built on the
+  // calling thread before a pair call's workers start, rebuilt only when alpha changes
+  double* survival = nullptr;
+  double survival_alpha = 0.0;
 };
 
 // The handle's batched-call state: the workspaces ("slots") of its batched queries and the arrays their dense levels
@@ -602,6 +606,14 @@ int launch_hold(hipStream_t stream, unsigned long long ticks);
 int launch_mc_plan(pprhip_graph* g, int variant, double alpha, double rsum, double nrw, double omega_dev, double* target,
                    const double* copy_src = nullptr, double* copy_dst = nullptr);
 int launch_mc_walk(pprhip_graph* g, double alpha, uint64_t seed, uint32_t stream, int no_zero_hop, double* target);
+// (rows of out-degree >= survival_heavy_degree() go in d_heavy: a workgroup each)
+int launch_survival_iter(pprhip_graph* g, const double* s_old, double* s_new, double alpha, const int32_t* d_heavy,
+                         uint32_t n_heavy, unsigned long long* dmax);
+uint32_t survival_heavy_degree();
+int launch_pair_walk(pprhip_graph* g, const int32_t* d_src, uint32_t n_pairs, uint32_t chunks, uint64_t chunk_walks,
+                     uint64_t walks, double alpha, uint64_t seed, double* d_part, unsigned long long* d_steps);
+int launch_pair_reduce(pprhip_graph* g, const int32_t* d_src, const int32_t* d_pos, uint32_t n_pairs, uint32_t chunks,
+                       const double* d_part, uint64_t walks, const double* survival, double* d_values);
 int launch_walk_batch(pprhip_graph* g, const int32_t* d_starts, const uint64_t* d_idx, uint64_t count, double alpha,
                       uint64_t seed, uint32_t stream, int no_zero_hop, int32_t* d_term, uint32_t* d_steps);
 int launch_mc_pure(pprhip_graph* g, int32_t src, uint64_t n_walks, double alpha, uint64_t seed, double inc,

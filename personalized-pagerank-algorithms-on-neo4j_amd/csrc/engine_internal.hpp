@@ -361,6 +361,28 @@ struct FetchPipe {
   void copier();
 };
 
+// A pair call (BatchJob kind 3, pairs.cpp): the pairs sorted by target; query i of the job is the i-th distinct target
+// (BatchJob::srcs) and covers the sorted pairs [first[i], first[i + 1]).  Device arrays of the call: the sources
+// (internal ids) and the call positions of the sorted pairs, the values by call position, per workspace (ws_index < kBatch)
+// a buffer of part_cap chunk sums and three events (push start, walks start, end).
+struct PairPlan {
+  std::vector<uint32_t> first;
+  const int32_t* d_src = nullptr;
+  const int32_t* d_pos = nullptr;
+  double* d_values = nullptr;
+  double* d_part = nullptr;  // [kBatch][part_cap]
+  size_t part_cap = 0;
+  unsigned long long* d_steps = nullptr;  // walk steps of the call
+  uint64_t walks = 0;       // w per pair
+  uint32_t chunks = 0;      // work items per pair ...
+  uint64_t chunk_walks = 0; // ... of this many walks (the last one shorter)
+  uint32_t block_pairs = 0; // pairs per walk launch (part_cap / chunks)
+  double alpha = 0.0, rmax = 0.0;
+  uint64_t seed = 0;
+  const double* survival = nullptr;
+  hipEvent_t ev[3 * kBatch] = {};
+};
+
 struct BatchJob {
   pprhip_graph* P;
   const int32_t* srcs;  // nullptr: a job of seed sets (sets)
@@ -375,7 +397,9 @@ struct BatchJob {
   double* vals_out;
   int* n_out;
   pprhip_stats_t* per_query;
-  int kind = 0;  // 0: whole-graph FORA per query, 1: FORA top-k per query (seed + query index), 2: backward search
+  int kind = 0;  // 0: whole-graph FORA per query, 1: FORA top-k per query (seed + query index), 2: backward search,
+                 // 3: single pairs (a backward push per distinct target, then its sources' walks)
+  PairPlan* pairs = nullptr;               // kind 3
   double alpha = 0.0, threshold = 0.0;   // kind 2
   std::vector<Triple>* triples = nullptr;  // kind 2: every search's entries >= threshold
   pprhip_results* keep = nullptr;          // kind 0: device-resident store of the queries' vectors

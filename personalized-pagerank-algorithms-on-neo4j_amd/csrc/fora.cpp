@@ -55,7 +55,7 @@ struct ForaRun {
   PushArgs a;
   RoundCut cut;
   enum Phase { kRoundStart, kLevels, kWalks, kWalkWait, kTopkRoundStart, kTopkLevels, kTopkRoundEnd, kTopkFinal, kBwdLevels,
-               kBwdFinal, kDone } phase = kDone;
+               kBwdFinal, kPairFinal, kDone } phase = kDone;
   hipStream_t side = nullptr;  // batch driver: the walk phase goes to this stream and the run yields until it has ended
   int query = -1;  // batch driver: index of the query this run serves
   detail::BatchJob* job = nullptr;  // ... and the call (or stream submission) that query belongs to
@@ -82,6 +82,10 @@ struct ForaRun {
   // backward searches of All-Pair (kind 2): entries >= threshold of the finished search
   int32_t target_orig = -1;
   std::vector<Triple> triples;
+  // single pairs (kind 3): the push runs in kBwdLevels, then the walks of the sorted pairs [pair_lo, pair_hi)
+  const detail::PairPlan* pp = nullptr;
+  uint32_t pair_lo = 0, pair_hi = 0;
+  bool pair_walks = false;  // the push left residue (the target has in-edges)
 };
 
 }  // namespace pprhip
@@ -596,6 +600,80 @@ int bwd_step(ForaRun& r, bool yield_dense) {
   return PPRHIP_OK;
 }
 
+// The backward push of a pair call (BatchJob kind 3): the standard start r(t) = 1, t popped - also for a target without
+// in-edges, where that leaves p_t(t) = alpha and no residue (not bwd_begin's reserve(t) = 1, Backward_Search.java:46-49).
+int pair_begin(ForaRun& r, pprhip_graph* g, const detail::PairPlan& pp, int32_t target_internal, uint32_t lo,
+               uint32_t hi) {
+  r.g = g;
+  r.kind = 3;
+  r.src = target_internal;
+  r.alpha = pp.alpha;
+  r.rmax_local = pp.rmax;
+  r.pp = &pp;
+  r.pair_lo = lo;
+  r.pair_hi = hi;
+  std::memset(&r.st, 0, sizeof r.st);
+  g->topk_active = false;
+  if (g->ws_index < 0 || g->ws_index >= kBatch) {
+    set_error("pair call: workspace %d has no pair buffers", g->ws_index);
+    return PPRHIP_ERR_STATE;
+  }
+  PPRHIP_TRY(reset_query_state(g, false, target_internal));
+  PPRHIP_CHECK_HIP(hipEventRecord(pp.ev[3 * g->ws_index], g->stream));
+  r.waiting = false;
+  r.in_push = false;
+  const uint32_t din = hdeg_in(g, target_internal);
+  r.pair_walks = din > 0;
+  if (!r.pair_walks) {
+    PPRHIP_TRY(launch_set_f64(g, g->reserve, (uint32_t)target_internal, pp.alpha));
+    r.phase = ForaRun::kPairFinal;
+    return PPRHIP_OK;
+  }
+  r.a = PushArgs{pp.alpha, pp.rmax, 0.0, target_internal, kBackward};
+  r.L = LevelCtx();
+  PPRHIP_TRY(launch_set_f64(g, g->residue, (uint32_t)target_internal, 1.0));
+  PPRHIP_TRY(seed_single(g, r.L, target_internal, din));
+  r.in_push = true;
+  r.phase = ForaRun::kBwdLevels;
+  return PPRHIP_OK;
+}
+
+int pair_step(ForaRun& r, bool yield_dense) {
+  pprhip_graph* g = r.g;
+  if (r.phase == ForaRun::kBwdLevels) {
+    const int rc = run_levels(g, r.a, r.L, r.st, nullptr, yield_dense);
+    if (rc != PPRHIP_OK) return rc;  // kYield or an error
+    leave_push(r);
+    r.phase = ForaRun::kPairFinal;
+  }
+  if (r.phase == ForaRun::kPairFinal) {
+    const detail::PairPlan& pp = *r.pp;
+    const int ws = g->ws_index;
+    PPRHIP_CHECK_HIP(hipEventRecord(pp.ev[3 * ws + 1], g->stream));
+    // a target without in-edges left no residue: its values are exact, no walks
+    const uint32_t chunks = r.pair_walks ? pp.chunks : 0u;
+    double* const part = pp.d_part + (size_t)ws * pp.part_cap;
+    ktimer().begin(PPRHIP_KERNEL_WALK, 0);
+    for (uint32_t lo = r.pair_lo; lo < r.pair_hi; lo += pp.block_pairs) {
+      const uint32_t np = std::min(pp.block_pairs, r.pair_hi - lo);
+      if (chunks)
+        PPRHIP_TRY(launch_pair_walk(g, pp.d_src + lo, np, chunks, pp.chunk_walks, pp.walks, pp.alpha, pp.seed, part,
+                                    pp.d_steps));
+      PPRHIP_TRY(launch_pair_reduce(g, pp.d_src + lo, pp.d_pos + lo, np, chunks, part, pp.walks, pp.survival,
+                                    pp.d_values));
+    }
+    ktimer().end();
+    PPRHIP_CHECK_HIP(hipEventRecord(pp.ev[3 * ws + 2], g->stream));
+    if (chunks) {
+      r.st.walks += pp.walks * (uint64_t)(r.pair_hi - r.pair_lo);
+      r.st.mc_sources += r.pair_hi - r.pair_lo;
+    }
+    r.st.rounds = 1;
+    r.phase = ForaRun::kDone;
+  }
+  return PPRHIP_OK;
+}
+
 void add_stats(pprhip_stats_t& sum, const pprhip_stats_t& st) {
   sum.pops += st.pops; sum.edge_pushes += st.edge_pushes; sum.enqueues += st.enqueues;
   sum.dead_end_pops += st.dead_end_pops; sum.dense_nodes += st.dense_nodes; sum.dense_edges += st.dense_edges;
@@ -896,7 +974,10 @@ int run_sweep(pprhip_graph* P, ForaRun* runs, const bool* active, int n_active) 
 
 
 int run_step(ForaRun& r, bool yield_dense) {
-  return r.kind == 2 ? bwd_step(r, yield_dense) : r.kind == 1 ? topk_step(r, yield_dense) : fora_step(r, yield_dense);
+  return r.kind == 3   ? pair_step(r, yield_dense)
+         : r.kind == 2 ? bwd_step(r, yield_dense)
+         : r.kind == 1 ? topk_step(r, yield_dense)
+                       : fora_step(r, yield_dense);
 }
 
 // outputs of a finished query (its slot still holds the vectors)
@@ -904,6 +985,17 @@ int finish_query(BatchJob& J, ForaRun& r) {
   pprhip_graph* S = r.g;
   const int i = r.query;
   S->seed_on = false;  // (the query's pushes are over: a later query of the workspace must not land on its table)
+  if (r.kind == 3) {  // the values are in the call's device array; the phase times before the events are reused
+    const hipEvent_t* ev = &r.pp->ev[3 * S->ws_index];
+    PPRHIP_CHECK_HIP(hipEventSynchronize(ev[2]));
+    r.st.push_ms = CallTimer::ms(ev[0], ev[1]);
+    r.st.mc_ms = CallTimer::ms(ev[1], ev[2]);
+    std::lock_guard<std::mutex> lk(J.sum_mu);
+    add_stats(J.sum, r.st);
+    r.phase = ForaRun::kDone;
+    r.query = -1;
+    return PPRHIP_OK;
+  }
   if (r.kind == 2) {
     std::lock_guard<std::mutex> lk(J.sum_mu);
     J.triples->insert(J.triples->end(), r.triples.begin(), r.triples.end());
@@ -959,9 +1051,11 @@ int finish_query(BatchJob& J, ForaRun& r) {
 int begin_query(BatchJob& J, ForaRun& r, pprhip_graph* S, int i) {
   S->tun = J.P->tun;
   S->seed_on = false;
-  const bool seeded = !J.srcs && J.kind != 2;
+  const bool seeded = !J.srcs && J.kind < 2;
   const int32_t src = seeded ? -1 : J.P->gr->h_old2new[J.srcs[i]];
-  if (J.kind == 2) {
+  if (J.kind == 3) {  // the handle's tuning (include/pprhip.h "single pairs")
+    PPRHIP_TRY(pair_begin(r, S, *J.pairs, src, J.pairs->first[(size_t)i], J.pairs->first[(size_t)i + 1]));
+  } else if (J.kind == 2) {
     pprhip_tuning_batch(&S->tun);  // level shapes only: a backward search has no cost-model decisions
     PPRHIP_TRY(bwd_begin(r, S, src, J.srcs[i], J.alpha, J.threshold));
   } else if (J.kind == 1) {
@@ -1722,7 +1816,7 @@ void pprhip::detail::FetchPipe::destroy() {
 // runs a prepared job on the handle's slots (both batched entry points)
 int pprhip::detail::batch_run(pprhip_graph_t* g, BatchJob& J, pprhip_stats_t* stats_sum) {
   PPRHIP_TRY(ensure_batch(g));
-  if (J.kind == 2) PPRHIP_TRY(ensure_bwd_layout(g));
+  if (J.kind >= 2) PPRHIP_TRY(ensure_bwd_layout(g));
   const int q = J.q;
   // Worker threads pay off where queries are latency-bound (top-k: short rounds of sparse levels, walks
   // and selections, 2.4x on R-MAT 22); whole-graph FORA keeps the memory system busy from one thread.

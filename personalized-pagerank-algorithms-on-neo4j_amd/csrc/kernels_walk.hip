@@ -495,8 +495,206 @@ __global__ void k_plan_single(int32_t src, double inc, unsigned long long n_walk
 }
 
 // ------------------------------------------------------------------------------------------------
+// single pairs (pprhip_ppr_pairs, DESIGN.md §2 "Single pairs")
+// ------------------------------------------------------------------------------------------------
+// One Jacobi iteration of the leaking walk's survival over the out-CSR: S'(u) = alpha + (1 - alpha) / d(u) *
+// sum_{u->v} S(v), alpha at dead ends.  A row of out-degree < kSurvHeavy is summed by a group of kSurvLanes lanes
+// (k_survival_iter); the few longer ones (the hubs of an R-MAT graph: a thread-per-row form of the kernel, whose waves wait
+// for their longest row, took 10.3 s for the whole solve at R-MAT 22) by a whole workgroup each (k_survival_heavy).  check != 0: max |S' - S|
+// goes to *dmax (non-negative doubles order as their bit patterns, so an integer maximum serves).
+constexpr uint32_t kSurvLanes = 8;
+constexpr uint32_t kSurvHeavy = 512;
+
+__device__ __forceinline__ void surv_max_out(unsigned long long mx, unsigned long long* __restrict__ dmax) {
+  __shared__ unsigned long long s_max[4];
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) {
+    const unsigned long long y = __shfl_down(mx, o);
+    mx = y > mx ? y : mx;
+  }
+  if (lane_id() == 0) s_max[wave_id()] = mx;
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    for (int w = 1; w < 4; ++w) mx = s_max[w] > mx ? s_max[w] : mx;
+    if (mx) atomicMax(dmax, mx);
+  }
+}
+
+__device__ __forceinline__ unsigned long long surv_diff_bits(double x, double old) {
+  const double dx = fabs(x - old);
+  unsigned long long bits;
+  __builtin_memcpy(&bits, &dx, 8);
+  return bits;
+}
+
+__global__ __launch_bounds__(256) void k_survival_iter(uint32_t n, const unsigned long long* __restrict__ out_ext,
+                                                        const int32_t* __restrict__ out_ci, const double* __restrict__ s_old,
+                                                        double* __restrict__ s_new, double alpha, int check,
+                                                        unsigned long long* __restrict__ dmax) {
+  unsigned long long mx = 0ull;
+  const uint32_t sub = threadIdx.x % kSurvLanes;
+  const uint32_t groups = gridDim.x * (256u / kSurvLanes);
+  for (uint32_t u = (blockIdx.x * 256u + threadIdx.x) / kSurvLanes; u < n; u += groups) {  // (uniform per group)
+    const unsigned long long ext = out_ext[u];
+    const uint32_t b = (uint32_t)ext, d = (uint32_t)(ext >> 32);
+    if (d >= kSurvHeavy) continue;
+    double sum = 0.0;
+    for (uint32_t j = sub; j < d; j += kSurvLanes) sum += s_old[out_ci[b + j]];
+#pragma unroll
+    for (uint32_t o = kSurvLanes / 2; o > 0; o >>= 1) sum += __shfl_xor(sum, o);
+    if (sub == 0) {
+      const double x = d ? alpha + (1.0 - alpha) * sum / (double)d : alpha;
+      s_new[u] = x;
+      if (check) {
+        const unsigned long long bits = surv_diff_bits(x, s_old[u]);
+        mx = bits > mx ? bits : mx;
+      }
+    }
+  }
+  if (check) surv_max_out(mx, dmax);
+}
+
+__global__ __launch_bounds__(256) void k_survival_heavy(const int32_t* __restrict__ rows, uint32_t count,
+                                                         const unsigned long long* __restrict__ out_ext,
+                                                         const int32_t* __restrict__ out_ci,
+                                                         const double* __restrict__ s_old, double* __restrict__ s_new,
+                                                         double alpha, int check, unsigned long long* __restrict__ dmax) {
+  __shared__ double s_red[4];
+  unsigned long long mx = 0ull;
+  for (uint32_t i = blockIdx.x; i < count; i += gridDim.x) {
+    const int32_t u = rows[i];
+    const unsigned long long ext = out_ext[u];
+    const uint32_t b = (uint32_t)ext, d = (uint32_t)(ext >> 32);
+    double sum = 0.0;
+    for (uint32_t j = threadIdx.x; j < d; j += 256u) sum += s_old[out_ci[b + j]];
+    sum = block_sum_f64(sum, s_red);
+    if (threadIdx.x == 0) {
+      const double x = alpha + (1.0 - alpha) * sum / (double)d;
+      s_new[u] = x;
+      if (check) {
+        const unsigned long long bits = surv_diff_bits(x, s_old[u]);
+        mx = bits > mx ? bits : mx;
+      }
+    }
+  }
+  if (check) surv_max_out(mx, dmax);
+}
+
+// Gather walks of one target's sources: work item (p, c) = the walks [c * chunk_walks, min(w, (c + 1) * chunk_walks))
+// of pair p, one wave per item.  The walks are pprhip_random_walk_batch's (walker_init / walker_step, stream
+// PPRHIP_PAIR_WALK_STREAM, no zero-hop skip); a lane whose walk has stopped adds residue[terminal] to its register and
+// takes the item's next walk (refill in ballot order, so which lane runs which walk depends on the item alone).  The
+// wave's sum goes to part[p * chunks + c]: no atomics on a pair's value, the same bits in every call.
+__global__ __launch_bounds__(64) void k_pair_walk(const int32_t* __restrict__ src, uint32_t n_pairs, uint32_t chunks,
+                                                   unsigned long long chunk_walks, unsigned long long walks,
+                                                   const unsigned long long* __restrict__ out_ext,
+                                                   const uint4* __restrict__ walk_rec, const int32_t* __restrict__ new2old,
+                                                   const double* __restrict__ residue, double alpha, uint32_t k0,
+                                                   uint32_t k1, double* __restrict__ part,
+                                                   unsigned long long* __restrict__ steps_out) {
+  const int lane = threadIdx.x;
+  const unsigned long long items = (unsigned long long)n_pairs * chunks;
+  unsigned long long steps = 0;
+  for (unsigned long long it = blockIdx.x; it < items; it += gridDim.x) {
+    const uint32_t p = (uint32_t)(it / chunks), c = (uint32_t)(it % chunks);
+    const int32_t s = src[p];
+    const unsigned long long sext = out_ext[s];
+    const int32_t s_orig = new2old[s];
+    const unsigned long long lo = (unsigned long long)c * chunk_walks;
+    const unsigned long long hi = lo + chunk_walks < walks ? lo + chunk_walks : walks;
+    unsigned long long cursor = lo;
+    double acc = 0.0;
+    Walker w;
+    bool walking = false;
+    for (;;) {
+      const unsigned long long need = __ballot(!walking);
+      if (need && cursor < hi) {
+        const unsigned long long avail = hi - cursor;
+        const uint32_t rank = __popcll(need & ((1ull << lane) - 1ull));
+        if (!walking && rank < avail) {
+          walker_init(w, s, sext, s_orig, cursor + rank, PPRHIP_PAIR_WALK_STREAM, false);
+          if ((sext >> 32) == 0) acc += residue[s];  // a dead-end start is its own terminal (k_walk_batch)
+          else walking = true;
+        }
+        const unsigned long long want = __popcll(need);
+        cursor += want < avail ? want : avail;
+      }
+      if (__ballot(walking) == 0) {
+        if (cursor >= hi) break;
+        continue;
+      }
+      if (walking && walker_step(w, walk_rec, alpha, k0, k1)) {
+        acc += residue[w.cur];
+        steps += w.moves;
+        walking = false;
+      }
+    }
+    acc = wave_sum_f64(acc);
+    if (lane == 0) part[(size_t)p * chunks + c] = acc;
+  }
+  steps = wave_sum_u64(steps);
+  if (lane == 0 && steps) atomic_add_u64(steps_out, steps);
+}
+
+// value of pair p = p_t(s) / S(s) + (sum of its chunks, in chunk order) / w, written at the pair's place in the call
+__global__ __launch_bounds__(256) void k_pair_reduce(const int32_t* __restrict__ src, const int32_t* __restrict__ pos,
+                                                      uint32_t n_pairs, uint32_t chunks, const double* __restrict__ part,
+                                                      double walks, const double* __restrict__ reserve,
+                                                      const double* __restrict__ survival, double* __restrict__ values) {
+  const uint32_t p = blockIdx.x * 256u + threadIdx.x;
+  if (p >= n_pairs) return;
+  const int32_t s = src[p];
+  double sum = 0.0;
+  for (uint32_t c = 0; c < chunks; ++c) sum += part[(size_t)p * chunks + c];
+  double v = reserve[s] / survival[s];
+  if (chunks) v += sum / walks;
+  values[pos[p]] = v;
+}
+
+// ------------------------------------------------------------------------------------------------
 // launchers
 // ------------------------------------------------------------------------------------------------
+int launch_survival_iter(pprhip_graph* g, const double* s_old, double* s_new, double alpha, const int32_t* d_heavy,
+                         uint32_t n_heavy, unsigned long long* dmax) {
+  const uint32_t n = g->gr->n;
+  const uint64_t b = ((uint64_t)n * kSurvLanes + 255) / 256;
+  const uint32_t grid = (uint32_t)(b > 16384 ? 16384 : (b < 1 ? 1 : b));
+  hipLaunchKernelGGL(k_survival_iter, dim3(grid), dim3(256), 0, g->stream, n, g->gr->out_ext, g->gr->out_ci, s_old, s_new,
+                     alpha, dmax ? 1 : 0, dmax);
+  PPRHIP_CHECK_HIP(hipGetLastError());
+  if (n_heavy) {
+    hipLaunchKernelGGL(k_survival_heavy, dim3(std::min<uint32_t>(n_heavy, 4096u)), dim3(256), 0, g->stream, d_heavy,
+                       n_heavy, g->gr->out_ext, g->gr->out_ci, s_old, s_new, alpha, dmax ? 1 : 0, dmax);
+    PPRHIP_CHECK_HIP(hipGetLastError());
+  }
+  return PPRHIP_OK;
+}
+
+uint32_t survival_heavy_degree() { return kSurvHeavy; }
+
+int launch_pair_walk(pprhip_graph* g, const int32_t* d_src, uint32_t n_pairs, uint32_t chunks, uint64_t chunk_walks,
+                     uint64_t walks, double alpha, uint64_t seed, double* d_part, unsigned long long* d_steps) {
+  const uint64_t items = (uint64_t)n_pairs * chunks;
+  if (items == 0) return PPRHIP_OK;
+  const uint64_t cap = (uint64_t)g->gr->n_cus * kWalkWavesPerCu;
+  const uint32_t grid = (uint32_t)(items < cap ? items : cap);
+  hipLaunchKernelGGL(k_pair_walk, dim3(grid), dim3(64), 0, g->stream, d_src, n_pairs, chunks,
+                     (unsigned long long)chunk_walks, (unsigned long long)walks, g->gr->out_ext,
+                     reinterpret_cast<const uint4*>(g->gr->walk_rec), g->gr->new2old, g->residue, alpha, (uint32_t)seed,
+                     (uint32_t)(seed >> 32), d_part, d_steps);
+  PPRHIP_CHECK_HIP(hipGetLastError());
+  return PPRHIP_OK;
+}
+
+int launch_pair_reduce(pprhip_graph* g, const int32_t* d_src, const int32_t* d_pos, uint32_t n_pairs, uint32_t chunks,
+                       const double* d_part, uint64_t walks, const double* survival, double* d_values) {
+  if (n_pairs == 0) return PPRHIP_OK;
+  hipLaunchKernelGGL(k_pair_reduce, dim3((n_pairs + 255) / 256), dim3(256), 0, g->stream, d_src, d_pos, n_pairs, chunks,
+                     d_part, (double)walks, g->reserve, survival, d_values);
+  PPRHIP_CHECK_HIP(hipGetLastError());
+  return PPRHIP_OK;
+}
+
 int init_kernels_walk() {  // loads this file's code object on the current device (see init_kernels_push)
   hipFuncAttributes fa;
   PPRHIP_CHECK_HIP(hipFuncGetAttributes(&fa, reinterpret_cast<const void*>(&k_mc_walk)));
