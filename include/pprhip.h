@@ -289,6 +289,7 @@ void pprhip_lift_destroy(pprhip_lift_t* lift);
  * thread uses the handle. */
 #define PPRHIP_RELEASE_ALL_PAIR 1u
 #define PPRHIP_RELEASE_BATCH 2u
+#define PPRHIP_RELEASE_WALK_INDEX 4u /* the walk index (pprhip_walk_index_build): as pprhip_walk_index_drop */
 int pprhip_graph_release(pprhip_graph_t* g, unsigned what);
 int pprhip_graph_info(const pprhip_graph_t* g, uint32_t* n, uint64_t* m, int* device);
 /* HBM of the handle's device: bytes free and in all (hipMemGetInfo) - what a job holds at a point of its run is
@@ -578,6 +579,54 @@ int pprhip_walk_survival(pprhip_graph_t* g, double alpha, double* survival_out);
 int pprhip_ppr_pairs(pprhip_graph_t* g, const int32_t* sources, const int32_t* targets, int q, double eps,
                      const pprhip_fora_conf_t* conf, double rmax, uint64_t seed, double* values_out,
                      pprhip_stats_t* stats_sum);
+
+/* ---------------------------------------------------------------- walk index (FORA+; beyond the reference)
+ * FORA as published has a second form, FORA+: the terminals of walks drawn once are kept per node and a query reads
+ * them instead of walking.  Here walk (seed, stream, start, walk_idx) is a pure function and every whole-graph FORA
+ * path - pprhip_fora_single_source, pprhip_fora_seeds, the batched calls, the resident store, the query stream,
+ * pprhip_fora_batch - draws the walks (seed, stream 0, v, 0 .. omega_v - 1) with the forced first hop for a residue
+ * node v, whatever the query's source (a walk restarts at its own start node at a dead end).  An index that holds, for
+ * node v, the terminals of the walks 0 .. cap(v) - 1 at one (alpha, seed) therefore serves such a query with the walks
+ * it would have drawn itself: the result is the same vector up to fp64 addition order.
+ * Use rule: a whole-graph FORA walk phase on a handle whose index was built at the call's alpha and seed (bit for bit)
+ * reads walk i of residue node v from the index when i < cap(v) and walks it live, with its own index i, otherwise; with
+ * another alpha or seed, or without an index, the phase runs as before.  Top-k rounds, pprhip_monte_carlo, the pair
+ * walks and pprhip_random_walk_batch never touch the index.  Statistics of a served phase: walks and mc_sources as
+ * without the index; walk_steps, walk_loads and walk_load_lanes count the live walks only.
+ * Capacity: a converged push at threshold rmax leaves r(v) < d(v) * rmax, so node v starts at most
+ * ceil(d(v) * (1 - alpha) * rmax * omega) walks: cap(v) = ceil(d(v) * density) with the density below covers every
+ * query whose last threshold is <= rmax (a last round the cost model cut short may overflow; those walks are walked). */
+/* While a query stream is open on the handle, _build, _drop, _fetch and _usage return PPRHIP_ERR_STATE like every other
+ * call (_info does not touch the device and answers): usage is read after the stream's close. */
+/* Pure: density = (1 - alpha) * rmax * omega * (1 + 2^-20) for conf and eps (pprhip_fora_whole_params); rmax == 0 means
+ * rmax0, else finite and > 0.  The 2^-20 guard keeps rounding in d * density from leaving a converged push a terminal
+ * short. */
+int pprhip_walk_index_density(const pprhip_fora_conf_t* conf, double eps, double rmax, double* density_out);
+/* Builds the index of (alpha, seed) on the handle: cap(v) = ceil(d_out(v) * density) terminals per node (none for a
+ * dead end), terminal j of node v = the terminal of pprhip_random_walk_batch(start = v, walk_idx = j, alpha, seed,
+ * stream = 0, no_zero_hop = 1).  density: finite and > 0, the total below 2^36 terminals (PPRHIP_ERR_INVALID
+ * otherwise).  It lives with the lifted graph - every batch workspace and stream slot of the handle reads it - and is
+ * read-only after the build; a second build replaces the first.  PPRHIP_ERR_OOM leaves the handle as it was; while a
+ * query stream is open: PPRHIP_ERR_STATE.  stats (may be NULL): walks, walk_steps, mc_ms of the build. */
+int pprhip_walk_index_build(pprhip_graph_t* g, double alpha, uint64_t seed, double density, pprhip_stats_t* stats);
+/* Frees the index (no-op without one); pprhip_graph_release(PPRHIP_RELEASE_WALK_INDEX) does the same and
+ * pprhip_graph_destroy frees it too. */
+int pprhip_walk_index_drop(pprhip_graph_t* g);
+/* What the handle's index holds (every output may be NULL; *present == 0: the others are zero). */
+int pprhip_walk_index_info(const pprhip_graph_t* g, int* present, double* alpha, uint64_t* seed, double* density,
+                           uint64_t* terminals, uint64_t* bytes);
+/* The terminals of one node in original ids: *count_out = cap(node), the first min(cap, count) of them written. */
+int pprhip_walk_index_fetch(pprhip_graph_t* g, int32_t node, int32_t* terminals_out, uint64_t cap, uint64_t* count_out);
+/* Walks of the whole-graph FORA phases since the build (or the last reset) that were read from the index (served),
+ * and walks of those phases that were walked live (walked: indices beyond a node's capacity, dead-end starts).  A phase
+ * that did not use the index (other alpha or seed) counts in neither.  Covers the whole handle, batched calls
+ * included; to be read when no call is in flight.  reset != 0 zeroes both afterwards. */
+int pprhip_walk_index_usage(pprhip_graph_t* g, uint64_t* served, uint64_t* walked, int reset);
+/* The single and the batch profile for a handle with an index.  They equal pprhip_tuning_default / pprhip_tuning_batch:
+ * with c_walk_ns at the measured cost of a served walk the served runs were slower (DESIGN.md 2 "Walk index" has the
+ * figures).  Nothing selects them implicitly: the caller sets them (pprhip_graph_set_tuning). */
+void pprhip_tuning_indexed(pprhip_tuning_t* t);
+void pprhip_tuning_indexed_batch(pprhip_tuning_t* t);
 
 /* ---------------------------------------------------------------- ground truth (a12) */
 /* Power_Method.computeWholeGraphPPR (Power_Method.java:44-101): `iters` synchronous sweeps. */

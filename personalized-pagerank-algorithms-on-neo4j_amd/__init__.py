@@ -86,6 +86,8 @@ EXPORTS = [
     "pprhip_set_kernel_timing", "pprhip_shard_target_cuts", "pprhip_forward_push_seeds", "pprhip_fora_seeds",
     "pprhip_fora_topk_seeds", "pprhip_fora_batch_seeds", "pprhip_fora_batch_topk_seeds",
     "pprhip_pair_params", "pprhip_walk_survival", "pprhip_ppr_pairs",
+    "pprhip_walk_index_density", "pprhip_walk_index_build", "pprhip_walk_index_drop", "pprhip_walk_index_info",
+    "pprhip_walk_index_fetch", "pprhip_walk_index_usage", "pprhip_tuning_indexed", "pprhip_tuning_indexed_batch",
 ]
 PAIR_WALK_STREAM = 0xFFFF  # PPRHIP_PAIR_WALK_STREAM: the walk stream of every single-pair walk
 COMM_ID_BYTES = 128
@@ -199,6 +201,16 @@ def lib():
     L.pprhip_pair_params.argtypes = [P(ForaConf), dbl, dbl, P(dbl), P(u64)]
     L.pprhip_walk_survival.argtypes = [vp, dbl, vp]
     L.pprhip_ppr_pairs.argtypes = [vp, vp, vp, ci, dbl, P(ForaConf), dbl, u64, vp, P(Stats)]
+    L.pprhip_walk_index_density.argtypes = [P(ForaConf), dbl, dbl, P(dbl)]
+    L.pprhip_walk_index_build.argtypes = [vp, dbl, u64, dbl, P(Stats)]
+    L.pprhip_walk_index_drop.argtypes = [vp]
+    L.pprhip_walk_index_info.argtypes = [vp, P(ci), P(dbl), P(u64), P(dbl), P(u64), P(u64)]
+    L.pprhip_walk_index_fetch.argtypes = [vp, i32, vp, u64, P(u64)]
+    L.pprhip_walk_index_usage.argtypes = [vp, P(u64), P(u64), ci]
+    L.pprhip_tuning_indexed.argtypes = [P(Tuning)]
+    L.pprhip_tuning_indexed.restype = None
+    L.pprhip_tuning_indexed_batch.argtypes = [P(Tuning)]
+    L.pprhip_tuning_indexed_batch.restype = None
     _lib = L
     # the destroy entry points, reachable from destructors that run while the interpreter shuts down (the name `lib`
     # may already be None then: "TypeError: 'NoneType' object is not callable" out of Index.__del__, round 3)
@@ -421,6 +433,28 @@ def tuning_batch():
     t = Tuning()
     lib().pprhip_tuning_batch(C.byref(t))
     return t
+
+
+def tuning_indexed():
+    """The single-query profile for a handle with a walk index (pprhip_tuning_indexed); set it with Graph.set_tuning."""
+    t = Tuning()
+    lib().pprhip_tuning_indexed(C.byref(t))
+    return t
+
+
+def tuning_indexed_batch():
+    """The batch profile for a handle with a walk index (pprhip_tuning_indexed_batch)."""
+    t = Tuning()
+    lib().pprhip_tuning_indexed_batch(C.byref(t))
+    return t
+
+
+def walk_index_density(conf, eps, rmax=0.0):
+    """Terminals per out-edge of a walk index that covers every whole-graph FORA query whose last push threshold is
+    <= rmax (0: rmax0 of conf and eps): (1 - alpha) * rmax * omega * (1 + 2^-20)  (pprhip_walk_index_density)."""
+    d = C.c_double()
+    _check(lib().pprhip_walk_index_density(C.byref(conf), eps, rmax, C.byref(d)))
+    return d.value
 
 
 def tuning_batch_for(q):
@@ -707,7 +741,7 @@ class Graph:
             _LIVE["graph_destroy"](self.h)
             self.h = None
 
-    RELEASE_ALL_PAIR, RELEASE_BATCH = 1, 2
+    RELEASE_ALL_PAIR, RELEASE_BATCH, RELEASE_WALK_INDEX = 1, 2, 4
 
     def release(self, what):
         """Hands the workspaces of the named entry points back (pprhip_graph_release); they come back on next use."""
@@ -773,6 +807,45 @@ class Graph:
         _check(lib().pprhip_random_walk_batch(self.h, _ptr(starts), _ptr(idx), starts.size, alpha, seed, stream,
                                               int(no_zero_hop), _ptr(term), _ptr(steps)))
         return term, steps
+
+    def build_walk_index(self, alpha, seed, density=None, eps=0.5, conf=None):
+        """Builds the FORA+ walk index of (alpha, seed) on the handle (pprhip_walk_index_build): ceil(d_out(v) * density)
+        stored walk terminals per node, which every whole-graph FORA call at that alpha and seed then reads instead of
+        walking.  density None: the density at rmax0 of eps and conf (walk_index_density).  Returns the build's Stats."""
+        if density is None:
+            density = walk_index_density(conf or conf_whole_graph(self.n, self.m, alpha), eps)
+        st = Stats()
+        _check(lib().pprhip_walk_index_build(self.h, alpha, seed, density, C.byref(st)))
+        return st
+
+    def drop_walk_index(self):
+        _check(lib().pprhip_walk_index_drop(self.h))
+
+    def walk_index_info(self):
+        """None without an index, else dict(alpha, seed, density, terminals, bytes)."""
+        present, a, s, d = C.c_int(), C.c_double(), C.c_uint64(), C.c_double()
+        t, b = C.c_uint64(), C.c_uint64()
+        _check(lib().pprhip_walk_index_info(self.h, C.byref(present), C.byref(a), C.byref(s), C.byref(d), C.byref(t),
+                                            C.byref(b)))
+        if not present.value:
+            return None
+        return dict(alpha=a.value, seed=s.value, density=d.value, terminals=t.value, bytes=b.value)
+
+    def walk_index_terminals(self, node):
+        """The stored terminals of one node (original ids), in walk-index order."""
+        cnt = C.c_uint64()
+        _check(lib().pprhip_walk_index_fetch(self.h, node, None, 0, C.byref(cnt)))
+        out = np.empty(cnt.value, dtype=np.int32)
+        if cnt.value:
+            _check(lib().pprhip_walk_index_fetch(self.h, node, _ptr(out), cnt.value, C.byref(cnt)))
+        return out
+
+    def walk_index_usage(self, reset=False):
+        """(served, walked): walks of whole-graph FORA phases read from the index / walked live in those phases, since
+        the build or the last reset."""
+        s, w = C.c_uint64(), C.c_uint64()
+        _check(lib().pprhip_walk_index_usage(self.h, C.byref(s), C.byref(w), int(bool(reset))))
+        return s.value, w.value
 
     def fora_single_source(self, src, eps, alpha, seed, n_rounds=0, conf=None, fetch=True):
         conf = conf or conf_whole_graph(self.n, self.m, alpha)

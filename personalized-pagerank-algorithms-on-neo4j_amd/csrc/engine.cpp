@@ -1006,8 +1006,8 @@ int device_sum(pprhip_graph* g, const double* x, double* out, uint32_t count) {
 // run since the workspace was reset counted on the device (steps, walks, sources: adjacent in DevCounters).
 int read_dead_pops(pprhip_graph* g, pprhip_stats_t& st) {
   poll_idle(g);
-  static_assert(offsetof(DevCounters, walk_lanes) == offsetof(DevCounters, dead_pops) + 40, "one copy for the six");
-  PPRHIP_TRY(fetch_small(g, &g->ctr->dead_pops, &g->h_ctr->dead_pops, 6 * sizeof(unsigned long long)));
+  static_assert(offsetof(DevCounters, walks_served) == offsetof(DevCounters, dead_pops) + 48, "one copy for the seven");
+  PPRHIP_TRY(fetch_small(g, &g->ctr->dead_pops, &g->h_ctr->dead_pops, 7 * sizeof(unsigned long long)));
   st.walk_loads = g->h_ctr->walk_loads;
   st.walk_load_lanes = g->h_ctr->walk_lanes;
   st.push_bytes += 16ull * (g->h_ctr->dead_pops - st.dead_end_pops);
@@ -1015,7 +1015,12 @@ int read_dead_pops(pprhip_graph* g, pprhip_stats_t& st) {
   // cumulative over the query's walk phases: what is new since the last read goes into the statistics
   const uint64_t steps = g->h_ctr->walk_steps, walks = g->h_ctr->walks_total, srcs = g->h_ctr->sources_total;
   if (steps >= st.walk_steps && walks >= st.walks && srcs >= st.mc_sources) {
-    const uint64_t more = 12ull * (steps - st.walk_steps) + 16ull * (walks - st.walks) + 12ull * (srcs - st.mc_sources);
+    // a walk served from the walk index (whole-graph queries: one walk phase, so the counter is the phase's) moves its
+    // 4-byte terminal and its 8-byte deposit instead of a live walk's 16 bytes, and the plan is streamed a second time
+    // (DESIGN.md §2 "Walk index")
+    const uint64_t served = std::min<uint64_t>(g->h_ctr->walks_served, walks - st.walks);
+    const uint64_t more = 12ull * (steps - st.walk_steps) + 16ull * (walks - st.walks - served) + 12ull * served +
+                          (served ? 24ull : 12ull) * (srcs - st.mc_sources);
     st.mc_bytes += more;
     ktimer().add_bytes(PPRHIP_KERNEL_WALK, more);
     st.walk_steps = steps;
@@ -1050,7 +1055,13 @@ int launch_walk_plan(pprhip_graph* g, int variant, double alpha, double rsum, lo
 int launch_walk_run(pprhip_graph* g, int variant, double alpha, uint64_t seed, uint32_t stream, double* target) {
   poll_idle(g);
   ktimer().begin(PPRHIP_KERNEL_WALK, 0);  // (its bytes are added when the counters are read)
-  PPRHIP_TRY(launch_mc_walk(g, alpha, seed, stream, variant == 0 ? 1 : 0, target));
+  // Whole-graph FORA walks (variant 0: stream 0, forced first hop, walk indices 0 .. omega_i - 1 per residue node) are
+  // read from the handle's walk index when it was built at this alpha and seed, bit for bit; everything else walks.
+  const WalkIndex* ix = g->gr->widx;
+  if (variant == 0 && stream == 0 && ix && std::memcmp(&ix->alpha, &alpha, sizeof alpha) == 0 && ix->seed == seed)
+    PPRHIP_TRY(launch_mc_walk_indexed(g, ix, alpha, seed, target));
+  else
+    PPRHIP_TRY(launch_mc_walk(g, alpha, seed, stream, variant == 0 ? 1 : 0, target));
   ktimer().end();
   return PPRHIP_OK;
 }
@@ -1492,6 +1503,12 @@ void pprhip_tuning_batch(pprhip_tuning_t* t) {
   t->gs_frac = 0.05;
 }
 
+// The single and the batch profile for a handle that carries a walk index (pprhip_walk_index_build): equal to the
+// profiles they start from, because c_walk_ns at the measured cost of a served walk lost (DESIGN.md §2 "Walk index").
+void pprhip_tuning_indexed(pprhip_tuning_t* t) { pprhip_tuning_default(t); }
+
+void pprhip_tuning_indexed_batch(pprhip_tuning_t* t) { pprhip_tuning_batch(t); }
+
 // The batch profile for a call of q queries on one GPU (config #4's shares: 50 queries over 8 GPUs are 6-7 per call).  A
 // sweep costs the same whatever the number of busy columns, so a dense level costs each query of a small call more:
 // the dense constants and the level-shape thresholds scale with 14.5 / min(q, 14.5) columns, up to the single-query
@@ -1679,6 +1696,7 @@ int pprhip_graph_create(uint32_t n, uint64_t m, const uint32_t* out_rp, const in
 
 // the lifted graph and every layout built from it (pprhip_graph_destroy, after everything that uses it)
 static void free_graph_data(GraphData* D) {
+  free_walk_index(D);
   void* ptrs[] = {D->walk_rec, D->out_ext, D->out_rp, D->out_ci, D->in_rp, D->in_ci, D->new2old, D->old2new, D->start_flags,
                   D->chunk_starts, D->nz_rows, D->zin_rows, D->cross_bits, D->start_flags_o, D->chunk_starts_o,
                   D->nz_rows_o, D->z_rows_o, D->cross_bits_o, D->survival};
@@ -1713,13 +1731,14 @@ static void free_all_pair(pprhip_graph* g) {
 
 int pprhip_graph_release(pprhip_graph_t* g, unsigned what) {
   PPRHIP_TRY(check_graph(g, "pprhip_graph_release"));
-  if (what & ~(PPRHIP_RELEASE_ALL_PAIR | PPRHIP_RELEASE_BATCH)) {
+  if (what & ~(PPRHIP_RELEASE_ALL_PAIR | PPRHIP_RELEASE_BATCH | PPRHIP_RELEASE_WALK_INDEX)) {
     set_error("pprhip_graph_release: unknown flag in %u", what);
     return PPRHIP_ERR_INVALID;
   }
   PPRHIP_CHECK_HIP(hipStreamSynchronize(g->stream));
   if (what & PPRHIP_RELEASE_ALL_PAIR) free_all_pair(g);
   if (what & PPRHIP_RELEASE_BATCH) free_batch(g);
+  if (what & PPRHIP_RELEASE_WALK_INDEX) PPRHIP_TRY(pprhip_walk_index_drop(g));
   return PPRHIP_OK;
 }
 

@@ -23,6 +23,7 @@ struct DevCounters {
   unsigned long long sources_total;  // residue entries that started walks
   unsigned long long walk_loads;     // load instructions the walk kernel's waves issued ...
   unsigned long long walk_lanes;     // ... and the lanes they carried (64 per load = full waves)
+  unsigned long long walks_served;   // walks whose terminal was read from the walk index (k_index_serve)
   double sum_out;                    // reduction result (the walk plan reads it on the device)
   // walk plan of a phase: sources << 36 | walks, counted by the plan kernel, read by the walk kernel on the device.
   // Three cells used in turn: the plan of phase p counts into cell p % 3 and clears cell (p + 1) % 3, which the walks
@@ -31,7 +32,9 @@ struct DevCounters {
   // the residue sum a top-k round's plan was derived from, kept per phase like the cells above: the selection that
   // ends the round hands it to the host in its header (no copy command of its own)
   double plan_sum[3];
-  unsigned long long pad[1];
+  // walks of the latest indexed walk phase that the index does not hold: k_mc_plan<0> zeroes it, k_index_serve counts
+  // them, k_mc_walk<true> returns at once when there are none (a whole-graph plan never runs ahead of the walks before)
+  unsigned long long walks_over;
   unsigned long long dhist[8];    // dense batch: dhist[i] = frontier that dense level i of the batch starts from
   int dstate[8];                  // dense batch: sweep state of level i (kGsNone: the level does not run)
 };
@@ -318,6 +321,18 @@ struct ClearList {  // ranges one k_clear launch zeroes
   int n;
 };
 
+// FORA+ walk index (walk_index.cpp; DESIGN.md §2 "Walk index"): per node v the terminals of the walks
+// (seed, stream 0, v, idx < cap(v)) with the forced first hop at one alpha, cap(v) = ceil(d_out(v) * density).  Lives on
+// the lifted graph, read-only after its build; the usage counters are the only cells kernels write.
+struct WalkIndex {
+  unsigned long long* off = nullptr;    // [n + 1] first terminal of every node, internal order
+  int32_t* term = nullptr;              // [total] terminals, internal ids
+  unsigned long long* usage = nullptr;  // [3] walks served from the index / walked live in served phases; the build's walk steps
+  std::vector<unsigned long long> h_off;
+  double alpha = 0.0, density = 0.0;
+  uint64_t seed = 0, total = 0;
+};
+
 struct WalkPlanRec {  // one residue entry of a walk phase (k_mc_plan -> k_mc_walk): 32 bytes
   unsigned long long woff;  // walks of the entries before it
   double inc;               // what each of its walks adds at its terminal
@@ -384,6 +399,7 @@ struct GraphData {
   // calling thread before a pair call's workers start, rebuilt only when alpha changes
   double* survival = nullptr;
   double survival_alpha = 0.0;
+  WalkIndex* widx = nullptr;  // the walk index, or none (pprhip_walk_index_build / _drop)
 };
 
 // The handle's batched-call state: the workspaces ("slots") of its batched queries and the arrays their dense levels
@@ -606,6 +622,11 @@ int launch_hold(hipStream_t stream, unsigned long long ticks);
 int launch_mc_plan(pprhip_graph* g, int variant, double alpha, double rsum, double nrw, double omega_dev, double* target,
                    const double* copy_src = nullptr, double* copy_dst = nullptr);
 int launch_mc_walk(pprhip_graph* g, double alpha, uint64_t seed, uint32_t stream, int no_zero_hop, double* target);
+// the walks of the latest plan with the index `ix`: k_index_serve deposits the stored terminals, k_mc_walk<true> walks
+// what the index does not hold (walk idx >= cap of its node, dead-end starts) with the walks' own indices
+int launch_mc_walk_indexed(pprhip_graph* g, const WalkIndex* ix, double alpha, uint64_t seed, double* target);
+// fills ix->term from ix->off (already in HBM): terminal j of node v = walk (seed, stream 0, v, j), forced first hop
+int launch_index_build(pprhip_graph* g, const WalkIndex* ix, unsigned long long* d_steps);
 // (rows of out-degree >= survival_heavy_degree() go in d_heavy: a workgroup each)
 int launch_survival_iter(pprhip_graph* g, const double* s_old, double* s_new, double alpha, const int32_t* d_heavy,
                          uint32_t n_heavy, unsigned long long* dmax);

@@ -129,7 +129,10 @@ __global__ __launch_bounds__(256) void k_mc_plan(uint32_t n, const double* __res
                                                   const int32_t* __restrict__ new2old, WalkPlanRec* __restrict__ plan,
                                                   DevCounters* ctr, int parity, int next_cell,
                                                   const double* __restrict__ copy_src, double* __restrict__ copy_dst) {
-  if (blockIdx.x == 0 && threadIdx.x == 0) ctr->mc_plan[next_cell] = 0ull;  // (engine.hpp: DevCounters::mc_plan)
+  if (blockIdx.x == 0 && threadIdx.x == 0) {
+    ctr->mc_plan[next_cell] = 0ull;  // (engine.hpp: DevCounters::mc_plan)
+    if (VARIANT == 0) ctr->walks_over = 0ull;  // (counted anew by the k_index_serve of this phase, if one runs)
+  }
   const uint32_t per = (n + gridDim.x - 1) / gridDim.x;
   const uint32_t lo = blockIdx.x * per;
   const uint32_t hi = lo + per < n ? lo + per : n;
@@ -305,10 +308,16 @@ __device__ __forceinline__ uint32_t plan_upper_bound(const WalkPlanRec* __restri
   return a;
 }
 
+// INDEXED (idx_off: the walk index's offsets): k_index_serve has deposited the stored terminals of this plan; a walk
+// whose index lies below its node's capacity is skipped here (a fourth early-out beside the dead-end start), the others
+// - an entry's tail [cap, omega_i), every walk of a dead-end start - run with their own indices.  The unindexed
+// instantiation is the kernel as it was.
+template <bool INDEXED>
 __global__ __launch_bounds__(64) void k_mc_walk(const WalkPlanRec* __restrict__ plan_rec,
                                                  const uint4* __restrict__ walk_rec, double* __restrict__ target,
                                                  double alpha, uint32_t k0, uint32_t k1, uint32_t stream,
-                                                 int no_zero_hop, DevCounters* ctr, int parity) {
+                                                 int no_zero_hop, DevCounters* ctr, int parity,
+                                                 const unsigned long long* __restrict__ idx_off) {
   // the plan kernel counted sources and walks into mc_plan[parity]; the query's totals grow by this phase
   const unsigned long long plan = ctr->mc_plan[parity];
   const uint32_t n_src = (uint32_t)(plan >> kPackShift);
@@ -317,6 +326,7 @@ __global__ __launch_bounds__(64) void k_mc_walk(const WalkPlanRec* __restrict__ 
     ctr->walks_total += n_walks;
     ctr->sources_total += n_src;
   }
+  if (INDEXED && ctr->walks_over == 0ull) return;  // the index held every walk of the phase
   __shared__ WalkWindow S;
   const int lane = threadIdx.x;
   // this wave's share: whole groups of 64 walks, so that a short phase still spreads over the grid
@@ -404,8 +414,12 @@ __global__ __launch_bounds__(64) void k_mc_walk(const WalkPlanRec* __restrict__ 
         const int32_t start = S.node[j];
         inc = S.inc[j];
         const unsigned long long sext = S.ext[j];
-        walker_init(w, start, sext, S.orig[j], gidx - S.woff[j], stream, no_zero_hop != 0);
-        if ((sext >> 32) == 0) {
+        const unsigned long long widx = gidx - S.woff[j];
+        walker_init(w, start, sext, S.orig[j], widx, stream, no_zero_hop != 0);
+        bool stored = false;
+        if (INDEXED) stored = widx < idx_off[start + 1] - idx_off[start];
+        if (stored) {  // k_index_serve has deposited this walk's terminal
+        } else if ((sext >> 32) == 0) {
           atomic_add_noret(&target[start], inc);  // Monte_Carlo.java:70-72 / :106-108
         } else {
           walking = true;
@@ -441,6 +455,153 @@ __global__ __launch_bounds__(64) void k_mc_walk(const WalkPlanRec* __restrict__ 
   if (lane == 0 && n_loads) {
     atomic_add_u64(&ctr->walk_loads, n_loads);
     atomic_add_u64(&ctr->walk_lanes, n_lanes);
+  }
+}
+
+// ------------------------------------------------------------------------------------------------
+// walk index (FORA+, DESIGN.md §2 "Walk index"): build and serve
+// ------------------------------------------------------------------------------------------------
+// the node whose terminals hold index position p: the largest v in [a, b] with off[v] <= p (off[a] <= p is given; nodes
+// of capacity 0 share their offset with the node behind them and are passed over)
+__device__ __forceinline__ uint32_t index_node_of(const unsigned long long* __restrict__ off, uint32_t a, uint32_t b,
+                                                  unsigned long long p) {
+  while (a < b) {
+    const uint32_t mid = a + (b - a + 1u) / 2u;
+    if (off[mid] <= p) a = mid;
+    else b = mid - 1u;
+  }
+  return a;
+}
+
+// A wave takes a contiguous range of index positions; a lane whose walk has stopped stores its terminal (internal id)
+// and takes the range's next position (refill in ballot order, as k_pair_walk).  Position p of node v is walk
+// (seed, stream 0, v, p - off[v]) with the forced first hop: what k_mc_walk would run for walk p - off[v] of a residue
+// entry v.  Only nodes with out-edges have positions.
+__global__ __launch_bounds__(64) void k_index_build(const unsigned long long* __restrict__ off, uint32_t n,
+                                                     unsigned long long total,
+                                                     const unsigned long long* __restrict__ out_ext,
+                                                     const uint4* __restrict__ walk_rec,
+                                                     const int32_t* __restrict__ new2old, double alpha, uint32_t k0,
+                                                     uint32_t k1, int32_t* __restrict__ term,
+                                                     unsigned long long* __restrict__ steps_out) {
+  const int lane = threadIdx.x;
+  const unsigned long long groups = (total + 63) / 64;
+  const unsigned long long per = (groups + gridDim.x - 1) / gridDim.x * 64;
+  const unsigned long long lo = (unsigned long long)blockIdx.x * per;
+  if (lo >= total) return;
+  const unsigned long long hi = lo + per < total ? lo + per : total;
+  const uint32_t va = index_node_of(off, 0u, n - 1u, lo);
+  const uint32_t vb = index_node_of(off, va, n - 1u, hi - 1ull);
+  unsigned long long cursor = lo, pos = 0, steps = 0;
+  Walker w;
+  bool walking = false;
+  for (;;) {
+    const unsigned long long need = __ballot(!walking);
+    if (need && cursor < hi) {
+      const unsigned long long avail = hi - cursor;
+      const uint32_t rank = __popcll(need & ((1ull << lane) - 1ull));
+      if (!walking && rank < avail) {
+        pos = cursor + rank;
+        const uint32_t v = index_node_of(off, va, vb, pos);
+        const unsigned long long sext = out_ext[v];
+        walker_init(w, (int32_t)v, sext, new2old[v], pos - off[v], 0u, true);
+        if ((sext >> 32) == 0) term[pos] = (int32_t)v;  // (no node without out-edges has a position)
+        else walking = true;
+      }
+      const unsigned long long want = __popcll(need);
+      cursor += want < avail ? want : avail;
+    }
+    if (__ballot(walking) == 0) {
+      if (cursor >= hi) break;
+      continue;
+    }
+    if (walking && walker_step(w, walk_rec, alpha, k0, k1)) {
+      term[pos] = w.cur;
+      steps += w.moves;
+      walking = false;
+    }
+  }
+  steps = wave_sum_u64(steps);
+  if (lane == 0 && steps) atomic_add_u64(steps_out, steps);
+}
+
+// The walks of a plan (the WalkPlanRec stream k_mc_plan<0> wrote) from the index: a wave has a contiguous share of the
+// phase's walks, as in k_mc_walk, and takes it 64 walks at a time - lane l the walk c + l.  The entries those walks
+// belong to are at most 64 from the entry of walk c on (every entry owns a walk): their walk offsets, increments and
+// nodes are staged in LDS, a lane finds its entry there, and walk i of node v reads term[off[v] + i] - consecutive
+// lanes inside an entry read consecutive terminals - and adds the entry's increment there.  No Philox, no edge record.
+// A walk the index does not hold (i >= cap(v); every walk of a dead-end start, whose capacity is 0) is counted in
+// ctr->walks_over and left to k_mc_walk<true>.
+struct ServeWindow {  // LDS, one per wave
+  unsigned long long woff[65];
+  double inc[64];
+  int32_t node[64];
+};
+
+__global__ __launch_bounds__(64) void k_index_serve(const WalkPlanRec* __restrict__ plan_rec,
+                                                     const unsigned long long* __restrict__ idx_off,
+                                                     const int32_t* __restrict__ idx_term, double* __restrict__ target,
+                                                     DevCounters* ctr, int parity,
+                                                     unsigned long long* __restrict__ usage) {
+  const unsigned long long plan = ctr->mc_plan[parity];
+  const uint32_t n_src = (uint32_t)(plan >> kPackShift);
+  const unsigned long long n_walks = plan & kPackMask;
+  __shared__ ServeWindow S;
+  const int lane = threadIdx.x;
+  const unsigned long long groups = (n_walks + 63) / 64;
+  const unsigned long long per = (groups + gridDim.x - 1) / gridDim.x * 64;
+  const unsigned long long lo = (unsigned long long)blockIdx.x * per;
+  if (lo >= n_walks) return;
+  const unsigned long long hi = lo + per < n_walks ? lo + per : n_walks;
+  uint32_t e = plan_upper_bound(plan_rec, n_src, lo, lane) - 1u;  // the entry that holds walk `lo`
+  unsigned long long served = 0, over = 0;
+  for (unsigned long long c = lo; c < hi; c += 64) {
+    __syncthreads();  // the chunk before has read the window
+    const unsigned long long ei = (unsigned long long)e + (unsigned long long)lane;
+    if (ei < n_src) {
+      const WalkPlanRec r = plan_rec[ei];
+      S.woff[lane] = r.woff;
+      S.inc[lane] = r.inc;
+      S.node[lane] = r.node;
+    } else {
+      S.woff[lane] = n_walks;
+      S.inc[lane] = 0.0;
+      S.node[lane] = 0;
+    }
+    if (lane == 0) S.woff[64] = (unsigned long long)e + 64ull < n_src ? plan_rec[(size_t)e + 64].woff : n_walks;
+    __syncthreads();
+    const unsigned long long gw = c + (unsigned long long)lane;
+    const unsigned long long gq = gw < hi ? gw : hi - 1ull;
+    uint32_t j = 0;  // the largest staged entry whose first walk is <= gq (woff[0] <= c: e holds walk c)
+#pragma unroll
+    for (uint32_t step = 32; step > 0; step >>= 1)
+      if (S.woff[j + step] <= gq) j += step;
+    if (gw < hi) {
+      const int32_t v = S.node[j];
+      const unsigned long long i = gw - S.woff[j];
+      const unsigned long long o0 = idx_off[v], o1 = idx_off[v + 1];
+      if (i < o1 - o0) {
+        atomic_add_noret(&target[idx_term[o0 + i]], S.inc[j]);
+        served++;
+      } else {
+        over++;
+      }
+    }
+    // e becomes the entry of walk c + 64: lane 63's entry, or the one behind it when that starts there
+    const uint32_t jl = (uint32_t)__shfl((int)j, 63);
+    e += S.woff[jl + 1] == c + 64ull ? jl + 1u : jl;
+  }
+  served = wave_sum_u64(served);
+  over = wave_sum_u64(over);
+  if (lane == 0) {
+    if (served) {
+      atomic_add_u64(&ctr->walks_served, served);
+      atomic_add_u64(&usage[0], served);
+    }
+    if (over) {
+      atomic_add_u64(&ctr->walks_over, over);
+      atomic_add_u64(&usage[1], over);
+    }
   }
 }
 
@@ -697,7 +858,7 @@ int launch_pair_reduce(pprhip_graph* g, const int32_t* d_src, const int32_t* d_p
 
 int init_kernels_walk() {  // loads this file's code object on the current device (see init_kernels_push)
   hipFuncAttributes fa;
-  PPRHIP_CHECK_HIP(hipFuncGetAttributes(&fa, reinterpret_cast<const void*>(&k_mc_walk)));
+  PPRHIP_CHECK_HIP(hipFuncGetAttributes(&fa, reinterpret_cast<const void*>(&k_mc_walk<false>)));
   return PPRHIP_OK;
 }
 
@@ -742,7 +903,7 @@ int launch_mc_plan(pprhip_graph* g, int variant, double alpha, double rsum, doub
 
 // The walk count is only known on the device: a fixed grid of waves, each with an equal share of whatever the plan
 // holds (g->walk_hint, the budget when the host knows it, only trims the grid of a short phase).
-int launch_mc_walk(pprhip_graph* g, double alpha, uint64_t seed, uint32_t stream, int no_zero_hop, double* target) {
+static uint32_t mc_walk_grid(pprhip_graph* g) {
   // (walk_waves: a walk phase that runs beside other kernels leaves them room - the walks are bound by the memory
   // system from a few waves per CU on, tools/micro/chain_rate.hip)
   // a slot of a threaded batch shares the chip with fifteen others: few waves per CU, like a walk phase beside sweeps
@@ -752,9 +913,41 @@ int launch_mc_walk(pprhip_graph* g, double alpha, uint64_t seed, uint32_t stream
                                                     : kWalkWavesPerCu);
   if (g->walk_hint) grid = (uint32_t)std::min<unsigned long long>(grid, std::max<unsigned long long>((g->walk_hint + 63) / 64, 1ull));
   g->walk_hint = 0;
-  hipLaunchKernelGGL(k_mc_walk, dim3(grid), dim3(64), 0, g->stream, plan_rec_of(g, g->mc_last_plan),
+  return grid;
+}
+
+int launch_mc_walk(pprhip_graph* g, double alpha, uint64_t seed, uint32_t stream, int no_zero_hop, double* target) {
+  const uint32_t grid = mc_walk_grid(g);
+  hipLaunchKernelGGL(k_mc_walk<false>, dim3(grid), dim3(64), 0, g->stream, plan_rec_of(g, g->mc_last_plan),
                      reinterpret_cast<const uint4*>(g->gr->walk_rec), target, alpha, (uint32_t)seed, (uint32_t)(seed >> 32), stream,
-                     no_zero_hop, g->ctr, (int)(g->mc_last_plan % 3u));
+                     no_zero_hop, g->ctr, (int)(g->mc_last_plan % 3u), (const unsigned long long*)nullptr);
+  PPRHIP_CHECK_HIP(hipGetLastError());
+  return PPRHIP_OK;
+}
+
+// The same grid for both kernels: the serve kernel's share of a wave is a stream of terminals, the walk kernel behind
+// it returns at once unless the serve kernel counted walks the index does not hold.
+int launch_mc_walk_indexed(pprhip_graph* g, const WalkIndex* ix, double alpha, uint64_t seed, double* target) {
+  const uint32_t grid = mc_walk_grid(g);
+  const int cell = (int)(g->mc_last_plan % 3u);
+  hipLaunchKernelGGL(k_index_serve, dim3(grid), dim3(64), 0, g->stream, plan_rec_of(g, g->mc_last_plan), ix->off, ix->term,
+                     target, g->ctr, cell, ix->usage);
+  PPRHIP_CHECK_HIP(hipGetLastError());
+  hipLaunchKernelGGL(k_mc_walk<true>, dim3(grid), dim3(64), 0, g->stream, plan_rec_of(g, g->mc_last_plan),
+                     reinterpret_cast<const uint4*>(g->gr->walk_rec), target, alpha, (uint32_t)seed, (uint32_t)(seed >> 32), 0u,
+                     1, g->ctr, cell, (const unsigned long long*)ix->off);
+  PPRHIP_CHECK_HIP(hipGetLastError());
+  return PPRHIP_OK;
+}
+
+int launch_index_build(pprhip_graph* g, const WalkIndex* ix, unsigned long long* d_steps) {
+  if (ix->total == 0) return PPRHIP_OK;
+  const uint64_t cap = (uint64_t)g->gr->n_cus * kWalkWavesPerCu;
+  const uint64_t groups = (ix->total + 63) / 64;
+  const uint32_t grid = (uint32_t)(groups < cap ? groups : cap);
+  hipLaunchKernelGGL(k_index_build, dim3(grid), dim3(64), 0, g->stream, ix->off, g->gr->n, (unsigned long long)ix->total,
+                     g->gr->out_ext, reinterpret_cast<const uint4*>(g->gr->walk_rec), g->gr->new2old, ix->alpha,
+                     (uint32_t)ix->seed, (uint32_t)(ix->seed >> 32), ix->term, d_steps);
   PPRHIP_CHECK_HIP(hipGetLastError());
   return PPRHIP_OK;
 }

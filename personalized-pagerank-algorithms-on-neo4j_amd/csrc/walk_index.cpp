@@ -1,0 +1,177 @@
+// walk_index.cpp — the FORA+ walk index (include/pprhip.h "walk index"; DESIGN.md §2 "Walk index"): per node the
+// terminals of the walks a whole-graph FORA walk phase would draw from it, built once per (alpha, seed) and kept with
+// the lifted graph.  The kernels are in kernels_walk.hip (k_index_build, k_index_serve, k_mc_walk<true>); the walk
+// phase picks the index in launch_walk_run (engine.cpp).
+#include <cmath>
+#include <cstring>
+#include <memory>
+#include <new>
+
+#include "engine_internal.hpp"
+
+using namespace pprhip;
+using namespace pprhip::detail;
+
+namespace pprhip {
+namespace detail {
+
+static void destroy_index(WalkIndex* ix) {
+  if (!ix) return;
+  void* ptrs[] = {ix->off, ix->term, ix->usage};
+  for (void* p : ptrs)
+    if (p) (void)hipFree(p);
+  delete ix;
+}
+
+void free_walk_index(GraphData* D) {
+  destroy_index(D->widx);
+  D->widx = nullptr;
+}
+
+}  // namespace detail
+}  // namespace pprhip
+
+extern "C" {
+
+int pprhip_walk_index_density(const pprhip_fora_conf_t* conf, double eps, double rmax, double* density_out) {
+  static const char* fn = "pprhip_walk_index_density";
+  PPRHIP_TRY(check_positive(eps, fn, "eps"));
+  PPRHIP_TRY(check_conf(conf, fn, false));
+  PPRHIP_TRY(check_threshold(rmax, fn, "rmax"));
+  if (!conf || !density_out) {
+    set_error("%s: null argument", fn);
+    return PPRHIP_ERR_INVALID;
+  }
+  double rmax0 = 0.0, omega = 0.0;
+  PPRHIP_TRY(pprhip_fora_whole_params(conf, eps, &rmax0, &omega));
+  if (rmax == 0.0) rmax = rmax0;
+  *density_out = (1.0 - conf->alpha) * rmax * omega * (1.0 + 0x1p-20);
+  return PPRHIP_OK;
+}
+
+int pprhip_walk_index_build(pprhip_graph_t* g, double alpha, uint64_t seed, double density, pprhip_stats_t* stats) {
+  static const char* fn = "pprhip_walk_index_build";
+  PPRHIP_TRY(check_alpha(alpha, fn));
+  PPRHIP_TRY(check_positive(density, fn, "density"));
+  PPRHIP_TRY(check_graph(g, fn));
+  if (g->parent) {
+    set_error("%s: not a graph handle", fn);
+    return PPRHIP_ERR_INVALID;
+  }
+  GraphData* D = g->gr;
+  // (the new index is complete before the old one goes: whatever fails below frees it and leaves the handle as it was)
+  std::unique_ptr<WalkIndex, void (*)(WalkIndex*)> ix(new (std::nothrow) WalkIndex(), destroy_index);
+  if (!ix) return PPRHIP_ERR_OOM;
+  ix->alpha = alpha;
+  ix->seed = seed;
+  ix->density = density;
+  // cap(v) = ceil(d_out(v) * density) in internal order; the total must stay below the engine's walk limit
+  try {
+    ix->h_off.resize((size_t)D->n + 1);
+  } catch (const std::bad_alloc&) {
+    set_error("%s: out of host memory", fn);
+    return PPRHIP_ERR_OOM;
+  }
+  const double limit = (double)(1ull << kPackShift);
+  unsigned long long run = 0;
+  for (uint32_t v = 0; v < D->n; ++v) {
+    ix->h_off[v] = run;
+    const uint32_t d = D->h_out_rp[v + 1] - D->h_out_rp[v];
+    const double c = d ? std::ceil((double)d * density) : 0.0;
+    if (!(c < limit) || (double)run + c >= limit) {
+      set_error("%s: density = %g asks for 2^36 terminals or more (the engine's walk limit)", fn, density);
+      return PPRHIP_ERR_INVALID;
+    }
+    run += (unsigned long long)c;
+  }
+  ix->h_off[D->n] = run;
+  ix->total = run;
+  PPRHIP_TRY(alloc_dev((void**)&ix->off, sizeof(unsigned long long) * ((size_t)D->n + 1)));
+  PPRHIP_TRY(alloc_dev((void**)&ix->term, sizeof(int32_t) * (size_t)ix->total));
+  PPRHIP_TRY(alloc_dev((void**)&ix->usage, 3 * sizeof(unsigned long long)));  // (WalkIndex::usage)
+  PPRHIP_CHECK_HIP(hipMemcpyAsync(ix->off, ix->h_off.data(), sizeof(unsigned long long) * ((size_t)D->n + 1),
+                                  hipMemcpyHostToDevice, g->stream));
+  PPRHIP_CHECK_HIP(hipMemsetAsync(ix->usage, 0, 3 * sizeof(unsigned long long), g->stream));
+  PPRHIP_CHECK_HIP(hipEventRecord(g->ev[0], g->stream));
+  PPRHIP_TRY(launch_index_build(g, ix.get(), ix->usage + 2));
+  PPRHIP_CHECK_HIP(hipEventRecord(g->ev[1], g->stream));
+  unsigned long long steps = 0;
+  PPRHIP_CHECK_HIP(hipMemcpyAsync(&steps, ix->usage + 2, sizeof steps, hipMemcpyDeviceToHost, g->stream));
+  PPRHIP_CHECK_HIP(hipStreamSynchronize(g->stream));
+  if (stats) {
+    std::memset(stats, 0, sizeof *stats);
+    stats->walks = ix->total;
+    stats->walk_steps = steps;
+    stats->mc_ms = stats->total_ms = CallTimer::ms(g->ev[0], g->ev[1]);
+    stats->mc_bytes = 12ull * steps + 4ull * ix->total + 8ull * ((uint64_t)D->n + 1);
+  }
+  PPRHIP_CHECK_HIP(hipDeviceSynchronize());  // nothing reads the old index any more
+  free_walk_index(D);
+  D->widx = ix.release();
+  return PPRHIP_OK;
+}
+
+int pprhip_walk_index_drop(pprhip_graph_t* g) {
+  PPRHIP_TRY(check_graph(g, "pprhip_walk_index_drop"));
+  if (!g->gr->widx) return PPRHIP_OK;
+  PPRHIP_CHECK_HIP(hipDeviceSynchronize());
+  free_walk_index(g->gr);
+  return PPRHIP_OK;
+}
+
+int pprhip_walk_index_info(const pprhip_graph_t* g, int* present, double* alpha, uint64_t* seed, double* density,
+                           uint64_t* terminals, uint64_t* bytes) {
+  if (!g) {
+    set_error("pprhip_walk_index_info: null graph handle");
+    return PPRHIP_ERR_INVALID;
+  }
+  const WalkIndex* ix = g->gr->widx;
+  if (present) *present = ix ? 1 : 0;
+  if (alpha) *alpha = ix ? ix->alpha : 0.0;
+  if (seed) *seed = ix ? ix->seed : 0;
+  if (density) *density = ix ? ix->density : 0.0;
+  if (terminals) *terminals = ix ? ix->total : 0;
+  if (bytes) *bytes = ix ? 4ull * ix->total + 8ull * ((uint64_t)g->gr->n + 1) + 3ull * 8ull : 0;  // terminals, offsets, the three counter cells
+  return PPRHIP_OK;
+}
+
+int pprhip_walk_index_fetch(pprhip_graph_t* g, int32_t node, int32_t* terminals_out, uint64_t cap, uint64_t* count_out) {
+  static const char* fn = "pprhip_walk_index_fetch";
+  PPRHIP_TRY(check_graph(g, fn));
+  PPRHIP_TRY(check_node(g, node, fn));
+  const WalkIndex* ix = g->gr->widx;
+  if (!ix) {
+    set_error("%s: the handle has no walk index", fn);
+    return PPRHIP_ERR_STATE;
+  }
+  if (cap && !terminals_out) {
+    set_error("%s: null output", fn);
+    return PPRHIP_ERR_INVALID;
+  }
+  const int32_t v = g->gr->h_old2new[node];
+  const unsigned long long o0 = ix->h_off[v], cnt = ix->h_off[(size_t)v + 1] - o0;
+  if (count_out) *count_out = cnt;
+  const uint64_t take = cnt < cap ? cnt : cap;
+  if (take == 0) return PPRHIP_OK;
+  PPRHIP_CHECK_HIP(hipMemcpyAsync(terminals_out, ix->term + o0, sizeof(int32_t) * take, hipMemcpyDeviceToHost, g->stream));
+  PPRHIP_CHECK_HIP(hipStreamSynchronize(g->stream));
+  for (uint64_t i = 0; i < take; ++i) terminals_out[i] = g->gr->h_new2old[terminals_out[i]];
+  return PPRHIP_OK;
+}
+
+int pprhip_walk_index_usage(pprhip_graph_t* g, uint64_t* served, uint64_t* walked, int reset) {
+  static const char* fn = "pprhip_walk_index_usage";
+  PPRHIP_TRY(check_graph(g, fn));
+  const WalkIndex* ix = g->gr->widx;
+  unsigned long long u[2] = {0ull, 0ull};
+  if (ix) {
+    PPRHIP_CHECK_HIP(hipDeviceSynchronize());  // (the batch workspaces' streams as well)
+    PPRHIP_CHECK_HIP(hipMemcpy(u, ix->usage, sizeof u, hipMemcpyDeviceToHost));
+    if (reset) PPRHIP_CHECK_HIP(hipMemset(ix->usage, 0, sizeof u));
+  }
+  if (served) *served = u[0];
+  if (walked) *walked = u[1];
+  return PPRHIP_OK;
+}
+
+}  // extern "C"
