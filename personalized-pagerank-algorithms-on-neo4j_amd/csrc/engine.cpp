@@ -872,6 +872,7 @@ void free_batch(pprhip_graph* P) {
     B->fetch->destroy();
     delete B->fetch;
   }
+  free_walk_share(B);
   if (B->walk_stream) (void)hipStreamDestroy(B->walk_stream);
   if (B->slot_stream) (void)hipStreamDestroy(B->slot_stream);
   for (pprhip_graph* S : B->slots) drop_slot(S);
@@ -1006,8 +1007,8 @@ int device_sum(pprhip_graph* g, const double* x, double* out, uint32_t count) {
 // run since the workspace was reset counted on the device (steps, walks, sources: adjacent in DevCounters).
 int read_dead_pops(pprhip_graph* g, pprhip_stats_t& st) {
   poll_idle(g);
-  static_assert(offsetof(DevCounters, walks_served) == offsetof(DevCounters, dead_pops) + 48, "one copy for the seven");
-  PPRHIP_TRY(fetch_small(g, &g->ctr->dead_pops, &g->h_ctr->dead_pops, 7 * sizeof(unsigned long long)));
+  static_assert(offsetof(DevCounters, share_stored) == offsetof(DevCounters, dead_pops) + 64, "one copy for the nine");
+  PPRHIP_TRY(fetch_small(g, &g->ctr->dead_pops, &g->h_ctr->dead_pops, 9 * sizeof(unsigned long long)));
   st.walk_loads = g->h_ctr->walk_loads;
   st.walk_load_lanes = g->h_ctr->walk_lanes;
   st.push_bytes += 16ull * (g->h_ctr->dead_pops - st.dead_end_pops);
@@ -1019,8 +1020,18 @@ int read_dead_pops(pprhip_graph* g, pprhip_stats_t& st) {
     // 4-byte terminal and its 8-byte deposit instead of a live walk's 16 bytes, and the plan is streamed a second time
     // (DESIGN.md §2 "Walk index")
     const uint64_t served = std::min<uint64_t>(g->h_ctr->walks_served, walks - st.walks);
-    const uint64_t more = 12ull * (steps - st.walk_steps) + 16ull * (walks - st.walks - served) + 12ull * served +
+    // the call's terminal cache (WalkShare): a walk it answered moves its 4-byte cell and its 8-byte deposit, a walk
+    // that filled a cell the probe and the store on top of a live walk's 16 bytes
+    const uint64_t shared = std::min<uint64_t>(g->h_ctr->share_served, walks - st.walks - served);
+    const uint64_t more = 12ull * (steps - st.walk_steps) + 16ull * (walks - st.walks - served - shared) +
+                          12ull * (served + shared) + 8ull * g->h_ctr->share_stored +
                           (served ? 24ull : 12ull) * (srcs - st.mc_sources);
+#ifdef PPRHIP_TEST_HOOKS
+    if (hook_env("PPRHIP_WALK_SHARE_LOG"))  // measurement switch: a line per finished query, in completion order
+      fprintf(stderr, "[walk-share] walks %llu served %llu stored %llu steps %llu\n", (unsigned long long)(walks - st.walks),
+              (unsigned long long)g->h_ctr->share_served, (unsigned long long)g->h_ctr->share_stored,
+              (unsigned long long)(steps - st.walk_steps));
+#endif
     st.mc_bytes += more;
     ktimer().add_bytes(PPRHIP_KERNEL_WALK, more);
     st.walk_steps = steps;
@@ -1058,9 +1069,16 @@ int launch_walk_run(pprhip_graph* g, int variant, double alpha, uint64_t seed, u
   // Whole-graph FORA walks (variant 0: stream 0, forced first hop, walk indices 0 .. omega_i - 1 per residue node) are
   // read from the handle's walk index when it was built at this alpha and seed, bit for bit; everything else walks.
   const WalkIndex* ix = g->gr->widx;
-  if (variant == 0 && stream == 0 && ix && std::memcmp(&ix->alpha, &alpha, sizeof alpha) == 0 && ix->seed == seed)
+  // ... and a slot of a batched call reads and fills the call's terminal cache when the call keeps one for this seed
+  // (walk_share_begin; a handle with a walk index has none)
+  const WalkShare* ws = g->parent && g->parent->batch ? g->parent->batch->share : nullptr;
+  if (variant == 0 && stream == 0 && ix && std::memcmp(&ix->alpha, &alpha, sizeof alpha) == 0 && ix->seed == seed) {
     PPRHIP_TRY(launch_mc_walk_indexed(g, ix, alpha, seed, target));
-  else
+  } else if (variant == 0 && stream == 0 && ws && ws->on && ws->seed == seed &&
+             std::memcmp(&ws->alpha, &alpha, sizeof alpha) == 0) {
+    PPRHIP_CHECK_HIP(hipStreamWaitEvent(g->stream, ws->cleared, 0));  // (the call's clear ran on the handle's stream)
+    PPRHIP_TRY(launch_mc_walk_shared(g, ws, alpha, seed, target));
+  } else
     PPRHIP_TRY(launch_mc_walk(g, alpha, seed, stream, variant == 0 ? 1 : 0, target));
   ktimer().end();
   return PPRHIP_OK;

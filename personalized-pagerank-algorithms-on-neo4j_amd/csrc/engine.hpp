@@ -24,6 +24,8 @@ struct DevCounters {
   unsigned long long walk_loads;     // load instructions the walk kernel's waves issued ...
   unsigned long long walk_lanes;     // ... and the lanes they carried (64 per load = full waves)
   unsigned long long walks_served;   // walks whose terminal was read from the walk index (k_index_serve)
+  unsigned long long share_served;   // walks a batched call's terminal cache answered (k_mc_walk<kWalkShared>) ...
+  unsigned long long share_stored;   // ... and walks that ran and left their terminal in it (WalkShare)
   double sum_out;                    // reduction result (the walk plan reads it on the device)
   // walk plan of a phase: sources << 36 | walks, counted by the plan kernel, read by the walk kernel on the device.
   // Three cells used in turn: the plan of phase p counts into cell p % 3 and clears cell (p + 1) % 3, which the walks
@@ -33,7 +35,7 @@ struct DevCounters {
   // ends the round hands it to the host in its header (no copy command of its own)
   double plan_sum[3];
   // walks of the latest indexed walk phase that the index does not hold: k_mc_plan<0> zeroes it, k_index_serve counts
-  // them, k_mc_walk<true> returns at once when there are none (a whole-graph plan never runs ahead of the walks before)
+  // them, k_mc_walk<kWalkIndexed> returns at once when there are none (a whole-graph plan never runs ahead of the walks before)
   unsigned long long walks_over;
   unsigned long long dhist[8];    // dense batch: dhist[i] = frontier that dense level i of the batch starts from
   int dstate[8];                  // dense batch: sweep state of level i (kGsNone: the level does not run)
@@ -333,6 +335,25 @@ struct WalkIndex {
   uint64_t seed = 0, total = 0;
 };
 
+// Call-scoped terminal cache of the batched whole-graph FORA paths (walk_index.cpp: walk_share_begin; DESIGN.md §2
+// "Walk index", "Terminals shared inside a call").  Every query of a batched call walks with the call's seed and stream
+// 0, so walk (v, j) ends at the same terminal whichever query draws it: the first one to walk it leaves the terminal in
+// term[off[v] + j] (j < cap(v), the walk index's capacity at the call's density), later ones read it and only deposit.
+// A cell is kWalkShareEmpty or the one value every writer would write, so no lock or fence orders readers and writers.
+// Owned by the batch state; valid for one (seed, alpha): cleared at the start of every call that uses it.
+constexpr uint32_t kWalkShareEmpty = 0xFFFFFFFFu;
+constexpr int kWalkShareMinQueries = 32;  // calls of fewer queries run without the cache
+struct WalkShare {
+  unsigned long long* off = nullptr;    // [n + 1] first cell of every node, internal order
+  uint32_t* term = nullptr;             // [total] terminals (internal ids) or kWalkShareEmpty
+  unsigned long long* usage = nullptr;  // [2] walks served from the cache / terminals stored, since the last reset
+  hipEvent_t cleared = nullptr;         // recorded behind the clear: the call's walk kernels wait for it
+  std::vector<unsigned long long> h_off;
+  double alpha = 0.0, density = 0.0;
+  uint64_t seed = 0, total = 0;
+  bool on = false;  // the queries in flight may use it (walk phases of its seed and alpha)
+};
+
 struct WalkPlanRec {  // one residue entry of a walk phase (k_mc_plan -> k_mc_walk): 32 bytes
   unsigned long long woff;  // walks of the entries before it
   double inc;               // what each of its walks adds at its terminal
@@ -433,6 +454,7 @@ struct BatchState {
   void* idle_arg = nullptr;
   int in_c8 = 0;  // C8Scopes open on the slots (poll_idle: the hook stays out while a slot borrows the sweeps' stream)
   detail::FetchPipe* fetch = nullptr;  // delivery of batched queries' vectors to host memory (engine_internal.hpp)
+  WalkShare* share = nullptr;  // terminals the queries of a call share, or none (allocated by the first call that uses it)
 };
 
 }  // namespace pprhip
@@ -622,9 +644,12 @@ int launch_hold(hipStream_t stream, unsigned long long ticks);
 int launch_mc_plan(pprhip_graph* g, int variant, double alpha, double rsum, double nrw, double omega_dev, double* target,
                    const double* copy_src = nullptr, double* copy_dst = nullptr);
 int launch_mc_walk(pprhip_graph* g, double alpha, uint64_t seed, uint32_t stream, int no_zero_hop, double* target);
-// the walks of the latest plan with the index `ix`: k_index_serve deposits the stored terminals, k_mc_walk<true> walks
+// the walks of the latest plan with the index `ix`: k_index_serve deposits the stored terminals, k_mc_walk<kWalkIndexed> walks
 // what the index does not hold (walk idx >= cap of its node, dead-end starts) with the walks' own indices
 int launch_mc_walk_indexed(pprhip_graph* g, const WalkIndex* ix, double alpha, uint64_t seed, double* target);
+// the walks of the latest plan (whole-graph FORA: stream 0, forced first hop) through the call's terminal cache: a walk
+// whose cell is filled deposits there at once, the others walk and fill their cells
+int launch_mc_walk_shared(pprhip_graph* g, const WalkShare* ws, double alpha, uint64_t seed, double* target);
 // fills ix->term from ix->off (already in HBM): terminal j of node v = walk (seed, stream 0, v, j), forced first hop
 int launch_index_build(pprhip_graph* g, const WalkIndex* ix, unsigned long long* d_steps);
 // (rows of out-degree >= survival_heavy_degree() go in d_heavy: a workgroup each)

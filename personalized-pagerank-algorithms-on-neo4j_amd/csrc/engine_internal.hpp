@@ -238,6 +238,9 @@ int lift_host(uint32_t n, uint64_t m, const uint32_t* out_rp, const int32_t* out
 unsigned host_threads();  // CPU affinity and cgroup quota of the process, at most 64 (PPRHIP_HOST_THREADS overrides)
 
 void free_walk_index(GraphData* D);  // walk_index.cpp: the lifted graph's walk index, if it has one
+// walk_index.cpp: the call-scoped terminal cache of the batched whole-graph FORA paths (engine.hpp: WalkShare)
+void walk_share_begin(pprhip_graph* P, int q, double alpha, double rmax, double omega, uint64_t seed);
+void free_walk_share(BatchState* B);
 void stream_detach(void* stream_obj);  // fora.cpp: ends a query stream's driver before its graph goes
 int alloc_dev(void** p, size_t bytes);
 double level_cost(const pprhip_graph* g, uint64_t nf, uint64_t ef, bool* dense);

@@ -110,6 +110,29 @@ void leave_push(ForaRun& r) {
   }
 }
 
+// omega and the threshold a whole-graph FORA query's first push runs at (every later one runs at a lower one)
+static int fora_start_params(const pprhip_graph* g, double eps, const pprhip_fora_conf_t* conf, int n_rounds,
+                             double* rmax_out, double* omega_out) {
+  double rmax = 0.0, omega = 0.0;
+  PPRHIP_TRY(pprhip_fora_whole_params(conf, eps, &rmax, &omega));  // Fora_Whole_Graph.java:86-87
+  if (n_rounds == 0 && g->tun.prior_levels > 0 && g->tun.halving_ratio > 1.0) {
+    // Loop turns that are known to pass before any push: after a push at rmax every r(v) < rmax * d(v), so
+    // rsum <= rmax * m and the walks cost at most c_walk * omega * (1 - alpha) * rmax * m; while that bound still
+    // covers prior_levels dense levels the turn would be repeated at half the threshold anyway (twin: same rule).
+    const pprhip_tuning_t& t = g->tun;
+    double walk_bound = t.c_walk_ns * omega * (1 - conf->alpha) * rmax * (double)g->gr->m;
+    const double push_est =
+        (double)t.prior_levels * (t.c_level_ns + t.c_dense_edge_ns * (double)g->gr->m + t.c_dense_node_ns * (double)g->gr->n);
+    for (int h = 0; h < t.max_halvings && walk_bound >= push_est; ++h) {
+      walk_bound /= 2.0;
+      rmax /= 2.0;
+    }
+  }
+  *rmax_out = rmax;
+  *omega_out = omega;
+  return PPRHIP_OK;
+}
+
 // src_internal -1: the query runs from the seed table (g->seeds), whose largest id bounds the reset (reset_node)
 static int fora_begin_at(ForaRun& r, pprhip_graph* g, int32_t src_internal, int32_t reset_node, double eps,
                          const pprhip_fora_conf_t* conf, uint64_t seed, int n_rounds) {
@@ -124,20 +147,7 @@ static int fora_begin_at(ForaRun& r, pprhip_graph* g, int32_t src_internal, int3
   PPRHIP_TRY(reset_query_state(g, false, reset_node));
   r.alpha = conf->alpha;
   r.rsum_local = conf->rsum;
-  PPRHIP_TRY(pprhip_fora_whole_params(conf, eps, &r.rmax_local, &r.omega_local));  // Fora_Whole_Graph.java:86-87
-  if (n_rounds == 0 && g->tun.prior_levels > 0 && g->tun.halving_ratio > 1.0) {
-    // Loop turns that are known to pass before any push: after a push at rmax every r(v) < rmax * d(v), so
-    // rsum <= rmax * m and the walks cost at most c_walk * omega * (1 - alpha) * rmax * m; while that bound still
-    // covers prior_levels dense levels the turn would be repeated at half the threshold anyway (twin: same rule).
-    const pprhip_tuning_t& t = g->tun;
-    double walk_bound = t.c_walk_ns * r.omega_local * (1 - r.alpha) * r.rmax_local * (double)g->gr->m;
-    const double push_est =
-        (double)t.prior_levels * (t.c_level_ns + t.c_dense_edge_ns * (double)g->gr->m + t.c_dense_node_ns * (double)g->gr->n);
-    for (int h = 0; h < t.max_halvings && walk_bound >= push_est; ++h) {
-      walk_bound /= 2.0;
-      r.rmax_local /= 2.0;
-    }
-  }
+  PPRHIP_TRY(fora_start_params(g, eps, conf, n_rounds, &r.rmax_local, &r.omega_local));
   r.rmax_used = r.rmax_local;
   r.model_cost = 0.0;
   r.rounds = 0;
@@ -1466,6 +1476,19 @@ int run_tail(BatchJob& J, int q_slots) {
   return PPRHIP_OK;
 }
 
+// The queries of a whole-graph FORA call (one seed, stream 0) draw the same walks: from kWalkShareMinQueries queries on
+// they share terminals through the batch state's cache (engine.hpp: WalkShare).  Called with no walk kernel of the
+// slots in flight: before a call's first query, or by a stream's driver that stands idle.
+void share_walks_of(BatchJob& J) {
+  pprhip_graph* P = J.P;
+  double rmax = 0.0, omega = 0.0;
+  if (J.kind != 0 || fora_start_params(P->batch->slots[0], J.eps, J.conf, J.n_rounds, &rmax, &omega) != PPRHIP_OK) {
+    if (P->batch->share) P->batch->share->on = false;
+    return;
+  }
+  walk_share_begin(P, J.q, J.conf->alpha, rmax, omega, J.seed);
+}
+
 // all queries on the calling thread (SlotDriver)
 int batch_sequential(BatchJob& J) {
   pprhip_graph* P = J.P;
@@ -1842,6 +1865,7 @@ int pprhip::detail::batch_run(pprhip_graph_t* g, BatchJob& J, pprhip_stats_t* st
   g->ktimer.stream = g->stream;
   g->ktimer.reset();
   const auto t0 = std::chrono::steady_clock::now();
+  share_walks_of(J);
   int rc = PPRHIP_OK;
   double tot[8] = {0};
   uint64_t bytes[8] = {0};
@@ -1886,6 +1910,7 @@ int pprhip::detail::batch_run(pprhip_graph_t* g, BatchJob& J, pprhip_stats_t* st
     g_timer_cur = saved;
   }
   (void)hipStreamSynchronize(g->stream);
+  if (g->batch->share) g->batch->share->on = false;  // (the cache lives for one call)
   if (J.pipe) {
     const std::string msg = rc != PPRHIP_OK ? get_error() : std::string();
     const int prc = J.pipe->finish();  // every vector submitted so far has reached its destination
@@ -2229,6 +2254,14 @@ void stream_driver(pprhip_stream* s) {
     *i = J->next_query.fetch_add(1);
     if (*i + 1 >= J->q) s->pending.pop_front();  // (the open map keeps the submission alive)
     ++started;
+    if (*i == 0) {
+      // A submission's first query: with no other query in flight its queries get the terminal cache for their seed.
+      // One that starts while an earlier one is still running shares that one's cache when the seeds agree and walks
+      // on its own otherwise (launch_walk_run compares seeds): the cache is never cleared under a running walk kernel.
+      bool idle = true;
+      for (int w = 0; w < D.n_ws && idle; ++w) idle = D.runs[w].query < 0;
+      if (idle) share_walks_of(*J);
+    }
     return true;
   };
   D.done = [&](BatchJob* job) {
@@ -2265,6 +2298,7 @@ void stream_driver(pprhip_stream* s) {
   // once, and copies or selections of other slots' queries can still be queued against those buffers.
   (void)hipStreamSynchronize(P->stream);
   D.teardown();
+  if (P->batch->share) P->batch->share->on = false;
   if (P->batch->walk_stream) (void)hipStreamSynchronize(P->batch->walk_stream);
   if (side && side != P->stream && side != P->batch->walk_stream) (void)hipStreamSynchronize(side);
   if (rc != PPRHIP_OK) stream_fail(s, rc);

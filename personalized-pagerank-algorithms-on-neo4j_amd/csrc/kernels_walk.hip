@@ -272,6 +272,10 @@ __global__ __launch_bounds__(256) void k_mc_plan_topk(uint32_t n, const double* 
 // where a walk kernel has four waves per CU and three to four decision rounds per load are not hidden (24.5 against
 // ~33 G steps/s, headline 312 against 329 queries/s): the rate is what the memory system gives this address stream,
 // not a matter of how full the loads are (gpurun_out/r04b_bench.json).
+// The queries of a batched call draw the same walks (one seed, stream 0): k_mc_walk<kWalkShared> reads a walk's terminal
+// from the call's cache when an earlier query has walked it - 4 bytes streamed and the deposit, no Philox, no record -
+// and 98.8 % of a 128-query call's walks on R-MAT 22 are served so: 713 us per query beside the sweeps against 1 124,
+// 0.163 ns per walk, which is the terminals' fp64 atomics (profiles/walk_share_ab.txt).
 // ------------------------------------------------------------------------------------------------
 constexpr int kWalkWindow = 128;
 constexpr uint32_t kWalkWavesBeside = 4;   // ... of a walk kernel that runs beside other queries' kernels
@@ -312,12 +316,26 @@ __device__ __forceinline__ uint32_t plan_upper_bound(const WalkPlanRec* __restri
 // whose index lies below its node's capacity is skipped here (a fourth early-out beside the dead-end start), the others
 // - an entry's tail [cap, omega_i), every walk of a dead-end start - run with their own indices.  The unindexed
 // instantiation is the kernel as it was.
-template <bool INDEXED>
+// SHARED (idx_off: the offsets of the call's terminal cache, engine.hpp: WalkShare): a lane that takes walk (v, j) with
+// j < cap(v) first reads the walk's cell - the plan is in node order, so the lanes of a refill read consecutive cells: a
+// streamed 4 bytes per walk.  A filled cell is the terminal an earlier query of the call (or another wave of this one)
+// reached with the same counter and key: the lane deposits there and takes the next walk, at the cost of the probe and
+// the deposit instead of ~6.7 gathered lines.  An empty cell: the walk runs as ever and stores its terminal with a
+// plain 4-byte store when it stops.  Nothing orders the store against other kernels' probes and nothing needs to: a
+// cell only goes from empty to the one value every writer writes, and a reader that still sees "empty" walks.  What
+// bounds a phase that is mostly served is its deposits: fp64 atomics on the terminals, the hubs among them hot.
+enum WalkMode : int { kWalkPlain = 0, kWalkIndexed = 1, kWalkShared = 2 };
+template <int MODE>
 __global__ __launch_bounds__(64) void k_mc_walk(const WalkPlanRec* __restrict__ plan_rec,
                                                  const uint4* __restrict__ walk_rec, double* __restrict__ target,
                                                  double alpha, uint32_t k0, uint32_t k1, uint32_t stream,
                                                  int no_zero_hop, DevCounters* ctr, int parity,
-                                                 const unsigned long long* __restrict__ idx_off) {
+                                                 const unsigned long long* __restrict__ idx_off,
+                                                 uint32_t* share_term, uint32_t n_nodes,
+                                                 unsigned long long* __restrict__ share_usage) {
+  constexpr bool INDEXED = MODE == kWalkIndexed;
+  constexpr bool SHARED = MODE == kWalkShared;
+  constexpr unsigned long long kNoCell = ~0ull;
   // the plan kernel counted sources and walks into mc_plan[parity]; the query's totals grow by this phase
   const unsigned long long plan = ctr->mc_plan[parity];
   const uint32_t n_src = (uint32_t)(plan >> kPackShift);
@@ -342,6 +360,8 @@ __global__ __launch_bounds__(64) void k_mc_walk(const WalkPlanRec* __restrict__ 
   double inc = 0.0;
   bool walking = false;
   unsigned long long n_loads = 0, n_lanes = 0;  // (wave-uniform) loads issued, lanes they carried
+  unsigned long long cell = kNoCell;            // SHARED: where this lane's walk leaves its terminal
+  unsigned long long n_served = 0, n_stored = 0;
   for (;;) {
     const unsigned long long need = __ballot(!walking);
     if (need && cursor < w_hi) {
@@ -421,6 +441,16 @@ __global__ __launch_bounds__(64) void k_mc_walk(const WalkPlanRec* __restrict__ 
         if (stored) {  // k_index_serve has deposited this walk's terminal
         } else if ((sext >> 32) == 0) {
           atomic_add_noret(&target[start], inc);  // Monte_Carlo.java:70-72 / :106-108
+        } else if (SHARED) {
+          const unsigned long long o0 = idx_off[start];
+          cell = widx < idx_off[start + 1] - o0 ? o0 + widx : kNoCell;
+          const uint32_t t = cell != kNoCell ? share_term[cell] : kWalkShareEmpty;
+          if (t < n_nodes) {  // (kWalkShareEmpty is no node)
+            atomic_add_noret(&target[t], inc);
+            n_served++;
+          } else {
+            walking = true;
+          }
         } else {
           walking = true;
         }
@@ -444,6 +474,10 @@ __global__ __launch_bounds__(64) void k_mc_walk(const WalkPlanRec* __restrict__ 
         atomic_add_noret(&target[w.cur], inc);
         steps_total += w.moves;
         walking = false;
+        if (SHARED && cell != kNoCell) {
+          share_term[cell] = (uint32_t)w.cur;
+          n_stored++;
+        }
       }
     }
     const unsigned long long loaded = __ballot(can_load && !stopped);
@@ -455,6 +489,18 @@ __global__ __launch_bounds__(64) void k_mc_walk(const WalkPlanRec* __restrict__ 
   if (lane == 0 && n_loads) {
     atomic_add_u64(&ctr->walk_loads, n_loads);
     atomic_add_u64(&ctr->walk_lanes, n_lanes);
+  }
+  if (SHARED) {
+    n_served = wave_sum_u64(n_served);
+    n_stored = wave_sum_u64(n_stored);
+    if (lane == 0 && n_served) {
+      atomic_add_u64(&ctr->share_served, n_served);
+      atomic_add_u64(&share_usage[0], n_served);
+    }
+    if (lane == 0 && n_stored) {
+      atomic_add_u64(&ctr->share_stored, n_stored);
+      atomic_add_u64(&share_usage[1], n_stored);
+    }
   }
 }
 
@@ -531,7 +577,7 @@ __global__ __launch_bounds__(64) void k_index_build(const unsigned long long* __
 // nodes are staged in LDS, a lane finds its entry there, and walk i of node v reads term[off[v] + i] - consecutive
 // lanes inside an entry read consecutive terminals - and adds the entry's increment there.  No Philox, no edge record.
 // A walk the index does not hold (i >= cap(v); every walk of a dead-end start, whose capacity is 0) is counted in
-// ctr->walks_over and left to k_mc_walk<true>.
+// ctr->walks_over and left to k_mc_walk<kWalkIndexed>.
 struct ServeWindow {  // LDS, one per wave
   unsigned long long woff[65];
   double inc[64];
@@ -858,7 +904,7 @@ int launch_pair_reduce(pprhip_graph* g, const int32_t* d_src, const int32_t* d_p
 
 int init_kernels_walk() {  // loads this file's code object on the current device (see init_kernels_push)
   hipFuncAttributes fa;
-  PPRHIP_CHECK_HIP(hipFuncGetAttributes(&fa, reinterpret_cast<const void*>(&k_mc_walk<false>)));
+  PPRHIP_CHECK_HIP(hipFuncGetAttributes(&fa, reinterpret_cast<const void*>(&k_mc_walk<kWalkPlain>)));
   return PPRHIP_OK;
 }
 
@@ -918,9 +964,10 @@ static uint32_t mc_walk_grid(pprhip_graph* g) {
 
 int launch_mc_walk(pprhip_graph* g, double alpha, uint64_t seed, uint32_t stream, int no_zero_hop, double* target) {
   const uint32_t grid = mc_walk_grid(g);
-  hipLaunchKernelGGL(k_mc_walk<false>, dim3(grid), dim3(64), 0, g->stream, plan_rec_of(g, g->mc_last_plan),
+  hipLaunchKernelGGL(k_mc_walk<kWalkPlain>, dim3(grid), dim3(64), 0, g->stream, plan_rec_of(g, g->mc_last_plan),
                      reinterpret_cast<const uint4*>(g->gr->walk_rec), target, alpha, (uint32_t)seed, (uint32_t)(seed >> 32), stream,
-                     no_zero_hop, g->ctr, (int)(g->mc_last_plan % 3u), (const unsigned long long*)nullptr);
+                     no_zero_hop, g->ctr, (int)(g->mc_last_plan % 3u), (const unsigned long long*)nullptr,
+                     (uint32_t*)nullptr, 0u, (unsigned long long*)nullptr);
   PPRHIP_CHECK_HIP(hipGetLastError());
   return PPRHIP_OK;
 }
@@ -933,9 +980,20 @@ int launch_mc_walk_indexed(pprhip_graph* g, const WalkIndex* ix, double alpha, u
   hipLaunchKernelGGL(k_index_serve, dim3(grid), dim3(64), 0, g->stream, plan_rec_of(g, g->mc_last_plan), ix->off, ix->term,
                      target, g->ctr, cell, ix->usage);
   PPRHIP_CHECK_HIP(hipGetLastError());
-  hipLaunchKernelGGL(k_mc_walk<true>, dim3(grid), dim3(64), 0, g->stream, plan_rec_of(g, g->mc_last_plan),
+  hipLaunchKernelGGL(k_mc_walk<kWalkIndexed>, dim3(grid), dim3(64), 0, g->stream, plan_rec_of(g, g->mc_last_plan),
                      reinterpret_cast<const uint4*>(g->gr->walk_rec), target, alpha, (uint32_t)seed, (uint32_t)(seed >> 32), 0u,
-                     1, g->ctr, cell, (const unsigned long long*)ix->off);
+                     1, g->ctr, cell, (const unsigned long long*)ix->off, (uint32_t*)nullptr, 0u,
+                     (unsigned long long*)nullptr);
+  PPRHIP_CHECK_HIP(hipGetLastError());
+  return PPRHIP_OK;
+}
+
+int launch_mc_walk_shared(pprhip_graph* g, const WalkShare* ws, double alpha, uint64_t seed, double* target) {
+  const uint32_t grid = mc_walk_grid(g);
+  hipLaunchKernelGGL(k_mc_walk<kWalkShared>, dim3(grid), dim3(64), 0, g->stream, plan_rec_of(g, g->mc_last_plan),
+                     reinterpret_cast<const uint4*>(g->gr->walk_rec), target, alpha, (uint32_t)seed, (uint32_t)(seed >> 32), 0u,
+                     1, g->ctr, (int)(g->mc_last_plan % 3u), (const unsigned long long*)ws->off, ws->term, g->gr->n,
+                     ws->usage);
   PPRHIP_CHECK_HIP(hipGetLastError());
   return PPRHIP_OK;
 }

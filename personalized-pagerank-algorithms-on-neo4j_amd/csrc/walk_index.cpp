@@ -1,6 +1,6 @@
 // walk_index.cpp — the FORA+ walk index (include/pprhip.h "walk index"; DESIGN.md §2 "Walk index"): per node the
 // terminals of the walks a whole-graph FORA walk phase would draw from it, built once per (alpha, seed) and kept with
-// the lifted graph.  The kernels are in kernels_walk.hip (k_index_build, k_index_serve, k_mc_walk<true>); the walk
+// the lifted graph.  The kernels are in kernels_walk.hip (k_index_build, k_index_serve, k_mc_walk<kWalkIndexed>); the walk
 // phase picks the index in launch_walk_run (engine.cpp).
 #include <cmath>
 #include <cstring>
@@ -26,6 +26,104 @@ static void destroy_index(WalkIndex* ix) {
 void free_walk_index(GraphData* D) {
   destroy_index(D->widx);
   D->widx = nullptr;
+}
+
+// cap(v) = ceil(d_out(v) * density) in internal order as a prefix: h_off[v] = the first position of node v, h_off[n] the
+// total, which must stay below the engine's walk limit (the walk index and the call-scoped terminal cache share it)
+int walk_offsets(const GraphData* D, double density, std::vector<unsigned long long>& h_off, uint64_t* total,
+                 const char* fn) {
+  try {
+    h_off.resize((size_t)D->n + 1);
+  } catch (const std::bad_alloc&) {
+    set_error("%s: out of host memory", fn);
+    return PPRHIP_ERR_OOM;
+  }
+  const double limit = (double)(1ull << kPackShift);
+  unsigned long long run = 0;
+  for (uint32_t v = 0; v < D->n; ++v) {
+    h_off[v] = run;
+    const uint32_t d = D->h_out_rp[v + 1] - D->h_out_rp[v];
+    const double c = d ? std::ceil((double)d * density) : 0.0;
+    if (!(c < limit) || (double)run + c >= limit) {
+      set_error("%s: density = %g asks for 2^36 terminals or more (the engine's walk limit)", fn, density);
+      return PPRHIP_ERR_INVALID;
+    }
+    run += (unsigned long long)c;
+  }
+  h_off[D->n] = run;
+  *total = run;
+  return PPRHIP_OK;
+}
+
+// ---- the call-scoped terminal cache (engine.hpp: WalkShare)
+void free_walk_share(BatchState* B) {
+  WalkShare* ws = B->share;
+  if (!ws) return;
+  void* ptrs[] = {ws->off, ws->term, ws->usage};
+  for (void* p : ptrs)
+    if (p) (void)hipFree(p);
+  if (ws->cleared) (void)hipEventDestroy(ws->cleared);
+  delete ws;
+  B->share = nullptr;
+}
+
+static int walk_share_alloc(pprhip_graph* P, double density) {
+  static const char* fn = "terminal cache";
+  BatchState* B = P->batch;
+  WalkShare* ws = new (std::nothrow) WalkShare();
+  if (!ws) return PPRHIP_ERR_OOM;
+  B->share = ws;
+  ws->density = density;
+  PPRHIP_TRY(walk_offsets(P->gr, density, ws->h_off, &ws->total, fn));
+  // the cache is an extra: it does not take memory the call itself may still ask for (workspaces, the fetch ring)
+  size_t free_b = 0, total_b = 0;
+  PPRHIP_CHECK_HIP(hipMemGetInfo(&free_b, &total_b));
+  const size_t bytes = sizeof(uint32_t) * (size_t)ws->total + sizeof(unsigned long long) * ((size_t)P->gr->n + 1);
+  if (bytes > free_b / 4) {
+    set_error("%s: %zu bytes are more than a quarter of the device's free memory", fn, bytes);
+    return PPRHIP_ERR_OOM;
+  }
+  PPRHIP_TRY(alloc_dev((void**)&ws->term, sizeof(uint32_t) * (size_t)ws->total));
+  PPRHIP_TRY(alloc_dev((void**)&ws->off, sizeof(unsigned long long) * ((size_t)P->gr->n + 1)));
+  PPRHIP_TRY(alloc_dev((void**)&ws->usage, 2 * sizeof(unsigned long long)));
+  PPRHIP_CHECK_HIP(hipEventCreateWithFlags(&ws->cleared, hipEventDisableTiming));
+  PPRHIP_CHECK_HIP(hipMemcpyAsync(ws->off, ws->h_off.data(), sizeof(unsigned long long) * ((size_t)P->gr->n + 1),
+                                  hipMemcpyHostToDevice, P->stream));
+  PPRHIP_CHECK_HIP(hipMemsetAsync(ws->usage, 0, 2 * sizeof(unsigned long long), P->stream));
+  PPRHIP_CHECK_HIP(hipStreamSynchronize(P->stream));  // (h_off is pageable)
+  return PPRHIP_OK;
+}
+
+// Called where a batched whole-graph FORA call (or a stream's submission that finds the driver idle) is about to start
+// its first query, with no walk kernel of the handle's slots in flight: decides whether the call's queries share
+// terminals, allocates the cache on first use and clears it for the call's seed.  Whatever fails leaves the call
+// without the cache and is no error.  cap(v) comes from the density bound at the threshold the queries start from
+// (`rmax`: omega_i <= ceil(d_out(v) * (1 - alpha) * rmax * omega) after a push at rmax or below).
+void walk_share_begin(pprhip_graph* P, int q, double alpha, double rmax, double omega, uint64_t seed) {
+  BatchState* B = P->batch;
+  if (B->share) B->share->on = false;
+  const char* sw = hook_env("PPRHIP_WALK_SHARE");  // measurement switch: 0 = every walk is walked
+  if ((sw && sw[0] == '0') || q < kWalkShareMinQueries || P->gr->widx) return;
+  const double density = (1.0 - alpha) * rmax * omega * (1.0 + 0x1p-20);
+  if (!(density > 0.0) || !std::isfinite(density)) return;
+  if (B->share && B->share->density != density) free_walk_share(B);
+  if (!B->share && walk_share_alloc(P, density) != PPRHIP_OK) {
+    (void)hipGetLastError();
+    free_walk_share(B);
+    return;
+  }
+  WalkShare* ws = B->share;
+  if (ws->total == 0) return;
+  if (hipMemsetAsync(ws->term, 0xFF, sizeof(uint32_t) * (size_t)ws->total, P->stream) != hipSuccess ||
+      hipEventRecord(ws->cleared, P->stream) != hipSuccess) {
+    (void)hipGetLastError();
+    (void)hipStreamSynchronize(P->stream);
+    free_walk_share(B);
+    return;
+  }
+  ws->alpha = alpha;
+  ws->seed = seed;
+  ws->on = true;
 }
 
 }  // namespace detail
@@ -65,27 +163,7 @@ int pprhip_walk_index_build(pprhip_graph_t* g, double alpha, uint64_t seed, doub
   ix->alpha = alpha;
   ix->seed = seed;
   ix->density = density;
-  // cap(v) = ceil(d_out(v) * density) in internal order; the total must stay below the engine's walk limit
-  try {
-    ix->h_off.resize((size_t)D->n + 1);
-  } catch (const std::bad_alloc&) {
-    set_error("%s: out of host memory", fn);
-    return PPRHIP_ERR_OOM;
-  }
-  const double limit = (double)(1ull << kPackShift);
-  unsigned long long run = 0;
-  for (uint32_t v = 0; v < D->n; ++v) {
-    ix->h_off[v] = run;
-    const uint32_t d = D->h_out_rp[v + 1] - D->h_out_rp[v];
-    const double c = d ? std::ceil((double)d * density) : 0.0;
-    if (!(c < limit) || (double)run + c >= limit) {
-      set_error("%s: density = %g asks for 2^36 terminals or more (the engine's walk limit)", fn, density);
-      return PPRHIP_ERR_INVALID;
-    }
-    run += (unsigned long long)c;
-  }
-  ix->h_off[D->n] = run;
-  ix->total = run;
+  PPRHIP_TRY(walk_offsets(D, density, ix->h_off, &ix->total, fn));
   PPRHIP_TRY(alloc_dev((void**)&ix->off, sizeof(unsigned long long) * ((size_t)D->n + 1)));
   PPRHIP_TRY(alloc_dev((void**)&ix->term, sizeof(int32_t) * (size_t)ix->total));
   PPRHIP_TRY(alloc_dev((void**)&ix->usage, 3 * sizeof(unsigned long long)));  // (WalkIndex::usage)
@@ -173,5 +251,58 @@ int pprhip_walk_index_usage(pprhip_graph_t* g, uint64_t* served, uint64_t* walke
   if (walked) *walked = u[1];
   return PPRHIP_OK;
 }
+
+#ifdef PPRHIP_TEST_HOOKS
+// Test hooks (libpprhip_hooks.so only) of the call-scoped terminal cache: whether the handle holds one and for which
+// seed; the walks it served / the terminals stored since the last reset; the cells of one node (original ids, -1: not
+// drawn yet), as pprhip_walk_index_fetch gives the index's.
+int pprhip_hook_walk_share_info(pprhip_graph_t* g, int* present, int* on, uint64_t* seed, uint64_t* cells,
+                                uint64_t* bytes) {
+  PPRHIP_TRY(check_graph(g, "pprhip_hook_walk_share_info"));
+  const WalkShare* ws = g->batch ? g->batch->share : nullptr;
+  if (present) *present = ws ? 1 : 0;
+  if (on) *on = ws && ws->on ? 1 : 0;
+  if (seed) *seed = ws ? ws->seed : 0;
+  if (cells) *cells = ws ? ws->total : 0;
+  if (bytes) *bytes = ws ? 4ull * ws->total + 8ull * ((uint64_t)g->gr->n + 1) + 2ull * 8ull : 0;
+  return PPRHIP_OK;
+}
+
+int pprhip_hook_walk_share_usage(pprhip_graph_t* g, uint64_t* served, uint64_t* stored, int reset) {
+  PPRHIP_TRY(check_graph(g, "pprhip_hook_walk_share_usage"));
+  const WalkShare* ws = g->batch ? g->batch->share : nullptr;
+  unsigned long long u[2] = {0ull, 0ull};
+  if (ws) {
+    PPRHIP_CHECK_HIP(hipDeviceSynchronize());
+    PPRHIP_CHECK_HIP(hipMemcpy(u, ws->usage, sizeof u, hipMemcpyDeviceToHost));
+    if (reset) PPRHIP_CHECK_HIP(hipMemset(ws->usage, 0, sizeof u));
+  }
+  if (served) *served = u[0];
+  if (stored) *stored = u[1];
+  return PPRHIP_OK;
+}
+
+int pprhip_hook_walk_share_fetch(pprhip_graph_t* g, int32_t node, int32_t* terminals_out, uint64_t cap,
+                                 uint64_t* count_out) {
+  static const char* fn = "pprhip_hook_walk_share_fetch";
+  PPRHIP_TRY(check_graph(g, fn));
+  PPRHIP_TRY(check_node(g, node, fn));
+  const WalkShare* ws = g->batch ? g->batch->share : nullptr;
+  if (!ws || (cap && !terminals_out)) {
+    set_error("%s: no terminal cache on the handle, or null output", fn);
+    return PPRHIP_ERR_STATE;
+  }
+  const int32_t v = g->gr->h_old2new[node];
+  const unsigned long long o0 = ws->h_off[v], cnt = ws->h_off[(size_t)v + 1] - o0;
+  if (count_out) *count_out = cnt;
+  const uint64_t take = cnt < cap ? cnt : cap;
+  if (take == 0) return PPRHIP_OK;
+  PPRHIP_CHECK_HIP(hipDeviceSynchronize());
+  PPRHIP_CHECK_HIP(hipMemcpy(terminals_out, ws->term + o0, sizeof(int32_t) * take, hipMemcpyDeviceToHost));
+  for (uint64_t i = 0; i < take; ++i)
+    terminals_out[i] = terminals_out[i] >= 0 && (uint32_t)terminals_out[i] < g->gr->n ? g->gr->h_new2old[terminals_out[i]] : -1;
+  return PPRHIP_OK;
+}
+#endif
 
 }  // extern "C"
