@@ -623,7 +623,7 @@ int all_pair_collect(pprhip_graph_t* g, double alpha, double threshold, uint32_t
     std::vector<Triple> tr3;
     BatchJob J;
     J.P = g;
-    J.kind = 2;
+    J.kind = QueryKind::kBackward;
     J.srcs = to_tier3.data();
     J.q = (int)to_tier3.size();
     J.eps = 0.0;

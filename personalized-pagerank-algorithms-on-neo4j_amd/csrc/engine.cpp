@@ -1,9 +1,9 @@
 // engine.cpp — host-side core of the pprhip engine: graph lift and workspaces, the level loop, and the
 // single-query entry points (forward push, top-k push rounds, FORA top-k, Monte-Carlo, backward push,
 // power method).  Everything numerical runs in the HIP kernels; the host only sequences launches on
-// the handle's stream and reads back 8-byte counters between levels.  FORA runs and the batched entry
-// points live in fora.cpp, All-Pair and the index in allpair.cpp (shared declarations:
-// engine_internal.hpp).
+// the handle's stream and reads back 8-byte counters between levels.  FORA runs live in fora.cpp,
+// the batched entry points in batch.cpp, batch_api.cpp and stream.cpp, All-Pair and the index in allpair.cpp
+// (shared declarations: engine_internal.hpp).
 #include <algorithm>
 #include <chrono>
 #include <cmath>
@@ -938,8 +938,8 @@ int seed_single(pprhip_graph* g, LevelCtx& L, int32_t node, uint32_t degree) {
 }
 
 // frontier from a predicate over all nodes (round starts)
-int seed_scan(pprhip_graph* g, const PushArgs& a, int kind, LevelCtx& L) {
-  if (kind == 1) {
+int seed_scan(pprhip_graph* g, const PushArgs& a, int seed_kind, LevelCtx& L) {
+  if (seed_kind == 1) {
     // top-k round starts: one pass that lists the start set, writes the armed bits and lets the parked nodes go, and
     // one read-back of its counter (a start set large enough for a sweep is prepared from the list by run_levels)
     {
@@ -956,7 +956,7 @@ int seed_scan(pprhip_graph* g, const PushArgs& a, int kind, LevelCtx& L) {
   }
   {
     SetupScope setup(g);
-    PPRHIP_TRY(launch_count_active(g, a, kind, L.pslot));
+    PPRHIP_TRY(launch_count_active(g, a, seed_kind, L.pslot));
   }
   PPRHIP_TRY(read_packed(g, L.pslot, &L.nf, &L.ef));
   L.dense_prepared = false;
@@ -975,18 +975,18 @@ int seed_scan(pprhip_graph* g, const PushArgs& a, int kind, LevelCtx& L) {
     }
     {
       SetupScope setup(g);
-      PPRHIP_TRY(launch_seed_dense(g, a, kind, L.ccur, L.pslot, L.dslot));
+      PPRHIP_TRY(launch_seed_dense(g, a, seed_kind, L.ccur, L.pslot, L.dslot));
     }
     PPRHIP_TRY(c8.leave());
     L.dense_prepared = true;
     L.dense_run = 0;
-  } else if (L.nf || kind == 1) {
-    // kind 1 also runs for an empty start set: parked nodes below min_rmax still leave the set
+  } else if (L.nf || seed_kind == 1) {
+    // seed kind 1 also runs for an empty start set: parked nodes below min_rmax still leave the set
     // (Forward_Push.java:241-247)
     // (its list counter, hist[kMaxBatch + 2], was cleared by the counting pass above)
     {
       SetupScope setup(g);
-      PPRHIP_TRY(launch_seed_list(g, a, kind, L.fcur, &g->ctr->hist[kMaxBatch + 2]));
+      PPRHIP_TRY(launch_seed_list(g, a, seed_kind, L.fcur, &g->ctr->hist[kMaxBatch + 2]));
     }
   }
   return PPRHIP_OK;
@@ -1360,7 +1360,7 @@ int select_finish(pprhip_graph* g, unsigned long long seq, const double* x, int 
 
 // A stream that really runs beside the handle's compute stream.  The runtime spreads streams over a few in-order
 // hardware queues, and which streams share one depends on what else the process has created: a stream that lands on
-// the compute stream's queue never overlaps it (fora.cpp: FetchPipe, tools/exp/copy_overlap.py: kernels ran during
+// the compute stream's queue never overlaps it (fetch_pipe.cpp: FetchPipe, tools/exp/copy_overlap.py: kernels ran during
 // 0.0 % of the copies' time).  So candidates are created - plain ones first, then of the other priorities - and each
 // is tried: a kernel holds the compute stream for a moment, a one-word k_publish goes to the candidate, and the
 // candidate is taken if the word arrives while the hold kernel still runs.  Rejected candidates stay alive until the

@@ -275,7 +275,7 @@ struct KernelTimer {
   }
 };
 
-struct BatchSync;  // engine.cpp: rendezvous of the batch workers at dense levels
+struct BatchSync;  // engine_internal.hpp, batch.cpp: rendezvous of the batch workers at dense levels
 
 // Contribution vector of a dense level: a plain array for a single query (stride 1), or one
 // column of the interleaved c8[v][slot] array that kBatch concurrent queries share.
@@ -323,17 +323,21 @@ struct ClearList {  // ranges one k_clear launch zeroes
   int n;
 };
 
-// FORA+ walk index (walk_index.cpp; DESIGN.md §2 "Walk index"): per node v the terminals of the walks
-// (seed, stream 0, v, idx < cap(v)) with the forced first hop at one alpha, cap(v) = ceil(d_out(v) * density).  Lives on
-// the lifted graph, read-only after its build; the usage counters are the only cells kernels write.
-struct WalkIndex {
-  unsigned long long* off = nullptr;    // [n + 1] first terminal of every node, internal order
-  int32_t* term = nullptr;              // [total] terminals, internal ids
-  unsigned long long* usage = nullptr;  // [3] walks served from the index / walked live in served phases; the build's walk steps
+// Terminals of the walks (seed, stream 0, v, idx < cap(v)) with the forced first hop at one alpha, per node v, with
+// cap(v) = ceil(d_out(v) * density): the table behind the walk index and the call's terminal cache (walk_index.cpp).
+struct TerminalTable {
+  unsigned long long* off = nullptr;    // [n + 1] first cell of every node, internal order
+  int32_t* term = nullptr;              // [total] terminals, internal ids (the cache's kernels take the cells as uint32_t)
+  unsigned long long* usage = nullptr;  // counter cells (WalkIndex: 3, WalkShare: 2)
   std::vector<unsigned long long> h_off;
   double alpha = 0.0, density = 0.0;
   uint64_t seed = 0, total = 0;
 };
+
+// FORA+ walk index (walk_index.cpp; DESIGN.md §2 "Walk index"): every cell of the table filled by its build.  Lives on
+// the lifted graph, read-only after its build; the usage counters are the only cells kernels write: [3] walks served
+// from the index / walked live in served phases; the build's walk steps.
+struct WalkIndex : TerminalTable {};
 
 // Call-scoped terminal cache of the batched whole-graph FORA paths (walk_index.cpp: walk_share_begin; DESIGN.md §2
 // "Walk index", "Terminals shared inside a call").  Every query of a batched call walks with the call's seed and stream
@@ -343,15 +347,9 @@ struct WalkIndex {
 // Owned by the batch state; valid for one (seed, alpha): cleared at the start of every call that uses it.
 constexpr uint32_t kWalkShareEmpty = 0xFFFFFFFFu;
 constexpr int kWalkShareMinQueries = 32;  // calls of fewer queries run without the cache
-struct WalkShare {
-  unsigned long long* off = nullptr;    // [n + 1] first cell of every node, internal order
-  uint32_t* term = nullptr;             // [total] terminals (internal ids) or kWalkShareEmpty
-  unsigned long long* usage = nullptr;  // [2] walks served from the cache / terminals stored, since the last reset
-  hipEvent_t cleared = nullptr;         // recorded behind the clear: the call's walk kernels wait for it
-  std::vector<unsigned long long> h_off;
-  double alpha = 0.0, density = 0.0;
-  uint64_t seed = 0, total = 0;
-  bool on = false;  // the queries in flight may use it (walk phases of its seed and alpha)
+struct WalkShare : TerminalTable {  // (usage: [2] walks served from the cache / terminals stored, since the last reset)
+  hipEvent_t cleared = nullptr;  // recorded behind the clear: the call's walk kernels wait for it
+  bool on = false;               // the queries in flight may use it (walk phases of its seed and alpha)
 };
 
 struct WalkPlanRec {  // one residue entry of a walk phase (k_mc_plan -> k_mc_walk): 32 bytes
@@ -440,7 +438,7 @@ struct BatchState {
   unsigned long long* blk_pack8 = nullptr;  // [kBatch][kApplyBlocks8]
   double* blk_dead8 = nullptr;
   uint32_t* blk_ndead8 = nullptr;
-  // Workspace pool (fora.cpp: SlotDriver; more workspaces than columns of c8): who holds each column (-1: nobody; an
+  // Workspace pool (batch_driver.hpp: SlotDriver; more workspaces than columns of c8): who holds each column (-1: nobody; an
   // index into `slots`)
   int col_owner[kBatch];
   // Sequential batch driver (SlotDriver): the one stream all slots work on beside the sweeps (sparse levels, seeds,
@@ -475,7 +473,7 @@ struct pprhip_graph {
   int slot_index = -1;
   pprhip::BatchSync* sync = nullptr;  // set on a slot while a batched call is running
   hipStream_t own_stream = nullptr;   // slot: the stream its worker thread uses
-  // Sequential batch driver (fora.cpp: SlotDriver): a slot's c8-touching kernels go to the parent's stream
+  // Sequential batch driver (batch_driver.hpp: SlotDriver): a slot's c8-touching kernels go to the parent's stream
   // (engine_internal.hpp: C8Scope), and the events that order them
   bool c8_via_parent = false;
   bool c8_settled = false;  // nothing of this slot is pending on its stream: C8Scope need not wait for that stream
@@ -488,7 +486,7 @@ struct pprhip_graph {
   bool pooled = false;
   bool has_col = false;
   uint32_t walk_waves = 0;  // waves per CU of the next walk kernels (0: the default)
-  bool stream_open = false;  // a query stream's driver thread owns the handle (fora.cpp: pprhip_stream)
+  bool stream_open = false;  // a query stream's driver thread owns the handle (stream.cpp: pprhip_stream)
   void* stream_obj = nullptr;  // ... that stream (pprhip_graph_destroy closes a stream its owner forgot)
   hipEvent_t walk_ev[3] = {nullptr, nullptr, nullptr};  // slot: the events around its walk phase on the walk stream
   pprhip::KernelTimer ktimer;  // kernel-class timer of this workspace's work (a slot's worker; a handle's batched sweeps)
@@ -646,12 +644,12 @@ int launch_mc_plan(pprhip_graph* g, int variant, double alpha, double rsum, doub
 int launch_mc_walk(pprhip_graph* g, double alpha, uint64_t seed, uint32_t stream, int no_zero_hop, double* target);
 // the walks of the latest plan with the index `ix`: k_index_serve deposits the stored terminals, k_mc_walk<kWalkIndexed> walks
 // what the index does not hold (walk idx >= cap of its node, dead-end starts) with the walks' own indices
-int launch_mc_walk_indexed(pprhip_graph* g, const WalkIndex* ix, double alpha, uint64_t seed, double* target);
+int launch_mc_walk_indexed(pprhip_graph* g, const TerminalTable* ix, double alpha, uint64_t seed, double* target);
 // the walks of the latest plan (whole-graph FORA: stream 0, forced first hop) through the call's terminal cache: a walk
 // whose cell is filled deposits there at once, the others walk and fill their cells
-int launch_mc_walk_shared(pprhip_graph* g, const WalkShare* ws, double alpha, uint64_t seed, double* target);
+int launch_mc_walk_shared(pprhip_graph* g, const TerminalTable* ws, double alpha, uint64_t seed, double* target);
 // fills ix->term from ix->off (already in HBM): terminal j of node v = walk (seed, stream 0, v, j), forced first hop
-int launch_index_build(pprhip_graph* g, const WalkIndex* ix, unsigned long long* d_steps);
+int launch_index_build(pprhip_graph* g, const TerminalTable* ix, unsigned long long* d_steps);
 // (rows of out-degree >= survival_heavy_degree() go in d_heavy: a workgroup each)
 int launch_survival_iter(pprhip_graph* g, const double* s_old, double* s_new, double alpha, const int32_t* d_heavy,
                          uint32_t n_heavy, unsigned long long* dmax);

@@ -1,6 +1,7 @@
 // engine_internal.hpp — declarations shared by the engine's translation units (engine.cpp: graph
-// lifecycle, level loop, single-query entry points; fora.cpp: resumable FORA / top-k / backward runs
-// and the batched entry points; allpair.cpp: All-Pair-Backward-Search and the inverted index).
+// lifecycle, level loop, single-query entry points; fora.cpp: resumable FORA / top-k / backward runs;
+// batch.cpp, batch_api.cpp, fetch_pipe.cpp, stream.cpp: the batched entry points; allpair.cpp:
+// All-Pair-Backward-Search and the inverted index).
 #pragma once
 
 #include <sys/mman.h>
@@ -26,7 +27,7 @@ struct pprhip_results {
 
 namespace pprhip {
 
-struct ForaRun;
+struct ForaRun;  // run.hpp
 
 // Rendezvous of the batch workers (one host thread and one stream per slot) with the sweeper
 // thread.  Workers run their queries' sparse levels, walks and selections concurrently; a worker
@@ -78,7 +79,7 @@ struct LevelCtx {
   // dense sweep - in place or flushing - has to follow whatever the frontier looks like)
   int gs_state = kGsJacobi;
   bool gs_dirty = false;
-  // Batch driver with the slots on a stream of their own (fora.cpp: SlotDriver).  defer_compact: run_levels returns
+  // Batch driver with the slots on a stream of their own (batch_driver.hpp: SlotDriver).  defer_compact: run_levels returns
   // kYieldDefer as soon as the way back to list form is queued (the compaction runs on the parent's stream, before the
   // next sweep; the sparse levels behind it are launched when the driver calls again, beside that sweep).
   // compacted: that compaction has been queued, the list form is (about to be) there.
@@ -97,8 +98,6 @@ struct RoundCut {
   double omega = 0.0, c_walk = 0.0, alpha = 0.0;
   double rsum = 0.0;  // (1 - alpha) * residue sum measured at the check (valid when !fixed and checked)
 };
-
-// kernel-class timer of the calling thread: its own, or the slot's while it works for a batch
 
 constexpr int kYield = 1;  // run_levels: the next level is dense and the caller runs it (batched sweeps)
 constexpr int kYieldColumn = 4;  // run_levels: the level is dense and no column of c8 is free (workspace pool)
@@ -241,7 +240,7 @@ void free_walk_index(GraphData* D);  // walk_index.cpp: the lifted graph's walk 
 // walk_index.cpp: the call-scoped terminal cache of the batched whole-graph FORA paths (engine.hpp: WalkShare)
 void walk_share_begin(pprhip_graph* P, int q, double alpha, double rmax, double omega, uint64_t seed);
 void free_walk_share(BatchState* B);
-void stream_detach(void* stream_obj);  // fora.cpp: ends a query stream's driver before its graph goes
+void stream_detach(void* stream_obj);  // stream.cpp: ends a query stream's driver before its graph goes
 int alloc_dev(void** p, size_t bytes);
 double level_cost(const pprhip_graph* g, uint64_t nf, uint64_t ef, bool* dense);
 uint64_t dense_level_bytes(const pprhip_graph* g);
@@ -261,8 +260,8 @@ int ensure_panel_part(pprhip_graph* g);  // the buffer of the panel sweep's part
 const GsBlock* gs_blocks_of(pprhip_graph* g, int* n_blocks);
 unsigned long long gs_thresh_of(const pprhip_graph* g);
 int seed_single(pprhip_graph* g, LevelCtx& L, int32_t node, uint32_t degree);
-int seed_scan(pprhip_graph* g, const PushArgs& a, int kind, LevelCtx& L);
-int ensure_workspaces(pprhip_graph* P, int count);  // more workspaces than columns of c8 (fora.cpp: SlotDriver)
+int seed_scan(pprhip_graph* g, const PushArgs& a, int seed_kind, LevelCtx& L);
+int ensure_workspaces(pprhip_graph* P, int count);  // more workspaces than columns of c8 (batch_driver.hpp: SlotDriver)
 // a stream that runs beside g->stream - and beside `also`, when given - (self-tested)
 int make_side_stream(pprhip_graph* g, hipStream_t* out, hipStream_t also = nullptr);
 int fetch_small(pprhip_graph* g, const void* dev, void* host, size_t bytes);  // a few words, without a copy command
@@ -291,6 +290,21 @@ uint32_t hdeg_in(const pprhip_graph* g, int32_t v);
 int select_topk(pprhip_graph* g, const double* x, int k, int32_t* ids_out, double* vals_out, int cap, int* n_out,
                 double* kth_out, bool* have_kth, pprhip_stats_t& st, bool with_plan_sum = false);
 
+// per-class kernel totals into a call's stats; the class with the largest total is the dominant one
+inline void fold_class_totals(pprhip_stats_t& st, const double tot[8], const uint64_t bytes[8], const uint32_t cnt[8]) {
+  int best = 0;
+  for (int c = 0; c < 8; ++c) {
+    st.class_ms[c] = tot[c];
+    st.class_bytes[c] = bytes[c];
+    st.class_launches[c] = cnt[c];
+    if (tot[c] > tot[best]) best = c;
+  }
+  st.dominant_kernel_id = (uint32_t)best;
+  st.dominant_kernel_ms = tot[best];
+  st.dominant_kernel_bytes = bytes[best];
+  st.dominant_kernel_launches = cnt[best];
+}
+
 struct CallTimer {
   pprhip_graph* g;
   explicit CallTimer(pprhip_graph* g_) : g(g_) {
@@ -313,22 +327,10 @@ struct CallTimer {
     uint64_t bytes[8] = {0};
     uint32_t cnt[8] = {0};
     ktimer().resolve(tot, bytes, cnt);
-    int best = 0;
-    for (int c = 1; c < 8; ++c)
-      if (tot[c] > tot[best]) best = c;
-    for (int c = 0; c < 8; ++c) {
-      st.class_ms[c] = tot[c];
-      st.class_bytes[c] = bytes[c];
-      st.class_launches[c] = cnt[c];
-    }
-    st.dominant_kernel_id = (uint32_t)best;
-    st.dominant_kernel_ms = tot[best];
-    st.dominant_kernel_bytes = bytes[best];
-    st.dominant_kernel_launches = cnt[best];
+    fold_class_totals(st, tot, bytes, cnt);
   }
 };
 
-// a batch of queries for the slot engine (fora.cpp)
 // Delivery of the queries' vectors to the caller's (pageable) host memory while the batch keeps running: a finished
 // query's vector is permuted to the caller's ids into one of kRing device staging buffers on the query's own stream,
 // copied to a pinned host buffer on a copy stream, and moved from there to its destination by a copier thread.  The
@@ -365,7 +367,7 @@ struct FetchPipe {
   void copier();
 };
 
-// A pair call (BatchJob kind 3, pairs.cpp): the pairs sorted by target; query i of the job is the i-th distinct target
+// A pair call (BatchJob kind kPairs, pairs.cpp): the pairs sorted by target; query i of the job is the i-th distinct target
 // (BatchJob::srcs) and covers the sorted pairs [first[i], first[i + 1]).  Device arrays of the call: the sources
 // (internal ids) and the call positions of the sorted pairs, the values by call position, per workspace (ws_index < kBatch)
 // a buffer of part_cap chunk sums and three events (push start, walks start, end).
@@ -387,6 +389,13 @@ struct PairPlan {
   hipEvent_t ev[3 * kBatch] = {};
 };
 
+// What a query of a batched job runs: whole-graph FORA, FORA top-k (seed + query index), a backward search of
+// All-Pair, or single pairs (a backward push per distinct target, then its sources' walks)
+enum class QueryKind : int { kFora, kTopk, kBackward, kPairs };
+inline bool is_whole_graph(QueryKind k) { return k == QueryKind::kFora; }
+inline bool pushes_backward(QueryKind k) { return k == QueryKind::kBackward || k == QueryKind::kPairs; }
+
+// a batch of queries for the slot engine (batch.cpp)
 struct BatchJob {
   pprhip_graph* P;
   const int32_t* srcs;  // nullptr: a job of seed sets (sets)
@@ -401,15 +410,14 @@ struct BatchJob {
   double* vals_out;
   int* n_out;
   pprhip_stats_t* per_query;
-  int kind = 0;  // 0: whole-graph FORA per query, 1: FORA top-k per query (seed + query index), 2: backward search,
-                 // 3: single pairs (a backward push per distinct target, then its sources' walks)
-  PairPlan* pairs = nullptr;               // kind 3
-  double alpha = 0.0, threshold = 0.0;   // kind 2
-  std::vector<Triple>* triples = nullptr;  // kind 2: every search's entries >= threshold
-  pprhip_results* keep = nullptr;          // kind 0: device-resident store of the queries' vectors
+  QueryKind kind = QueryKind::kFora;
+  PairPlan* pairs = nullptr;               // kPairs
+  double alpha = 0.0, threshold = 0.0;   // kBackward
+  std::vector<Triple>* triples = nullptr;  // kBackward: every search's entries >= threshold
+  pprhip_results* keep = nullptr;          // kFora: device-resident store of the queries' vectors
   int keep_first = 0;                      // ... query i goes to slot keep_first + i of it
   FetchPipe* pipe = nullptr;               // reserve_out given: asynchronous delivery (batch_run opens / closes it)
-  // kinds 0 and 1 without srcs: query i runs from seed set i, its host plan (seed_plan) made before anything runs; the
+  // kFora and kTopk without srcs: query i runs from seed set i, its host plan (seed_plan) made before anything runs; the
   // query's workspace takes it over (seed_upload) when the query begins
   std::vector<SeedTable> sets;
   pprhip_stats_t sum;

@@ -647,7 +647,7 @@ constexpr int kHotBytes = 128 * 1024;  // LDS table of the hottest vertices' lin
 // The batched edge kernel takes 32 KB of it (256 lines) since round 5: the table's size never mattered to the sweep
 // itself (0 / 256 / 512 / 1024 lines within 0.5 %, round 2), but a workgroup that holds 128 of a CU's 160 KB keeps
 // every kernel with a larger LDS block of its own - the sparse push's 48 KB - off the CU while it runs, and the
-// queries that work beside the sweeps (fora.cpp: SlotDriver) wait for the gaps between the sweep's kernels:
+// queries that work beside the sweeps (batch_driver.hpp: SlotDriver) wait for the gaps between the sweep's kernels:
 // k_sparse_push took 99 us per launch beside the sweeps against 14 us alone.  128 -> 32 KB: 344-347 -> 352 queries/s.
 constexpr int kHotDefaultBytes = 32 * 1024;
 

@@ -974,7 +974,7 @@ int launch_mc_walk(pprhip_graph* g, double alpha, uint64_t seed, uint32_t stream
 
 // The same grid for both kernels: the serve kernel's share of a wave is a stream of terminals, the walk kernel behind
 // it returns at once unless the serve kernel counted walks the index does not hold.
-int launch_mc_walk_indexed(pprhip_graph* g, const WalkIndex* ix, double alpha, uint64_t seed, double* target) {
+int launch_mc_walk_indexed(pprhip_graph* g, const TerminalTable* ix, double alpha, uint64_t seed, double* target) {
   const uint32_t grid = mc_walk_grid(g);
   const int cell = (int)(g->mc_last_plan % 3u);
   hipLaunchKernelGGL(k_index_serve, dim3(grid), dim3(64), 0, g->stream, plan_rec_of(g, g->mc_last_plan), ix->off, ix->term,
@@ -988,17 +988,17 @@ int launch_mc_walk_indexed(pprhip_graph* g, const WalkIndex* ix, double alpha, u
   return PPRHIP_OK;
 }
 
-int launch_mc_walk_shared(pprhip_graph* g, const WalkShare* ws, double alpha, uint64_t seed, double* target) {
+int launch_mc_walk_shared(pprhip_graph* g, const TerminalTable* ws, double alpha, uint64_t seed, double* target) {
   const uint32_t grid = mc_walk_grid(g);
   hipLaunchKernelGGL(k_mc_walk<kWalkShared>, dim3(grid), dim3(64), 0, g->stream, plan_rec_of(g, g->mc_last_plan),
                      reinterpret_cast<const uint4*>(g->gr->walk_rec), target, alpha, (uint32_t)seed, (uint32_t)(seed >> 32), 0u,
-                     1, g->ctr, (int)(g->mc_last_plan % 3u), (const unsigned long long*)ws->off, ws->term, g->gr->n,
+                     1, g->ctr, (int)(g->mc_last_plan % 3u), (const unsigned long long*)ws->off, (uint32_t*)ws->term, g->gr->n,
                      ws->usage);
   PPRHIP_CHECK_HIP(hipGetLastError());
   return PPRHIP_OK;
 }
 
-int launch_index_build(pprhip_graph* g, const WalkIndex* ix, unsigned long long* d_steps) {
+int launch_index_build(pprhip_graph* g, const TerminalTable* ix, unsigned long long* d_steps) {
   if (ix->total == 0) return PPRHIP_OK;
   const uint64_t cap = (uint64_t)g->gr->n_cus * kWalkWavesPerCu;
   const uint64_t groups = (ix->total + 63) / 64;

@@ -1,7 +1,7 @@
 // pairs.cpp — single-pair PPR (beyond the reference): the bidirectional estimator of include/pprhip.h "single pairs"
 // (DESIGN.md §2 "Single pairs").  Argument checks, the grouping of a call's pairs by target, the survival vector S that
 // turns the backward push's leaking PPR into the engine's restarting one (kept on the lifted graph per alpha), and the
-// entry points.  The pushes and walks run as BatchJob kind 3 of the batch driver (fora.cpp: pair_begin / pair_step).
+// entry points.  The pushes and walks run as BatchJob kind kPairs of the batch driver (fora.cpp: pair_begin / pair_step).
 #include <algorithm>
 #include <chrono>
 #include <cmath>
@@ -244,7 +244,7 @@ int pprhip_ppr_pairs(pprhip_graph_t* g, const int32_t* sources, const int32_t* t
   if (rc == PPRHIP_OK) {
     BatchJob J;
     J.P = g;
-    J.kind = 3;
+    J.kind = QueryKind::kPairs;
     J.srcs = distinct.data();
     J.q = (int)distinct.size();
     J.eps = eps;

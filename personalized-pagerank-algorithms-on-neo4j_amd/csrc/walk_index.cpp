@@ -15,19 +15,6 @@ using namespace pprhip::detail;
 namespace pprhip {
 namespace detail {
 
-static void destroy_index(WalkIndex* ix) {
-  if (!ix) return;
-  void* ptrs[] = {ix->off, ix->term, ix->usage};
-  for (void* p : ptrs)
-    if (p) (void)hipFree(p);
-  delete ix;
-}
-
-void free_walk_index(GraphData* D) {
-  destroy_index(D->widx);
-  D->widx = nullptr;
-}
-
 // cap(v) = ceil(d_out(v) * density) in internal order as a prefix: h_off[v] = the first position of node v, h_off[n] the
 // total, which must stay below the engine's walk limit (the walk index and the call-scoped terminal cache share it)
 int walk_offsets(const GraphData* D, double density, std::vector<unsigned long long>& h_off, uint64_t* total,
@@ -55,41 +42,97 @@ int walk_offsets(const GraphData* D, double density, std::vector<unsigned long l
   return PPRHIP_OK;
 }
 
+// ---- the table behind both (engine.hpp: TerminalTable)
+// The offsets for `density`, the three device arrays, the offsets' upload and the counters' clear on `stream` (not waited
+// for).  as_extra: more than a quarter of the device's free memory is refused.  Whatever fails leaves T to table_free.
+static int table_alloc(TerminalTable& T, const GraphData* D, double density, int usage_cells, bool as_extra,
+                       hipStream_t stream, const char* fn) {
+  const size_t off_bytes = sizeof(unsigned long long) * ((size_t)D->n + 1);
+  T.density = density;
+  PPRHIP_TRY(walk_offsets(D, density, T.h_off, &T.total, fn));
+  if (as_extra) {
+    size_t free_b = 0, total_b = 0;
+    PPRHIP_CHECK_HIP(hipMemGetInfo(&free_b, &total_b));
+    const size_t bytes = sizeof(int32_t) * (size_t)T.total + off_bytes;
+    if (bytes > free_b / 4) {
+      set_error("%s: %zu bytes are more than a quarter of the device's free memory", fn, bytes);
+      return PPRHIP_ERR_OOM;
+    }
+  }
+  PPRHIP_TRY(alloc_dev((void**)&T.off, off_bytes));
+  PPRHIP_TRY(alloc_dev((void**)&T.term, sizeof(int32_t) * (size_t)T.total));
+  PPRHIP_TRY(alloc_dev((void**)&T.usage, usage_cells * sizeof(unsigned long long)));
+  PPRHIP_CHECK_HIP(hipMemcpyAsync(T.off, T.h_off.data(), off_bytes, hipMemcpyHostToDevice, stream));
+  PPRHIP_CHECK_HIP(hipMemsetAsync(T.usage, 0, usage_cells * sizeof(unsigned long long), stream));
+  return PPRHIP_OK;
+}
+
+static void table_free(TerminalTable& T) {
+  for (void* p : {(void*)T.off, (void*)T.term, (void*)T.usage})
+    if (p) (void)hipFree(p);
+}
+
+// The cells of one node back in original ids, at most cap of them; -1 for a cell without a terminal (kWalkShareEmpty:
+// the cache only).  all_streams: the cells are written on other streams than g's (the cache: the batch workspaces').
+static int table_fetch_node(pprhip_graph* g, const TerminalTable& T, int32_t node, bool all_streams,
+                            int32_t* terminals_out, uint64_t cap, uint64_t* count_out) {
+  const int32_t v = g->gr->h_old2new[node];
+  const unsigned long long o0 = T.h_off[v], cnt = T.h_off[(size_t)v + 1] - o0;
+  if (count_out) *count_out = cnt;
+  const uint64_t take = cnt < cap ? cnt : cap;
+  if (take == 0) return PPRHIP_OK;
+  if (all_streams) PPRHIP_CHECK_HIP(hipDeviceSynchronize());
+  PPRHIP_CHECK_HIP(hipMemcpyAsync(terminals_out, T.term + o0, sizeof(int32_t) * take, hipMemcpyDeviceToHost, g->stream));
+  PPRHIP_CHECK_HIP(hipStreamSynchronize(g->stream));
+  for (uint64_t i = 0; i < take; ++i)
+    terminals_out[i] = (uint32_t)terminals_out[i] < g->gr->n ? g->gr->h_new2old[terminals_out[i]] : -1;
+  return PPRHIP_OK;
+}
+
+// the table's first two counter cells since the last reset (no table: zeros)
+static int table_usage(const TerminalTable* T, uint64_t* first, uint64_t* second, int reset) {
+  unsigned long long u[2] = {0ull, 0ull};
+  if (T) {
+    PPRHIP_CHECK_HIP(hipDeviceSynchronize());  // (the batch workspaces' streams as well)
+    PPRHIP_CHECK_HIP(hipMemcpy(u, T->usage, sizeof u, hipMemcpyDeviceToHost));
+    if (reset) PPRHIP_CHECK_HIP(hipMemset(T->usage, 0, sizeof u));
+  }
+  if (first) *first = u[0];
+  if (second) *second = u[1];
+  return PPRHIP_OK;
+}
+
+static uint64_t table_bytes(const TerminalTable& T, uint32_t n, int usage_cells) {  // terminals, offsets, counters
+  return 4ull * T.total + 8ull * ((uint64_t)n + 1) + 8ull * (uint64_t)usage_cells;
+}
+
+static void destroy_index(WalkIndex* ix) {
+  if (ix) table_free(*ix);
+  delete ix;
+}
+
+void free_walk_index(GraphData* D) {
+  destroy_index(D->widx);
+  D->widx = nullptr;
+}
+
 // ---- the call-scoped terminal cache (engine.hpp: WalkShare)
 void free_walk_share(BatchState* B) {
   WalkShare* ws = B->share;
   if (!ws) return;
-  void* ptrs[] = {ws->off, ws->term, ws->usage};
-  for (void* p : ptrs)
-    if (p) (void)hipFree(p);
+  table_free(*ws);
   if (ws->cleared) (void)hipEventDestroy(ws->cleared);
   delete ws;
   B->share = nullptr;
 }
 
 static int walk_share_alloc(pprhip_graph* P, double density) {
-  static const char* fn = "terminal cache";
-  BatchState* B = P->batch;
   WalkShare* ws = new (std::nothrow) WalkShare();
   if (!ws) return PPRHIP_ERR_OOM;
-  B->share = ws;
-  ws->density = density;
-  PPRHIP_TRY(walk_offsets(P->gr, density, ws->h_off, &ws->total, fn));
-  // the cache is an extra: it does not take memory the call itself may still ask for (workspaces, the fetch ring)
-  size_t free_b = 0, total_b = 0;
-  PPRHIP_CHECK_HIP(hipMemGetInfo(&free_b, &total_b));
-  const size_t bytes = sizeof(uint32_t) * (size_t)ws->total + sizeof(unsigned long long) * ((size_t)P->gr->n + 1);
-  if (bytes > free_b / 4) {
-    set_error("%s: %zu bytes are more than a quarter of the device's free memory", fn, bytes);
-    return PPRHIP_ERR_OOM;
-  }
-  PPRHIP_TRY(alloc_dev((void**)&ws->term, sizeof(uint32_t) * (size_t)ws->total));
-  PPRHIP_TRY(alloc_dev((void**)&ws->off, sizeof(unsigned long long) * ((size_t)P->gr->n + 1)));
-  PPRHIP_TRY(alloc_dev((void**)&ws->usage, 2 * sizeof(unsigned long long)));
+  P->batch->share = ws;
+  // (as an extra: it does not take memory the call itself may still ask for - workspaces, the fetch ring)
+  PPRHIP_TRY(table_alloc(*ws, P->gr, density, 2, true, P->stream, "terminal cache"));
   PPRHIP_CHECK_HIP(hipEventCreateWithFlags(&ws->cleared, hipEventDisableTiming));
-  PPRHIP_CHECK_HIP(hipMemcpyAsync(ws->off, ws->h_off.data(), sizeof(unsigned long long) * ((size_t)P->gr->n + 1),
-                                  hipMemcpyHostToDevice, P->stream));
-  PPRHIP_CHECK_HIP(hipMemsetAsync(ws->usage, 0, 2 * sizeof(unsigned long long), P->stream));
   PPRHIP_CHECK_HIP(hipStreamSynchronize(P->stream));  // (h_off is pageable)
   return PPRHIP_OK;
 }
@@ -114,7 +157,7 @@ void walk_share_begin(pprhip_graph* P, int q, double alpha, double rmax, double 
   }
   WalkShare* ws = B->share;
   if (ws->total == 0) return;
-  if (hipMemsetAsync(ws->term, 0xFF, sizeof(uint32_t) * (size_t)ws->total, P->stream) != hipSuccess ||
+  if (hipMemsetAsync(ws->term, 0xFF, sizeof(int32_t) * (size_t)ws->total, P->stream) != hipSuccess ||
       hipEventRecord(ws->cleared, P->stream) != hipSuccess) {
     (void)hipGetLastError();
     (void)hipStreamSynchronize(P->stream);
@@ -162,14 +205,7 @@ int pprhip_walk_index_build(pprhip_graph_t* g, double alpha, uint64_t seed, doub
   if (!ix) return PPRHIP_ERR_OOM;
   ix->alpha = alpha;
   ix->seed = seed;
-  ix->density = density;
-  PPRHIP_TRY(walk_offsets(D, density, ix->h_off, &ix->total, fn));
-  PPRHIP_TRY(alloc_dev((void**)&ix->off, sizeof(unsigned long long) * ((size_t)D->n + 1)));
-  PPRHIP_TRY(alloc_dev((void**)&ix->term, sizeof(int32_t) * (size_t)ix->total));
-  PPRHIP_TRY(alloc_dev((void**)&ix->usage, 3 * sizeof(unsigned long long)));  // (WalkIndex::usage)
-  PPRHIP_CHECK_HIP(hipMemcpyAsync(ix->off, ix->h_off.data(), sizeof(unsigned long long) * ((size_t)D->n + 1),
-                                  hipMemcpyHostToDevice, g->stream));
-  PPRHIP_CHECK_HIP(hipMemsetAsync(ix->usage, 0, 3 * sizeof(unsigned long long), g->stream));
+  PPRHIP_TRY(table_alloc(*ix, D, density, 3, false, g->stream, fn));
   PPRHIP_CHECK_HIP(hipEventRecord(g->ev[0], g->stream));
   PPRHIP_TRY(launch_index_build(g, ix.get(), ix->usage + 2));
   PPRHIP_CHECK_HIP(hipEventRecord(g->ev[1], g->stream));
@@ -209,7 +245,7 @@ int pprhip_walk_index_info(const pprhip_graph_t* g, int* present, double* alpha,
   if (seed) *seed = ix ? ix->seed : 0;
   if (density) *density = ix ? ix->density : 0.0;
   if (terminals) *terminals = ix ? ix->total : 0;
-  if (bytes) *bytes = ix ? 4ull * ix->total + 8ull * ((uint64_t)g->gr->n + 1) + 3ull * 8ull : 0;  // terminals, offsets, the three counter cells
+  if (bytes) *bytes = ix ? table_bytes(*ix, g->gr->n, 3) : 0;
   return PPRHIP_OK;
 }
 
@@ -226,30 +262,12 @@ int pprhip_walk_index_fetch(pprhip_graph_t* g, int32_t node, int32_t* terminals_
     set_error("%s: null output", fn);
     return PPRHIP_ERR_INVALID;
   }
-  const int32_t v = g->gr->h_old2new[node];
-  const unsigned long long o0 = ix->h_off[v], cnt = ix->h_off[(size_t)v + 1] - o0;
-  if (count_out) *count_out = cnt;
-  const uint64_t take = cnt < cap ? cnt : cap;
-  if (take == 0) return PPRHIP_OK;
-  PPRHIP_CHECK_HIP(hipMemcpyAsync(terminals_out, ix->term + o0, sizeof(int32_t) * take, hipMemcpyDeviceToHost, g->stream));
-  PPRHIP_CHECK_HIP(hipStreamSynchronize(g->stream));
-  for (uint64_t i = 0; i < take; ++i) terminals_out[i] = g->gr->h_new2old[terminals_out[i]];
-  return PPRHIP_OK;
+  return table_fetch_node(g, *ix, node, false, terminals_out, cap, count_out);
 }
 
 int pprhip_walk_index_usage(pprhip_graph_t* g, uint64_t* served, uint64_t* walked, int reset) {
-  static const char* fn = "pprhip_walk_index_usage";
-  PPRHIP_TRY(check_graph(g, fn));
-  const WalkIndex* ix = g->gr->widx;
-  unsigned long long u[2] = {0ull, 0ull};
-  if (ix) {
-    PPRHIP_CHECK_HIP(hipDeviceSynchronize());  // (the batch workspaces' streams as well)
-    PPRHIP_CHECK_HIP(hipMemcpy(u, ix->usage, sizeof u, hipMemcpyDeviceToHost));
-    if (reset) PPRHIP_CHECK_HIP(hipMemset(ix->usage, 0, sizeof u));
-  }
-  if (served) *served = u[0];
-  if (walked) *walked = u[1];
-  return PPRHIP_OK;
+  PPRHIP_TRY(check_graph(g, "pprhip_walk_index_usage"));
+  return table_usage(g->gr->widx, served, walked, reset);
 }
 
 #ifdef PPRHIP_TEST_HOOKS
@@ -264,22 +282,13 @@ int pprhip_hook_walk_share_info(pprhip_graph_t* g, int* present, int* on, uint64
   if (on) *on = ws && ws->on ? 1 : 0;
   if (seed) *seed = ws ? ws->seed : 0;
   if (cells) *cells = ws ? ws->total : 0;
-  if (bytes) *bytes = ws ? 4ull * ws->total + 8ull * ((uint64_t)g->gr->n + 1) + 2ull * 8ull : 0;
+  if (bytes) *bytes = ws ? table_bytes(*ws, g->gr->n, 2) : 0;
   return PPRHIP_OK;
 }
 
 int pprhip_hook_walk_share_usage(pprhip_graph_t* g, uint64_t* served, uint64_t* stored, int reset) {
   PPRHIP_TRY(check_graph(g, "pprhip_hook_walk_share_usage"));
-  const WalkShare* ws = g->batch ? g->batch->share : nullptr;
-  unsigned long long u[2] = {0ull, 0ull};
-  if (ws) {
-    PPRHIP_CHECK_HIP(hipDeviceSynchronize());
-    PPRHIP_CHECK_HIP(hipMemcpy(u, ws->usage, sizeof u, hipMemcpyDeviceToHost));
-    if (reset) PPRHIP_CHECK_HIP(hipMemset(ws->usage, 0, sizeof u));
-  }
-  if (served) *served = u[0];
-  if (stored) *stored = u[1];
-  return PPRHIP_OK;
+  return table_usage(g->batch ? g->batch->share : nullptr, served, stored, reset);
 }
 
 int pprhip_hook_walk_share_fetch(pprhip_graph_t* g, int32_t node, int32_t* terminals_out, uint64_t cap,
@@ -292,16 +301,7 @@ int pprhip_hook_walk_share_fetch(pprhip_graph_t* g, int32_t node, int32_t* termi
     set_error("%s: no terminal cache on the handle, or null output", fn);
     return PPRHIP_ERR_STATE;
   }
-  const int32_t v = g->gr->h_old2new[node];
-  const unsigned long long o0 = ws->h_off[v], cnt = ws->h_off[(size_t)v + 1] - o0;
-  if (count_out) *count_out = cnt;
-  const uint64_t take = cnt < cap ? cnt : cap;
-  if (take == 0) return PPRHIP_OK;
-  PPRHIP_CHECK_HIP(hipDeviceSynchronize());
-  PPRHIP_CHECK_HIP(hipMemcpy(terminals_out, ws->term + o0, sizeof(int32_t) * take, hipMemcpyDeviceToHost));
-  for (uint64_t i = 0; i < take; ++i)
-    terminals_out[i] = terminals_out[i] >= 0 && (uint32_t)terminals_out[i] < g->gr->n ? g->gr->h_new2old[terminals_out[i]] : -1;
-  return PPRHIP_OK;
+  return table_fetch_node(g, *ws, node, true, terminals_out, cap, count_out);
 }
 #endif
 

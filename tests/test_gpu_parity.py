@@ -234,7 +234,7 @@ def test_fora_batch_rmat12(pkg, orc, rmat12, threads, monkeypatch):
 def test_fora_batch_leftover_queries_run_singly(pkg, orc, rmat15, dev_rmat15, q, monkeypatch):
     """With one workspace per column (PPRHIP_BATCH_WORKSPACES=16: a device without room for the pool) a call whose query
     count leaves one to three queries over after the full rounds of 16 (PPR.java:179's 50 = 3 x 16 + 2) runs those on the
-    handle's own workspace, one at a time (fora.cpp: kTailSingle): every query - the leftovers too - equals the twin
+    handle's own workspace, one at a time (batch.cpp: kTailSingle): every query - the leftovers too - equals the twin
     and what the call gives with the leftovers on the slots (PPRHIP_BATCH_NO_TAIL) and with the pool (the default, which
     has no such rule), vectors kept in a store and delivered to the host alike, top-k per query included."""
     og = to_oracle(orc, rmat15)
@@ -299,7 +299,7 @@ def test_fora_batch_rmat15_many_queries(pkg, orc, rmat15, dev_rmat15):
                                  {"PPRHIP_BATCH_WORKSPACES": "48"}, {"PPRHIP_BATCH_SLOTS_BESIDE": "0"},
                                  {"PPRHIP_BATCH_NO_HOOK": "1"}, {"PPRHIP_BATCH_NO_EARLY": "1", "PPRHIP_BATCH_WALKS_BESIDE": "0"}])
 def test_batch_driver_variants(pkg, orc, rmat15, env, monkeypatch):
-    """The sequential batch driver of round 5 (fora.cpp: SlotDriver): sweeps launched and collected separately, the
+    """The sequential batch driver of round 5 (batch_driver.hpp: SlotDriver): sweeps launched and collected separately, the
     queries outside a sweep stepped on a second stream beside it, a pool of workspaces (default 32) for the 16 columns
     of the contribution array, turns taken from inside a workspace's read-back wait.  Each query is the single-query
     algorithm whatever the driver does around it: with one workspace per column, an odd number of them, three per

@@ -2,7 +2,7 @@
 
     python3 tools/exp/q50_tail.py            -> queries/s of six 50-query calls, PPRHIP_BATCH_NO_TAIL unset / set
 
-The rule (fora.cpp: kTailSingle) runs a call's last q % 16 <= 3 queries one at a time on the handle's own workspace
+The rule (batch.cpp: kTailSingle) runs a call's last q % 16 <= 3 queries one at a time on the handle's own workspace
 instead of as a last round of sweeps with nearly empty columns.  With the workspace pool there are no rounds of 16 any
 more: this measures whether the rule still pays.
 """
