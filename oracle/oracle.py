@@ -74,6 +74,9 @@ def lib():
         L.orc_random_walk.restype = C.c_int32
         L.orc_random_walk.argtypes = [C.POINTER(Graph), C.c_int32, C.c_double, C.c_uint64, C.c_uint32, C.c_uint64,
                                       C.c_int, C.POINTER(C.c_uint32)]
+        L.orc_pair_walk_sum.restype = None
+        L.orc_pair_walk_sum.argtypes = [C.POINTER(Graph), C.c_int32, C.c_double, C.c_uint64, C.c_uint64, C.c_void_p,
+                                        C.POINTER(C.c_longdouble), C.POINTER(C.c_uint64)]
         L.orc_fora_whole.restype = None
         L.orc_fora_whole.argtypes = [C.POINTER(Graph), C.c_int, C.c_int32, C.c_double, C.POINTER(Conf), C.c_uint64,
                                      C.c_int, C.POINTER(Tuning), C.c_void_p, C.POINTER(Stats)]
@@ -202,6 +205,15 @@ class OracleGraph:
         steps = C.c_uint32(0)
         t = lib().orc_random_walk(C.byref(self.c), start, alpha, seed, stream, idx, int(no_zero_hop), C.byref(steps))
         return t, steps.value
+
+    def pair_walk_sum(self, s, alpha, seed, walks, residue):
+        """(sum of residue[terminal] over the pair walks (seed, stream 0xFFFF, s, i), i < walks, added in long double
+        and rounded to a double once; their summed steps)."""
+        r = np.ascontiguousarray(residue, dtype=np.float64)
+        assert r.size == self.n
+        total, steps = C.c_longdouble(0.0), C.c_uint64(0)
+        lib().orc_pair_walk_sum(C.byref(self.c), s, alpha, seed, walks, _ptr(r), C.byref(total), C.byref(steps))
+        return float(total.value), steps.value
 
     def fora_whole(self, src, eps, alpha, seed, n_rounds=1, schedule=SYNC, tuning=None, conf=None):
         conf = conf or self.conf_whole(alpha)

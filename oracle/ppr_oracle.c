@@ -970,6 +970,23 @@ int32_t orc_random_walk(const orc_graph* g, int32_t start, double alpha, uint64_
   return cur;
 }
 
+void orc_pair_walk_sum(const orc_graph* g, int32_t s, double alpha, uint64_t seed, uint64_t walks,
+                       const double* residue, long double* sum_out, uint64_t* steps_out) {
+  /* The walk term of a single pair (DESIGN.md §2 "Single pairs"): walks (seed, stream 0xFFFF, s, i), i < walks, with
+   * the zero-hop stop; residue[terminal] summed in index order in long double, so that this side's rounding stays far
+   * below the bar it is compared at. */
+  long double sum = 0.0L;
+  uint64_t total = 0;
+  for (uint64_t i = 0; i < walks; ++i) {
+    uint32_t steps;
+    int32_t t = orc_random_walk(g, s, alpha, seed, 0xFFFFu, i, 0, &steps);
+    sum += (long double)residue[t];
+    total += steps;
+  }
+  if (sum_out) *sum_out = sum;
+  if (steps_out) *steps_out = total;
+}
+
 /* ------------------------------------------------------------------ FORA whole graph (a5) */
 
 static void fora_mc_phase(const orc_graph* g, const double* residue, double rsum_local, double omega, double alpha,

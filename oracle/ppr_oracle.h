@@ -99,6 +99,11 @@ void orc_topk_push_free(orc_topk_push* p);
 int32_t orc_random_walk(const orc_graph* g, int32_t start, double alpha, uint64_t seed, uint32_t stream,
                         uint64_t walk_idx, int no_zero_hop, uint32_t* steps_out);
 
+/* Single pairs (DESIGN.md §2 "Single pairs"; beyond the reference): the walk term's sum over walks (seed, stream
+ * 0xFFFF, s, i), i < walks, zero-hop stop included - residue[terminal] added in long double - and their step count. */
+void orc_pair_walk_sum(const orc_graph* g, int32_t s, double alpha, uint64_t seed, uint64_t walks,
+                       const double* residue, long double* sum_out, uint64_t* steps_out);
+
 /* Fora_Whole_Graph.java:82-146.  n_rounds > 0: exactly that many threshold rounds; 0: the
  * deterministic cost model.  FIFO restarts every round from scratch (as the reference does);
  * SYNC resumes (as the HIP engine does). */

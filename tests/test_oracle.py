@@ -202,6 +202,33 @@ def test_walk_semantics(orc, toy_graphs, got):
     assert len({og.random_walk(17, A, 5, s, 123, True) for s in range(16)}) > 1
 
 
+def test_pair_walk_sum_equals_a_loop_over_random_walk(orc, toy_graphs, got):
+    """orc_pair_walk_sum is orc_random_walk on stream 0xFFFF with the zero-hop stop, walk by walk: exactly the same
+    steps, and the residues of the same terminals summed - against math.fsum's exactly rounded sum, which the long
+    double sum rounded to a double misses by an ulp at the most; a dead-end or isolated start is its own terminal
+    w times."""
+    rng = np.random.default_rng(2)
+    for host, starts in ((got, (17, 0, 42, int(np.flatnonzero(np.diff(got.out_rp) == 0)[0]))),
+                         (toy_graphs["isolated_mix"], (0, 2, 3, 4))):  # 3: dead end with in-edges, 4: isolated
+        og = to_oracle(orc, host)
+        res = rng.random(host.n) * 1e-2
+        for s in starts:
+            for walks, seed in ((0, 1), (1, 1), (300, 7), (777, 2 ** 40 + 5)):
+                loop = [og.random_walk(s, A, seed, 0xFFFF, i, False) for i in range(walks)]
+                total, steps = og.pair_walk_sum(s, A, seed, walks, res)
+                assert steps == sum(m for _, m in loop)
+                ref = math.fsum(res[t] for t, _ in loop)
+                assert abs(total - ref) <= 2.0 ** -52 * abs(ref)
+                if host.out_rp[s + 1] == host.out_rp[s]:
+                    assert steps == 0 and all(t == s for t, _ in loop)
+                    assert total == pytest.approx(walks * res[s], rel=1e-15)
+    # the walks are the pair stream's, no other's
+    og = to_oracle(orc, got)
+    res = np.arange(got.n, dtype=np.float64)
+    assert og.pair_walk_sum(17, A, 7, 300, res)[0] != math.fsum(
+        res[og.random_walk(17, A, 7, 0, i, False)[0]] for i in range(300))
+
+
 # ------------------------------------------------------------------ FORA
 @pytest.mark.parametrize("schedule", [0, 1])
 def test_fora_whole_guarantee_got(orc, got, schedule):
