@@ -74,6 +74,9 @@ def lib():
         L.orc_random_walk.restype = C.c_int32
         L.orc_random_walk.argtypes = [C.POINTER(Graph), C.c_int32, C.c_double, C.c_uint64, C.c_uint32, C.c_uint64,
                                       C.c_int, C.POINTER(C.c_uint32)]
+        L.orc_random_walk_batch.restype = None
+        L.orc_random_walk_batch.argtypes = [C.POINTER(Graph), C.c_void_p, C.c_void_p, C.c_uint64, C.c_double, C.c_uint64,
+                                            C.c_uint32, C.c_int, C.c_void_p, C.c_void_p]
         L.orc_pair_walk_sum.restype = None
         L.orc_pair_walk_sum.argtypes = [C.POINTER(Graph), C.c_int32, C.c_double, C.c_uint64, C.c_uint64, C.c_void_p,
                                         C.POINTER(C.c_longdouble), C.POINTER(C.c_uint64)]
@@ -205,6 +208,18 @@ class OracleGraph:
         steps = C.c_uint32(0)
         t = lib().orc_random_walk(C.byref(self.c), start, alpha, seed, stream, idx, int(no_zero_hop), C.byref(steps))
         return t, steps.value
+
+    def random_walks(self, starts, idx, alpha, seed, stream=0, no_zero_hop=False):
+        """(terminals int32, steps uint32) of the walks (seed, stream, starts[i], idx[i]): random_walk, many per call."""
+        starts = np.ascontiguousarray(starts, dtype=np.int32)
+        idx = np.ascontiguousarray(idx, dtype=np.uint64)
+        assert starts.shape == idx.shape and starts.ndim == 1
+        assert starts.size == 0 or (0 <= int(starts.min()) and int(starts.max()) < self.n)
+        term = np.empty(starts.size, dtype=np.int32)
+        steps = np.empty(starts.size, dtype=np.uint32)
+        lib().orc_random_walk_batch(C.byref(self.c), _ptr(starts), _ptr(idx), starts.size, alpha, seed, stream,
+                                    int(no_zero_hop), _ptr(term), _ptr(steps))
+        return term, steps
 
     def pair_walk_sum(self, s, alpha, seed, walks, residue):
         """(sum of residue[terminal] over the pair walks (seed, stream 0xFFFF, s, i), i < walks, added in long double

@@ -970,6 +970,17 @@ int32_t orc_random_walk(const orc_graph* g, int32_t start, double alpha, uint64_
   return cur;
 }
 
+void orc_random_walk_batch(const orc_graph* g, const int32_t* starts, const uint64_t* walk_idx, uint64_t count,
+                           double alpha, uint64_t seed, uint32_t stream, int no_zero_hop, int32_t* term_out,
+                           uint32_t* steps_out) {
+  /* orc_random_walk for walk i = (seed, stream, starts[i], walk_idx[i]), i < count: one call for the walks of a plan */
+  for (uint64_t i = 0; i < count; ++i) {
+    uint32_t steps;
+    term_out[i] = orc_random_walk(g, starts[i], alpha, seed, stream, walk_idx[i], no_zero_hop, &steps);
+    if (steps_out) steps_out[i] = steps;
+  }
+}
+
 void orc_pair_walk_sum(const orc_graph* g, int32_t s, double alpha, uint64_t seed, uint64_t walks,
                        const double* residue, long double* sum_out, uint64_t* steps_out) {
   /* The walk term of a single pair (DESIGN.md §2 "Single pairs"): walks (seed, stream 0xFFFF, s, i), i < walks, with

@@ -99,6 +99,11 @@ void orc_topk_push_free(orc_topk_push* p);
 int32_t orc_random_walk(const orc_graph* g, int32_t start, double alpha, uint64_t seed, uint32_t stream,
                         uint64_t walk_idx, int no_zero_hop, uint32_t* steps_out);
 
+/* The same for count walks at once: walk i is (seed, stream, starts[i], walk_idx[i]); steps_out may be NULL. */
+void orc_random_walk_batch(const orc_graph* g, const int32_t* starts, const uint64_t* walk_idx, uint64_t count,
+                           double alpha, uint64_t seed, uint32_t stream, int no_zero_hop, int32_t* term_out,
+                           uint32_t* steps_out);
+
 /* Single pairs (DESIGN.md §2 "Single pairs"; beyond the reference): the walk term's sum over walks (seed, stream
  * 0xFFFF, s, i), i < walks, zero-hop stop included - residue[terminal] added in long double - and their step count. */
 void orc_pair_walk_sum(const orc_graph* g, int32_t s, double alpha, uint64_t seed, uint64_t walks,
