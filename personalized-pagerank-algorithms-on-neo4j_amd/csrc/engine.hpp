@@ -157,7 +157,7 @@ struct PushArgs {
 // the stream, and between the short kernels of a top-k round or a sparse level those cost the latency-bound paths
 // 2-8 % (round 4: top-k 16 in flight 1 640-1 720 -> 1 800-1 850 queries/s without them).  Without the option the
 // brackets are only counted: class_launches and class_bytes are filled, class_ms stay zero.
-extern std::atomic<int> g_kernel_timing;  // engine.cpp; -1: not decided yet (the environment is read on first use)
+extern std::atomic<int> g_kernel_timing;  // device_io.cpp; -1: not decided yet (the environment is read on first use)
 bool kernel_timing_on();
 int kernel_timing_level();  // 0: counted only; 1: every class timed; 2: the dense sweeps (classes 1 and 5) timed only
 struct KernelTimer {
@@ -534,7 +534,7 @@ struct pprhip_graph {
   pprhip::HostMail* mail = nullptr;      // mapped pinned memory: small read-backs without a copy command (fetch_small)
   pprhip::HostMail* mail_dev = nullptr;  // the same, as the device sees it
   unsigned long long mail_seq = 0;
-  // a second stream with its own mail and timer: the next top-k round's push beside this round's walks (engine.cpp:
+  // a second stream with its own mail and timer: the next top-k round's push beside this round's walks (fora.cpp:
   // pprhip_fora_topk); created on first use
   hipStream_t spec_stream = nullptr;
   pprhip::HostMail* spec_mail = nullptr;
@@ -590,7 +590,7 @@ struct DenseLaunch {
 int launch_dense_level(pprhip_graph* g, const PushArgs& a, int cbuf, int out_slot, int dead_slot,
                        const DenseLaunch& d = DenseLaunch());
 namespace detail {
-// engine.cpp: the sliced layout's edge windows of every block (nullptr / 1: the whole sweep)
+// levels.cpp: the sliced layout's edge windows of every block (nullptr / 1: the whole sweep)
 const EdgeWindows* sliced_windows_of(pprhip_graph* g, const GsBlock* blocks, int nb);
 }
 constexpr uint32_t kApplyBlocks8 = 2048;  // workgroups of the batched apply kernel (per-slot partials each)

@@ -1,5 +1,6 @@
-// engine_internal.hpp — declarations shared by the engine's translation units (engine.cpp: graph
-// lifecycle, level loop, single-query entry points; fora.cpp: resumable FORA / top-k / backward runs;
+// engine_internal.hpp — declarations shared by the engine's translation units (engine.cpp: single-query
+// entry points; graph.cpp: graph lifecycle and workspaces; levels.cpp: level loop; select.cpp: top-k selection;
+// device_io.cpp: read-backs, scopes, walk launchers; fora.cpp: resumable FORA / top-k / backward runs;
 // batch.cpp, batch_api.cpp, fetch_pipe.cpp, stream.cpp: the batched entry points; allpair.cpp:
 // All-Pair-Backward-Search and the inverted index).
 #pragma once
@@ -236,12 +237,26 @@ int lift_host(uint32_t n, uint64_t m, const uint32_t* out_rp, const int32_t* out
               const int32_t* in_ci, unsigned threads, HostLift& H);
 unsigned host_threads();  // CPU affinity and cgroup quota of the process, at most 64 (PPRHIP_HOST_THREADS overrides)
 
-void free_walk_index(GraphData* D);  // walk_index.cpp: the lifted graph's walk index, if it has one
-// walk_index.cpp: the call-scoped terminal cache of the batched whole-graph FORA paths (engine.hpp: WalkShare)
+// ---- walk_index.cpp
+void free_walk_index(GraphData* D);  // the lifted graph's walk index, if it has one
+// the call-scoped terminal cache of the batched whole-graph FORA paths (engine.hpp: WalkShare)
 void walk_share_begin(pprhip_graph* P, int q, double alpha, double rmax, double omega, uint64_t seed);
 void free_walk_share(BatchState* B);
-void stream_detach(void* stream_obj);  // stream.cpp: ends a query stream's driver before its graph goes
+
+// ---- stream.cpp
+void stream_detach(void* stream_obj);  // ends a query stream's driver before its graph goes
+
+// ---- graph.cpp
 int alloc_dev(void** p, size_t bytes);
+int alloc_pinned(void** p, size_t bytes, unsigned flags);  // pinned host memory, zeroed
+int reset_query_state(pprhip_graph* g, bool clear_flags, int32_t node = -1);  // node: the query's source / target (internal id)
+int ensure_batch(pprhip_graph* P);
+void free_batch(pprhip_graph* P);
+int ensure_bwd_layout(pprhip_graph* P);
+int ensure_panel_part(pprhip_graph* g);  // the buffer of the panel sweep's partial sums (first forward dense level)
+int ensure_workspaces(pprhip_graph* P, int count);  // more workspaces than columns of c8 (batch_driver.hpp: SlotDriver)
+
+// ---- levels.cpp
 double level_cost(const pprhip_graph* g, uint64_t nf, uint64_t ef, bool* dense);
 uint64_t dense_level_bytes(const pprhip_graph* g);
 double dense_sweep_cost(const pprhip_graph* g);
@@ -249,27 +264,23 @@ uint64_t dense_level_min_bytes(const pprhip_graph* g);  // compulsory bytes of o
 uint64_t batch_sweep_min_bytes(const pprhip_graph* P, bool backward, int n_active);  // ... of one batched sweep
 void finish_dense(LevelCtx& L, pprhip_stats_t& st, uint64_t level_bytes, uint64_t min_bytes, uint32_t nf_next,
                   uint64_t ef_next);
+// one single-query dense level, timed as PPRHIP_KERNEL_DENSE_PULL; first_of_phase: the first level since the seeding
+int launch_dense_pull(pprhip_graph* g, const PushArgs& a, int cc, int out, int ds, bool first_of_phase,
+                      const DenseLaunch& dl = DenseLaunch());
 int run_levels(pprhip_graph* g, const PushArgs& a, LevelCtx& L, pprhip_stats_t& st, double* model_cost,
                bool yield_dense = false, RoundCut* cut = nullptr);
-int reset_query_state(pprhip_graph* g, bool clear_flags, int32_t node = -1);  // node: the query's source / target (internal id)
-int ensure_batch(pprhip_graph* P);
-void free_batch(pprhip_graph* P);
-int ensure_bwd_layout(pprhip_graph* P);
-int ensure_panel_part(pprhip_graph* g);  // the buffer of the panel sweep's partial sums (first forward dense level)
 // blocks of the forward Gauss-Seidel sweep for the handle's tuning (nullptr / 1 block when switched off)
 const GsBlock* gs_blocks_of(pprhip_graph* g, int* n_blocks);
 unsigned long long gs_thresh_of(const pprhip_graph* g);
 int seed_single(pprhip_graph* g, LevelCtx& L, int32_t node, uint32_t degree);
 int seed_scan(pprhip_graph* g, const PushArgs& a, int seed_kind, LevelCtx& L);
-int ensure_workspaces(pprhip_graph* P, int count);  // more workspaces than columns of c8 (batch_driver.hpp: SlotDriver)
+
+// ---- device_io.cpp
 // a stream that runs beside g->stream - and beside `also`, when given - (self-tested)
 int make_side_stream(pprhip_graph* g, hipStream_t* out, hipStream_t also = nullptr);
 int fetch_small(pprhip_graph* g, const void* dev, void* host, size_t bytes);  // a few words, without a copy command
 int fetch_begin(pprhip_graph* g, const void* dev, size_t bytes, unsigned long long* seq_out);  // ... in two halves
 int fetch_end(pprhip_graph* g, unsigned long long seq, const void* dev, void* host, size_t bytes);
-int select_launch(pprhip_graph* g, const double* x, int k, unsigned long long* seq_out, bool with_plan_sum = false);
-int select_finish(pprhip_graph* g, unsigned long long seq, const double* x, int k, int32_t* ids_out, double* vals_out,
-                  int cap, int* n_out, double* kth_out, bool* have_kth, pprhip_stats_t& st);
 int device_sum(pprhip_graph* g, const double* x, double* out, uint32_t count = 0);  // count 0: the query's scan bound
 int read_dead_pops(pprhip_graph* g, pprhip_stats_t& st);
 int run_walk_phase(pprhip_graph* g, int variant, double alpha, double rsum, long long nrw, uint64_t seed, uint32_t stream,
@@ -277,6 +288,15 @@ int run_walk_phase(pprhip_graph* g, int variant, double alpha, double rsum, long
 int launch_walk_plan(pprhip_graph* g, int variant, double alpha, double rsum, long long nrw, double* target, double omega_dev,
                      const double* copy_src = nullptr, double* copy_dst = nullptr);
 int launch_walk_run(pprhip_graph* g, int variant, double alpha, uint64_t seed, uint32_t stream, double* target);
+
+// ---- select.cpp
+int select_launch(pprhip_graph* g, const double* x, int k, unsigned long long* seq_out, bool with_plan_sum = false);
+int select_finish(pprhip_graph* g, unsigned long long seq, const double* x, int k, int32_t* ids_out, double* vals_out,
+                  int cap, int* n_out, double* kth_out, bool* have_kth, pprhip_stats_t& st);
+int select_topk(pprhip_graph* g, const double* x, int k, int32_t* ids_out, double* vals_out, int cap, int* n_out,
+                double* kth_out, bool* have_kth, pprhip_stats_t& st, bool with_plan_sum = false);
+
+// ---- engine.cpp
 int copy_out(pprhip_graph* g, const double* dev, double* host);
 int check_graph(const pprhip_graph* g, const char* fn);
 int check_node(const pprhip_graph* g, int32_t v, const char* fn);
@@ -287,8 +307,6 @@ int check_threshold(double v, const char* fn, const char* name);
 int check_conf(const pprhip_fora_conf_t* c, const char* fn, bool topk);
 uint32_t hdeg_out(const pprhip_graph* g, int32_t v);
 uint32_t hdeg_in(const pprhip_graph* g, int32_t v);
-int select_topk(pprhip_graph* g, const double* x, int k, int32_t* ids_out, double* vals_out, int cap, int* n_out,
-                double* kth_out, bool* have_kth, pprhip_stats_t& st, bool with_plan_sum = false);
 
 // per-class kernel totals into a call's stats; the class with the largest total is the dominant one
 inline void fold_class_totals(pprhip_stats_t& st, const double tot[8], const uint64_t bytes[8], const uint32_t cnt[8]) {
@@ -425,8 +443,10 @@ struct BatchJob {
   std::atomic<int> next_query{0};
 };
 
+// ---- batch.cpp
 int batch_run(pprhip_graph_t* g, BatchJob& J, pprhip_stats_t* stats_sum);
 
+// ---- allpair.cpp
 // where the entries of All-Pair's backward searches go: to the host at once, or into an HBM record store that the
 // sharded call partitions by owner of the source and exchanges over RCCL before anything crosses PCIe
 struct TripleSink {
@@ -450,8 +470,8 @@ struct DeviceTripleSink : TripleSink {
 int all_pair_collect(pprhip_graph_t* g, double alpha, double threshold, uint32_t t_begin, uint32_t t_end,
                      TripleSink& sink, pprhip_stats_t& st);
 // Backward_Search.backward_search_whole_graph on the handle's own vectors (internal id); reserve / residue stay in HBM
+// (engine.cpp)
 int backward_search_whole(pprhip_graph_t* g, int32_t target_internal, double alpha, double rmax, pprhip_stats_t& st);
-int ensure_bwd_layout(pprhip_graph* P);
 int index_from_triples(uint32_t n, std::vector<Triple>& tr, int k, pprhip_index_t** out);
 // the same from records in HBM: row order and k rule on the device (kernels_sort.hip), the index arrays downloaded as
 // they are; sources must lie in [v_lo, v_hi)
@@ -488,7 +508,7 @@ struct SeedScope {
   }
 };
 
-// ---- the top-k push session (Forward_Push.forward_push_topk, resumed round after round by Fora_Topk)
+// ---- engine.cpp: the top-k push session (Forward_Push.forward_push_topk, resumed round after round by Fora_Topk)
 // a new session from one source (internal id src; Q = {s} parked) or from a seed table (plan; src is ignored), its
 // residue sum rsum until a round has measured one
 int topk_session_reset(pprhip_graph* g, int32_t src, SeedTable* plan, double alpha, double rsum);

@@ -2217,7 +2217,7 @@ int launch_permute_out(pprhip_graph* g, const double* x, double* out) {
 }
 
 // Current device: code object loaded, large dynamic LDS opted in (above 64 KB it needs an explicit opt-in per
-// device).  Called once per device under the graph-lift lock (engine.cpp), never from a launch path.
+// device).  Called once per device under the graph-lift lock (graph.cpp), never from a launch path.
 int init_kernels_push() {
   PPRHIP_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_dense_edges<true, false>),
                                        hipFuncAttributeMaxDynamicSharedMemorySize, (int)(sizeof(double) * kHotMax)));

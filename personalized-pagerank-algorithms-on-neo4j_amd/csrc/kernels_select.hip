@@ -29,7 +29,7 @@ __global__ __launch_bounds__(256) void k_select_hist(const double* __restrict__ 
   __syncthreads();
   const int shift = 64 - prefix_bits - digit_bits;
   const int lane = lane_id();
-  const uint32_t n4 = (n + 3u) / 4u;  // groups of 4 entries (the array is allocated for n rounded up: engine.cpp)
+  const uint32_t n4 = (n + 3u) / 4u;  // groups of 4 entries (the array is allocated for n rounded up: graph.cpp)
   for (uint32_t g4 = blockIdx.x * blockDim.x + threadIdx.x; g4 - threadIdx.x % 64u < n4; g4 += gridDim.x * blockDim.x) {
     double v[4] = {0.0, 0.0, 0.0, 0.0};
     if (g4 < n4) {

@@ -1,7 +1,7 @@
 // walk_index.cpp — the FORA+ walk index (include/pprhip.h "walk index"; DESIGN.md §2 "Walk index"): per node the
 // terminals of the walks a whole-graph FORA walk phase would draw from it, built once per (alpha, seed) and kept with
 // the lifted graph.  The kernels are in kernels_walk.hip (k_index_build, k_index_serve, k_mc_walk<kWalkIndexed>); the walk
-// phase picks the index in launch_walk_run (engine.cpp).
+// phase picks the index in launch_walk_run (device_io.cpp).
 #include <cmath>
 #include <cstring>
 #include <memory>

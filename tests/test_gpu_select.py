@@ -1,4 +1,4 @@
-"""The top-k radix select (kernels_select.hip, driven by select_finish / select_topk_passes in engine.cpp) past its
+"""The top-k radix select (kernels_select.hip, driven by select_finish / select_topk_passes in select.cpp) past its
 first pass and past its candidate buffer, and the same overflow in the backward search (bwd_step in fora.cpp).
 
 A seed set whose seeds are all dead ends leaves reserve = w / sum(w) and runs no level (seeds.cpp: seed_plan), so on an
@@ -40,8 +40,8 @@ A = 0.15
 EPS = 0.5
 TOL_PUSH = 1e-12  # as tests/test_gpu_parity.py: the engine and the twin differ in fp64 addition order only
 
-SEL_CAP = 1 << 18  # engine.cpp: alloc_workspace, G->sel_cap (records the candidate buffer holds)
-SEL_PRE = 2048     # engine.cpp: kSelPre (records the fast path's one read-back brings along)
+SEL_CAP = 1 << 18  # graph.cpp: alloc_workspace, G->sel_cap (records the candidate buffer holds)
+SEL_PRE = 2048     # select.cpp: kSelPre (records the fast path's one read-back brings along)
 
 N_CLUSTER = (1 << 18) + 8192
 N_HEAD, N_TAIL = 100, 1000
@@ -63,7 +63,7 @@ FAMILY_PATHS = {
 
 # ------------------------------------------------------------------ the path model
 def select_path(p, k):
-    """What select_finish and select_topk_passes (engine.cpp) do with the vector p and k, from their histograms alone:
+    """What select_finish and select_topk_passes (select.cpp) do with the vector p and k, from their histograms alone:
     (path, select_passes, candidates).  path: "empty" (no entry > 0), "fast" / "fast2" (one pass; fast2: more than
     SEL_PRE candidates, fetched by a second copy), "passesNN" (the multi-pass form stopped at pbits = NN with at most
     SEL_CAP candidates), "whole" (it ran to pbits = 64, the gather overflowed and the host finished on the whole
