@@ -290,6 +290,7 @@ void pprhip_lift_destroy(pprhip_lift_t* lift);
 #define PPRHIP_RELEASE_ALL_PAIR 1u
 #define PPRHIP_RELEASE_BATCH 2u
 #define PPRHIP_RELEASE_WALK_INDEX 4u /* the walk index (pprhip_walk_index_build): as pprhip_walk_index_drop */
+#define PPRHIP_RELEASE_SWEEP 8u      /* the sweep cut's workspace (pprhip_sweep_cut: ranks, sort buffers, the profile) */
 int pprhip_graph_release(pprhip_graph_t* g, unsigned what);
 int pprhip_graph_info(const pprhip_graph_t* g, uint32_t* n, uint64_t* m, int* device);
 /* HBM of the handle's device: bytes free and in all (hipMemGetInfo) - what a job holds at a point of its run is
@@ -627,6 +628,50 @@ int pprhip_walk_index_usage(pprhip_graph_t* g, uint64_t* served, uint64_t* walke
  * figures).  Nothing selects them implicitly: the caller sets them (pprhip_graph_set_tuning). */
 void pprhip_tuning_indexed(pprhip_tuning_t* t);
 void pprhip_tuning_indexed_batch(pprhip_tuning_t* t);
+
+/* ---------------------------------------------------------------- local clustering (beyond the reference)
+ * The sweep cut of PageRank-Nibble (Andersen, Chung, Lang) over a PPR vector, on the device: order the support by
+ * x(v) / deg(v) and return the prefix of least conductance - "the cluster around these nodes".  The graph is read as
+ * undirected; every relationship counts once whatever its direction, parallel relationships count each:
+ *   deg(v) = d_out(v) + d_in(v) (a self loop adds 2); vol(S) = sum of deg over S, the total volume is 2m;
+ *   cut(S) = relationships (a -> b), a != b, with exactly one endpoint in S (self loops never cut);
+ *   phi(S) = cut(S) / min(vol(S), 2m - vol(S)), the fp64 quotient of the two integers; a prefix whose denominator is
+ *   0 is not a candidate.
+ * The input x is the result vector currently in HBM - what pprhip_get_reserve returns and pprhip_topk_select reads.
+ * Node v is ranked when x(v) > 0 and deg(v) > 0.  Score: x(v) / (double)deg(v) with normalize = 1, x(v) with
+ * normalize = 0.  Order: score descending, ties by original id ascending; position i is 0-based, prefix i is the
+ * positions 0..i; vol[i] / cut[i] are those of prefix i (64-bit).  Best prefix: the candidate of smallest phi, ties to
+ * the shortest; max_size > 0 admits prefixes of at most max_size nodes (and ends the profile there), max_vol > 0 those
+ * with vol[i] <= max_vol.  Without a candidate: best_size = best_cut = best_vol = 0, best_conductance = +inf.
+ * order_out / vol_out / cut_out receive the first min(cap, profiled) positions (ids are original ids); each may be
+ * NULL, all must be NULL when cap == 0; info is required.  normalize outside {0, 1}, a null info and a buffer with
+ * cap == 0 are PPRHIP_ERR_INVALID, checked before the handle; while a query stream is open: PPRHIP_ERR_STATE.  The
+ * vector is not modified.  The workspace (76 bytes per node) is allocated by the handle's first sweep and kept:
+ * pprhip_graph_release(PPRHIP_RELEASE_SWEEP) and pprhip_graph_destroy free it.  Every sum is an integer: the same
+ * result every run. */
+typedef struct pprhip_sweep {
+  uint64_t support;      /* ranked nodes */
+  uint64_t profiled;     /* prefixes whose vol / cut were computed (== support unless cut short by max_size) */
+  uint64_t best_size, best_cut, best_vol;
+  double best_conductance;
+  uint64_t total_vol;    /* 2m */
+  uint64_t edge_slots;   /* adjacency entries scanned (sum of deg over the profiled nodes) */
+  double sort_ms, scan_ms, total_ms;  /* HIP-event times: support and order (with the count's read-back); the edge
+                                       * scan kernel; the whole sweep up to the best prefix */
+} pprhip_sweep_t;
+
+/* over the vector pprhip_get_reserve would return */
+int pprhip_sweep_cut(pprhip_graph_t* g, int normalize, uint64_t max_size, uint64_t max_vol,
+                     int32_t* order_out, uint64_t* vol_out, uint64_t* cut_out, uint64_t cap, pprhip_sweep_t* info);
+/* the same over vector i of a device-resident store (after pprhip_fora_batch_*_resident / _batch_seeds with keep) */
+int pprhip_results_sweep_cut(pprhip_results_t* r, int i, int normalize, uint64_t max_size, uint64_t max_vol,
+                             int32_t* order_out, uint64_t* vol_out, uint64_t* cut_out, uint64_t cap, pprhip_sweep_t* info);
+/* PageRank-Nibble in one call: pprhip_forward_push_seeds(seeds, weights, alpha, rmax) with its outputs left in HBM,
+ * then the sweep; members_out: the first min(cap, best_size) nodes of the order (the cluster).  alpha, rmax and the seed
+ * set are checked by that call's rules (a bad set leaves the handle untouched); push_stats may be NULL. */
+int pprhip_local_cluster_seeds(pprhip_graph_t* g, const int32_t* seeds, const double* weights, int n_seeds, double alpha,
+                               double rmax, int normalize, uint64_t max_size, uint64_t max_vol, int32_t* members_out,
+                               uint64_t cap, pprhip_sweep_t* info, pprhip_stats_t* push_stats);
 
 /* ---------------------------------------------------------------- ground truth (a12) */
 /* Power_Method.computeWholeGraphPPR (Power_Method.java:44-101): `iters` synchronous sweeps. */

@@ -50,6 +50,16 @@ class Stats(C.Structure):
         return d
 
 
+class Sweep(C.Structure):
+    """pprhip_sweep_t: what a sweep cut found (support, the best prefix, the volume scanned, HIP-event times)."""
+    _fields_ = [("support", C.c_uint64), ("profiled", C.c_uint64), ("best_size", C.c_uint64), ("best_cut", C.c_uint64),
+                ("best_vol", C.c_uint64), ("best_conductance", C.c_double), ("total_vol", C.c_uint64),
+                ("edge_slots", C.c_uint64), ("sort_ms", C.c_double), ("scan_ms", C.c_double), ("total_ms", C.c_double)]
+
+    def as_dict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_}
+
+
 class Tuning(C.Structure):
     _fields_ = [("c_walk_ns", C.c_double), ("c_edge_ns", C.c_double), ("c_pop_ns", C.c_double),
                 ("c_level_ns", C.c_double), ("c_dense_edge_ns", C.c_double), ("c_dense_node_ns", C.c_double),
@@ -88,6 +98,7 @@ EXPORTS = [
     "pprhip_pair_params", "pprhip_walk_survival", "pprhip_ppr_pairs",
     "pprhip_walk_index_density", "pprhip_walk_index_build", "pprhip_walk_index_drop", "pprhip_walk_index_info",
     "pprhip_walk_index_fetch", "pprhip_walk_index_usage", "pprhip_tuning_indexed", "pprhip_tuning_indexed_batch",
+    "pprhip_sweep_cut", "pprhip_results_sweep_cut", "pprhip_local_cluster_seeds",
 ]
 PAIR_WALK_STREAM = 0xFFFF  # PPRHIP_PAIR_WALK_STREAM: the walk stream of every single-pair walk
 COMM_ID_BYTES = 128
@@ -211,6 +222,9 @@ def lib():
     L.pprhip_tuning_indexed.restype = None
     L.pprhip_tuning_indexed_batch.argtypes = [P(Tuning)]
     L.pprhip_tuning_indexed_batch.restype = None
+    L.pprhip_sweep_cut.argtypes = [vp, ci, u64, u64, vp, vp, vp, u64, P(Sweep)]
+    L.pprhip_results_sweep_cut.argtypes = [vp, ci, ci, u64, u64, vp, vp, vp, u64, P(Sweep)]
+    L.pprhip_local_cluster_seeds.argtypes = [vp, vp, vp, ci, dbl, dbl, ci, u64, u64, vp, u64, P(Sweep), P(Stats)]
     _lib = L
     # the destroy entry points, reachable from destructors that run while the interpreter shuts down (the name `lib`
     # may already be None then: "TypeError: 'NoneType' object is not callable" out of Index.__del__, round 3)
@@ -259,6 +273,21 @@ def _seed_set_arrays(sets, weights):
         ws.append(w)
     wv = np.concatenate(ws).astype(np.float64, copy=False) if ws else np.zeros(0)
     return np.ascontiguousarray(seeds), np.ascontiguousarray(wv), offsets
+
+
+def _sweep_call(n, max_size, cap, call):
+    """The output arrays of a sweep cut for `cap` positions (None: everything profiled), the call, the filled parts."""
+    room = n if not max_size else min(n, int(max_size))
+    cap = room if cap is None else min(int(cap), room)
+    order = np.empty(cap, dtype=np.int32) if cap else None
+    vol = np.empty(cap, dtype=np.uint64) if cap else None
+    cut = np.empty(cap, dtype=np.uint64) if cap else None
+    info = Sweep()
+    _check(call(_ptr(order), _ptr(vol), _ptr(cut), cap, C.byref(info)))
+    k = min(cap, info.profiled)
+    if not cap:
+        return np.zeros(0, dtype=np.int32), np.zeros(0, dtype=np.uint64), np.zeros(0, dtype=np.uint64), info
+    return order[:k].copy(), vol[:k].copy(), cut[:k].copy(), info
 
 
 def set_kernel_timing(on):
@@ -656,6 +685,11 @@ class Results:
         _check(lib().pprhip_results_fetch(self.h, i, _ptr(out)))
         return out
 
+    def sweep_cut(self, i, normalize=True, max_size=0, max_vol=0, cap=None):
+        """Graph.sweep_cut over vector i of the store (pprhip_results_sweep_cut)."""
+        return _sweep_call(self.n, max_size, cap, lambda o, v, c, k, info: lib().pprhip_results_sweep_cut(
+            self.h, int(i), int(bool(normalize)), int(max_size), int(max_vol), o, v, c, k, info))
+
     def sum(self, i):
         s = C.c_double()
         _check(lib().pprhip_results_sum(self.h, i, C.byref(s)))
@@ -741,7 +775,7 @@ class Graph:
             _LIVE["graph_destroy"](self.h)
             self.h = None
 
-    RELEASE_ALL_PAIR, RELEASE_BATCH, RELEASE_WALK_INDEX = 1, 2, 4
+    RELEASE_ALL_PAIR, RELEASE_BATCH, RELEASE_WALK_INDEX, RELEASE_SWEEP = 1, 2, 4, 8
 
     def release(self, what):
         """Hands the workspaces of the named entry points back (pprhip_graph_release); they come back on next use."""
@@ -782,6 +816,28 @@ class Graph:
         out = np.empty(self.n)
         _check(lib().pprhip_get_residue(self.h, _ptr(out)))
         return out
+
+    def sweep_cut(self, normalize=True, max_size=0, max_vol=0, cap=None):
+        """The sweep cut over the result vector in HBM (what reserve() returns; pprhip_sweep_cut): the support ordered by
+        x(v) / deg(v) (normalize False: by x(v)), ties by id, and the prefix of least conductance.  Returns (order, vol,
+        cut, Sweep): the first `cap` positions of the order (node ids) with the volume and the cut of every prefix
+        (cap None: everything profiled; 0: the Sweep alone).  max_size / max_vol > 0 bound the prefixes considered."""
+        return _sweep_call(self.n, max_size, cap, lambda o, v, c, k, info: lib().pprhip_sweep_cut(
+            self.h, int(bool(normalize)), int(max_size), int(max_vol), o, v, c, k, info))
+
+    def local_cluster(self, seeds, alpha, rmax, weights=None, normalize=True, max_size=0, max_vol=0, cap=None):
+        """PageRank-Nibble (pprhip_local_cluster_seeds): forward_push_seeds(seeds, alpha, rmax, weights) left in HBM,
+        then sweep_cut.  Returns (members, Sweep, Stats): the nodes of the best prefix, at most `cap` of them."""
+        s, w = _seed_arrays(seeds, weights)
+        room = self.n if not max_size else min(self.n, int(max_size))
+        cap = room if cap is None else min(int(cap), room)
+        members = np.empty(cap, dtype=np.int32) if cap else None
+        info, st = Sweep(), Stats()
+        _check(lib().pprhip_local_cluster_seeds(self.h, _ptr(s), _ptr(w), s.size, alpha, rmax, int(bool(normalize)),
+                                                int(max_size), int(max_vol), _ptr(members), cap, C.byref(info),
+                                                C.byref(st)))
+        k = min(cap, info.best_size)
+        return (members[:k].copy() if cap else np.zeros(0, dtype=np.int32)), info, st
 
     def forward_push(self, src, alpha, rmax, fetch=True):
         reserve = np.empty(self.n) if fetch else None

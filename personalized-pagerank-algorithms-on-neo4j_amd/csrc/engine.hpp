@@ -352,6 +352,30 @@ struct WalkShare : TerminalTable {  // (usage: [2] walks served from the cache /
   bool on = false;               // the queries in flight may use it (walk phases of its seed and alpha)
 };
 
+// Workspace of the sweep cut (sweep.cpp, kernels_sweep.hip; DESIGN.md §2 "Sweep cut"): allocated by the handle's first
+// sweep for all n nodes, kept until pprhip_graph_release(PPRHIP_RELEASE_SWEEP) or the handle's end.
+constexpr uint32_t kSweepTile = 4096;        // adjacency slots one workgroup turn of the edge scan covers
+constexpr uint32_t kSweepBestBlocks = 1024;  // partial minima of the best-prefix reduction
+constexpr int kSweepHdrWords = 8;            // [0] support, [1] best_size, [2] best_cut, [3] best_vol, [4] phi bits, [5] edge slots
+struct SweepWs {
+  unsigned long long* key[2] = {nullptr, nullptr};  // [n] sort keys (inverted score bits), double-buffered
+  uint32_t* id[2] = {nullptr, nullptr};             // [n] original ids riding along
+  const uint32_t* order = nullptr;                  // the id buffer that holds the order after the sorts
+  uint32_t* rank = nullptr;                         // [n] internal id -> position; 0xFFFFFFFF: none
+  uint4* rec = nullptr;                             // [n] per position: internal id, out-row begin, out-degree, in-row begin
+  unsigned long long* deg = nullptr;                // [n] per position
+  unsigned long long* volx = nullptr;               // [n + 1] exclusive vol: volx[i + 1] = vol[i]
+  uint32_t* tile_node = nullptr;                    // [tile_cap] first position of every tile of the slot space
+  size_t tile_cap = 0;
+  long long* delta = nullptr;                       // [n] per position
+  unsigned long long* cut = nullptr;                // [n]
+  double* part_phi = nullptr;                       // [kSweepBestBlocks]
+  unsigned long long* part_idx = nullptr;
+  unsigned long long* hdr = nullptr;                // [kSweepHdrWords]
+  void* tmp = nullptr;                              // scratch of the library sorts and scans
+  size_t tmp_bytes = 0;
+};
+
 struct WalkPlanRec {  // one residue entry of a walk phase (k_mc_plan -> k_mc_walk): 32 bytes
   unsigned long long woff;  // walks of the entries before it
   double inc;               // what each of its walks adds at its terminal
@@ -557,6 +581,7 @@ struct pprhip_graph {
   // seed-set query in progress (seeds.cpp: SeedScope): dead-end mass lands on the seed table, PushArgs::src is -1
   pprhip::SeedTable* seeds = nullptr;
   bool seed_on = false;
+  pprhip::SweepWs* sweep = nullptr;  // the sweep cut's workspace, or none (sweep.cpp)
 };
 
 namespace pprhip {
@@ -719,6 +744,14 @@ int finalize_rows_device(pprhip_graph* g, const TripleRec* rec, unsigned long lo
                          uint32_t v_hi, DeviceRows* out);
 void device_rows_free(DeviceRows* r);
 int init_kernels_sort();
+
+// ---- kernels_sweep.hip (the steps of a sweep cut, in launch order; sweep.cpp drives them)
+int launch_sweep_support(pprhip_graph* g, SweepWs* w, const double* x, int normalize);  // count -> w->hdr[0]
+int launch_sweep_sort(pprhip_graph* g, SweepWs* w, uint32_t count);
+int launch_sweep_rank(pprhip_graph* g, SweepWs* w, uint32_t profiled);
+int launch_sweep_edges(pprhip_graph* g, SweepWs* w, uint32_t profiled, hipEvent_t before, hipEvent_t after);
+int launch_sweep_best(pprhip_graph* g, SweepWs* w, uint32_t profiled, uint64_t max_vol);
+int init_kernels_sweep();
 
 // ---- kernels_select.hip
 int launch_select_hist(pprhip_graph* g, const double* x, uint32_t n, unsigned long long prefix, int prefix_bits,

@@ -1,6 +1,6 @@
 // engine_internal.hpp — declarations shared by the engine's translation units (engine.cpp: single-query
 // entry points; graph.cpp: graph lifecycle and workspaces; levels.cpp: level loop; select.cpp: top-k selection;
-// device_io.cpp: read-backs, scopes, walk launchers; fora.cpp: resumable FORA / top-k / backward runs;
+// device_io.cpp: read-backs, scopes, walk launchers; fora.cpp: resumable FORA / top-k / backward runs; sweep.cpp: sweep cut;
 // batch.cpp, batch_api.cpp, fetch_pipe.cpp, stream.cpp: the batched entry points; allpair.cpp:
 // All-Pair-Backward-Search and the inverted index).
 #pragma once
@@ -242,6 +242,9 @@ void free_walk_index(GraphData* D);  // the lifted graph's walk index, if it has
 // the call-scoped terminal cache of the batched whole-graph FORA paths (engine.hpp: WalkShare)
 void walk_share_begin(pprhip_graph* P, int q, double alpha, double rmax, double omega, uint64_t seed);
 void free_walk_share(BatchState* B);
+
+// ---- sweep.cpp
+void free_sweep(pprhip_graph* g);  // the handle's sweep-cut workspace, if it has one
 
 // ---- stream.cpp
 void stream_detach(void* stream_obj);  // ends a query stream's driver before its graph goes
