@@ -607,7 +607,7 @@ int all_pair_sharded(pprhip_comm* c, double alpha, double threshold, int k, pprh
   }
   pprhip_stats_t st;
   std::memset(&st, 0, sizeof st);
-  DeviceTripleSink sink;
+  TripleStore sink;
   unsigned long long* d_cur = nullptr;
   TripleRec* d_part = nullptr;
   void* d_recv = nullptr;

@@ -3,8 +3,8 @@
 // parameter checks every entry point runs and the top-k push session.  Everything numerical runs in the HIP kernels;
 // the host only sequences launches on the handle's stream.  The handle's lifecycle lives in graph.cpp, the level loop
 // in levels.cpp, the selection driver in select.cpp, read-backs and walk launchers in device_io.cpp, FORA runs in
-// fora.cpp, the batched entry points in batch.cpp, batch_api.cpp and stream.cpp, All-Pair and the index in
-// allpair.cpp (shared declarations: engine_internal.hpp).
+// fora.cpp, the batched entry points in batch.cpp, batch_api.cpp and stream.cpp, All-Pair in allpair.cpp and its
+// index in index.cpp (shared declarations: engine_internal.hpp).
 #include <algorithm>
 #include <cmath>
 #include <cstring>

@@ -479,6 +479,13 @@ struct BatchState {
   WalkShare* share = nullptr;  // terminals the queries of a call share, or none (allocated by the first call that uses it)
 };
 
+// A set of All-Pair dense workspaces (allpair.cpp: ensure_apbs_workspace): `blocks` of them in one allocation, their
+// lists sized for cap_t popped nodes and a frontier of cap_f; blocks == 0: not there
+struct ApbsWorkspace {
+  char* ws = nullptr;
+  uint32_t blocks = 0, cap_t = 0, cap_f = 0;
+};
+
 }  // namespace pprhip
 
 // A graph handle or one of its batch slots: the per-query workspace, the stream it runs on, and the lifted graph it
@@ -515,15 +522,14 @@ struct pprhip_graph {
   hipEvent_t walk_ev[3] = {nullptr, nullptr, nullptr};  // slot: the events around its walk phase on the walk stream
   pprhip::KernelTimer ktimer;  // kernel-class timer of this workspace's work (a slot's worker; a handle's batched sweeps)
   // All-Pair: in-edge records {source, its out-degree} (8 B per edge, built on first use), and tier 2's dense
-  // workspaces of apbs_blocks workgroups (16n bytes + lists each, all-zero between searches), kept between calls
+  // workspaces (16n bytes + lists per workgroup, all-zero between searches), kept between calls: apbs_dense for the
+  // workgroups in flight, apbs_xl a few whose lists hold every node, for the searches that outgrow the others
   void* in_rec = nullptr;
-  char* apbs_ws = nullptr;
+  pprhip::ApbsWorkspace apbs_dense, apbs_xl;
   void* apbs_board = nullptr;
+  uint32_t apbs_chunk = 0;
   void* ix_stage = nullptr;  // pinned ring the index arrays are downloaded through (index_from_device)
   size_t ix_stage_bytes = 0;
-  char* apbs_xl_ws = nullptr;  // a few workspaces whose lists hold every node, for the searches that outgrow the others
-  uint32_t apbs_xl_blocks = 0, apbs_xl_cap_t = 0, apbs_xl_cap_f = 0;
-  uint32_t apbs_blocks = 0, apbs_cap_t = 0, apbs_cap_f = 0, apbs_chunk = 0;
   uint32_t n_act = 0;    // scan bound of the query this workspace is running (0: n; GraphData::n_live)
   uint32_t n_dirty = 0;  // ... of the query before it (what the reset has to clear)
   // per-query state
@@ -702,19 +708,34 @@ struct TripleRec {  // one index entry of All-Pair-Backward-Search on the device
   int32_t v, t;
   double p;
 };
+// the control words of one All-Pair launch: 16 words in one allocation (ApbsBuffers::cells), written whole before the
+// launch and read back whole after it
+enum ApbsCell {
+  kApNextTarget = 0,     // target cursor of the large table / the dense tier
+  kApOutCount = 1,       // entries the searches wanted to write
+  kApOutValid = 2,       // entries below this position are complete (starts at ~0)
+  kApOverflowCount = 3,  // length of the list of targets for another pass or the next tier
+  kApPops = 4,
+  kApEdges = 5,
+  kApListLen = 6,        // tier 1 over a range: length of the list of targets with in-edges
+  kApSmallCursor = 7,    // ... the small table's target cursor
+  kApTargetsDone = 8,    // dense tier: targets finished in this launch
+  kApLevelsPosted = 9,   // ... levels that are posted for helpers right now
+  kApAbort = 10,         // ... set by a workgroup that waited too long: the launch ends
+  kApGiveUpLen = 11,     // tier 1 over a range: length of the small table's give-up list
+  kApCells = 16
+};
 struct ApbsBuffers {
-  unsigned long long *next_target = nullptr, *out_count = nullptr, *out_valid = nullptr, *overflow_count = nullptr;
-  unsigned long long *stat_pops = nullptr, *stat_edges = nullptr;
+  unsigned long long* cells = nullptr;  // kApCells control words, indexed by ApbsCell
   TripleRec* out_rec = nullptr;  // the searches' entries >= threshold, 16-byte records
   int32_t* overflow = nullptr;
   int32_t *list0 = nullptr, *list1 = nullptr;  // tier 1 over a range: the non-trivial targets, the small table's give-ups
   unsigned long long out_cap = 0;
-  char* ws = nullptr;  // tier 2: per-workgroup dense workspaces (owned by the graph handle, see apbs_ws)
+  char* ws = nullptr;  // tier 2: per-workgroup dense workspaces (owned by the graph handle, see ApbsWorkspace)
   void* board = nullptr;  // tier 2: one entry per workgroup on which it posts a level for helpers (zero at launch)
-  unsigned long long* done_targets = nullptr;  // tier 2: targets finished in this launch
   uint32_t ws_blocks = 0, cap_t = 0, cap_f = 0, chunk = 0;
   uint32_t helpers = 0;  // tier 2: workgroups a launch may use in all (those beyond ws_blocks only help)
-  unsigned long long* dbg = nullptr;  // developer switch PPRHIP_APBS_DEBUG: 10 words per workgroup (kernels_apbs.hip)
+  unsigned long long* dbg = nullptr;  // developer switch PPRHIP_APBS_DEBUG: 12 words per workgroup (kernels_apbs.hip)
 };
 int launch_owner_partition(pprhip_graph* g, const TripleRec* rec, unsigned long long count, int world,
                            unsigned long long* cursors, TripleRec* out);

@@ -2,7 +2,7 @@
 // entry points; graph.cpp: graph lifecycle and workspaces; levels.cpp: level loop; select.cpp: top-k selection;
 // device_io.cpp: read-backs, scopes, walk launchers; fora.cpp: resumable FORA / top-k / backward runs; sweep.cpp: sweep cut;
 // batch.cpp, batch_api.cpp, fetch_pipe.cpp, stream.cpp: the batched entry points; allpair.cpp:
-// All-Pair-Backward-Search and the inverted index).
+// All-Pair-Backward-Search; index.cpp: its inverted index).
 #pragma once
 
 #include <sys/mman.h>
@@ -450,37 +450,32 @@ struct BatchJob {
 int batch_run(pprhip_graph_t* g, BatchJob& J, pprhip_stats_t* stats_sum);
 
 // ---- allpair.cpp
-// where the entries of All-Pair's backward searches go: to the host at once, or into an HBM record store that the
-// sharded call partitions by owner of the source and exchanges over RCCL before anything crosses PCIe
-struct TripleSink {
-  virtual ~TripleSink() = default;
-  virtual int take_device(pprhip_graph* g, const TripleRec* d_rec, unsigned long long count) = 0;
-  virtual int take_host(pprhip_graph* g, std::vector<Triple>& more) = 0;
-};
-struct HostTripleSink : TripleSink {
-  std::vector<Triple> tr;
-  int take_device(pprhip_graph* g, const TripleRec* d_rec, unsigned long long count) override;
-  int take_host(pprhip_graph* g, std::vector<Triple>& more) override;
-};
-struct DeviceTripleSink : TripleSink {
+// where the entries of All-Pair's backward searches go: an HBM record store, which the single-GPU call hands to the index
+// finalisation and the sharded call partitions by owner of the source and exchanges over RCCL before anything crosses PCIe
+struct TripleStore {
   TripleRec* rec = nullptr;
   unsigned long long count = 0, cap = 0;
-  ~DeviceTripleSink() override;
+  ~TripleStore();
   int reserve(pprhip_graph* g, unsigned long long extra);
-  int take_device(pprhip_graph* g, const TripleRec* d_rec, unsigned long long count) override;
-  int take_host(pprhip_graph* g, std::vector<Triple>& more) override;
+  int take_device(pprhip_graph* g, const TripleRec* d_rec, unsigned long long count);
+  int take_host(pprhip_graph* g, std::vector<Triple>& more);
 };
+// the searches of the targets [t_begin, t_end), tier by tier; their entries >= threshold are added to `store`
 int all_pair_collect(pprhip_graph_t* g, double alpha, double threshold, uint32_t t_begin, uint32_t t_end,
-                     TripleSink& sink, pprhip_stats_t& st);
+                     TripleStore& store, pprhip_stats_t& st);
 // Backward_Search.backward_search_whole_graph on the handle's own vectors (internal id); reserve / residue stay in HBM
 // (engine.cpp)
 int backward_search_whole(pprhip_graph_t* g, int32_t target_internal, double alpha, double rmax, pprhip_stats_t& st);
+
+// ---- index.cpp
+// the index over all n sources from entries on the host: bucketed by source, row order and k rule on the host's threads
 int index_from_triples(uint32_t n, std::vector<Triple>& tr, int k, pprhip_index_t** out);
 // the same from records in HBM: row order and k rule on the device (kernels_sort.hip), the index arrays downloaded as
 // they are; sources must lie in [v_lo, v_hi)
 int index_from_device(pprhip_graph* g, const TripleRec* rec, unsigned long long count, int k, uint32_t v_lo, uint32_t v_hi,
                       pprhip_index_t** out);
 int index_concat(const std::vector<pprhip_index_t*>& parts, pprhip_index_t** out);
+int ensure_ring(pprhip_graph* g);  // the pinned ring index_from_device downloads through (g->ix_stage), on first use
 
 // ---- seed sets (seeds.cpp)
 // the caller's seeds / weights (NULL: uniform) / count as p: distinct original ids ascending and their normalized

@@ -538,12 +538,11 @@ static void free_graph_data(GraphData* D) {
 }
 
 static void free_all_pair(pprhip_graph* g) {
-  void** ptrs[] = {(void**)&g->apbs_ws, (void**)&g->apbs_board, (void**)&g->apbs_xl_ws, (void**)&g->in_rec};
-  for (void** p : ptrs) {
-    if (*p) (void)hipFree(*p);
-    *p = nullptr;
-  }
-  g->apbs_blocks = 0;  // (all_pair_collect sizes and allocates the workspaces when it finds none)
+  void* ptrs[] = {g->apbs_dense.ws, g->apbs_xl.ws, g->apbs_board, g->in_rec};
+  for (void* p : ptrs)
+    if (p) (void)hipFree(p);
+  g->apbs_dense = g->apbs_xl = pprhip::ApbsWorkspace{};  // (allpair.cpp sizes and allocates the workspaces it does not find)
+  g->apbs_board = g->in_rec = nullptr;
   if (g->ix_stage) (void)hipHostFree(g->ix_stage);
   g->ix_stage = nullptr;
   g->ix_stage_bytes = 0;

@@ -1357,11 +1357,12 @@ int launch_build_in_rec(pprhip_graph* g, void* rec) {
 
 int launch_apbs(pprhip_graph* g, bool dense_tier, const int32_t* d_targets, uint32_t t_begin, uint32_t n_targets,
                 double alpha, double rmax, ApbsBuffers& b) {
-  const ApOut O{b.out_rec, b.out_cap, b.out_count, b.out_valid, b.overflow, b.overflow_count,
-                b.stat_pops, b.stat_edges};
+  unsigned long long* const cells = b.cells;
+  const ApOut O{b.out_rec, b.out_cap, cells + kApOutCount, cells + kApOutValid, b.overflow, cells + kApOverflowCount,
+                cells + kApPops, cells + kApEdges};
   const InRec* rec = (const InRec*)g->in_rec;
   if (dense_tier) {
-    if (!d_targets || !b.ws || !b.ws_blocks || !b.board || !b.done_targets || !b.chunk) {
+    if (!d_targets || !b.ws || !b.ws_blocks || !b.board || !b.chunk) {
       set_error("All-Pair dense tier: no target list or workspace");
       return PPRHIP_ERR_STATE;
     }
@@ -1383,14 +1384,12 @@ int launch_apbs(pprhip_graph* g, bool dense_tier, const int32_t* d_targets, uint
     const char* hb = hook_env("PPRHIP_APBS_HELP_BETWEEN");
     const int help_between = hb ? (hb[0] != '0') : (n_targets < (1u << 17));
     k_apbs_dense<<<dim3(grid), dim3(kDnThreads), 2 * sizeof(double) * (size_t)hot_n, g->stream>>>(
-        d_targets, n_targets, b.next_target, g->gr->in_rp, rec, g->gr->old2new, g->gr->new2old, alpha, rmax, O, b.ws, (DnBoard*)b.board,
-        b.done_targets, b.done_targets + 1, b.done_targets + 2, dims_of(g->gr->n, (unsigned long long)g->gr->m, b.cap_t, b.cap_f, b.chunk), share,
-        owners, hot_n, help_between, b.dbg);
+        d_targets, n_targets, cells + kApNextTarget, g->gr->in_rp, rec, g->gr->old2new, g->gr->new2old, alpha, rmax, O, b.ws,
+        (DnBoard*)b.board, cells + kApTargetsDone, cells + kApLevelsPosted, cells + kApAbort,
+        dims_of(g->gr->n, (unsigned long long)g->gr->m, b.cap_t, b.cap_f, b.chunk), share, owners, hot_n, help_between, b.dbg);
   } else if (!d_targets && b.list0 && b.list1) {
     // a range, in three steps on the device: trivial targets and the list of the others; the small table; the large
-    // table for what the small one gave up (cells: +6 the list's length, +7 the small table's target cursor, +11 the
-    // length of its give-up list; b.next_target is the large table's cursor)
-    unsigned long long* cells = b.next_target;
+    // table for what the small one gave up
     const uint32_t sgrid = (uint32_t)std::min<uint64_t>(((uint64_t)n_targets + 255) / 256, 2048);
     // (PPRHIP_APBS_DEG=big,dense: the in-degrees from which a search starts in the large table / in the dense tier -
     // developer and test switch; "0,0" sends everything through both tables as before round 4)
@@ -1404,23 +1403,24 @@ int launch_apbs(pprhip_graph* g, bool dense_tier, const int32_t* d_targets, uint
         deg_dense = c ? std::max(c, a) : 0xFFFFFFFFu;
       }
     }
-    k_apbs_split<<<dim3(sgrid), dim3(256), 0, g->stream>>>(t_begin, n_targets, g->gr->in_rp, g->gr->old2new, rmax, O, b.list0, cells + 6,
-                                                           b.list1, cells + 11, deg_big, deg_dense);
+    k_apbs_split<<<dim3(sgrid), dim3(256), 0, g->stream>>>(t_begin, n_targets, g->gr->in_rp, g->gr->old2new, rmax, O, b.list0,
+                                                           cells + kApListLen, b.list1, cells + kApGiveUpLen, deg_big, deg_dense);
     PPRHIP_CHECK_HIP(hipGetLastError());
     ApOut O0 = O;  // the small table's give-ups (and retries) go to the second list
     O0.overflow_list = b.list1;
-    O0.overflow_count = cells + 11;
+    O0.overflow_count = cells + kApGiveUpLen;
     const uint32_t grid0 = std::min<uint32_t>((uint32_t)g->gr->n_cus * 8u, std::max(1u, n_targets));
     k_apbs_lds<kApSmallCap, kApSmallFront, kApSmallThreads><<<dim3(grid0), dim3(kApSmallThreads), 0, g->stream>>>(
-        b.list0, 0u, 0u, cells + 6, cells + 7, g->gr->in_rp, rec, g->gr->old2new, g->gr->new2old, alpha, rmax, O0);
+        b.list0, 0u, 0u, cells + kApListLen, cells + kApSmallCursor, g->gr->in_rp, rec, g->gr->old2new, g->gr->new2old, alpha, rmax, O0);
     PPRHIP_CHECK_HIP(hipGetLastError());
     const uint32_t grid1 = std::min<uint32_t>((uint32_t)g->gr->n_cus * 2u, std::max(1u, n_targets));
     k_apbs_lds<kApLdsCap, kApFront, 256><<<dim3(grid1), dim3(256), 0, g->stream>>>(
-        b.list1, 0u, 0u, cells + 11, b.next_target, g->gr->in_rp, rec, g->gr->old2new, g->gr->new2old, alpha, rmax, O);
+        b.list1, 0u, 0u, cells + kApGiveUpLen, cells + kApNextTarget, g->gr->in_rp, rec, g->gr->old2new, g->gr->new2old, alpha, rmax,
+        O);
   } else {
     const uint32_t grid = std::min<uint32_t>((uint32_t)g->gr->n_cus * 2u, std::max(1u, n_targets));
-    k_apbs_lds<kApLdsCap, kApFront, 256><<<dim3(grid), dim3(256), 0, g->stream>>>(d_targets, t_begin, n_targets, nullptr, b.next_target,
-                                                                             g->gr->in_rp, rec, g->gr->old2new, g->gr->new2old, alpha, rmax, O);
+    k_apbs_lds<kApLdsCap, kApFront, 256><<<dim3(grid), dim3(256), 0, g->stream>>>(d_targets, t_begin, n_targets, nullptr,
+                                                                             cells + kApNextTarget, g->gr->in_rp, rec, g->gr->old2new, g->gr->new2old, alpha, rmax, O);
   }
   PPRHIP_CHECK_HIP(hipGetLastError());
   return PPRHIP_OK;

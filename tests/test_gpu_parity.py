@@ -688,6 +688,26 @@ def test_released_workspaces_come_back(pkg, rmat12):
             g.release(64)
 
 
+def test_released_full_size_workspaces_come_back(pkg, orc, rmat12, monkeypatch):
+    """pprhip_graph_release also takes the few full-size workspaces ("xl") that searches get which outgrow the dense
+    tier's lists; the next call that needs them notices, allocates them again and returns what it returned before."""
+    monkeypatch.setenv("PPRHIP_APBS_TIER", "2")
+    monkeypatch.setenv("PPRHIP_APBS_CAP_T", "4096")
+    monkeypatch.setenv("PPRHIP_APBS_CAP_F", "3")
+    monkeypatch.setenv("PPRHIP_APBS_WHOLE", "0")
+    ooff, otg, ovl = to_oracle(orc, rmat12).all_pair_backward(ALPHA, 5e-4, 6, 100, 400, schedule=orc.SYNC)
+    with pkg.Graph(rmat12) as g:
+        for call in range(2):
+            ix, st = g.all_pair_backward(ALPHA, 5e-4, 6, 100, 400)
+            off, tg, vl = ix.arrays()
+            assert st.xl_targets > 0 and st.dense_nodes == 0    # the full-size pass ran and left nothing for tier 3
+            assert np.array_equal(off, ooff) and np.array_equal(tg, otg)
+            assert np.max(np.abs(vl - ovl)) <= TOL_PUSH
+            ix.close()
+            if call == 0:
+                g.release(g.RELEASE_ALL_PAIR)
+
+
 def test_batch_directions_share_a_handle(pkg, orc, rmat12, dev_rmat12, monkeypatch):
     """Forward batches and batched backward searches (All-Pair tier 3) alternate on one handle: the shared sweep
     arrays are handed over clean in both directions."""

@@ -174,7 +174,7 @@ def test_tuning_defaults_match_oracle_twin(pkg, orc):
 
 def test_index_arrays_are_validated(pkg):
     """Targets outside [0, n) are an error at the boundary, not an out-of-range write later (the same check guards
-    the entries that arrive from the device and from the exchange, allpair.cpp: index_from_triples)."""
+    the entries that arrive from the device and from the exchange, index.cpp: index_from_triples)."""
     off = np.array([0, 1, 2], dtype=np.uint64)
     with pytest.raises(pkg.PprhipError):
         pkg.index_from_arrays(2, off, np.array([0, 2], dtype=np.int32), np.array([0.5, 0.5]))
