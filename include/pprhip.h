@@ -581,6 +581,46 @@ int pprhip_ppr_pairs(pprhip_graph_t* g, const int32_t* sources, const int32_t* t
                      const pprhip_fora_conf_t* conf, double rmax, uint64_t seed, double* values_out,
                      pprhip_stats_t* stats_sum);
 
+/* ---------------------------------------------------------------- single targets (beyond the reference)
+ * The other direction as a query: which sources s rank a target t highly ("who reaches t": reverse recommendation,
+ * audience, influence), for many targets and weighted target sets per call.  For a target set T with weights w (finite
+ * values >= 0, NOT normalized; weights NULL: every w_t = 1, so that pi(s, T) is the probability that the walk from s
+ * ends in T):
+ *     value(s) ~ pi(s, T) = sum_t w_t pi(s, t)            for every source s,
+ * with pi the engine's restarting PPR - the pi of pprhip_power_method, FORA and the pair call.  Estimator: a backward
+ * push at threshold rmax from r = w (duplicates in a set summed, zero weights dropped), by the backward kernels and the
+ * push test of pprhip_backward_push under the handle's tuning (pprhip_graph_set_tuning); then
+ *     value(s) = p(s) / S(s),   S = pprhip_walk_survival(alpha)
+ * (p the push's reserve; DESIGN.md §2 "Single targets").  A member whose weight does not pass the push test (w <= rmax)
+ * starts as residue; a member without in-edges has nobody to push to and takes p = alpha * w at once.  A single target
+ * (a set of one with weight 1) starts exactly as the pair call's push: r(t) = 1 and t is popped, also without in-edges
+ * (p(t) = alpha, no residue - not Backward_Search.java:46-49's reserve(t) = 1).  So for a target with in-edges
+ * value * S equals pprhip_backward_push's reserve under the same tuning, up to fp64 addition order.
+ * Guarantee: the push invariant pi'(s, t) = p_t(s) + sum_v pi'(s, v) r_t(v) of the leaking PPR pi' is linear in the
+ * start, after the push every residue is at most rmax, and sum_v pi'(s, v) = S(s); dividing by S(s):
+ *     0 <= pi(s, T) - value(s) <= rmax       for every s.
+ * The bound is deterministic: no walks, no seed.  A caller who wants relative error eps on values >= delta passes
+ * rmax = eps * delta.  Top-k ranks by the lower bound `value`: it is not an exact top-k of pi (two sources whose
+ * values differ by less than rmax may be swapped).
+ * Checks, in this order and before any device work (PPRHIP_ERR_INVALID, the handle and a result on it untouched):
+ * alpha ("Parameter ranges"), rmax finite with 0 < rmax <= 1; then q >= 0, k >= 0 and the buffers k asks for, the
+ * store, offsets[0] == 0 and non-decreasing offsets; then per set, by the seed-set rules, with the set named in the
+ * message (", set i: "): at least one member, every id in [0, n), every weight finite and >= 0, a weight sum > 0.
+ * q == 0 is an empty call; while a query stream is open: PPRHIP_ERR_STATE.  After the call pprhip_get_reserve /
+ * _get_residue are undefined, as after a pair call. */
+/* q target sets described like the seed sets of pprhip_fora_batch_seeds: set i = targets / weights [offsets[i],
+ * offsets[i + 1]); offsets NULL: q single targets, set i = {targets[i]} (weights NULL or q of them).  Up to
+ * PPRHIP_BATCH sets are in flight on the handle's batch workspaces, their dense levels sharing the batched sweeps.
+ * keep / values_out (q*n, query-major, original ids) / k / ids_out / vals_out / n_out / per_query / stats_sum as in
+ * pprhip_fora_batch_single_source_resident; the top-k is selected over the scaled vector `value` by Algo_Util.kth_ppr's
+ * rule (rows padded with -1 / 0; n_out may exceed k on ties).  Stats: the push counters (pops, edge_pushes, levels,
+ * dense_levels), push_ms (host wall time of a set's push on its workspace, shared sweeps included; summed over sets in
+ * stats_sum: they overlap), rmax_final = rmax and rounds = 1 per set; no walk field is set. */
+int pprhip_ppr_targets(pprhip_graph_t* g, const int32_t* targets, const double* weights,
+                       const uint64_t* offsets /* q+1, or NULL: q single targets */, int q, double alpha, double rmax,
+                       pprhip_results_t* keep, double* values_out /* q*n or NULL */, int k, int32_t* ids_out,
+                       double* vals_out, int* n_out, pprhip_stats_t* per_query, pprhip_stats_t* stats_sum);
+
 /* ---------------------------------------------------------------- walk index (FORA+; beyond the reference)
  * FORA as published has a second form, FORA+: the terminals of walks drawn once are kept per node and a query reads
  * them instead of walking.  Here walk (seed, stream, start, walk_idx) is a pure function and every whole-graph FORA

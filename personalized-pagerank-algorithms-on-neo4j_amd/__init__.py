@@ -95,7 +95,7 @@ EXPORTS = [
     "pprhip_fora_stream_open", "pprhip_fora_stream_submit", "pprhip_fora_stream_wait", "pprhip_fora_stream_close",
     "pprhip_set_kernel_timing", "pprhip_shard_target_cuts", "pprhip_forward_push_seeds", "pprhip_fora_seeds",
     "pprhip_fora_topk_seeds", "pprhip_fora_batch_seeds", "pprhip_fora_batch_topk_seeds",
-    "pprhip_pair_params", "pprhip_walk_survival", "pprhip_ppr_pairs",
+    "pprhip_pair_params", "pprhip_walk_survival", "pprhip_ppr_pairs", "pprhip_ppr_targets",
     "pprhip_walk_index_density", "pprhip_walk_index_build", "pprhip_walk_index_drop", "pprhip_walk_index_info",
     "pprhip_walk_index_fetch", "pprhip_walk_index_usage", "pprhip_tuning_indexed", "pprhip_tuning_indexed_batch",
     "pprhip_sweep_cut", "pprhip_results_sweep_cut", "pprhip_local_cluster_seeds",
@@ -212,6 +212,7 @@ def lib():
     L.pprhip_pair_params.argtypes = [P(ForaConf), dbl, dbl, P(dbl), P(u64)]
     L.pprhip_walk_survival.argtypes = [vp, dbl, vp]
     L.pprhip_ppr_pairs.argtypes = [vp, vp, vp, ci, dbl, P(ForaConf), dbl, u64, vp, P(Stats)]
+    L.pprhip_ppr_targets.argtypes = [vp, vp, vp, vp, ci, dbl, dbl, vp, vp, ci, vp, vp, vp, vp, P(Stats)]
     L.pprhip_walk_index_density.argtypes = [P(ForaConf), dbl, dbl, P(dbl)]
     L.pprhip_walk_index_build.argtypes = [vp, dbl, u64, dbl, P(Stats)]
     L.pprhip_walk_index_drop.argtypes = [vp]
@@ -1062,6 +1063,32 @@ class Graph:
         _check(lib().pprhip_ppr_pairs(self.h, _ptr(s), _ptr(t), s.size, eps, C.byref(conf), rmax, seed, _ptr(out),
                                       C.byref(st)))
         return out, st
+
+    def _ppr_targets(self, t, w, offsets, q, alpha, rmax, k, keep, fetch):
+        values = np.empty((q, self.n)) if fetch else None
+        ids = np.empty((q, k), dtype=np.int32) if k > 0 else None
+        vals = np.empty((q, k)) if k > 0 else None
+        nsel = np.zeros(q, dtype=np.int32) if k > 0 else None
+        pq = (Stats * q)() if q else None
+        st = Stats()
+        _check(lib().pprhip_ppr_targets(
+            self.h, _ptr(t), _ptr(w), _ptr(offsets), q, alpha, rmax, keep.h if keep is not None else None, _ptr(values),
+            k, _ptr(ids), _ptr(vals), _ptr(nsel), C.cast(pq, C.c_void_p) if pq is not None else None, C.byref(st)))
+        return values, ((ids, vals, nsel) if k > 0 else None), st, (list(pq) if pq is not None else [])
+
+    def ppr_targets(self, targets, alpha, rmax, k=0, keep=None, fetch=True):
+        """Single-target PPR (pprhip_ppr_targets): for every target t the vector value(s) <= pi(s, t) <= value(s) + rmax
+        over all sources s.  Returns (values[q, n] | None, (ids[q, k], vals[q, k], n_sel[q]) | None, summed Stats,
+        per-query Stats list).  keep: a Results store that receives every target's vector (device-resident)."""
+        t = np.ascontiguousarray(np.atleast_1d(targets), dtype=np.int32).ravel()
+        return self._ppr_targets(t, None, None, int(t.size), alpha, rmax, k, keep, fetch)
+
+    def ppr_target_sets(self, sets, alpha, rmax, weights=None, k=0, keep=None, fetch=True):
+        """ppr_targets over weighted target sets: query i is pi(s, sets[i]) = sum_t w_t pi(s, t), the weights NOT
+        normalized (None: 1 each, the probability that the walk from s ends in the set).  sets: a sequence of array-likes
+        of node ids; weights: None or one entry per set (None: ones).  The same return tuple."""
+        t, w, offsets = _seed_set_arrays(sets, weights)
+        return self._ppr_targets(t, w, offsets, int(offsets.size - 1), alpha, rmax, k, keep, fetch)
 
     def backward_push(self, target, alpha, rmax):
         reserve = np.empty(self.n)

@@ -196,8 +196,10 @@ int begin_query(BatchJob& J, ForaRun& r, pprhip_graph* S, int i) {
   S->tun = J.P->tun;
   S->seed_on = false;
   const bool seeded = !J.srcs && !pushes_backward(J.kind);
-  const int32_t src = seeded ? -1 : J.P->gr->h_old2new[J.srcs[i]];
-  if (J.kind == QueryKind::kPairs) {  // the handle's tuning (include/pprhip.h "single pairs")
+  const int32_t src = (seeded || J.kind == QueryKind::kTargets) ? -1 : J.P->gr->h_old2new[J.srcs[i]];
+  if (J.kind == QueryKind::kTargets) {  // the handle's tuning (include/pprhip.h "single targets")
+    PPRHIP_TRY(target_begin(r, S, *J.targets, i));
+  } else if (J.kind == QueryKind::kPairs) {  // the handle's tuning (include/pprhip.h "single pairs")
     PPRHIP_TRY(pair_begin(r, S, *J.pairs, src, J.pairs->first[(size_t)i], J.pairs->first[(size_t)i + 1]));
   } else if (J.kind == QueryKind::kBackward) {
     pprhip_tuning_batch(&S->tun);  // level shapes only: a backward search has no cost-model decisions

@@ -774,6 +774,16 @@ int launch_sweep_edges(pprhip_graph* g, SweepWs* w, uint32_t profiled, hipEvent_
 int launch_sweep_best(pprhip_graph* g, SweepWs* w, uint32_t profiled, uint64_t max_vol);
 int init_kernels_sweep();
 
+// ---- kernels_target.hip (single targets)
+// the start of a backward push from a target set: d_id / d_w are `count` distinct internal ids and their weights, padded
+// to whole groups of eight entries and 32- / 64-byte aligned; the members over rmax that have in-edges become the
+// frontier list fbuf (*d_counter: 0 before, their count << 36 | in-edges after)
+int launch_target_init(pprhip_graph* g, const int32_t* d_id, const double* d_w, uint32_t count, int fbuf,
+                       unsigned long long* d_counter, double alpha, double rmax);
+// g->reserve[v] /= d_survival[v] for v < n, or (lone >= 0) for the entry `lone` alone
+int launch_target_finish(pprhip_graph* g, const double* d_survival, uint32_t n, int32_t lone);
+int init_kernels_target();
+
 // ---- kernels_select.hip
 int launch_select_hist(pprhip_graph* g, const double* x, uint32_t n, unsigned long long prefix, int prefix_bits,
                        int digit_bits, bool first_pass);

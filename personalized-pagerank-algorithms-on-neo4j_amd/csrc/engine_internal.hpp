@@ -2,7 +2,7 @@
 // entry points; graph.cpp: graph lifecycle and workspaces; levels.cpp: level loop; select.cpp: top-k selection;
 // device_io.cpp: read-backs, scopes, walk launchers; fora.cpp: resumable FORA / top-k / backward runs; sweep.cpp: sweep cut;
 // batch.cpp, batch_api.cpp, fetch_pipe.cpp, stream.cpp: the batched entry points; allpair.cpp:
-// All-Pair-Backward-Search; index.cpp: its inverted index).
+// All-Pair-Backward-Search; index.cpp: its inverted index; pairs.cpp, targets.cpp: single pairs and single targets).
 #pragma once
 
 #include <sys/mman.h>
@@ -410,11 +410,31 @@ struct PairPlan {
   hipEvent_t ev[3 * kBatch] = {};
 };
 
+// A single-target call (BatchJob kind kTargets, targets.cpp): query i is the backward push from set i of the table -
+// members [first[i], first[i + 1]) of d_id / d_w (distinct internal ids, duplicates summed, zero weights dropped; every
+// set starts on a multiple of eight entries and is padded to one, kernels_target.hip) - and the division by S.
+// single[i]: one member of weight 1, started the pair call's way (r(t) = 1, t popped).  nf / ef: the first frontier of
+// a set as k_target_init lists it (members with in-edges over rmax, their in-edges), known to the host beforehand.
+struct TargetPlan {
+  std::vector<uint64_t> first;
+  std::vector<uint32_t> count, nf;
+  std::vector<uint64_t> ef;
+  std::vector<int32_t> single;   // the internal id of a single target, else -1
+  std::vector<int32_t> max_id;   // largest internal id of the set (the scan bound, reset_query_state)
+  const int32_t* d_id = nullptr;
+  const double* d_w = nullptr;
+  double alpha = 0.0, rmax = 0.0;
+  const double* survival = nullptr;
+};
+
 // What a query of a batched job runs: whole-graph FORA, FORA top-k (seed + query index), a backward search of
-// All-Pair, or single pairs (a backward push per distinct target, then its sources' walks)
-enum class QueryKind : int { kFora, kTopk, kBackward, kPairs };
+// All-Pair, single pairs (a backward push per distinct target, then its sources' walks), or a single-target query (a
+// backward push from a target set, scaled by the survival vector)
+enum class QueryKind : int { kFora, kTopk, kBackward, kPairs, kTargets };
 inline bool is_whole_graph(QueryKind k) { return k == QueryKind::kFora; }
-inline bool pushes_backward(QueryKind k) { return k == QueryKind::kBackward || k == QueryKind::kPairs; }
+inline bool pushes_backward(QueryKind k) {
+  return k == QueryKind::kBackward || k == QueryKind::kPairs || k == QueryKind::kTargets;
+}
 
 // a batch of queries for the slot engine (batch.cpp)
 struct BatchJob {
@@ -433,6 +453,7 @@ struct BatchJob {
   pprhip_stats_t* per_query;
   QueryKind kind = QueryKind::kFora;
   PairPlan* pairs = nullptr;               // kPairs
+  TargetPlan* targets = nullptr;           // kTargets (srcs is nullptr: the plan holds the sets)
   double alpha = 0.0, threshold = 0.0;   // kBackward
   std::vector<Triple>* triples = nullptr;  // kBackward: every search's entries >= threshold
   pprhip_results* keep = nullptr;          // kFora: device-resident store of the queries' vectors
@@ -445,6 +466,9 @@ struct BatchJob {
   std::mutex sum_mu;
   std::atomic<int> next_query{0};
 };
+
+// ---- pairs.cpp
+int ensure_survival(pprhip_graph* g, double alpha);  // S at alpha on the lifted graph (GraphData::survival), cached per alpha
 
 // ---- batch.cpp
 int batch_run(pprhip_graph_t* g, BatchJob& J, pprhip_stats_t* stats_sum);

@@ -1,6 +1,7 @@
 // fora.cpp — FORA, FORA top-k, backward searches and pair pushes as resumable runs (run.hpp), and the single-query
 // entry points that drive them.  The batched entry points that keep kBatch of them in flight are in batch.cpp.
 #include <algorithm>
+#include <chrono>
 #include <cmath>
 #include <cstring>
 
@@ -605,6 +606,79 @@ int pair_step(ForaRun& r, bool yield_dense) {
   return PPRHIP_OK;
 }
 
+// A single-target query (BatchJob kTargets, targets.cpp): the backward push from set i of the call's table at the
+// call's threshold, under the handle's tuning, then value = p / S in place of the reserve (k_target_finish), which the
+// batch driver delivers like a whole-graph vector (top-k, result store, values_out).  A single target starts as
+// pair_begin starts its push; a set starts from r = w (k_target_init), its first frontier known to the host.
+static double host_ms() {
+  return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch()).count();
+}
+
+int target_begin(ForaRun& r, pprhip_graph* g, const detail::TargetPlan& tp, int i) {
+  const int32_t lone = tp.single[(size_t)i];
+  r.g = g;
+  r.kind = QueryKind::kTargets;
+  r.src = lone;
+  r.alpha = tp.alpha;
+  r.rmax_local = tp.rmax;
+  r.tp = &tp;
+  r.target_lone = -1;
+  std::memset(&r.st, 0, sizeof r.st);
+  g->topk_active = false;
+  PPRHIP_TRY(reset_query_state(g, false, tp.max_id[(size_t)i]));
+  r.push_t0 = host_ms();
+  r.waiting = false;
+  r.in_push = false;
+  r.a = PushArgs{tp.alpha, tp.rmax, 0.0, lone, kBackward};
+  r.L = LevelCtx();
+  if (lone >= 0) {
+    const uint32_t din = hdeg_in(g, lone);
+    if (din == 0) {  // p(t) = alpha, no residue (pair_begin)
+      PPRHIP_TRY(launch_set_f64(g, g->reserve, (uint32_t)lone, tp.alpha));
+      r.target_lone = lone;
+      r.phase = ForaRun::kTargetFinal;
+      return PPRHIP_OK;
+    }
+    PPRHIP_TRY(launch_set_f64(g, g->residue, (uint32_t)lone, 1.0));
+    PPRHIP_TRY(seed_single(g, r.L, lone, din));
+  } else {
+    // (the list counter is zero: reset_query_state cleared the counters, and a level's first prepare clears it again)
+    {
+      SetupScope setup(g);
+      PPRHIP_TRY(launch_target_init(g, tp.d_id + tp.first[(size_t)i], tp.d_w + tp.first[(size_t)i], tp.count[(size_t)i],
+                                    r.L.fcur, &g->ctr->hist[kMaxBatch + 2], tp.alpha, tp.rmax));
+    }
+    r.L.nf = tp.nf[(size_t)i];
+    r.L.ef = tp.ef[(size_t)i];
+    r.L.dense_prepared = false;
+    r.L.gs_dirty = false;
+  }
+  r.in_push = true;
+  r.phase = ForaRun::kBwdLevels;
+  return PPRHIP_OK;
+}
+
+int target_step(ForaRun& r, bool yield_dense) {
+  pprhip_graph* g = r.g;
+  if (r.phase == ForaRun::kBwdLevels) {
+    const int rc = run_levels(g, r.a, r.L, r.st, nullptr, yield_dense);
+    if (rc != PPRHIP_OK) return rc;  // kYield or an error
+    leave_push(r);
+    r.phase = ForaRun::kTargetFinal;
+  }
+  if (r.phase == ForaRun::kTargetFinal) {
+    r.st.push_ms = host_ms() - r.push_t0;  // (the last level's counters have been read: the push is over on the device)
+    {
+      SetupScope setup(g);
+      PPRHIP_TRY(launch_target_finish(g, r.tp->survival, act_n(g), r.target_lone));
+    }
+    r.st.rmax_final = r.rmax_local;
+    r.st.rounds = 1;
+    r.phase = ForaRun::kDone;
+  }
+  return PPRHIP_OK;
+}
+
 void add_stats(pprhip_stats_t& sum, const pprhip_stats_t& st) {
   sum.pops += st.pops; sum.edge_pushes += st.edge_pushes; sum.enqueues += st.enqueues;
   sum.dead_end_pops += st.dead_end_pops; sum.dense_nodes += st.dense_nodes; sum.dense_edges += st.dense_edges;
@@ -625,6 +699,7 @@ void add_stats(pprhip_stats_t& sum, const pprhip_stats_t& st) {
 int run_step(ForaRun& r, bool yield_dense) {
   switch (r.kind) {
     case QueryKind::kPairs: return pair_step(r, yield_dense);
+    case QueryKind::kTargets: return target_step(r, yield_dense);
     case QueryKind::kBackward: return bwd_step(r, yield_dense);
     case QueryKind::kTopk: return topk_step(r, yield_dense);
     case QueryKind::kFora: break;

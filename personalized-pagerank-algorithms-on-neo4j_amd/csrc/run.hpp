@@ -1,6 +1,6 @@
-// run.hpp — one query as a resumable run (ForaRun) and the four kinds of run: whole-graph FORA, FORA top-k, a backward
-// search of All-Pair, the push and walks of a pair call.  fora.cpp defines them; the batch drivers (batch.cpp) and the
-// query stream (stream.cpp) step them.
+// run.hpp — one query as a resumable run (ForaRun) and the five kinds of run: whole-graph FORA, FORA top-k, a backward
+// search of All-Pair, the push and walks of a pair call, the push and scaling of a single-target query.  fora.cpp
+// defines them; the batch drivers (batch.cpp) and the query stream (stream.cpp) step them.
 #pragma once
 
 #include <algorithm>
@@ -44,7 +44,7 @@ struct ForaRun {
   PushArgs a;
   detail::RoundCut cut;
   enum Phase { kRoundStart, kLevels, kWalks, kWalkWait, kTopkRoundStart, kTopkLevels, kTopkRoundEnd, kTopkFinal, kBwdLevels,
-               kBwdFinal, kPairFinal, kDone } phase = kDone;
+               kBwdFinal, kPairFinal, kTargetFinal, kDone } phase = kDone;
   hipStream_t side = nullptr;  // batch driver: the walk phase goes to this stream and the run yields until it has ended
   int query = -1;  // batch driver: index of the query this run serves
   detail::BatchJob* job = nullptr;  // ... and the call (or stream submission) that query belongs to
@@ -75,6 +75,10 @@ struct ForaRun {
   const detail::PairPlan* pp = nullptr;
   uint32_t pair_lo = 0, pair_hi = 0;
   bool pair_walks = false;  // the push left residue (the target has in-edges)
+  // single targets (kTargets): the push runs in kBwdLevels, then the division by S and the delivery of the vector
+  const detail::TargetPlan* tp = nullptr;
+  int32_t target_lone = -1;  // a single target without in-edges: the only entry of its vector (no level runs)
+  double push_t0 = 0.0;      // host clock at the query's begin (ms): push_ms is wall time on the workspace
 };
 
 }  // namespace pprhip
@@ -98,6 +102,8 @@ int bwd_begin(ForaRun& r, pprhip_graph* g, int32_t target_internal, int32_t targ
 int bwd_step(ForaRun& r, bool yield_dense);
 int pair_begin(ForaRun& r, pprhip_graph* g, const PairPlan& pp, int32_t target_internal, uint32_t lo, uint32_t hi);
 int pair_step(ForaRun& r, bool yield_dense);
+int target_begin(ForaRun& r, pprhip_graph* g, const TargetPlan& tp, int i);  // set i of the plan
+int target_step(ForaRun& r, bool yield_dense);
 int run_step(ForaRun& r, bool yield_dense);  // the step of r's kind
 void leave_push(ForaRun& r);                 // the run's push phase is over (or given up): it stops holding sweeps off
 // omega and the threshold a whole-graph FORA query's first push runs at (every later one runs at a lower one)
