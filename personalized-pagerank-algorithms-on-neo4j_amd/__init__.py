@@ -252,6 +252,21 @@ def _seed_arrays(seeds, weights):
     return s, w
 
 
+def _batch_outputs(q, n, k, fetch, out, per_query):
+    """The output arrays of a batched call of q queries: (vectors[q, n] | None, ids[q, k] | None, vals[q, k] | None,
+    n_sel[q] | None, Stats array | None).  out: the caller's array for the vectors (with fetch), checked here."""
+    if fetch and out is not None:
+        assert out.dtype == np.float64 and out.flags["C_CONTIGUOUS"] and out.shape == (q, n)
+    elif fetch:
+        out = np.empty((q, n))
+    else:
+        out = None
+    ids = np.empty((q, k), dtype=np.int32) if k > 0 else None
+    vals = np.empty((q, k)) if k > 0 else None
+    nsel = np.zeros(q, dtype=np.int32) if k > 0 else None
+    return out, ids, vals, nsel, ((Stats * q)() if per_query and q else None)
+
+
 def _seed_set_arrays(sets, weights):
     """q seed sets as the batched C calls take them: (seeds int32, weights float64 | None, offsets uint64 [q + 1]).
     weights: None (every set uniform) or one entry per set, each None (that set uniform: ones) or as long as its set."""
@@ -983,16 +998,7 @@ class Graph:
         srcs = np.ascontiguousarray(srcs, dtype=np.int32)
         q = int(srcs.size)
         conf = conf or conf_whole_graph(self.n, self.m, alpha)
-        if fetch and out is not None:
-            assert out.dtype == np.float64 and out.flags["C_CONTIGUOUS"] and out.shape == (q, self.n)
-        elif fetch:
-            out = np.empty((q, self.n))
-        else:
-            out = None
-        ids = np.empty((q, k), dtype=np.int32) if k > 0 else None
-        vals = np.empty((q, k)) if k > 0 else None
-        nsel = np.zeros(q, dtype=np.int32) if k > 0 else None
-        pq = (Stats * q)() if per_query and q else None
+        out, ids, vals, nsel, pq = _batch_outputs(q, self.n, k, fetch, out, per_query)
         st = Stats()
         _check(lib().pprhip_fora_batch_single_source_resident(
             self.h, _ptr(srcs), q, eps, C.byref(conf), seed, n_rounds, keep.h if keep is not None else None, _ptr(out),
@@ -1006,16 +1012,7 @@ class Graph:
         s, w, offsets = _seed_set_arrays(sets, weights)
         q = int(offsets.size - 1)
         conf = conf or conf_whole_graph(self.n, self.m, alpha)
-        if fetch and out is not None:
-            assert out.dtype == np.float64 and out.flags["C_CONTIGUOUS"] and out.shape == (q, self.n)
-        elif fetch:
-            out = np.empty((q, self.n))
-        else:
-            out = None
-        ids = np.empty((q, k), dtype=np.int32) if k > 0 else None
-        vals = np.empty((q, k)) if k > 0 else None
-        nsel = np.zeros(q, dtype=np.int32) if k > 0 else None
-        pq = (Stats * q)() if per_query and q else None
+        out, ids, vals, nsel, pq = _batch_outputs(q, self.n, k, fetch, out, per_query)
         st = Stats()
         _check(lib().pprhip_fora_batch_seeds(
             self.h, _ptr(s), _ptr(w), _ptr(offsets), q, eps, C.byref(conf), seed, n_rounds,
@@ -1065,11 +1062,7 @@ class Graph:
         return out, st
 
     def _ppr_targets(self, t, w, offsets, q, alpha, rmax, k, keep, fetch):
-        values = np.empty((q, self.n)) if fetch else None
-        ids = np.empty((q, k), dtype=np.int32) if k > 0 else None
-        vals = np.empty((q, k)) if k > 0 else None
-        nsel = np.zeros(q, dtype=np.int32) if k > 0 else None
-        pq = (Stats * q)() if q else None
+        values, ids, vals, nsel, pq = _batch_outputs(q, self.n, k, fetch, None, True)  # (always per-query stats)
         st = Stats()
         _check(lib().pprhip_ppr_targets(
             self.h, _ptr(t), _ptr(w), _ptr(offsets), q, alpha, rmax, keep.h if keep is not None else None, _ptr(values),

@@ -451,21 +451,11 @@ int batch_tier(ApbsCall& c, std::vector<int32_t>& to_tier3, pprhip_stats_t& st3)
   if (to_tier3.empty()) return PPRHIP_OK;  // Base_Whole_Graph.java:76-92
   pprhip_stats_t& st = c.st;
   std::vector<Triple> tr3;
-  BatchJob J;  // (the members set to zero here have no initialiser of their own)
+  BatchJob J;
   J.P = c.g;
   J.kind = QueryKind::kBackward;
   J.srcs = to_tier3.data();
   J.q = (int)to_tier3.size();
-  J.eps = 0.0;
-  J.conf = nullptr;
-  J.seed = 0;
-  J.n_rounds = 0;
-  J.reserve_out = nullptr;
-  J.k = 0;
-  J.ids_out = nullptr;
-  J.vals_out = nullptr;
-  J.n_out = nullptr;
-  J.per_query = nullptr;
   J.alpha = c.alpha;
   J.threshold = c.threshold;
   J.triples = &tr3;

@@ -171,13 +171,18 @@ static int deliver_vector(BatchJob& J, ForaRun& r) {
 int finish_query(BatchJob& J, ForaRun& r) {
   pprhip_graph* S = r.g;
   S->seed_on = false;  // (the query's pushes are over: a later query of the workspace must not land on its table)
-  if (r.kind == QueryKind::kPairs) {  // the values are in the call's device array; the phase times before the events are reused
-    const hipEvent_t* ev = &r.pp->ev[3 * S->ws_index];
-    PPRHIP_CHECK_HIP(hipEventSynchronize(ev[2]));
-    r.st.push_ms = CallTimer::ms(ev[0], ev[1]);
-    r.st.mc_ms = CallTimer::ms(ev[1], ev[2]);
-  } else if (r.kind != QueryKind::kBackward) {
-    PPRHIP_TRY(deliver_vector(J, r));
+  switch (r.kind) {
+    case QueryKind::kFora:
+    case QueryKind::kTopk:
+    case QueryKind::kTargets: PPRHIP_TRY(deliver_vector(J, r)); break;
+    case QueryKind::kPairs: {  // the values are in the call's device array; the phase times before the events are reused
+      const hipEvent_t* ev = &r.pp->ev[3 * S->ws_index];
+      PPRHIP_CHECK_HIP(hipEventSynchronize(ev[2]));
+      r.st.push_ms = CallTimer::ms(ev[0], ev[1]);
+      r.st.mc_ms = CallTimer::ms(ev[1], ev[2]);
+      break;
+    }
+    case QueryKind::kBackward: break;  // (its triples join the job's below)
   }
   {
     std::lock_guard<std::mutex> lk(J.sum_mu);
@@ -195,24 +200,33 @@ int finish_query(BatchJob& J, ForaRun& r) {
 int begin_query(BatchJob& J, ForaRun& r, pprhip_graph* S, int i) {
   S->tun = J.P->tun;
   S->seed_on = false;
-  const bool seeded = !J.srcs && !pushes_backward(J.kind);
-  const int32_t src = (seeded || J.kind == QueryKind::kTargets) ? -1 : J.P->gr->h_old2new[J.srcs[i]];
-  if (J.kind == QueryKind::kTargets) {  // the handle's tuning (include/pprhip.h "single targets")
-    PPRHIP_TRY(target_begin(r, S, *J.targets, i));
-  } else if (J.kind == QueryKind::kPairs) {  // the handle's tuning (include/pprhip.h "single pairs")
-    PPRHIP_TRY(pair_begin(r, S, *J.pairs, src, J.pairs->first[(size_t)i], J.pairs->first[(size_t)i + 1]));
-  } else if (J.kind == QueryKind::kBackward) {
-    pprhip_tuning_batch(&S->tun);  // level shapes only: a backward search has no cost-model decisions
-    PPRHIP_TRY(bwd_begin(r, S, src, J.srcs[i], J.alpha, J.threshold));
-  } else if (J.kind == QueryKind::kTopk) {
-    int32_t* const ids = J.ids_out + (size_t)i * J.k;
-    double* const vals = J.vals_out + (size_t)i * J.k;
-    const uint64_t seed = J.seed + (uint64_t)i;
-    if (seeded) PPRHIP_TRY(topk_begin_seeds(r, S, J.sets[(size_t)i], J.eps, J.conf, seed, ids, vals, J.k));
-    else PPRHIP_TRY(topk_begin(r, S, src, J.eps, J.conf, seed, ids, vals, J.k));
-  } else {
-    if (seeded) PPRHIP_TRY(fora_begin_seeds(r, S, J.sets[(size_t)i], J.eps, J.conf, J.seed, J.n_rounds));
-    else PPRHIP_TRY(fora_begin(r, S, src, J.eps, J.conf, J.seed, J.n_rounds));
+  bool seeded = false;  // kFora and kTopk without sources: the query runs from seed set i
+  const auto src = [&] { return J.P->gr->h_old2new[J.srcs[i]]; };  // internal id of source / target i
+  switch (J.kind) {
+    case QueryKind::kFora:
+      seeded = !J.srcs;
+      if (seeded) PPRHIP_TRY(fora_begin_seeds(r, S, J.sets[(size_t)i], J.eps, J.conf, J.seed, J.n_rounds));
+      else PPRHIP_TRY(fora_begin(r, S, src(), J.eps, J.conf, J.seed, J.n_rounds));
+      break;
+    case QueryKind::kTopk: {
+      seeded = !J.srcs;
+      int32_t* const ids = J.ids_out + (size_t)i * J.k;
+      double* const vals = J.vals_out + (size_t)i * J.k;
+      const uint64_t seed = J.seed + (uint64_t)i;
+      if (seeded) PPRHIP_TRY(topk_begin_seeds(r, S, J.sets[(size_t)i], J.eps, J.conf, seed, ids, vals, J.k));
+      else PPRHIP_TRY(topk_begin(r, S, src(), J.eps, J.conf, seed, ids, vals, J.k));
+      break;
+    }
+    case QueryKind::kBackward:
+      pprhip_tuning_batch(&S->tun);  // level shapes only: a backward search has no cost-model decisions
+      PPRHIP_TRY(bwd_begin(r, S, src(), J.srcs[i], J.alpha, J.threshold));
+      break;
+    case QueryKind::kPairs:  // the handle's tuning (include/pprhip.h "single pairs")
+      PPRHIP_TRY(pair_begin(r, S, *J.pairs, src(), J.pairs->first[(size_t)i], J.pairs->first[(size_t)i + 1]));
+      break;
+    case QueryKind::kTargets:  // the handle's tuning (include/pprhip.h "single targets")
+      PPRHIP_TRY(target_begin(r, S, *J.targets, i));
+      break;
   }
   S->seed_on = seeded;
   r.query = i;

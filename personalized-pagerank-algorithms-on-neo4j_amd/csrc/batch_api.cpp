@@ -8,6 +8,50 @@
 using namespace pprhip;
 using namespace pprhip::detail;
 
+// The checked arguments of the two whole-graph FORA entry points as a job: q queries from srcs, or (srcs NULL) from
+// the seed sets whose plans the caller has put into J.sets.
+static int fora_batch(BatchJob& J, pprhip_graph_t* g, const int32_t* srcs, int q, double eps,
+                      const pprhip_fora_conf_t* conf, uint64_t seed, int n_rounds, pprhip_results_t* keep,
+                      double* reserve_out, int k, int32_t* ids_out, double* vals_out, int* n_out,
+                      pprhip_stats_t* per_query, pprhip_stats_t* stats_sum) {
+  J.P = g;
+  J.srcs = srcs;
+  J.q = q;
+  J.eps = eps;
+  J.conf = conf;
+  J.seed = seed;
+  J.n_rounds = n_rounds;
+  J.reserve_out = reserve_out;
+  J.k = k;
+  J.ids_out = ids_out;
+  J.vals_out = vals_out;
+  J.n_out = n_out;
+  J.per_query = per_query;
+  J.keep = keep;
+  if (keep) keep->count = 0;
+  PPRHIP_TRY(batch_run(g, J, stats_sum));
+  if (keep) keep->count = q;
+  return PPRHIP_OK;
+}
+
+// ... and of the two top-k entry points: query i runs with seed + i, as pprhip_fora_topk(srcs[i], ..., seed + i) or
+// pprhip_fora_topk_seeds(set i, ..., seed + i) would
+static int topk_batch(BatchJob& J, pprhip_graph_t* g, const int32_t* srcs, int q, int k, double eps,
+                      const pprhip_fora_conf_t* conf, uint64_t seed, int32_t* ids_out, double* vals_out,
+                      pprhip_stats_t* stats_sum) {
+  J.P = g;
+  J.kind = QueryKind::kTopk;
+  J.srcs = srcs;
+  J.q = q;
+  J.eps = eps;
+  J.conf = conf;
+  J.seed = seed;
+  J.k = k;
+  J.ids_out = ids_out;
+  J.vals_out = vals_out;
+  return batch_run(g, J, stats_sum);
+}
+
 // Batched single-source FORA: up to kBatch queries in flight on kBatch workspaces of this handle.
 // Every query runs the single-query algorithm unchanged (same levels, same thresholds, same walks
 // for the same seed); whenever the queries in a push phase all stand at a dense level, one sweep of
@@ -28,31 +72,11 @@ int pprhip_fora_batch_single_source_resident(pprhip_graph_t* g, const int32_t* s
     set_error("pprhip_fora_batch_single_source: bad arguments (q=%d eps=%g n_rounds=%d k=%d)", q, eps, n_rounds, k);
     return PPRHIP_ERR_INVALID;
   }
-  if (keep && (keep->g != g || q > keep->capacity)) {
-    set_error("pprhip_fora_batch_single_source_resident: the result store belongs to another graph or holds %d < %d "
-              "queries", keep->capacity, q);
-    return PPRHIP_ERR_INVALID;
-  }
+  PPRHIP_TRY(check_keep(keep, g, q, "pprhip_fora_batch_single_source_resident"));
   for (int i = 0; i < q; ++i) PPRHIP_TRY(check_node(g, srcs[i], "pprhip_fora_batch_single_source"));
   BatchJob J;
-  J.P = g;
-  J.srcs = srcs;
-  J.q = q;
-  J.eps = eps;
-  J.conf = conf;
-  J.seed = seed;
-  J.n_rounds = n_rounds;
-  J.reserve_out = reserve_out;
-  J.k = k;
-  J.ids_out = ids_out;
-  J.vals_out = vals_out;
-  J.n_out = n_out;
-  J.per_query = per_query;
-  J.keep = keep;
-  if (keep) keep->count = 0;
-  PPRHIP_TRY(batch_run(g, J, stats_sum));
-  if (keep) keep->count = q;
-  return PPRHIP_OK;
+  return fora_batch(J, g, srcs, q, eps, conf, seed, n_rounds, keep, reserve_out, k, ids_out, vals_out, n_out, per_query,
+                    stats_sum);
 }
 
 int pprhip_fora_batch_single_source(pprhip_graph_t* g, const int32_t* srcs, int q, double eps,
@@ -141,21 +165,7 @@ int pprhip_fora_batch_topk(pprhip_graph_t* g, const int32_t* srcs, int q, int k,
   pprhip_fora_conf_t conf;
   PPRHIP_TRY(pprhip_conf_fora_topk(g->gr->n, g->gr->m, k, alpha, &conf));
   BatchJob J;
-  J.P = g;
-  J.kind = QueryKind::kTopk;
-  J.srcs = srcs;
-  J.q = q;
-  J.eps = eps;
-  J.conf = &conf;
-  J.seed = seed;  // query i runs with seed + i, as pprhip_fora_topk(srcs[i], ..., seed + i) would
-  J.n_rounds = 0;
-  J.reserve_out = nullptr;
-  J.k = k;
-  J.ids_out = ids_out;
-  J.vals_out = vals_out;
-  J.n_out = nullptr;
-  J.per_query = nullptr;
-  return batch_run(g, J, stats_sum);
+  return topk_batch(J, g, srcs, q, k, eps, &conf, seed, ids_out, vals_out, stats_sum);
 }
 
 // ------------------------------------------------------------------ batched seed sets
@@ -173,30 +183,11 @@ int pprhip_fora_batch_seeds(pprhip_graph_t* g, const int32_t* seeds, const doubl
     set_error("%s: bad arguments (q=%d eps=%g n_rounds=%d k=%d)", fn, q, eps, n_rounds, k);
     return PPRHIP_ERR_INVALID;
   }
-  if (keep && (keep->g != g || q > keep->capacity)) {
-    set_error("%s: the result store belongs to another graph or holds %d < %d queries", fn, keep->capacity, q);
-    return PPRHIP_ERR_INVALID;
-  }
+  PPRHIP_TRY(check_keep(keep, g, q, fn));
   BatchJob J;
   PPRHIP_TRY(seed_plan_sets(g, seeds, weights, offsets, q, conf->alpha, fn, J.sets));
-  J.P = g;
-  J.srcs = nullptr;
-  J.q = q;
-  J.eps = eps;
-  J.conf = conf;
-  J.seed = seed;
-  J.n_rounds = n_rounds;
-  J.reserve_out = reserve_out;
-  J.k = k;
-  J.ids_out = ids_out;
-  J.vals_out = vals_out;
-  J.n_out = n_out;
-  J.per_query = per_query;
-  J.keep = keep;
-  if (keep) keep->count = 0;
-  PPRHIP_TRY(batch_run(g, J, stats_sum));
-  if (keep) keep->count = q;
-  return PPRHIP_OK;
+  return fora_batch(J, g, nullptr, q, eps, conf, seed, n_rounds, keep, reserve_out, k, ids_out, vals_out, n_out,
+                    per_query, stats_sum);
 }
 
 int pprhip_fora_batch_topk_seeds(pprhip_graph_t* g, const int32_t* seeds, const double* weights,
@@ -214,19 +205,5 @@ int pprhip_fora_batch_topk_seeds(pprhip_graph_t* g, const int32_t* seeds, const 
   PPRHIP_TRY(pprhip_conf_fora_topk(g->gr->n, g->gr->m, k, alpha, &conf));
   BatchJob J;
   PPRHIP_TRY(seed_plan_sets(g, seeds, weights, offsets, q, conf.alpha, fn, J.sets));
-  J.P = g;
-  J.kind = QueryKind::kTopk;
-  J.srcs = nullptr;
-  J.q = q;
-  J.eps = eps;
-  J.conf = &conf;
-  J.seed = seed;  // query i runs with seed + i, as pprhip_fora_topk_seeds(set i, ..., seed + i) would
-  J.n_rounds = 0;
-  J.reserve_out = nullptr;
-  J.k = k;
-  J.ids_out = ids_out;
-  J.vals_out = vals_out;
-  J.n_out = nullptr;
-  J.per_query = nullptr;
-  return batch_run(g, J, stats_sum);
+  return topk_batch(J, g, nullptr, q, k, eps, &conf, seed, ids_out, vals_out, stats_sum);
 }

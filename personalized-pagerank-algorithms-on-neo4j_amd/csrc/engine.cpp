@@ -3,11 +3,13 @@
 // parameter checks every entry point runs and the top-k push session.  Everything numerical runs in the HIP kernels;
 // the host only sequences launches on the handle's stream.  The handle's lifecycle lives in graph.cpp, the level loop
 // in levels.cpp, the selection driver in select.cpp, read-backs and walk launchers in device_io.cpp, FORA runs in
-// fora.cpp, the batched entry points in batch.cpp, batch_api.cpp and stream.cpp, All-Pair in allpair.cpp and its
-// index in index.cpp (shared declarations: engine_internal.hpp).
+// fora.cpp, the runs that push backward in bwd_runs.cpp, the batched entry points in batch.cpp, batch_api.cpp and
+// stream.cpp, All-Pair in allpair.cpp and its index in index.cpp (shared declarations: engine_internal.hpp).
 #include <algorithm>
+#include <climits>
 #include <cmath>
 #include <cstring>
+#include <string>
 
 #include "engine_internal.hpp"
 
@@ -93,6 +95,75 @@ int check_conf(const pprhip_fora_conf_t* c, const char* fn, bool topk) {
     return PPRHIP_ERR_INVALID;
   }
   return check_positive(c->min_delta, fn, "conf->min_delta");
+}
+
+int check_set_offsets(const uint64_t* offsets, int q, const char* fn) {
+  if (offsets[0] != 0) {
+    set_error("%s: offsets[0] = %llu, not 0", fn, (unsigned long long)offsets[0]);
+    return PPRHIP_ERR_INVALID;
+  }
+  for (int i = 0; i < q; ++i)
+    if (offsets[i + 1] < offsets[i] || offsets[i + 1] - offsets[i] > (uint64_t)INT32_MAX) {
+      set_error("%s: set %d: offsets %llu .. %llu do not describe a set", fn, i, (unsigned long long)offsets[i],
+                (unsigned long long)offsets[i + 1]);
+      return PPRHIP_ERR_INVALID;
+    }
+  return PPRHIP_OK;
+}
+
+int check_keep(const pprhip_results* keep, const pprhip_graph* g, int q, const char* fn) {
+  if (keep && (keep->g != g || q > keep->capacity)) {
+    set_error("%s: the result store belongs to another graph or holds %d < %d queries", fn, keep->capacity, q);
+    return PPRHIP_ERR_INVALID;
+  }
+  return PPRHIP_OK;
+}
+
+int parse_weighted_set(uint32_t n, const int32_t* ids_in, const double* weights, int k, bool normalize, const char* noun,
+                       const char* fn, int set, WeightedSet& e) {
+  e.clear();
+  const auto where = [&] { return set < 0 ? std::string(fn) : std::string(fn) + ": set " + std::to_string(set); };
+  const auto refused = [&] {  // (after set_error)
+    e.clear();
+    return PPRHIP_ERR_INVALID;
+  };
+  if (k <= 0 || !ids_in) {
+    set_error("%s: a %s set needs at least one %s (n_%ss=%d)", where().c_str(), noun, noun, noun, k);
+    return refused();
+  }
+  e.reserve((size_t)k);
+  for (int i = 0; i < k; ++i) {
+    const int32_t v = ids_in[i];
+    if (v < 0 || (uint32_t)v >= n) {
+      set_error("%s: %s %d: node id %d outside [0, %u)", where().c_str(), noun, i, v, n);
+      return refused();
+    }
+    const double w = weights ? weights[i] : 1.0;
+    if (!std::isfinite(w) || w < 0.0) {
+      set_error("%s: %s %d: weight %g is not a finite non-negative number", where().c_str(), noun, i, w);
+      return refused();
+    }
+    e.push_back({v, w});
+  }
+  std::sort(e.begin(), e.end(), [](const std::pair<int32_t, double>& a, const std::pair<int32_t, double>& b) {
+    return a.first < b.first;
+  });
+  double sum = 0.0;
+  for (const auto& x : e) sum += x.second;
+  if (!(sum > 0.0) || !std::isfinite(sum)) {
+    set_error("%s: the %s weights sum to %g", where().c_str(), noun, sum);
+    return refused();
+  }
+  size_t kept = 0;
+  for (size_t i = 0; i < e.size();) {  // duplicates are summed, zero weights dropped (in place: kept <= i)
+    size_t j = i;
+    double w = 0.0;
+    for (; j < e.size() && e[j].first == e[i].first; ++j) w += e[j].second;
+    if (w > 0.0) e[kept++] = {e[i].first, normalize ? w / sum : w};
+    i = j;
+  }
+  e.resize(kept);
+  return PPRHIP_OK;
 }
 
 uint32_t hdeg_out(const pprhip_graph* g, int32_t v) { return g->gr->h_out_rp[v + 1] - g->gr->h_out_rp[v]; }
@@ -464,16 +535,11 @@ int pprhip_monte_carlo(pprhip_graph_t* g, int32_t src, double eps, const pprhip_
 // ------------------------------------------------------------------ backward search (a8)
 static int backward_push_impl(pprhip_graph_t* g, int32_t target, double alpha, double rmax, pprhip_stats_t& st) {
   PPRHIP_TRY(reset_query_state(g, false, target));
-  if (hdeg_in(g, target) == 0) {  // Backward_Search.java:46-49
-    PPRHIP_TRY(launch_set_f64(g, g->reserve, (uint32_t)target, 1.0));
-    return PPRHIP_OK;
-  }
-  PushArgs a{alpha, rmax, 0.0, target, kBackward};
+  PushArgs a;
   LevelCtx L;
-  PPRHIP_TRY(launch_set_f64(g, g->residue, (uint32_t)target, 1.0));
-  PPRHIP_TRY(seed_single(g, L, target, hdeg_in(g, target)));
-  PPRHIP_TRY(run_levels(g, a, L, st, nullptr));
-  return PPRHIP_OK;
+  bool pushing = false;
+  PPRHIP_TRY(backward_start(g, L, a, target, alpha, rmax, 1.0, &pushing));
+  return pushing ? run_levels(g, a, L, st, nullptr) : PPRHIP_OK;
 }
 
 int pprhip_backward_push(pprhip_graph_t* g, int32_t target, double alpha, double rmax, double* reserve_out,

@@ -1,6 +1,7 @@
 // engine_internal.hpp — declarations shared by the engine's translation units (engine.cpp: single-query
 // entry points; graph.cpp: graph lifecycle and workspaces; levels.cpp: level loop; select.cpp: top-k selection;
-// device_io.cpp: read-backs, scopes, walk launchers; fora.cpp: resumable FORA / top-k / backward runs; sweep.cpp: sweep cut;
+// device_io.cpp: read-backs, scopes, walk launchers; fora.cpp: resumable FORA / top-k runs; bwd_runs.cpp: the resumable
+// runs that push backward; sweep.cpp: sweep cut;
 // batch.cpp, batch_api.cpp, fetch_pipe.cpp, stream.cpp: the batched entry points; allpair.cpp:
 // All-Pair-Backward-Search; index.cpp: its inverted index; pairs.cpp, targets.cpp: single pairs and single targets).
 #pragma once
@@ -308,6 +309,18 @@ int check_alpha(double alpha, const char* fn, const char* name = "alpha");
 int check_positive(double v, const char* fn, const char* name);
 int check_threshold(double v, const char* fn, const char* name);
 int check_conf(const pprhip_fora_conf_t* c, const char* fn, bool topk);
+// q sets described like a CSR: offsets[0] = 0, ascending, no set of more than INT32_MAX members (the message names the set)
+int check_set_offsets(const uint64_t* offsets, int q, const char* fn);
+// a batched call's result store (NULL: none) belongs to the call's graph and holds its q queries
+int check_keep(const pprhip_results* keep, const pprhip_graph* g, int q, const char* fn);
+// The caller's ids / weights (NULL: uniform) / count as a weighted set of `noun`s ("seed", "target"): distinct original
+// ids ascending and their weights, duplicates summed, zero weights dropped - divided by the sum of all weights with
+// `normalize`, as given without.  PPRHIP_ERR_INVALID for an empty set, an id outside [0, n), a negative or non-finite
+// weight, or weights that sum to 0; set >= 0: the messages name it ("fn: set N: ...").  `out` is the parser's only
+// buffer: a caller with many sets passes the same one again.
+using WeightedSet = std::vector<std::pair<int32_t, double>>;
+int parse_weighted_set(uint32_t n, const int32_t* ids_in, const double* weights, int k, bool normalize, const char* noun,
+                       const char* fn, int set, WeightedSet& out);
 uint32_t hdeg_out(const pprhip_graph* g, int32_t v);
 uint32_t hdeg_in(const pprhip_graph* g, int32_t v);
 
@@ -438,19 +451,19 @@ inline bool pushes_backward(QueryKind k) {
 
 // a batch of queries for the slot engine (batch.cpp)
 struct BatchJob {
-  pprhip_graph* P;
-  const int32_t* srcs;  // nullptr: a job of seed sets (sets)
-  int q;
-  double eps;
-  const pprhip_fora_conf_t* conf;
-  uint64_t seed;
-  int n_rounds;
-  double* reserve_out;
-  int k;
-  int32_t* ids_out;
-  double* vals_out;
-  int* n_out;
-  pprhip_stats_t* per_query;
+  pprhip_graph* P = nullptr;
+  const int32_t* srcs = nullptr;  // nullptr: a job of seed sets (sets) or of target sets (targets)
+  int q = 0;
+  double eps = 0.0;
+  const pprhip_fora_conf_t* conf = nullptr;
+  uint64_t seed = 0;
+  int n_rounds = 0;
+  double* reserve_out = nullptr;
+  int k = 0;
+  int32_t* ids_out = nullptr;
+  double* vals_out = nullptr;
+  int* n_out = nullptr;
+  pprhip_stats_t* per_query = nullptr;
   QueryKind kind = QueryKind::kFora;
   PairPlan* pairs = nullptr;               // kPairs
   TargetPlan* targets = nullptr;           // kTargets (srcs is nullptr: the plan holds the sets)
@@ -462,7 +475,7 @@ struct BatchJob {
   // kFora and kTopk without srcs: query i runs from seed set i, its host plan (seed_plan) made before anything runs; the
   // query's workspace takes it over (seed_upload) when the query begins
   std::vector<SeedTable> sets;
-  pprhip_stats_t sum;
+  pprhip_stats_t sum{};
   std::mutex sum_mu;
   std::atomic<int> next_query{0};
 };
@@ -491,6 +504,15 @@ int all_pair_collect(pprhip_graph_t* g, double alpha, double threshold, uint32_t
 // (engine.cpp)
 int backward_search_whole(pprhip_graph_t* g, int32_t target_internal, double alpha, double rmax, pprhip_stats_t& st);
 
+// ---- bwd_runs.cpp
+// The start of every backward push from one target (internal id), on a workspace the caller has just reset: a and L for
+// run_levels, r(t) = 1 and t as the first frontier.  A target without in-edges gets reserve(t) = lone_value instead and
+// no push (*pushing false).  lone_value, the one deliberate difference between the callers: 1.0 for All-Pair's searches
+// and pprhip_backward_push, which is what Backward_Search.java:46-49 writes; alpha for pairs and targets, which is what
+// the standard start (r(t) = 1, t popped) leaves there - p_t(t) = alpha and no residue.
+int backward_start(pprhip_graph* g, LevelCtx& L, PushArgs& a, int32_t target_internal, double alpha, double rmax,
+                   double lone_value, bool* pushing);
+
 // ---- index.cpp
 // the index over all n sources from entries on the host: bucketed by source, row order and k rule on the host's threads
 int index_from_triples(uint32_t n, std::vector<Triple>& tr, int k, pprhip_index_t** out);
@@ -502,16 +524,12 @@ int index_concat(const std::vector<pprhip_index_t*>& parts, pprhip_index_t** out
 int ensure_ring(pprhip_graph* g);  // the pinned ring index_from_device downloads through (g->ix_stage), on first use
 
 // ---- seed sets (seeds.cpp)
-// the caller's seeds / weights (NULL: uniform) / count as p: distinct original ids ascending and their normalized
-// weights, duplicates summed, zero weights dropped; PPRHIP_ERR_INVALID for an empty set, an id outside [0, n), a
-// negative or non-finite weight, or weights that sum to 0
-int seed_normalize(uint32_t n, const int32_t* seeds, const double* weights, int k, const char* fn,
-                   std::vector<int32_t>& ids, std::vector<double>& p);
-// ... resolved for the dead-end seeds under alpha into the host half of a seed table (h_* arrays and counts)
+// the caller's seeds / weights / count as p (parse_weighted_set for seeds, normalized; set: as there), resolved for the
+// dead-end seeds under alpha into the host half of a seed table (h_* arrays and counts)
 int seed_plan(pprhip_graph* g, const int32_t* seeds, const double* weights, int k, double alpha, const char* fn,
-              SeedTable& plan);
+              SeedTable& plan, int set = -1);
 // q seed sets described like a CSR (set i = seeds / weights [offsets[i], offsets[i + 1])) as q plans: the checks of
-// seed_normalize for every set (the message names the set); bad offsets and q < 0 are PPRHIP_ERR_INVALID as well.
+// parse_weighted_set for every set (the message names the set); bad offsets and q < 0 are PPRHIP_ERR_INVALID as well.
 // Host only.
 int seed_plan_sets(pprhip_graph* g, const int32_t* seeds, const double* weights, const uint64_t* offsets, int q,
                    double alpha, const char* fn, std::vector<SeedTable>& plans);

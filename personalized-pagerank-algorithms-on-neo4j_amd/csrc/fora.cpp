@@ -1,7 +1,6 @@
-// fora.cpp — FORA, FORA top-k, backward searches and pair pushes as resumable runs (run.hpp), and the single-query
-// entry points that drive them.  The batched entry points that keep kBatch of them in flight are in batch.cpp.
+// fora.cpp — FORA and FORA top-k as resumable runs (run.hpp), and the single-query entry points that drive them.  The
+// runs that push backward are in bwd_runs.cpp, the batched entry points that keep kBatch runs in flight in batch.cpp.
 #include <algorithm>
-#include <chrono>
 #include <cmath>
 #include <cstring>
 
@@ -471,214 +470,6 @@ int topk_step(ForaRun& r, bool yield_dense) {
   }
 }
 
-// One backward search of All-Pair (Backward_Search.java:38-100 + the >= threshold filter of
-// Base_Whole_Graph.java:80-88) as a resumable run.
-int bwd_begin(ForaRun& r, pprhip_graph* g, int32_t target_internal, int32_t target_orig, double alpha, double rmax) {
-  r.g = g;
-  r.kind = QueryKind::kBackward;
-  r.src = target_internal;
-  r.target_orig = target_orig;
-  r.alpha = alpha;
-  r.rmax_local = rmax;
-  r.triples.clear();
-  std::memset(&r.st, 0, sizeof r.st);
-  g->topk_active = false;
-  PPRHIP_TRY(reset_query_state(g, false, target_internal));
-  r.waiting = false;
-  r.in_push = false;
-  if (hdeg_in(g, target_internal) == 0) {  // :46-49
-    PPRHIP_TRY(launch_set_f64(g, g->reserve, (uint32_t)target_internal, 1.0));
-    r.phase = ForaRun::kBwdFinal;
-    return PPRHIP_OK;
-  }
-  r.a = PushArgs{alpha, rmax, 0.0, target_internal, kBackward};
-  r.L = LevelCtx();
-  PPRHIP_TRY(launch_set_f64(g, g->residue, (uint32_t)target_internal, 1.0));
-  PPRHIP_TRY(seed_single(g, r.L, target_internal, hdeg_in(g, target_internal)));
-  r.in_push = true;
-  r.phase = ForaRun::kBwdLevels;
-  return PPRHIP_OK;
-}
-
-int bwd_step(ForaRun& r, bool yield_dense) {
-  pprhip_graph* g = r.g;
-  if (r.phase == ForaRun::kBwdLevels) {
-    const int rc = run_levels(g, r.a, r.L, r.st, nullptr, yield_dense);
-    if (rc != PPRHIP_OK) return rc;  // kYield or an error
-    leave_push(r);
-    r.phase = ForaRun::kBwdFinal;
-  }
-  if (r.phase == ForaRun::kBwdFinal) {
-    const double threshold = r.rmax_local;
-    unsigned long long thr_bits = 1ull;
-    if (threshold > 0.0) std::memcpy(&thr_bits, &threshold, 8);
-    PPRHIP_TRY(launch_select_gather(g, g->reserve, act_n(g), thr_bits, true));  // Base_Whole_Graph.java:83 pi >= threshold
-    unsigned long long cnt = 0;
-    PPRHIP_TRY(fetch_small(g, g->sel_blob, &cnt, sizeof cnt));
-    const std::vector<int32_t>& n2o = g->gr->h_new2old;
-    if (cnt > g->sel_cap) {
-      std::vector<double> all(g->gr->n);
-      PPRHIP_TRY(copy_out(g, g->reserve, all.data()));
-      for (uint32_t v = 0; v < g->gr->n; ++v)  // copy_out already returned original ids
-        if (all[v] > 0.0 && all[v] >= threshold) r.triples.push_back({(int32_t)v, r.target_orig, all[v]});
-    } else if (cnt) {
-      std::vector<SelRec> recs(cnt);
-      PPRHIP_CHECK_HIP(hipMemcpyAsync(recs.data(), g->sel_blob + kSelHeader, sizeof(SelRec) * cnt, hipMemcpyDeviceToHost, g->stream));
-      PPRHIP_CHECK_HIP(hipStreamSynchronize(g->stream));
-      for (uint64_t i = 0; i < cnt; ++i) r.triples.push_back({n2o[recs[i].id], r.target_orig, recs[i].val});
-    }
-    r.phase = ForaRun::kDone;
-  }
-  return PPRHIP_OK;
-}
-
-// The backward push of a pair call (BatchJob kPairs): the standard start r(t) = 1, t popped - also for a target without
-// in-edges, where that leaves p_t(t) = alpha and no residue (not bwd_begin's reserve(t) = 1, Backward_Search.java:46-49).
-int pair_begin(ForaRun& r, pprhip_graph* g, const detail::PairPlan& pp, int32_t target_internal, uint32_t lo,
-               uint32_t hi) {
-  r.g = g;
-  r.kind = QueryKind::kPairs;
-  r.src = target_internal;
-  r.alpha = pp.alpha;
-  r.rmax_local = pp.rmax;
-  r.pp = &pp;
-  r.pair_lo = lo;
-  r.pair_hi = hi;
-  std::memset(&r.st, 0, sizeof r.st);
-  g->topk_active = false;
-  if (g->ws_index < 0 || g->ws_index >= kBatch) {
-    set_error("pair call: workspace %d has no pair buffers", g->ws_index);
-    return PPRHIP_ERR_STATE;
-  }
-  PPRHIP_TRY(reset_query_state(g, false, target_internal));
-  PPRHIP_CHECK_HIP(hipEventRecord(pp.ev[3 * g->ws_index], g->stream));
-  r.waiting = false;
-  r.in_push = false;
-  const uint32_t din = hdeg_in(g, target_internal);
-  r.pair_walks = din > 0;
-  if (!r.pair_walks) {
-    PPRHIP_TRY(launch_set_f64(g, g->reserve, (uint32_t)target_internal, pp.alpha));
-    r.phase = ForaRun::kPairFinal;
-    return PPRHIP_OK;
-  }
-  r.a = PushArgs{pp.alpha, pp.rmax, 0.0, target_internal, kBackward};
-  r.L = LevelCtx();
-  PPRHIP_TRY(launch_set_f64(g, g->residue, (uint32_t)target_internal, 1.0));
-  PPRHIP_TRY(seed_single(g, r.L, target_internal, din));
-  r.in_push = true;
-  r.phase = ForaRun::kBwdLevels;
-  return PPRHIP_OK;
-}
-
-int pair_step(ForaRun& r, bool yield_dense) {
-  pprhip_graph* g = r.g;
-  if (r.phase == ForaRun::kBwdLevels) {
-    const int rc = run_levels(g, r.a, r.L, r.st, nullptr, yield_dense);
-    if (rc != PPRHIP_OK) return rc;  // kYield or an error
-    leave_push(r);
-    r.phase = ForaRun::kPairFinal;
-  }
-  if (r.phase == ForaRun::kPairFinal) {
-    const detail::PairPlan& pp = *r.pp;
-    const int ws = g->ws_index;
-    PPRHIP_CHECK_HIP(hipEventRecord(pp.ev[3 * ws + 1], g->stream));
-    // a target without in-edges left no residue: its values are exact, no walks
-    const uint32_t chunks = r.pair_walks ? pp.chunks : 0u;
-    double* const part = pp.d_part + (size_t)ws * pp.part_cap;
-    ktimer().begin(PPRHIP_KERNEL_WALK, 0);
-    for (uint32_t lo = r.pair_lo; lo < r.pair_hi; lo += pp.block_pairs) {
-      const uint32_t np = std::min(pp.block_pairs, r.pair_hi - lo);
-      if (chunks)
-        PPRHIP_TRY(launch_pair_walk(g, pp.d_src + lo, np, chunks, pp.chunk_walks, pp.walks, pp.alpha, pp.seed, part,
-                                    pp.d_steps));
-      PPRHIP_TRY(launch_pair_reduce(g, pp.d_src + lo, pp.d_pos + lo, np, chunks, part, pp.walks, pp.survival,
-                                    pp.d_values));
-    }
-    ktimer().end();
-    PPRHIP_CHECK_HIP(hipEventRecord(pp.ev[3 * ws + 2], g->stream));
-    if (chunks) {
-      r.st.walks += pp.walks * (uint64_t)(r.pair_hi - r.pair_lo);
-      r.st.mc_sources += r.pair_hi - r.pair_lo;
-    }
-    r.st.rounds = 1;
-    r.phase = ForaRun::kDone;
-  }
-  return PPRHIP_OK;
-}
-
-// A single-target query (BatchJob kTargets, targets.cpp): the backward push from set i of the call's table at the
-// call's threshold, under the handle's tuning, then value = p / S in place of the reserve (k_target_finish), which the
-// batch driver delivers like a whole-graph vector (top-k, result store, values_out).  A single target starts as
-// pair_begin starts its push; a set starts from r = w (k_target_init), its first frontier known to the host.
-static double host_ms() {
-  return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch()).count();
-}
-
-int target_begin(ForaRun& r, pprhip_graph* g, const detail::TargetPlan& tp, int i) {
-  const int32_t lone = tp.single[(size_t)i];
-  r.g = g;
-  r.kind = QueryKind::kTargets;
-  r.src = lone;
-  r.alpha = tp.alpha;
-  r.rmax_local = tp.rmax;
-  r.tp = &tp;
-  r.target_lone = -1;
-  std::memset(&r.st, 0, sizeof r.st);
-  g->topk_active = false;
-  PPRHIP_TRY(reset_query_state(g, false, tp.max_id[(size_t)i]));
-  r.push_t0 = host_ms();
-  r.waiting = false;
-  r.in_push = false;
-  r.a = PushArgs{tp.alpha, tp.rmax, 0.0, lone, kBackward};
-  r.L = LevelCtx();
-  if (lone >= 0) {
-    const uint32_t din = hdeg_in(g, lone);
-    if (din == 0) {  // p(t) = alpha, no residue (pair_begin)
-      PPRHIP_TRY(launch_set_f64(g, g->reserve, (uint32_t)lone, tp.alpha));
-      r.target_lone = lone;
-      r.phase = ForaRun::kTargetFinal;
-      return PPRHIP_OK;
-    }
-    PPRHIP_TRY(launch_set_f64(g, g->residue, (uint32_t)lone, 1.0));
-    PPRHIP_TRY(seed_single(g, r.L, lone, din));
-  } else {
-    // (the list counter is zero: reset_query_state cleared the counters, and a level's first prepare clears it again)
-    {
-      SetupScope setup(g);
-      PPRHIP_TRY(launch_target_init(g, tp.d_id + tp.first[(size_t)i], tp.d_w + tp.first[(size_t)i], tp.count[(size_t)i],
-                                    r.L.fcur, &g->ctr->hist[kMaxBatch + 2], tp.alpha, tp.rmax));
-    }
-    r.L.nf = tp.nf[(size_t)i];
-    r.L.ef = tp.ef[(size_t)i];
-    r.L.dense_prepared = false;
-    r.L.gs_dirty = false;
-  }
-  r.in_push = true;
-  r.phase = ForaRun::kBwdLevels;
-  return PPRHIP_OK;
-}
-
-int target_step(ForaRun& r, bool yield_dense) {
-  pprhip_graph* g = r.g;
-  if (r.phase == ForaRun::kBwdLevels) {
-    const int rc = run_levels(g, r.a, r.L, r.st, nullptr, yield_dense);
-    if (rc != PPRHIP_OK) return rc;  // kYield or an error
-    leave_push(r);
-    r.phase = ForaRun::kTargetFinal;
-  }
-  if (r.phase == ForaRun::kTargetFinal) {
-    r.st.push_ms = host_ms() - r.push_t0;  // (the last level's counters have been read: the push is over on the device)
-    {
-      SetupScope setup(g);
-      PPRHIP_TRY(launch_target_finish(g, r.tp->survival, act_n(g), r.target_lone));
-    }
-    r.st.rmax_final = r.rmax_local;
-    r.st.rounds = 1;
-    r.phase = ForaRun::kDone;
-  }
-  return PPRHIP_OK;
-}
-
 void add_stats(pprhip_stats_t& sum, const pprhip_stats_t& st) {
   sum.pops += st.pops; sum.edge_pushes += st.edge_pushes; sum.enqueues += st.enqueues;
   sum.dead_end_pops += st.dead_end_pops; sum.dense_nodes += st.dense_nodes; sum.dense_edges += st.dense_edges;
@@ -698,9 +489,9 @@ void add_stats(pprhip_stats_t& sum, const pprhip_stats_t& st) {
 
 int run_step(ForaRun& r, bool yield_dense) {
   switch (r.kind) {
-    case QueryKind::kPairs: return pair_step(r, yield_dense);
-    case QueryKind::kTargets: return target_step(r, yield_dense);
-    case QueryKind::kBackward: return bwd_step(r, yield_dense);
+    case QueryKind::kBackward:
+    case QueryKind::kPairs:
+    case QueryKind::kTargets: return bwd_step(r, yield_dense);
     case QueryKind::kTopk: return topk_step(r, yield_dense);
     case QueryKind::kFora: break;
   }

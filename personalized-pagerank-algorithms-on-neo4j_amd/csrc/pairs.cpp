@@ -1,7 +1,7 @@
 // pairs.cpp — single-pair PPR (beyond the reference): the bidirectional estimator of include/pprhip.h "single pairs"
 // (DESIGN.md §2 "Single pairs").  Argument checks, the grouping of a call's pairs by target, the survival vector S that
 // turns the backward push's leaking PPR into the engine's restarting one (kept on the lifted graph per alpha), and the
-// entry points.  The pushes and walks run as BatchJob kind kPairs of the batch driver (fora.cpp: pair_begin / pair_step).
+// entry points.  The pushes and walks run as BatchJob kind kPairs of the batch driver (bwd_runs.cpp: pair_begin / bwd_step).
 #include <algorithm>
 #include <chrono>
 #include <cmath>
@@ -250,13 +250,6 @@ int pprhip_ppr_pairs(pprhip_graph_t* g, const int32_t* sources, const int32_t* t
     J.eps = eps;
     J.conf = conf;
     J.seed = seed;
-    J.n_rounds = 0;
-    J.reserve_out = nullptr;
-    J.k = 0;
-    J.ids_out = nullptr;
-    J.vals_out = nullptr;
-    J.n_out = nullptr;
-    J.per_query = nullptr;
     J.alpha = conf->alpha;
     J.threshold = pp.rmax;
     J.pairs = &pp;

@@ -1,6 +1,7 @@
 // run.hpp — one query as a resumable run (ForaRun) and the five kinds of run: whole-graph FORA, FORA top-k, a backward
 // search of All-Pair, the push and walks of a pair call, the push and scaling of a single-target query.  fora.cpp
-// defines them; the batch drivers (batch.cpp) and the query stream (stream.cpp) step them.
+// defines the first two, bwd_runs.cpp the three that push backward; the batch drivers (batch.cpp) and the query stream
+// (stream.cpp) step them.
 #pragma once
 
 #include <algorithm>
@@ -44,7 +45,7 @@ struct ForaRun {
   PushArgs a;
   detail::RoundCut cut;
   enum Phase { kRoundStart, kLevels, kWalks, kWalkWait, kTopkRoundStart, kTopkLevels, kTopkRoundEnd, kTopkFinal, kBwdLevels,
-               kBwdFinal, kPairFinal, kTargetFinal, kDone } phase = kDone;
+               kBwdFinal, kDone } phase = kDone;  // kBwdLevels / kBwdFinal: every run that pushes backward (bwd_runs.cpp)
   hipStream_t side = nullptr;  // batch driver: the walk phase goes to this stream and the run yields until it has ended
   int query = -1;  // batch driver: index of the query this run serves
   detail::BatchJob* job = nullptr;  // ... and the call (or stream submission) that query belongs to
@@ -68,17 +69,17 @@ struct ForaRun {
   bool ahead_pending = false;    // a push ahead is queued and the compute stream has not joined it yet
   bool ahead_discarded = false;  // the last push ahead was not needed
   unsigned long long dead_before_ahead = 0;
+  // the runs that push backward (kBwdLevels, then kBwdFinal finishes by kind)
+  bool lone = false;  // the single target src has no in-edges: no level ran, src is the only entry of the vector
   // backward searches of All-Pair (kBackward): entries >= threshold of the finished search
   int32_t target_orig = -1;
   std::vector<detail::Triple> triples;
-  // single pairs (kPairs): the push runs in kBwdLevels, then the walks of the sorted pairs [pair_lo, pair_hi)
+  // single pairs (kPairs): after the push the walks of the sorted pairs [pair_lo, pair_hi) - none for a lone target
   const detail::PairPlan* pp = nullptr;
   uint32_t pair_lo = 0, pair_hi = 0;
-  bool pair_walks = false;  // the push left residue (the target has in-edges)
-  // single targets (kTargets): the push runs in kBwdLevels, then the division by S and the delivery of the vector
+  // single targets (kTargets): after the push the division by S and the delivery of the vector
   const detail::TargetPlan* tp = nullptr;
-  int32_t target_lone = -1;  // a single target without in-edges: the only entry of its vector (no level runs)
-  double push_t0 = 0.0;      // host clock at the query's begin (ms): push_ms is wall time on the workspace
+  double push_t0 = 0.0;  // host clock at the query's begin (ms): push_ms is wall time on the workspace
 };
 
 }  // namespace pprhip
@@ -99,11 +100,9 @@ int topk_begin_seeds(ForaRun& r, pprhip_graph* g, SeedTable& plan, double eps, c
                      uint64_t seed, int32_t* ids_out, double* vals_out, int cap);
 int topk_step(ForaRun& r, bool yield_dense);
 int bwd_begin(ForaRun& r, pprhip_graph* g, int32_t target_internal, int32_t target_orig, double alpha, double rmax);
-int bwd_step(ForaRun& r, bool yield_dense);
 int pair_begin(ForaRun& r, pprhip_graph* g, const PairPlan& pp, int32_t target_internal, uint32_t lo, uint32_t hi);
-int pair_step(ForaRun& r, bool yield_dense);
 int target_begin(ForaRun& r, pprhip_graph* g, const TargetPlan& tp, int i);  // set i of the plan
-int target_step(ForaRun& r, bool yield_dense);
+int bwd_step(ForaRun& r, bool yield_dense);  // the step of all three
 int run_step(ForaRun& r, bool yield_dense);  // the step of r's kind
 void leave_push(ForaRun& r);                 // the run's push phase is over (or given up): it stops holding sweeps off
 // omega and the threshold a whole-graph FORA query's first push runs at (every later one runs at a lower one)

@@ -3,79 +3,31 @@
 // the seed table in HBM, and the forward push from p (FORA: fora.cpp, top-k: engine.cpp).  DESIGN.md §2 "Seed sets"
 // states the rule.
 #include <algorithm>
-#include <cmath>
-#include <climits>
 #include <cstdint>
 #include <cstring>
-#include <string>
 
 #include "engine_internal.hpp"
 
 namespace pprhip {
 namespace detail {
 
-int seed_normalize(uint32_t n, const int32_t* seeds, const double* weights, int k, const char* fn,
-                   std::vector<int32_t>& ids, std::vector<double>& p) {
-  ids.clear();
-  p.clear();
-  if (k <= 0 || !seeds) {
-    set_error("%s: a seed set needs at least one seed (n_seeds=%d)", fn, k);
-    return PPRHIP_ERR_INVALID;
-  }
-  std::vector<std::pair<int32_t, double>> e((size_t)k);
-  for (int i = 0; i < k; ++i) {
-    const int32_t v = seeds[i];
-    if (v < 0 || (uint32_t)v >= n) {
-      set_error("%s: seed %d: node id %d outside [0, %u)", fn, i, v, n);
-      return PPRHIP_ERR_INVALID;
-    }
-    const double w = weights ? weights[i] : 1.0;
-    if (!std::isfinite(w) || w < 0.0) {
-      set_error("%s: seed %d: weight %g is not a finite non-negative number", fn, i, w);
-      return PPRHIP_ERR_INVALID;
-    }
-    e[(size_t)i] = {v, w};
-  }
-  std::sort(e.begin(), e.end(), [](const std::pair<int32_t, double>& a, const std::pair<int32_t, double>& b) {
-    return a.first < b.first;
-  });
-  double sum = 0.0;
-  for (const auto& x : e) sum += x.second;
-  if (!(sum > 0.0) || !std::isfinite(sum)) {
-    set_error("%s: the seed weights sum to %g", fn, sum);
-    return PPRHIP_ERR_INVALID;
-  }
-  for (size_t i = 0; i < e.size();) {  // duplicates are summed, zero weights dropped
-    size_t j = i;
-    double w = 0.0;
-    for (; j < e.size() && e[j].first == e[i].first; ++j) w += e[j].second;
-    if (w > 0.0) {
-      ids.push_back(e[i].first);
-      p.push_back(w / sum);
-    }
-    i = j;
-  }
-  return PPRHIP_OK;
-}
-
 int seed_plan(pprhip_graph* g, const int32_t* seeds, const double* weights, int k, double alpha, const char* fn,
-              SeedTable& t) {
-  std::vector<int32_t> ids;
-  std::vector<double> p;
-  PPRHIP_TRY(seed_normalize(g->gr->n, seeds, weights, k, fn, ids, p));
+              SeedTable& t, int set) {
+  WeightedSet p;  // distinct original ids and their normalized weights
+  PPRHIP_TRY(parse_weighted_set(g->gr->n, seeds, weights, k, true, "seed", fn, set, p));
   struct E {
     int32_t v;
     double p;
   };
   std::vector<E> live, dead;
   double D = 0.0;
-  for (size_t i = 0; i < ids.size(); ++i) {
-    const int32_t v = g->gr->h_old2new[ids[i]];
+  for (const auto& x : p) {
+    const int32_t v = g->gr->h_old2new[x.first];
     if (hdeg_out(g, v) == 0) {
-      dead.push_back({v, p[i]});
-      D += p[i];
+      dead.push_back({v, x.second});
+      D += x.second;
     } else {
-      live.push_back({v, p[i]});
+      live.push_back({v, x.second});
     }
   }
   auto by_id = [](const E& a, const E& b) { return a.v < b.v; };
@@ -117,28 +69,17 @@ int seed_plan_sets(pprhip_graph* g, const int32_t* seeds, const double* weights,
     return PPRHIP_ERR_INVALID;
   }
   if (q == 0) return PPRHIP_OK;
-  if (offsets[0] != 0) {
-    set_error("%s: offsets[0] = %llu, not 0", fn, (unsigned long long)offsets[0]);
-    return PPRHIP_ERR_INVALID;
-  }
-  for (int i = 0; i < q; ++i)
-    if (offsets[i + 1] < offsets[i] || offsets[i + 1] - offsets[i] > (uint64_t)INT32_MAX) {
-      set_error("%s: set %d: offsets %llu .. %llu do not describe a set", fn, i, (unsigned long long)offsets[i],
-                (unsigned long long)offsets[i + 1]);
-      return PPRHIP_ERR_INVALID;
-    }
+  PPRHIP_TRY(check_set_offsets(offsets, q, fn));
   if (offsets[q] > 0 && !seeds) {
     set_error("%s: seeds is NULL for %llu entries", fn, (unsigned long long)offsets[q]);
     return PPRHIP_ERR_INVALID;
   }
   try {
     plans.resize((size_t)q);
-    std::string where;
     for (int i = 0; i < q; ++i) {
-      where = std::string(fn) + ": set " + std::to_string(i);
       const size_t o = (size_t)offsets[i];
       const int rc = seed_plan(g, seeds ? seeds + o : nullptr, weights ? weights + o : nullptr,
-                               (int)(offsets[i + 1] - offsets[i]), alpha, where.c_str(), plans[(size_t)i]);
+                               (int)(offsets[i + 1] - offsets[i]), alpha, fn, plans[(size_t)i], i);
       if (rc != PPRHIP_OK) {
         plans.clear();
         return rc;
@@ -273,19 +214,27 @@ int pprhip_forward_push_seeds(pprhip_graph_t* g, const int32_t* seeds, const dou
 }
 
 #ifdef PPRHIP_TEST_HOOKS
+// Test hook (libpprhip_hooks.so only): the parser behind the seed sets and behind the target sets of pprhip_ppr_targets,
+// without a device, as `fn` would call it: `noun` "seed" or "target", the weights divided by their sum (normalize != 0)
+// or as given.  ids_out / w_out hold `count` entries; *count_out receives the distinct ids of non-zero weight.
+int pprhip_hook_parse_weighted_set(uint32_t n, const int32_t* ids_in, const double* weights, int count, int normalize,
+                                   const char* noun, const char* fn, int32_t* ids_out, double* w_out, int* count_out) {
+  WeightedSet e;
+  PPRHIP_TRY(parse_weighted_set(n, ids_in, weights, count, normalize != 0, noun, fn, -1, e));
+  for (size_t i = 0; i < e.size(); ++i) {
+    if (ids_out) ids_out[i] = e[i].first;
+    if (w_out) w_out[i] = e[i].second;
+  }
+  if (count_out) *count_out = (int)e.size();
+  return PPRHIP_OK;
+}
+
 // Test hook (libpprhip_hooks.so only): the argument normalization of the seed-set entry points, without a device.
 // ids_out / p_out hold n_seeds entries; *count_out receives the distinct seeds of non-zero weight.
 int pprhip_hook_seed_normalize(uint32_t n, const int32_t* seeds, const double* weights, int n_seeds, int32_t* ids_out,
                                double* p_out, int* count_out) {
-  std::vector<int32_t> ids;
-  std::vector<double> p;
-  PPRHIP_TRY(seed_normalize(n, seeds, weights, n_seeds, "pprhip_hook_seed_normalize", ids, p));
-  for (size_t i = 0; i < ids.size(); ++i) {
-    if (ids_out) ids_out[i] = ids[i];
-    if (p_out) p_out[i] = p[i];
-  }
-  if (count_out) *count_out = (int)ids.size();
-  return PPRHIP_OK;
+  return pprhip_hook_parse_weighted_set(n, seeds, weights, n_seeds, 1, "seed", "pprhip_hook_seed_normalize", ids_out,
+                                        p_out, count_out);
 }
 #endif
 

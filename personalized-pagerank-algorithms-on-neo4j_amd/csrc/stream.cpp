@@ -7,7 +7,6 @@
 // pprhip_fora_batch_single_source would run it (same seed, same tuning, same result).
 #include <chrono>
 #include <condition_variable>
-#include <cstring>
 #include <deque>
 #include <map>
 #include <memory>
@@ -207,16 +206,12 @@ int pprhip_fora_stream_submit(pprhip_stream_t* s, const int32_t* srcs, int q, ui
   J->eps = s->eps;
   J->conf = &s->conf;
   J->seed = seed;
-  J->n_rounds = 0;
-  J->reserve_out = nullptr;
   J->k = s->k;
   J->ids_out = ids_out;
   J->vals_out = vals_out;
   J->n_out = n_out;
-  J->per_query = nullptr;
   J->keep = keep;
   J->keep_first = keep_first;
-  std::memset(&J->sum, 0, sizeof J->sum);
   J->t0 = std::chrono::steady_clock::now();
   std::lock_guard<std::mutex> lk(s->mu);
   if (s->err != PPRHIP_OK) return stream_error(s, "pprhip_fora_stream_submit");

@@ -1,6 +1,6 @@
 """Single pairs beyond the two operating points of tests/test_gpu_pairs.py (DESIGN.md §2 "Single pairs", §3): every
 walk-count regime of k_pair_walk against the oracle-side twin (tests/test_pairs_twin.py: nothing of the engine's goes
-into the expected value), the block loop of pair_step over a target's sources, the exact identity the estimator rests on
+into the expected value), the block loop of finish_pairs (bwd_runs.cpp) over a target's sources, the exact identity the estimator rests on
 with the engine's push and survival, a Hoeffding-tight accuracy bound, and the survival kernels on a graph built to
 straddle every row split (8 lanes per row below out-degree 512, a workgroup per row from 512 on).
 
@@ -129,7 +129,7 @@ def test_walk_count_ladder_rmat12_dense_push(pkg, rmat12, dev_r12, r12_twin, w):
 # ------------------------------------------------------------------ b. the block loop
 def _block_conf(pkg, got, rmax):
     """w = 524 289 gives 512 items per pair, so a walk launch takes PART_CAP / 512 = 1 024 pairs and a target with more
-    sources runs the loop of pair_step more than once."""
+    sources runs the loop of finish_pairs (bwd_runs.cpp) more than once."""
     w = 524289
     conf = conf_for_walks(pkg, got, A, rmax, w)
     assert pkg.pair_params(conf, PAIR_EPS, rmax) == (rmax, w)

@@ -1,5 +1,5 @@
 """The top-k radix select (kernels_select.hip, driven by select_finish / select_topk_passes in select.cpp) past its
-first pass and past its candidate buffer, and the same overflow in the backward search (bwd_step in fora.cpp).
+first pass and past its candidate buffer, and the same overflow in the backward search (finish_search in bwd_runs.cpp).
 
 A seed set whose seeds are all dead ends leaves reserve = w / sum(w) and runs no level (seeds.cpp: seed_plan), so on an
 out-star the seed weights load any vector into the reserve, up to one common correctly rounded division;
@@ -25,7 +25,7 @@ finish (7 passes counted); all-whole: no k-th, one histogram, whole-vector finis
 
 The other cases: candidate-count edge 2047 / 2048 (fast) and 2049 (fast2); wide range, small-after-large, isolated
 seeds, tiny-after-whole: fast, and "all" for k > entries; fora_topk_seeds s16 k = 101: p48; fora_batch_topk_seeds
-k = 128: p48, whole, all; all_pair_backward from tier 3: the bwd_step overflow.
+k = 128: p48, whole, all; all_pair_backward from tier 3: the finish_search overflow.
 Wall time of this file on an MI355X: 6.5 s for its 25 cases (pytest's total); the slowest, a family of 11 selects with
 the oracle's sorts, takes 0.9 s.
 """
@@ -138,7 +138,7 @@ def family_ks(npos):
 
 
 def shuffled_seeds(ids, w, seed=7):
-    """the set in a shuffled order (seed_normalize sorts it by id again)"""
+    """the set in a shuffled order (parse_weighted_set sorts it by id again)"""
     perm = np.random.default_rng(seed).permutation(len(ids))
     return np.asarray(ids, dtype=np.int32)[perm], np.asarray(w, dtype=np.float64)[perm]
 
@@ -238,7 +238,7 @@ def test_model_and_builders():
         w = family_weights(name)
         assert w.size == N_LEAVES and np.all(w > 0.0) and np.array_equal(w, family_weights(name))
         assert int(((w >= 1.0) & (w < 2.0)).sum()) == N_CLUSTER and int((w >= 2.0).sum()) == N_HEAD
-        p = w / np.cumsum(w)[-1]  # what seed_normalize makes of it (sum in id order, one division per entry)
+        p = w / np.cumsum(w)[-1]  # what parse_weighted_set makes of it (sum in id order, one division per entry)
         got = {select_path(p, k)[0] for k in family_ks(N_LEAVES)}
         assert FAMILY_PATHS[name] | {"all-whole"} <= got, (name, got)
 
@@ -422,7 +422,7 @@ def test_all_pair_backward_overflow(pkg, dev_in_star, in_star_ref, k, tier, monk
     """One target, the hub, whose search finds every node: 2^18 + 9293 sources, more than the candidate buffer holds.
     By the default routing and from each tier PPRHIP_APBS_TIER can start at; every tier takes a search of this size
     and returns rows (none answers with an error code).  Started at tier 3 the search runs on a batch workspace and
-    ends in bwd_step, whose gather overflows (cnt > sel_cap) and whose entries then come from the whole vector."""
+    ends in finish_search (bwd_runs.cpp), whose gather overflows (cnt > sel_cap) and whose entries then come from the whole vector."""
     if tier is not None:
         monkeypatch.setenv("PPRHIP_APBS_TIER", tier)
     _, thr, ref = in_star_ref

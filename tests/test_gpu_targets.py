@@ -39,12 +39,18 @@ def exact(cache, name, host, alpha):
     return cache[key]
 
 
+def hub_and_no_in(host):
+    """The largest in-degree node and the first node without in-edges (but with out-edges)."""
+    od, idg = np.diff(host.out_rp.astype(np.int64)), np.diff(host.in_rp.astype(np.int64))
+    return int(np.argmax(idg)), int(np.flatnonzero((idg == 0) & (od > 0))[0])
+
+
 def special_targets(host, rng, count):
     """`count` targets that include the largest in-degree node, a node without in-edges (but with out-edges), a dead
     end, a node with a self loop and an isolated node."""
     od, idg = np.diff(host.out_rp.astype(np.int64)), np.diff(host.in_rp.astype(np.int64))
     loops = [u for u in range(host.n) if u in host.out_ci[int(host.out_rp[u]):int(host.out_rp[u + 1])]]
-    picks = [int(np.argmax(idg)), int(np.flatnonzero((idg == 0) & (od > 0))[0]), int(np.flatnonzero((od == 0) & (idg > 0))[0]),
+    picks = [*hub_and_no_in(host), int(np.flatnonzero((od == 0) & (idg > 0))[0]),
              int(loops[0]), int(np.flatnonzero((od == 0) & (idg == 0))[0])]
     rest = [int(v) for v in rng.permutation(host.n) if int(v) not in picks][:count - len(picks)]
     return np.array(picks + rest, dtype=np.int32), picks
@@ -105,6 +111,50 @@ def test_targets_equal_their_parts(pkg, rmat12, dev_r12):
             assert pq[i].pops == 0 and pq[i].levels == 0
             seen.add("noin")
     assert seen == {"in", "noin"}
+
+
+def test_backward_kinds_share_their_push(pkg, got, dev_got, rmat12, dev_r12, monkeypatch):
+    """The backward kinds share their push and differ only at a target without in-edges.  For a target without in-edges,
+    the hub and an ordinary target of each graph: (a) backward_push(t), (b) all_pair_backward over [t, t + 1) started at
+    tier 3, a kBackward job on the batch slots, (c) ppr_targets([t]) multiplied back by the survival vector.  With
+    in-edges (b) holds (a)'s reserve entries at or above the threshold and (c) * S is (a)'s reserve, both to the
+    tolerance of test_targets_equal_their_parts; without, (a) and (b) hold reserve(t) = 1.0 (Backward_Search.java:46-49)
+    and (c) holds alpha / S(t), and nothing else.  That is the exact statement after the kernel's division; "(c) * S is
+    exactly alpha" is asserted as |value * S(t) - alpha| <= 2^-52 alpha, a rounding for the division and one for the
+    product.  (Pairs: test_pairs_equal_host_recomputation_from_parts.)"""
+    rmax, rtol = 1e-4, 1e-12
+    for g, host in ((dev_got, got), (dev_r12, rmat12)):
+        g.set_tuning(pkg.tuning_default())
+        idg = np.diff(host.in_rp.astype(np.int64))
+        picks = list(hub_and_no_in(host))  # (special_targets' first two; GOT has neither a self loop nor an isolated node)
+        picks.append(next(int(v) for v in np.random.default_rng(12).permutation(host.n)
+                          if int(v) not in picks and idg[v] > 0))
+        S = g.walk_survival(A)
+        for t in picks:
+            p, r, _ = g.backward_push(t, A, rmax)
+            monkeypatch.setenv("PPRHIP_APBS_TIER", "3")
+            ix, st = g.all_pair_backward(A, rmax, -1, t_begin=t, t_end=t + 1)
+            monkeypatch.delenv("PPRHIP_APBS_TIER")
+            off, tg, vl = ix.arrays()
+            ix.close()
+            assert st.dense_nodes == 1 and np.all(tg == t) and np.all(np.diff(off) <= 1)  # the batch tier; one target
+            entries = np.zeros(host.n)
+            entries[np.flatnonzero(np.diff(off))] = vl
+            values, _, _, pq = g.ppr_targets([t], A, rmax)
+            if idg[t] > 0:
+                held = entries > 0
+                assert np.allclose(entries[held], p[held], rtol=rtol, atol=0), t
+                assert np.all(p[held] >= rmax * (1 - rtol)) and np.all(held[p >= rmax * (1 + rtol)]), t
+                assert np.allclose(values[0] * S, p, rtol=rtol, atol=0), t
+                assert pq[0].pops > 0
+            else:
+                e_t = np.zeros(host.n)
+                e_t[t] = 1.0
+                assert np.array_equal(p, e_t) and not r.any(), t
+                assert np.array_equal(entries, e_t), t
+                assert np.array_equal(values[0], A / S[t] * e_t), t  # alpha, divided by S(t) once ...
+                assert abs(values[0][t] * S[t] - A) <= 2.0 ** -52 * A  # ... and multiplied back: a rounding each
+                assert pq[0].pops == 0 and pq[0].levels == 0
 
 
 # ------------------------------------------------------------------ 3. batch invariance

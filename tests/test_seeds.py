@@ -131,6 +131,69 @@ def test_normalization_rules(pkg):
         assert rc == -1, (seeds, w)
 
 
+def _parse_set(pkg, n, ids_in, weights, normalize, noun):
+    """The parser the seed sets and the target sets share, through its hook: (rc, ids, weights, message)."""
+    L = pkg.lib()
+    L.pprhip_hook_parse_weighted_set.argtypes = [C.c_uint32, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_char_p,
+                                                  C.c_char_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_int)]
+    s = np.ascontiguousarray(ids_in, dtype=np.int32)
+    w = None if weights is None else np.ascontiguousarray(weights, dtype=np.float64)
+    ids = np.zeros(max(s.size, 1), dtype=np.int32)
+    out = np.zeros(max(s.size, 1))
+    cnt = C.c_int(-1)
+    rc = L.pprhip_hook_parse_weighted_set(n, s.ctypes.data if s.size else None, None if w is None else w.ctypes.data,
+                                          s.size, int(normalize), noun.encode(), b"caller", ids.ctypes.data,
+                                          out.ctypes.data, C.byref(cnt))
+    msg = L.pprhip_last_error().decode("utf-8", "replace") if rc != 0 else ""
+    return rc, ids[:max(cnt.value, 0)], out[:max(cnt.value, 0)], msg
+
+
+# sets of at most 12 entries; the weights of a repeated id are dyadic, so their sum is exact in any order
+PARSED_SETS = [
+    ([3, 1, 3, 7], None),                                                       # duplicates, uniform weights
+    ([4, 2, 4, 9], [1.0, 0.0, 3.0, 4.0]),                                       # ... and a zero weight
+    ([5], [0.3]),                                                               # a lone member, weight not 1
+    ([5], None),
+    ([11, 0, 6, 0, 2, 11, 8, 0, 6, 3, 9, 1],
+     [0.5, 0.25, 0.1, 0.125, 0.7, 1.5, 0.0, 2.0, 0.3, 1e-9, 3.3, 0.0]),         # 12 entries, 0 three times, 6 and 11 twice
+]
+
+
+@pytest.mark.hooks
+@pytest.mark.parametrize("noun", ["seed", "target"])
+def test_shared_set_parser_against_numpy_and_the_seed_hook(pkg, noun):
+    n = 12
+    for ids_in, w in PARSED_SETS:
+        wv = np.ones(len(ids_in)) if w is None else np.asarray(w, dtype=np.float64)
+        dense = np.bincount(np.asarray(ids_in), weights=wv, minlength=n)  # (per id: one weight, a + b, or dyadic sums)
+        want_ids = np.flatnonzero(dense > 0)
+        rc, ids, got, _ = _parse_set(pkg, n, ids_in, w, False, noun)
+        assert rc == 0 and ids.tolist() == want_ids.tolist(), (ids_in, w)
+        assert got.tolist() == dense[want_ids].tolist(), (ids_in, w)  # unchanged, duplicates as their sum: exactly
+        rc, ids, got, _ = _parse_set(pkg, n, ids_in, w, True, noun)
+        rc0, ids0, p0 = _normalize(pkg, n, ids_in, w)
+        assert rc == 0 and rc0 == 0 and ids.tolist() == ids0.tolist()
+        assert got.tobytes() == p0.tobytes(), (ids_in, w)  # bit for bit what the seed-set entry points get
+        # against numpy: two sums of k <= 12 non-negative terms differ by at most 2 (k - 1) u, each division adds u
+        assert np.allclose(got, dense[want_ids] / wv.sum(), rtol=24 * 2.0 ** -53, atol=0)
+
+
+@pytest.mark.hooks
+@pytest.mark.parametrize("noun", ["seed", "target"])
+@pytest.mark.parametrize("normalize", [False, True])
+def test_shared_set_parser_refusals_name_the_noun(pkg, noun, normalize):
+    n = 12
+    refused = [([], None),                                  # the empty set
+               ([n], None), ([1, n, 2], [1.0, 1.0, 1.0]),   # an id of n
+               ([1, 2], [1.0, -0.5]),                       # a negative weight
+               ([1], [float("nan")]),                       # a NaN weight
+               ([1, 2, 2], [0.0, 0.0, 0.0])]                # all-zero weights
+    for ids_in, w in refused:
+        rc, ids, got, msg = _parse_set(pkg, n, ids_in, w, normalize, noun)
+        assert rc == pkg.ERR_INVALID and ids.size == 0 and got.size == 0, (ids_in, w)
+        assert msg.startswith("caller: ") and noun in msg, msg  # (the calling function's name, then the noun)
+
+
 # ------------------------------------------------------------------ the rule-B oracle on closed forms
 def test_rule_b_cycle_two_seeds_is_linear(pkg_product):
     n = 5
