@@ -64,7 +64,7 @@ constexpr uint32_t kNoFold = 0xffffffffu;
 struct PanelDesc {                       // per panel: its S parts' sums are part[base + k * rows + local row], k < S;
   uint32_t base, parts, rows, fold;      // fold != kNoFold: ceil(S / kFoldParts) sums of kFoldParts parts each at
 };                                       // part[fold + g * rows + local row] (k_panel_fold)
-constexpr int kTileRows = 64;   // rows per tile of the batched apply kernel (kernels_push.hip: kApplyRows)
+constexpr int kTileRows = 64;   // rows per tile of the batched apply kernel (kernels_dense_batch.hip: kApplyRows)
 
 // packed frontier counter: entries in the high 28 bits, edge total in the low 36 bits
 constexpr int kPackShift = 36;

@@ -605,6 +605,17 @@ int launch_sparse_levels_wg(pprhip_graph* g, const pprhip::PushArgs& a, int fbuf
                             unsigned long long pk0);
 int launch_sparse_push(pprhip_graph* g, const PushArgs& a, int fbuf, int level, uint64_t ef_upper,
                        unsigned long long dense_thresh, int dead_slot, unsigned long long pk0 = ~0ull);
+// seed sets (g->seeds): the landing of a sparse level's dead-end mass on p (between the level's two kernels; the dense
+// levels land in launch_dense_level)
+int launch_seed_land_sparse(pprhip_graph* g, const PushArgs& a, int fbuf, int level, unsigned long long dense_thresh,
+                            int dead_slot, unsigned long long pk0);
+// Every kernel file has an init_kernels_*: it loads the file's code object and opts the file's own kernels into
+// their large dynamic LDS.  Once per device, the thread that lifts the first graph onto it calls them all
+// (graph.cpp: init_device_once), so that no launch path sets function attributes or triggers a module load
+// later (worker threads launch concurrently).
+int init_kernels_push();
+
+// ---- kernels_dense.hip
 // One dense level of a single query, block by block (blocks: nullptr / 1 = the whole sweep at once).  state_in:
 // device cell holding this level's GsState (a level launched behind another one without a host round trip; kGsNone:
 // the kernels return at once), or nullptr: `state0` applies.  hist_out / state_out (nullable) receive the frontier
@@ -624,6 +635,9 @@ namespace detail {
 // levels.cpp: the sliced layout's edge windows of every block (nullptr / 1: the whole sweep)
 const EdgeWindows* sliced_windows_of(pprhip_graph* g, const GsBlock* blocks, int nb);
 }
+int init_kernels_dense();
+
+// ---- kernels_dense_batch.hip
 constexpr uint32_t kApplyBlocks8 = 2048;  // workgroups of the batched apply kernel (per-slot partials each)
 // slot arguments already staged in parent->batch->h_slot_args; blocks: Gauss-Seidel blocks (nullptr / 1: one launch)
 int launch_dense_level_b8(pprhip_graph* parent, bool backward, const pprhip::GsBlock* blocks = nullptr, int n_blocks = 1);
@@ -631,6 +645,9 @@ int launch_dense_level_b8(pprhip_graph* parent, bool backward, const pprhip::GsB
 int launch_sweep_edges_only(pprhip_graph* parent, const pprhip::GsBlock& B);
 int launch_count_live_lines(pprhip_graph* P, unsigned long long* d_out);
 #endif
+int init_kernels_dense_batch();
+
+// ---- kernels_frontier.hip
 int launch_compact_prepared(pprhip_graph* g, int cbuf, int out_fbuf, unsigned long long* d_counter, bool backward);
 int launch_count_active(pprhip_graph* g, const PushArgs& a, int seed_kind, int out_slot);
 int launch_seed_list(pprhip_graph* g, const PushArgs& a, int seed_kind, int out_fbuf, unsigned long long* d_counter,
@@ -643,17 +660,12 @@ inline uint32_t act_n(const pprhip_graph* g) { return g->n_act ? g->n_act : g->g
 int launch_set_f64(pprhip_graph* g, double* p, uint32_t idx, double value);
 int launch_permute_out(pprhip_graph* g, const double* x, double* out);  // out[old] = x[old2new[old]]
 // seed sets (g->seeds): the query's start from p (residue, dead-end reserves, landing weights, and the frontier list
-// fbuf - top-k: the parked flags instead), the landing weights of the set before cleared (its first `count` entries), and
-// the landing of a sparse level's dead-end mass on p (between the level's two kernels; the dense levels land in
-// launch_dense_level)
+// fbuf - top-k: the parked flags instead), and the landing weights of the set before cleared (its first `count` entries)
 int launch_seed_init(pprhip_graph* g, int fbuf, bool topk = false);
 int launch_seed_clear(pprhip_graph* g, uint32_t count);
-int launch_seed_land_sparse(pprhip_graph* g, const PushArgs& a, int fbuf, int level, unsigned long long dense_thresh,
-                            int dead_slot, unsigned long long pk0);
-// Once per device, from the thread that lifts the first graph onto it: loads the code object of every
-// kernel file and opts the persistent sweep kernels into their large dynamic LDS, so that no launch
-// path sets function attributes or triggers a module load later (worker threads launch concurrently).
-int init_kernels_push();
+int init_kernels_frontier();
+
+// ---- the other kernel files' init_kernels_* (see init_kernels_push)
 int init_kernels_walk();
 int init_kernels_select();
 int init_kernels_apbs();

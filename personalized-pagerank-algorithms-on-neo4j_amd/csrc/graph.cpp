@@ -37,6 +37,9 @@ int init_device_once(int device) {
   std::lock_guard<std::mutex> lk(g_dev_init_mu);
   if ((size_t)device < g_dev_inited.size() && g_dev_inited[device]) return PPRHIP_OK;
   PPRHIP_TRY(init_kernels_push());
+  PPRHIP_TRY(init_kernels_dense());
+  PPRHIP_TRY(init_kernels_dense_batch());
+  PPRHIP_TRY(init_kernels_frontier());
   PPRHIP_TRY(init_kernels_walk());
   PPRHIP_TRY(init_kernels_select());
   PPRHIP_TRY(init_kernels_apbs());

@@ -1,7 +1,8 @@
 // kernels_target.hip — single-target queries (include/pprhip.h "single targets", DESIGN.md §2 "Single targets") for
 // gfx950: the start of a backward push from a weighted target set, and the pass that turns the finished push's
 // reserve p (the leaking PPR's lower bound) into the engine's restarting PPR, value(s) = p(s) / S(s).  The levels in
-// between are the backward kernels of kernels_push.hip unchanged: sharing their batched sweeps is the point.
+// between are the backward kernels of kernels_push.hip and kernels_dense_batch.hip unchanged: sharing their batched
+// sweeps is the point.
 #include <algorithm>
 
 #include "device_utils.hpp"

@@ -1,7 +1,8 @@
 // levels.cpp — the level loop (run_levels: batches of dense and of sparse levels until the frontier is empty) and
 // what only it uses: the packed frontier counters, the level cost model, the Gauss-Seidel block plan and the sliced
 // layout's windows, and the scans that seed a frontier.  Read-backs and scopes: device_io.cpp; workspaces and
-// layouts: graph.cpp; the kernels: kernels_push.hip (shared declarations: engine_internal.hpp).
+// layouts: graph.cpp; the kernels: kernels_push.hip, kernels_dense.hip, kernels_frontier.hip (shared declarations:
+// engine_internal.hpp).
 #include <algorithm>
 #include <cmath>
 #include <cstdio>

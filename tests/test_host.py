@@ -34,6 +34,23 @@ def test_product_never_touches_the_oracle():
                     assert needle not in txt, "%s references the oracle (%s)" % (f, needle)
 
 
+def test_every_kernel_file_is_initialised_once_per_device():
+    """Every csrc/kernels_X.hip defines init_kernels_X (code object loaded, its own kernels' LDS opt-ins) and
+    graph.cpp's init_device_once calls it: a forgotten call loads the code object lazily, on whichever worker thread
+    launches first, and no functional test catches that reliably."""
+    pk = os.path.join(ROOT, "personalized-pagerank-algorithms-on-neo4j_amd")
+    src_hip = re.search(r"^SRC_HIP\s*:=\s*(.*)$", open(os.path.join(pk, "Makefile")).read(), re.M).group(1).split()
+    names = [re.fullmatch(r"csrc/kernels_(\w+)\.hip", f) for f in src_hip]
+    assert names and all(names), src_hip
+    graph = open(os.path.join(pk, "csrc", "graph.cpp")).read()
+    once = re.search(r"^int init_device_once\(int device\) \{\n(.*?)^\}", graph, re.M | re.S).group(1)
+    for m in names:
+        init = "init_kernels_%s" % m.group(1)
+        assert re.search(r"^int %s\(\) \{" % init, open(os.path.join(pk, m.group(0))).read(), re.M), \
+            "%s does not define %s()" % (m.group(0), init)
+        assert re.search(r"\b%s\(\)" % init, once), "init_device_once does not call %s()" % init
+
+
 def test_no_gpu_fails_loudly(pkg, got):
     if pkg.device_count() > 0:
         pytest.skip("a GPU is present")
