@@ -291,6 +291,7 @@ void pprhip_lift_destroy(pprhip_lift_t* lift);
 #define PPRHIP_RELEASE_BATCH 2u
 #define PPRHIP_RELEASE_WALK_INDEX 4u /* the walk index (pprhip_walk_index_build): as pprhip_walk_index_drop */
 #define PPRHIP_RELEASE_SWEEP 8u      /* the sweep cut's workspace (pprhip_sweep_cut: ranks, sort buffers, the profile) */
+#define PPRHIP_RELEASE_SPARSE 16u    /* the sparse getters' workspace (tile counts, compacted entries, sort buffers) */
 int pprhip_graph_release(pprhip_graph_t* g, unsigned what);
 int pprhip_graph_info(const pprhip_graph_t* g, uint32_t* n, uint64_t* m, int* device);
 /* HBM of the handle's device: bytes free and in all (hipMemGetInfo) - what a job holds at a point of its run is
@@ -301,6 +302,29 @@ int pprhip_graph_get_tuning(const pprhip_graph_t* g, pprhip_tuning_t* t);
 /* Results of the last compute call that left them in HBM. */
 int pprhip_get_reserve(pprhip_graph_t* g, double* reserve_out /* n */);
 int pprhip_get_residue(pprhip_graph_t* g, double* residue_out /* n */);
+/* ---- sparse results (beyond the reference)
+ * The sparse form of a vector x (in original ids: what the dense getter returns) is its entries with x(v) > threshold,
+ * each a pair (id, value) whose value has the bits the dense getter returns; compacted on the device, so that
+ * 12 bytes per kept entry cross PCIe and not 8 per node.  threshold is finite and >= 0; threshold = 0 gives the
+ * reference's HashMap<Long, Double> (entries > 0; -0.0 and NaN are never kept).  Orders:
+ *   PPRHIP_SPARSE_BY_ID     id ascending: the ids are flatnonzero(x > threshold);
+ *   PPRHIP_SPARSE_BY_VALUE  value descending, ties by id ascending - the order of the top-k calls.
+ * The result is deterministic: the same bytes every run.  *count_out is the number of kept entries whatever cap is; the
+ * first min(cap, count) entries of the ordered sequence are written (the convention of pprhip_walk_index_fetch and the
+ * top-k calls), so by-value with a small cap is "the cap largest", and cap = 0 with null buffers is the counting
+ * call.  ids_out and vals_out may each be NULL.  Checked before the handle is looked at, PPRHIP_ERR_INVALID: threshold
+ * finite and >= 0, order in {0, 1}, a non-null count pointer (and offsets_out), no output buffer with cap == 0.  While a
+ * query stream is open: PPRHIP_ERR_STATE.  The vector is not modified: the dense getters, pprhip_topk_select and
+ * pprhip_sweep_cut give afterwards what they gave before.  The workspace (8 bytes per 1024 nodes and vector, 12 bytes per
+ * kept entry, 24 more per entry for by-value) grows on demand and stays on the handle: pprhip_graph_release(
+ * PPRHIP_RELEASE_SPARSE) and pprhip_graph_destroy free it. */
+#define PPRHIP_SPARSE_BY_ID 0
+#define PPRHIP_SPARSE_BY_VALUE 1
+/* over the vector pprhip_get_reserve / pprhip_get_residue would return */
+int pprhip_get_reserve_sparse(pprhip_graph_t* g, double threshold, int order, int32_t* ids_out, double* vals_out,
+                              uint64_t cap, uint64_t* count_out);
+int pprhip_get_residue_sparse(pprhip_graph_t* g, double threshold, int order, int32_t* ids_out, double* vals_out,
+                              uint64_t cap, uint64_t* count_out);
 
 /* ---------------------------------------------------------------- forward push (a1, a2) */
 /* Forward_Push.computeWholeGraphPPR(Long s, Object rmax) (Forward_Push.java:63-142), run as a
@@ -369,6 +393,14 @@ void pprhip_results_destroy(pprhip_results_t* r);
 int pprhip_results_info(const pprhip_results_t* r, int* capacity, int* count, uint32_t* n);
 /* vector of query i, caller's ids (n doubles) */
 int pprhip_results_fetch(pprhip_results_t* r, int i, double* reserve_out);
+/* vector of query i in sparse form ("sparse results" above) */
+int pprhip_results_fetch_sparse(pprhip_results_t* r, int i, double threshold, int order, int32_t* ids_out,
+                                double* vals_out, uint64_t cap, uint64_t* count_out);
+/* every vector the store holds, as one CSR: offsets_out[count + 1] (always filled), row i = entries
+ * [offsets[i], offsets[i + 1]) of vector i in the chosen order; *total_out = offsets[count]; the first min(cap, total)
+ * entries of the concatenated rows are written.  An empty store gives offsets {0} and total 0. */
+int pprhip_results_fetch_sparse_all(pprhip_results_t* r, double threshold, int order, uint64_t* offsets_out,
+                                    int32_t* ids_out, double* vals_out, uint64_t cap, uint64_t* total_out);
 /* sum of the vector of query i, computed on the device (a cheap mass check: 1 up to rounding when walks ran) */
 int pprhip_results_sum(pprhip_results_t* r, int i, double* sum_out);
 /* pprhip_fora_batch_single_source with the vectors kept in `keep` (q <= capacity); reserve_out may still be given. */

@@ -99,7 +99,11 @@ EXPORTS = [
     "pprhip_walk_index_density", "pprhip_walk_index_build", "pprhip_walk_index_drop", "pprhip_walk_index_info",
     "pprhip_walk_index_fetch", "pprhip_walk_index_usage", "pprhip_tuning_indexed", "pprhip_tuning_indexed_batch",
     "pprhip_sweep_cut", "pprhip_results_sweep_cut", "pprhip_local_cluster_seeds",
+    "pprhip_get_reserve_sparse", "pprhip_get_residue_sparse", "pprhip_results_fetch_sparse",
+    "pprhip_results_fetch_sparse_all",
 ]
+SPARSE_BY_ID, SPARSE_BY_VALUE = 0, 1  # PPRHIP_SPARSE_BY_*: the orders of the sparse getters
+RELEASE_SPARSE = 16  # PPRHIP_RELEASE_SPARSE
 PAIR_WALK_STREAM = 0xFFFF  # PPRHIP_PAIR_WALK_STREAM: the walk stream of every single-pair walk
 COMM_ID_BYTES = 128
 
@@ -226,6 +230,10 @@ def lib():
     L.pprhip_sweep_cut.argtypes = [vp, ci, u64, u64, vp, vp, vp, u64, P(Sweep)]
     L.pprhip_results_sweep_cut.argtypes = [vp, ci, ci, u64, u64, vp, vp, vp, u64, P(Sweep)]
     L.pprhip_local_cluster_seeds.argtypes = [vp, vp, vp, ci, dbl, dbl, ci, u64, u64, vp, u64, P(Sweep), P(Stats)]
+    L.pprhip_get_reserve_sparse.argtypes = [vp, dbl, ci, vp, vp, u64, P(u64)]
+    L.pprhip_get_residue_sparse.argtypes = [vp, dbl, ci, vp, vp, u64, P(u64)]
+    L.pprhip_results_fetch_sparse.argtypes = [vp, ci, dbl, ci, vp, vp, u64, P(u64)]
+    L.pprhip_results_fetch_sparse_all.argtypes = [vp, dbl, ci, vp, vp, vp, u64, P(u64)]
     _lib = L
     # the destroy entry points, reachable from destructors that run while the interpreter shuts down (the name `lib`
     # may already be None then: "TypeError: 'NoneType' object is not callable" out of Index.__del__, round 3)
@@ -682,6 +690,31 @@ def all_pair_backward_multi(graphs, alpha, threshold, k):
     return Index(out), list(sts)
 
 
+def _sparse_order(order):
+    """"id" / "value" or the constants SPARSE_BY_ID / SPARSE_BY_VALUE; anything else goes to the library as it is."""
+    return {"id": SPARSE_BY_ID, "value": SPARSE_BY_VALUE}.get(order, order)
+
+
+def _sparse_call(threshold, order, cap, call):
+    """One sparse getter: call(threshold, order, ids, vals, cap, count*) is the C entry point.  cap None: count first,
+    then fetch everything.  Returns (ids int32, vals float64, count): min(cap, count) entries, count whatever cap is."""
+    order = _sparse_order(order)
+    cnt = C.c_uint64()
+    counted = cap is None
+    if counted:
+        _check(call(threshold, order, None, None, 0, C.byref(cnt)))
+        cap = cnt.value
+    cap = int(cap)
+    ids = np.empty(cap, dtype=np.int32)
+    vals = np.empty(cap)
+    if cap > 0:
+        _check(call(threshold, order, _ptr(ids), _ptr(vals), cap, C.byref(cnt)))
+    elif not counted:
+        _check(call(threshold, order, None, None, 0, C.byref(cnt)))
+    k = min(cap, cnt.value)
+    return ids[:k], vals[:k], cnt.value
+
+
 class Results:
     """Device-resident result vectors of a batched call (slot i = query i)."""
 
@@ -700,6 +733,29 @@ class Results:
         out = np.empty(self.n)
         _check(lib().pprhip_results_fetch(self.h, i, _ptr(out)))
         return out
+
+    def fetch_sparse(self, i, threshold=0.0, order="id", cap=None):
+        """Graph.reserve_sparse over vector i of the store (pprhip_results_fetch_sparse)."""
+        return _sparse_call(threshold, order, cap, lambda t, o, ids, vals, k, cnt: lib().pprhip_results_fetch_sparse(
+            self.h, int(i), t, o, ids, vals, k, cnt))
+
+    def fetch_sparse_all(self, threshold=0.0, order="id", cap=None):
+        """Every vector of the store in sparse form, as one CSR (pprhip_results_fetch_sparse_all).  Returns (offsets
+        uint64[count + 1], ids, vals, total): row i is the entries [offsets[i], offsets[i + 1]) of vector i in the chosen
+        order; the first min(cap, total) entries of the concatenated rows are returned (cap None: all of them)."""
+        order = _sparse_order(order)
+        offs = np.zeros(self.info()[1] + 1, dtype=np.uint64)
+        tot = C.c_uint64()
+        if cap is None:
+            _check(lib().pprhip_results_fetch_sparse_all(self.h, threshold, order, _ptr(offs), None, None, 0, C.byref(tot)))
+            cap = tot.value
+        cap = int(cap)
+        ids = np.empty(cap, dtype=np.int32)
+        vals = np.empty(cap)
+        _check(lib().pprhip_results_fetch_sparse_all(self.h, threshold, order, _ptr(offs), _ptr(ids) if cap else None,
+                                                     _ptr(vals) if cap else None, cap, C.byref(tot)))
+        k = min(cap, tot.value)
+        return offs, ids[:k], vals[:k], tot.value
 
     def sweep_cut(self, i, normalize=True, max_size=0, max_vol=0, cap=None):
         """Graph.sweep_cut over vector i of the store (pprhip_results_sweep_cut)."""
@@ -791,7 +847,7 @@ class Graph:
             _LIVE["graph_destroy"](self.h)
             self.h = None
 
-    RELEASE_ALL_PAIR, RELEASE_BATCH, RELEASE_WALK_INDEX, RELEASE_SWEEP = 1, 2, 4, 8
+    RELEASE_ALL_PAIR, RELEASE_BATCH, RELEASE_WALK_INDEX, RELEASE_SWEEP, RELEASE_SPARSE = 1, 2, 4, 8, 16
 
     def release(self, what):
         """Hands the workspaces of the named entry points back (pprhip_graph_release); they come back on next use."""
@@ -832,6 +888,19 @@ class Graph:
         out = np.empty(self.n)
         _check(lib().pprhip_get_residue(self.h, _ptr(out)))
         return out
+
+    def reserve_sparse(self, threshold=0.0, order="id", cap=None):
+        """The entries of reserve() with value > threshold, compacted on the device (pprhip_get_reserve_sparse).  order
+        "id": id ascending; "value": value descending, ties by id ascending.  Returns (ids int32, vals float64, count):
+        the first min(cap, count) entries of that order (cap None: all of them; 0: the count alone); the values are the
+        bits reserve() returns."""
+        return _sparse_call(threshold, order, cap, lambda t, o, ids, vals, k, cnt: lib().pprhip_get_reserve_sparse(
+            self.h, t, o, ids, vals, k, cnt))
+
+    def residue_sparse(self, threshold=0.0, order="id", cap=None):
+        """reserve_sparse over the vector residue() returns (pprhip_get_residue_sparse)."""
+        return _sparse_call(threshold, order, cap, lambda t, o, ids, vals, k, cnt: lib().pprhip_get_residue_sparse(
+            self.h, t, o, ids, vals, k, cnt))
 
     def sweep_cut(self, normalize=True, max_size=0, max_vol=0, cap=None):
         """The sweep cut over the result vector in HBM (what reserve() returns; pprhip_sweep_cut): the support ordered by

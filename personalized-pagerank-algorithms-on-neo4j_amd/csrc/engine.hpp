@@ -376,6 +376,27 @@ struct SweepWs {
   size_t tmp_bytes = 0;
 };
 
+// Workspace of the sparse getters (sparse.cpp, kernels_compact.hip; DESIGN.md §2 "Sparse results"): three groups, each
+// grown on demand and kept until pprhip_graph_release(PPRHIP_RELEASE_SPARSE) or the handle's end.  A TILE is
+// kCompactTile consecutive original ids of one vector; the tiles of a call are numbered vector-major.
+constexpr uint32_t kCompactPer = 4;                     // ids a thread takes per tile, 256 apart
+constexpr uint32_t kCompactTile = 256u * kCompactPer;   // ids one workgroup covers
+struct SparseWs {
+  unsigned long long* cnt = nullptr;   // [tile_cap + 1] kept entries per tile, one zero behind the last
+  unsigned long long* base = nullptr;  // [tile_cap + 1] their exclusive scan: a tile's first output position; the total
+  size_t tile_cap = 0;
+  unsigned long long* offs = nullptr;  // [offs_cap] base at every vector's first tile, then the total: the CSR offsets
+  size_t offs_cap = 0;
+  unsigned long long* val[2] = {nullptr, nullptr};  // [ent_cap] / [sort_cap] value bits of the kept entries
+  uint32_t* id = nullptr;                           // [ent_cap] their original ids
+  size_t ent_cap = 0;
+  unsigned long long* pk[2] = {nullptr, nullptr};   // [sort_cap] by value: vector << 32 | id riding along the sorts
+  size_t sort_cap = 0;
+  const unsigned long long* val_out = nullptr;      // the value buffer that holds the call's entries in their order
+  void* tmp = nullptr;                              // scratch of the library scan and sorts
+  size_t tmp_bytes = 0;
+};
+
 struct WalkPlanRec {  // one residue entry of a walk phase (k_mc_plan -> k_mc_walk): 32 bytes
   unsigned long long woff;  // walks of the entries before it
   double inc;               // what each of its walks adds at its terminal
@@ -588,6 +609,7 @@ struct pprhip_graph {
   pprhip::SeedTable* seeds = nullptr;
   bool seed_on = false;
   pprhip::SweepWs* sweep = nullptr;  // the sweep cut's workspace, or none (sweep.cpp)
+  pprhip::SparseWs* sparse = nullptr;  // the sparse getters' workspace, or none (sparse.cpp)
 };
 
 namespace pprhip {
@@ -785,6 +807,16 @@ int launch_sweep_rank(pprhip_graph* g, SweepWs* w, uint32_t profiled);
 int launch_sweep_edges(pprhip_graph* g, SweepWs* w, uint32_t profiled, hipEvent_t before, hipEvent_t after);
 int launch_sweep_best(pprhip_graph* g, SweepWs* w, uint32_t profiled, uint64_t max_vol);
 int init_kernels_sweep();
+
+// ---- kernels_compact.hip (ordered stream compaction of result vectors; sparse.cpp drives the steps)
+// x: `rows` vectors of n doubles in internal order, one behind the other.  Kept entries: x(v) > threshold.
+// tile counts, their scan, the CSR offsets (w->offs[0 .. rows], the last one the total)
+int launch_compact_count(pprhip_graph* g, SparseWs* w, const double* x, uint32_t rows, double threshold);
+// the kept entries in (vector, id) order: value bits -> w->val[0], ids -> w->id, or (packed) vector << 32 | id -> w->pk[0]
+int launch_compact_scatter(pprhip_graph* g, SparseWs* w, const double* x, uint32_t rows, double threshold, bool packed);
+// packed entries into (vector, value descending, id ascending) order; ids -> w->id, values -> w->val_out
+int launch_compact_sort(pprhip_graph* g, SparseWs* w, uint64_t total, uint32_t rows);
+int init_kernels_compact();
 
 // ---- kernels_target.hip (single targets)
 // the start of a backward push from a target set: d_id / d_w are `count` distinct internal ids and their weights, padded

@@ -1,7 +1,7 @@
 // engine_internal.hpp — declarations shared by the engine's translation units (engine.cpp: single-query
 // entry points; graph.cpp: graph lifecycle and workspaces; levels.cpp: level loop; select.cpp: top-k selection;
 // device_io.cpp: read-backs, scopes, walk launchers; fora.cpp: resumable FORA / top-k runs; bwd_runs.cpp: the resumable
-// runs that push backward; sweep.cpp: sweep cut;
+// runs that push backward; sweep.cpp: sweep cut; sparse.cpp: sparse getters;
 // batch.cpp, batch_api.cpp, fetch_pipe.cpp, stream.cpp: the batched entry points; allpair.cpp:
 // All-Pair-Backward-Search; index.cpp: its inverted index; pairs.cpp, targets.cpp: single pairs and single targets).
 #pragma once
@@ -246,6 +246,9 @@ void free_walk_share(BatchState* B);
 
 // ---- sweep.cpp
 void free_sweep(pprhip_graph* g);  // the handle's sweep-cut workspace, if it has one
+
+// ---- sparse.cpp
+void free_sparse(pprhip_graph* g);  // the handle's workspace of the sparse getters, if it has one
 
 // ---- stream.cpp
 void stream_detach(void* stream_obj);  // ends a query stream's driver before its graph goes

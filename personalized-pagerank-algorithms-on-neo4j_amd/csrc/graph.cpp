@@ -45,6 +45,7 @@ int init_device_once(int device) {
   PPRHIP_TRY(init_kernels_apbs());
   PPRHIP_TRY(init_kernels_sort());
   PPRHIP_TRY(init_kernels_sweep());
+  PPRHIP_TRY(init_kernels_compact());
   PPRHIP_TRY(init_kernels_host());
   PPRHIP_TRY(init_kernels_target());
   if ((size_t)device >= g_dev_inited.size()) g_dev_inited.resize((size_t)device + 1, 0);
@@ -554,7 +555,8 @@ static void free_all_pair(pprhip_graph* g) {
 
 int pprhip_graph_release(pprhip_graph_t* g, unsigned what) {
   PPRHIP_TRY(check_graph(g, "pprhip_graph_release"));
-  if (what & ~(PPRHIP_RELEASE_ALL_PAIR | PPRHIP_RELEASE_BATCH | PPRHIP_RELEASE_WALK_INDEX | PPRHIP_RELEASE_SWEEP)) {
+  if (what & ~(PPRHIP_RELEASE_ALL_PAIR | PPRHIP_RELEASE_BATCH | PPRHIP_RELEASE_WALK_INDEX | PPRHIP_RELEASE_SWEEP |
+               PPRHIP_RELEASE_SPARSE)) {
     set_error("pprhip_graph_release: unknown flag in %u", what);
     return PPRHIP_ERR_INVALID;
   }
@@ -563,6 +565,7 @@ int pprhip_graph_release(pprhip_graph_t* g, unsigned what) {
   if (what & PPRHIP_RELEASE_BATCH) free_batch(g);
   if (what & PPRHIP_RELEASE_WALK_INDEX) PPRHIP_TRY(pprhip_walk_index_drop(g));
   if (what & PPRHIP_RELEASE_SWEEP) free_sweep(g);
+  if (what & PPRHIP_RELEASE_SPARSE) free_sparse(g);
   return PPRHIP_OK;
 }
 
@@ -575,6 +578,7 @@ void pprhip_graph_destroy(pprhip_graph_t* g) {
   free_all_pair(g);
   seed_free(g);
   free_sweep(g);
+  free_sparse(g);
   free_workspace(g);
   if (g->stream) (void)hipStreamDestroy(g->stream);
   free_graph_data(g->gr);

@@ -166,11 +166,15 @@ std::string Graph::nodeName(long v) const {
 // ------------------------------------------------------------------ Algo_Util
 void Algo_Util::fetchReserve() {
   if (fetched) return;
-  dense.resize(adjM->nodeCount());
-  check(pprhip_get_reserve(adjM->handle(), dense.data()));
+  // the reference's map holds touched nodes only: the entries > 0, compacted on the device (count first, then fetch)
+  uint64_t count = 0;
+  check(pprhip_get_reserve_sparse(adjM->handle(), 0.0, PPRHIP_SPARSE_BY_ID, nullptr, nullptr, 0, &count));
+  std::vector<int32_t> ids(count);
+  std::vector<double> vals(count);
+  if (count)
+    check(pprhip_get_reserve_sparse(adjM->handle(), 0.0, PPRHIP_SPARSE_BY_ID, ids.data(), vals.data(), count, &count));
   ppr.clear();
-  for (size_t v = 0; v < dense.size(); ++v)
-    if (dense[v] > 0.0) ppr[(long)v] = dense[v];  // the reference's map holds touched nodes only
+  for (size_t i = 0; i < ids.size() && i < count; ++i) ppr[(long)ids[i]] = vals[i];
   fetched = true;
 }
 

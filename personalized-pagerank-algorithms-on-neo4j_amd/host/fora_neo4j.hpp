@@ -91,7 +91,7 @@ class Algo_Util {
  protected:
   Algo_Util(std::shared_ptr<Graph> adjM, double alpha, std::string dir_db)
       : adjM(std::move(adjM)), alpha(alpha), dir_db(std::move(dir_db)) {}
-  void fetchReserve();                       // HBM -> `dense`, `ppr` (entries > 0 only)
+  void fetchReserve();                       // HBM -> `ppr`: the entries > 0, compacted on the device
   void retrieveTopK(int k, bool from_device);  // Fora_Topk.java:186-199 / Forward_Push.java:413-429
   void printSorted(const char* title, int limit);
   std::shared_ptr<Graph> adjM;

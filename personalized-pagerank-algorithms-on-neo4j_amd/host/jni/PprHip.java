@@ -111,6 +111,17 @@ public final class PprHip implements AutoCloseable {
     /** Residue vector of the last push. */
     public native double[] residue();
 
+    /** Orders of the sparse getters: id ascending; value descending, ties by id ascending. */
+    public static final int SPARSE_BY_ID = 0, SPARSE_BY_VALUE = 1;
+
+    /** The entries of reserve() with value > threshold, compacted on the device: the first idsOut.length of them in the
+     *  chosen order go to idsOut / valsOut; returns how many there are (may exceed the arrays; both arrays null: the count
+     *  alone).  threshold 0, SPARSE_BY_ID is Whole_Graph_Util_Interface.getWholeGraphPPR()'s map. */
+    public native long reserveSparse(double threshold, int order, int[] idsOut, double[] valsOut);
+
+    /** reserveSparse over the vector of query i of the last foraBatchResident call. */
+    public native long batchResultSparse(int i, double threshold, int order, int[] idsOut, double[] valsOut);
+
     /** Algo_Util.kth_ppr + retrieveTopK on the vector in HBM: returns the count selected, fills at most idsOut.length. */
     public native int topk(int k, int[] idsOut, double[] valsOut);
 

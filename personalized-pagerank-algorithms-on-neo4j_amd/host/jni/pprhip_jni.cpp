@@ -7,6 +7,7 @@
 
 #include <cstring>
 #include <map>
+#include <string>
 #include <vector>
 
 #include "../../../include/pprhip.h"
@@ -146,6 +147,29 @@ void batch(JNIEnv* e, jobject self, jintArray srcs, jdouble eps, jdouble alpha, 
 }
 
 }  // namespace
+
+// the sparse getters' shared half: cap = the ids array's length (both arrays null: the counting call); `call` is the
+// entry point with its handle bound
+template <class Call>
+static jlong sparse(JNIEnv* e, const char* who, jintArray idsOut, jdoubleArray valsOut, Call call) {
+  if ((idsOut == nullptr) != (valsOut == nullptr) ||
+      (idsOut && e->GetArrayLength(valsOut) < e->GetArrayLength(idsOut))) {
+    throw_new(e, "java/lang/IllegalArgumentException",
+              (std::string(who) + ": one output array null, or values shorter than ids").c_str());
+    return 0;
+  }
+  const jsize cap = idsOut ? e->GetArrayLength(idsOut) : 0;
+  std::vector<int32_t> ids((size_t)cap);
+  std::vector<double> vals((size_t)cap);
+  uint64_t count = 0;
+  if (fail(e, call(cap > 0 ? ids.data() : nullptr, cap > 0 ? vals.data() : nullptr, (uint64_t)cap, &count))) return 0;
+  const jsize w = count < (uint64_t)cap ? (jsize)count : cap;
+  if (w > 0) {
+    e->SetIntArrayRegion(idsOut, 0, w, (const jint*)ids.data());
+    e->SetDoubleArrayRegion(valsOut, 0, w, vals.data());
+  }
+  return (jlong)count;
+}
 
 extern "C" {
 
@@ -343,6 +367,29 @@ JNIEXPORT jdoubleArray JNICALL Java_joezie_fora_1neo4j_PprHip_reserve(JNIEnv* e,
 
 JNIEXPORT jdoubleArray JNICALL Java_joezie_fora_1neo4j_PprHip_residue(JNIEnv* e, jobject self) {
   return dense(e, G(e, self), pprhip_get_residue);
+}
+
+JNIEXPORT jlong JNICALL Java_joezie_fora_1neo4j_PprHip_reserveSparse(JNIEnv* e, jobject self, jdouble threshold,
+                                                                     jint order, jintArray idsOut, jdoubleArray valsOut) {
+  pprhip_graph_t* g = G(e, self);
+  if (!g) return 0;
+  return sparse(e, "PprHip.reserveSparse", idsOut, valsOut, [&](int32_t* ids, double* vals, uint64_t cap, uint64_t* count) {
+    return pprhip_get_reserve_sparse(g, threshold, order, ids, vals, cap, count);
+  });
+}
+
+JNIEXPORT jlong JNICALL Java_joezie_fora_1neo4j_PprHip_batchResultSparse(JNIEnv* e, jobject self, jint i,
+                                                                         jdouble threshold, jint order,
+                                                                         jintArray idsOut, jdoubleArray valsOut) {
+  pprhip_results_t* r = R(e, self);
+  if (!r) {
+    throw_new(e, "java/lang/IllegalStateException", "no foraBatchResident call yet");
+    return 0;
+  }
+  return sparse(e, "PprHip.batchResultSparse", idsOut, valsOut,
+                [&](int32_t* ids, double* vals, uint64_t cap, uint64_t* count) {
+                  return pprhip_results_fetch_sparse(r, i, threshold, order, ids, vals, cap, count);
+                });
 }
 
 JNIEXPORT jint JNICALL Java_joezie_fora_1neo4j_PprHip_topk(JNIEnv* e, jobject self, jint k, jintArray idsOut,
