@@ -745,6 +745,64 @@ int pprhip_local_cluster_seeds(pprhip_graph_t* g, const int32_t* seeds, const do
                                double rmax, int normalize, uint64_t max_size, uint64_t max_vol, int32_t* members_out,
                                uint64_t cap, pprhip_sweep_t* info, pprhip_stats_t* push_stats);
 
+/* ---------------------------------------------------------------- weighted relationships (beyond the reference)
+ * Neo4j's PageRank takes a relationshipWeightProperty; the reference reads relationships as present or absent.  With
+ * weights on the handle the four calls below run over the transition matrix
+ *   P(u, v) = sum of w(u -> v) / W(u),   W(u) = the sum of u's out-weights,
+ * and compute the restarting pi of pprhip_power_method with this P: the walk stops with probability alpha per step and
+ * jumps back to its start at a dead end.  EVERY OTHER ENTRY POINT IGNORES THE WEIGHTS: seed sets, top-k rounds, the
+ * batched calls and streams, backward push, pairs, targets, the walk index, All-Pair, the sweep cut (which ranks by the
+ * relationship count, not by weighted degree), the multi-GPU calls; they give what they gave before pprhip_graph_set_weights.
+ *
+ * Weights: m doubles aligned with the out_col_idx given to pprhip_graph_create, every one finite and > 0 (a caller
+ * drops relationships of weight <= 0 before the lift, so dead ends are exactly the unweighted dead ends), every row sum
+ * finite.  A violation is PPRHIP_ERR_INVALID (the message names the edge index or the node), the handle and earlier
+ * weights untouched; PPRHIP_ERR_OOM leaves the handle as it was; while a query stream is open: PPRHIP_ERR_STATE.  A
+ * second call replaces the first; weights = NULL drops them.  pprhip_graph_release(PPRHIP_RELEASE_WEIGHTS) and
+ * pprhip_graph_destroy free them.  HBM: out-weights, their per-row prefix and the in-row copy of the weights, 8 bytes
+ * per edge each, and W per node: 24 m + 8 n bytes (R-MAT 22: 1.6 GB).
+ * The prefix is part of the contract (walks are reproducible off the device): cum of a row is the left-to-right
+ * sequential fp64 sum in row order, W its last element.  pprhip_weight_table_host is that rule and the same validation
+ * as a pure host function, in the caller's order (cum_out: m doubles, wsum_out: n doubles; either may be NULL).
+ *
+ * Push: popping u with residue r credits reserve(u) += alpha r and deposits c w(e) along every out-edge, c =
+ * (1 - alpha) r / W(u); a dead end returns (1 - alpha) r to the source as pprhip_forward_push does.  The push test is
+ * the unweighted one, r / (double)d_out >= rmax with the relationship COUNT: a pop costs d_out edge visits whatever the
+ * weights are, the test does not depend on the scale of the weights, and rsum <= rmax m, the walk budget,
+ * pprhip_fora_whole_params and pprhip_walk_index_density hold unchanged.  Schedule: plain
+ * frontier-synchronous Jacobi levels (every node active at level start pops from the level-start residues); the
+ * tuning's gs_blocks / gs_frac are ignored, dense_frac only picks the kernel of a level.
+ * Walk (seed, stream, start, idx): pprhip_random_walk_batch's function - same Philox key and counter, same words, stop
+ * test, forced first hop, dead-end restart and step count - with the neighbour pick x = ((double)word * 2^-32) * W(cur),
+ * j = the number of entries of the row's prefix that are <= x, clamped to d - 1, next = out_col_idx[row + j].
+ *
+ * Checks: the numeric parameters first ("Parameter ranges"), then the handle, then PPRHIP_ERR_STATE when the handle has
+ * no weights.  Results stay in HBM as after the unweighted calls: pprhip_get_reserve / _residue, the sparse getters,
+ * pprhip_topk_select and pprhip_sweep_cut work on them. */
+/* (32u and 64u stay unassigned: the release tests of the handle use them as the flags nobody knows) */
+#define PPRHIP_RELEASE_WEIGHTS 128u /* the relationship weights (pprhip_graph_set_weights): as set_weights(g, NULL) */
+int pprhip_graph_set_weights(pprhip_graph_t* g, const double* weights /* m, or NULL: drop */);
+int pprhip_weights_info(const pprhip_graph_t* g, int* present, uint64_t* bytes);
+int pprhip_weight_table_host(uint32_t n, uint64_t m, const uint32_t* out_row_ptr, const double* weights,
+                             double* cum_out, double* wsum_out);
+/* the contract of pprhip_power_method */
+int pprhip_weighted_power_method(pprhip_graph_t* g, int32_t src, double alpha, int iters, double* reserve_out,
+                                 pprhip_stats_t* stats);
+/* the contract of pprhip_forward_push */
+int pprhip_weighted_forward_push(pprhip_graph_t* g, int32_t src, double alpha, double rmax, double* reserve_out,
+                                 double* residue_out, double* rsum_out, pprhip_stats_t* stats);
+/* the contract of pprhip_random_walk_batch */
+int pprhip_weighted_random_walk_batch(pprhip_graph_t* g, const int32_t* starts, const uint64_t* walk_idx, uint64_t count,
+                                      double alpha, uint64_t seed, uint32_t stream, int no_zero_hop,
+                                      int32_t* terminals_out, uint32_t* steps_out /* may be NULL */);
+/* One weighted push at rmax (0: rmax0 of pprhip_fora_whole_params), run to its end, then the walk phase of the
+ * unweighted whole-graph FORA with weighted walks: rsum = (1 - alpha) * the residue sum, nrw = (long long)(omega rsum);
+ * a residue entry r credits alpha r to its own reserve and starts omega_i = ceil(x) walks, x = (1 - alpha) r / rsum * nrw,
+ * each adding (x / omega_i) / nrw * rsum at its terminal; walks (seed, stream 0, node, j < omega_i), forced first hop.
+ * No threshold rounds and no cost model (the tuning constants were fitted on the unweighted kernels): rounds = 1. */
+int pprhip_weighted_fora(pprhip_graph_t* g, int32_t src, double eps, const pprhip_fora_conf_t* conf, uint64_t seed,
+                         double rmax, double* reserve_out, pprhip_stats_t* stats);
+
 /* ---------------------------------------------------------------- ground truth (a12) */
 /* Power_Method.computeWholeGraphPPR (Power_Method.java:44-101): `iters` synchronous sweeps. */
 int pprhip_power_method(pprhip_graph_t* g, int32_t src, double alpha, int iters, double* reserve_out,

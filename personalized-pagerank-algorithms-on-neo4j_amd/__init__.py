@@ -101,9 +101,12 @@ EXPORTS = [
     "pprhip_sweep_cut", "pprhip_results_sweep_cut", "pprhip_local_cluster_seeds",
     "pprhip_get_reserve_sparse", "pprhip_get_residue_sparse", "pprhip_results_fetch_sparse",
     "pprhip_results_fetch_sparse_all",
+    "pprhip_graph_set_weights", "pprhip_weights_info", "pprhip_weight_table_host", "pprhip_weighted_power_method",
+    "pprhip_weighted_forward_push", "pprhip_weighted_random_walk_batch", "pprhip_weighted_fora",
 ]
 SPARSE_BY_ID, SPARSE_BY_VALUE = 0, 1  # PPRHIP_SPARSE_BY_*: the orders of the sparse getters
 RELEASE_SPARSE = 16  # PPRHIP_RELEASE_SPARSE
+RELEASE_WEIGHTS = 128  # PPRHIP_RELEASE_WEIGHTS
 PAIR_WALK_STREAM = 0xFFFF  # PPRHIP_PAIR_WALK_STREAM: the walk stream of every single-pair walk
 COMM_ID_BYTES = 128
 
@@ -234,6 +237,13 @@ def lib():
     L.pprhip_get_residue_sparse.argtypes = [vp, dbl, ci, vp, vp, u64, P(u64)]
     L.pprhip_results_fetch_sparse.argtypes = [vp, ci, dbl, ci, vp, vp, u64, P(u64)]
     L.pprhip_results_fetch_sparse_all.argtypes = [vp, dbl, ci, vp, vp, vp, u64, P(u64)]
+    L.pprhip_graph_set_weights.argtypes = [vp, vp]
+    L.pprhip_weights_info.argtypes = [vp, P(ci), P(u64)]
+    L.pprhip_weight_table_host.argtypes = [u32, u64, vp, vp, vp, vp]
+    L.pprhip_weighted_power_method.argtypes = [vp, i32, dbl, ci, vp, P(Stats)]
+    L.pprhip_weighted_forward_push.argtypes = [vp, i32, dbl, dbl, vp, vp, P(dbl), P(Stats)]
+    L.pprhip_weighted_random_walk_batch.argtypes = [vp, vp, vp, u64, dbl, u64, u32, ci, vp, vp]
+    L.pprhip_weighted_fora.argtypes = [vp, i32, dbl, P(ForaConf), u64, dbl, vp, P(Stats)]
     _lib = L
     # the destroy entry points, reachable from destructors that run while the interpreter shuts down (the name `lib`
     # may already be None then: "TypeError: 'NoneType' object is not callable" out of Index.__del__, round 3)
@@ -365,6 +375,29 @@ def load_neo4j_csv(nodes_csv, rels_csv):
     finally:
         lib().pprhip_edgelist_destroy(h)
     return n.value, src, dst, names
+
+
+def out_edge_order(src, newest_first=False):
+    """The permutation from an edge list's order to the order of HostCsr(n, src, dst, newest_first).out_ci (csr_build:
+    stable by source; inside a row descending edge index with newest_first): out_ci == dst[perm].  A caller holding
+    (src, dst, w) aligns its relationship weights with it: Graph.set_weights(w[perm])."""
+    src = np.asarray(src)
+    idx = np.arange(src.size, dtype=np.int64)
+    if newest_first:
+        idx = idx[::-1]
+    return idx[np.argsort(src[idx], kind="stable")]
+
+
+def weight_table_host(out_rp, weights):
+    """The prefix rule of the relationship weights without a device (pprhip_weight_table_host): (cum[m], wsum[n]) -
+    cum of a row is the left-to-right sequential fp64 sum in row order, wsum its last element.  The validation of
+    Graph.set_weights: PprhipError(ERR_INVALID) names the edge or the node."""
+    rp = np.ascontiguousarray(out_rp, dtype=np.uint32)
+    w = np.ascontiguousarray(weights, dtype=np.float64).ravel()
+    n, m = rp.size - 1, w.size
+    cum, ws = np.empty(m), np.empty(max(n, 1))
+    _check(lib().pprhip_weight_table_host(n, m, _ptr(rp), _ptr(w), _ptr(cum), _ptr(ws)))
+    return cum, ws[:n]
 
 
 class HostCsr:
@@ -848,6 +881,7 @@ class Graph:
             self.h = None
 
     RELEASE_ALL_PAIR, RELEASE_BATCH, RELEASE_WALK_INDEX, RELEASE_SWEEP, RELEASE_SPARSE = 1, 2, 4, 8, 16
+    RELEASE_WEIGHTS = 128
 
     def release(self, what):
         """Hands the workspaces of the named entry points back (pprhip_graph_release); they come back on next use."""
@@ -1169,4 +1203,56 @@ class Graph:
         out = np.empty(self.n)
         st = Stats()
         _check(lib().pprhip_power_method(self.h, src, alpha, iters, _ptr(out), C.byref(st)))
+        return out, st
+
+    # ---- weighted relationships (include/pprhip.h "weighted relationships"): P(u, v) = w(u -> v) / W(u)
+    def set_weights(self, weights):
+        """Relationship weights on the handle (pprhip_graph_set_weights): m doubles aligned with the host's out_ci
+        (out_edge_order aligns an edge list's), every one finite and > 0; None drops them.  Only the weighted_* calls
+        read them."""
+        w = None
+        if weights is not None:
+            w = np.ascontiguousarray(weights, dtype=np.float64).ravel()
+            if w.size != self.m:
+                raise ValueError("weights: %d entries for %d relationships" % (w.size, self.m))
+        _check(lib().pprhip_graph_set_weights(self.h, _ptr(w)))
+
+    def weights_info(self):
+        """(present, bytes of HBM the weights hold)."""
+        p, b = C.c_int(), C.c_uint64()
+        _check(lib().pprhip_weights_info(self.h, C.byref(p), C.byref(b)))
+        return bool(p.value), b.value
+
+    def weighted_power_method(self, src, alpha, iters=100):
+        out = np.empty(self.n)
+        st = Stats()
+        _check(lib().pprhip_weighted_power_method(self.h, src, alpha, iters, _ptr(out), C.byref(st)))
+        return out, st
+
+    def weighted_forward_push(self, src, alpha, rmax, fetch=True):
+        """forward_push over the weighted transition matrix; the same return shape."""
+        reserve = np.empty(self.n) if fetch else None
+        residue = np.empty(self.n) if fetch else None
+        rsum, st = C.c_double(), Stats()
+        _check(lib().pprhip_weighted_forward_push(self.h, src, alpha, rmax, _ptr(reserve), _ptr(residue), C.byref(rsum),
+                                                  C.byref(st)))
+        return reserve, residue, rsum.value, st
+
+    def weighted_random_walks(self, starts, idx, alpha, seed, stream=0, no_zero_hop=False):
+        """random_walks with the weighted neighbour pick; the same return shape."""
+        starts = np.ascontiguousarray(starts, dtype=np.int32)
+        idx = np.ascontiguousarray(idx, dtype=np.uint64)
+        term = np.empty(starts.size, dtype=np.int32)
+        steps = np.empty(starts.size, dtype=np.uint32)
+        _check(lib().pprhip_weighted_random_walk_batch(self.h, _ptr(starts), _ptr(idx), starts.size, alpha, seed, stream,
+                                                       int(no_zero_hop), _ptr(term), _ptr(steps)))
+        return term, steps
+
+    def weighted_fora(self, src, eps, alpha, seed, rmax=0.0, conf=None, fetch=True):
+        """One weighted push at rmax (0: rmax0 of conf and eps), then the whole-graph FORA walk phase with weighted
+        walks (pprhip_weighted_fora).  Returns (estimate | None, Stats)."""
+        conf = conf or conf_whole_graph(self.n, self.m, alpha)
+        out = np.empty(self.n) if fetch else None
+        st = Stats()
+        _check(lib().pprhip_weighted_fora(self.h, src, eps, C.byref(conf), seed, rmax, _ptr(out), C.byref(st)))
         return out, st

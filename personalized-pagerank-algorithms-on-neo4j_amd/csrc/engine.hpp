@@ -464,6 +464,12 @@ struct GraphData {
   double* survival = nullptr;
   double survival_alpha = 0.0;
   WalkIndex* widx = nullptr;  // the walk index, or none (pprhip_walk_index_build / _drop)
+  // relationship weights (weighted.cpp: pprhip_graph_set_weights; DESIGN.md §2 "Weighted relationships"), or none:
+  // fp64 arrays beside the CSR pair, internal order, read-only after the call.  out_w / out_cum are aligned with
+  // out_ci (out_cum: the inclusive left-to-right prefix of each out-row), wsum is W(u), a row's last prefix; in_w is
+  // aligned with in_ci and padded like it with 0.0.  24 m + 8 n bytes.
+  double *out_w = nullptr, *out_cum = nullptr, *wsum = nullptr, *in_w = nullptr;
+  uint64_t w_bytes = 0;  // what the four arrays hold in HBM (0: no weights)
 };
 
 // The handle's batched-call state: the workspaces ("slots") of its batched queries and the arrays their dense levels
@@ -827,6 +833,24 @@ int launch_target_init(pprhip_graph* g, const int32_t* d_id, const double* d_w, 
 // g->reserve[v] /= d_survival[v] for v < n, or (lone >= 0) for the entry `lone` alone
 int launch_target_finish(pprhip_graph* g, const double* d_survival, uint32_t n, int32_t lone);
 int init_kernels_target();
+
+// ---- kernels_weighted.hip (weighted relationships; weighted.cpp drives them, one level per host round trip)
+// step 1 of a level that starts from the list fbuf (nf entries): every entry gives up its residue; its per-weight
+// contribution c = (1 - alpha) r / W goes to cF[i], or (scatter_dense) to cdense[cbuf][node].  Clears *next_counter.
+int launch_w_prepare(pprhip_graph* g, const PushArgs& a, int fbuf, uint32_t nf, bool scatter_dense, int cbuf, int dead_slot,
+                     unsigned long long* next_counter);
+// step 2 of a sparse level: the list's ef out-edges deposit c * w; the level's dead-end mass lands on a.src; crossings
+// are appended to list fbuf ^ 1 and counted into *next_counter (entries << 36 | edges)
+int launch_w_push(pprhip_graph* g, const PushArgs& a, int fbuf, uint32_t nf, uint64_t ef, int dead_slot,
+                  unsigned long long* next_counter);
+// one dense level (a.mode: kFwdWhole, or kPower: every node with mass pops): cdense[cbuf] -> cdense[cbuf ^ 1], the
+// frontier it leaves counted into ctr->packed[out_slot], its dead-end mass into ctr->dead[dead_slot ^ 1]
+int launch_w_dense_level(pprhip_graph* g, const PushArgs& a, int cbuf, int out_slot, int dead_slot);
+int launch_w_walk_batch(pprhip_graph* g, const int32_t* d_starts, const uint64_t* d_idx, uint64_t count, double alpha,
+                        uint64_t seed, uint32_t stream, int no_zero_hop, int32_t* d_term, uint32_t* d_steps);
+// the weighted walks of the latest plan (launch_mc_plan): stream 0, forced first hop
+int launch_w_walk_plan(pprhip_graph* g, double alpha, uint64_t seed, double* target);
+int init_kernels_weighted();
 
 // ---- kernels_select.hip
 int launch_select_hist(pprhip_graph* g, const double* x, uint32_t n, unsigned long long prefix, int prefix_bits,

@@ -3,7 +3,8 @@
 // device_io.cpp: read-backs, scopes, walk launchers; fora.cpp: resumable FORA / top-k runs; bwd_runs.cpp: the resumable
 // runs that push backward; sweep.cpp: sweep cut; sparse.cpp: sparse getters;
 // batch.cpp, batch_api.cpp, fetch_pipe.cpp, stream.cpp: the batched entry points; allpair.cpp:
-// All-Pair-Backward-Search; index.cpp: its inverted index; pairs.cpp, targets.cpp: single pairs and single targets).
+// All-Pair-Backward-Search; index.cpp: its inverted index; pairs.cpp, targets.cpp: single pairs and single targets;
+// weighted.cpp: relationship weights and the weighted calls).
 #pragma once
 
 #include <sys/mman.h>
@@ -249,6 +250,9 @@ void free_sweep(pprhip_graph* g);  // the handle's sweep-cut workspace, if it ha
 
 // ---- sparse.cpp
 void free_sparse(pprhip_graph* g);  // the handle's workspace of the sparse getters, if it has one
+
+// ---- weighted.cpp
+void free_weights(GraphData* D);  // the lifted graph's relationship weights, if it has them
 
 // ---- stream.cpp
 void stream_detach(void* stream_obj);  // ends a query stream's driver before its graph goes
