@@ -167,14 +167,19 @@ int read_dead_pops(pprhip_graph* g, pprhip_stats_t& st) {
     const uint64_t more = 12ull * (steps - st.walk_steps) + 16ull * (walks - st.walks - served - shared) +
                           12ull * (served + shared) + 8ull * g->h_ctr->share_stored +
                           (served ? 24ull : 12ull) * (srcs - st.mc_sources);
+    // a walk that left a deposit record (WalkDeposit) writes 12 bytes in place of its 8-byte add; the records are read
+    // by the count (4), read and written by the scatter (12 + 12) and read by the sum (12): 44 bytes more per such walk
+    uint64_t recorded = 0;
+    if (g->walk_dep_cap && walks - st.walks >= g->walk_dep_min) recorded = std::min<uint64_t>(walks - st.walks, g->walk_dep_cap);
+    g->walk_dep_cap = g->walk_dep_min = 0;
 #ifdef PPRHIP_TEST_HOOKS
     if (hook_env("PPRHIP_WALK_SHARE_LOG"))  // measurement switch: a line per finished query, in completion order
       fprintf(stderr, "[walk-share] walks %llu served %llu stored %llu steps %llu\n", (unsigned long long)(walks - st.walks),
               (unsigned long long)g->h_ctr->share_served, (unsigned long long)g->h_ctr->share_stored,
               (unsigned long long)(steps - st.walk_steps));
 #endif
-    st.mc_bytes += more;
-    ktimer().add_bytes(PPRHIP_KERNEL_WALK, more);
+    st.mc_bytes += more + 44ull * recorded;
+    ktimer().add_bytes(PPRHIP_KERNEL_WALK, more + 44ull * recorded);
     st.walk_steps = steps;
     st.walks = walks;
     st.mc_sources = srcs;
@@ -218,7 +223,12 @@ int launch_walk_run(pprhip_graph* g, int variant, double alpha, uint64_t seed, u
   } else if (variant == 0 && stream == 0 && ws && ws->on && ws->seed == seed &&
              std::memcmp(&ws->alpha, &alpha, sizeof alpha) == 0) {
     PPRHIP_CHECK_HIP(hipStreamWaitEvent(g->stream, ws->cleared, 0));  // (the call's clear ran on the handle's stream)
-    PPRHIP_TRY(launch_mc_walk_shared(g, ws, alpha, seed, target));
+    // ... and leaves its deposits as records when it runs on the call's one walk stream (one set of buffers per handle)
+    const hipStream_t walk_stream = g->parent->batch->walk_stream;
+    const WalkDeposit* dep = walk_stream && g->stream == walk_stream && ws->dep.on ? &ws->dep : nullptr;
+    g->walk_dep_cap = dep ? dep->a.cap : 0ull;
+    g->walk_dep_min = dep ? dep->a.min_walks : 0ull;
+    PPRHIP_TRY(launch_mc_walk_shared(g, ws, alpha, seed, target, dep));
   } else
     PPRHIP_TRY(launch_mc_walk(g, alpha, seed, stream, variant == 0 ? 1 : 0, target));
   ktimer().end();

@@ -347,9 +347,40 @@ struct WalkIndex : TerminalTable {};
 // Owned by the batch state; valid for one (seed, alpha): cleared at the start of every call that uses it.
 constexpr uint32_t kWalkShareEmpty = 0xFFFFFFFFu;
 constexpr int kWalkShareMinQueries = 32;  // calls of fewer queries run without the cache
+// Deposit records of a batched call's walk phases (kernels_walk.hip "deposits by tile"): walk
+// gidx < cap of a phase stores (terminal, increment) at position gidx instead of adding at the terminal; the records are
+// binned by tile of `1 << tile_shift` consecutive ids, summed per tile in LDS and added to the vector in runs.  One set
+// per handle: the phases that use it run one after another on the batch state's walk stream.  Lives and dies with the
+// call's terminal cache (WalkShare), under the same memory rule.
+constexpr uint32_t kDepTileShift = 11;     // 2 048 doubles: 16 KB of LDS in the sum kernel
+constexpr uint32_t kDepMaxTiles = 4096;    // more tiles than this (16 KB of counters in LDS): the walks keep their atomics
+constexpr uint32_t kDepSlice = 16384;      // records of a work item: a hot tile is summed by several workgroups
+constexpr unsigned long long kDepMinWalks = 1ull << 18;  // a phase of fewer walks keeps its atomics
+struct DepositArgs {  // what the kernels take, by value
+  uint32_t* key = nullptr;   // [cap] terminal of walk gidx (internal id) ...
+  double* inc = nullptr;     // [cap] ... and what it adds there
+  uint32_t* bkey = nullptr;  // [cap] the same records in per-tile runs
+  double* binc = nullptr;
+  uint32_t* tile_cnt = nullptr;  // [n_tiles] records per tile: counted, turned into items and zeroed again per phase
+  uint32_t* tile_cur = nullptr;  // [n_tiles] next free position of every tile's run
+  uint4* items = nullptr;        // [items_cap] {tile, first record, records, the tile has other items}
+  // [0] items of the phase in flight; since the last reset: [1] binned phases, [2] records, [3] walks beyond cap
+  unsigned long long* stat = nullptr;
+  unsigned long long cap = 0, min_walks = 0;
+  uint32_t tile_shift = 0, n_tiles = 0, slice = 0, items_cap = 0, n = 0;
+};
+struct WalkDeposit {
+  DepositArgs a;
+  void* block = nullptr;  // the one allocation behind the arrays
+  size_t bytes = 0;
+  unsigned long long want = 0;  // the capacity asked for (a.cap: what a quarter of the free memory allowed)
+  bool on = false;        // the call's walk phases record (off: atomics, as without the buffers)
+};
+
 struct WalkShare : TerminalTable {  // (usage: [2] walks served from the cache / terminals stored, since the last reset)
   hipEvent_t cleared = nullptr;  // recorded behind the clear: the call's walk kernels wait for it
   bool on = false;               // the queries in flight may use it (walk phases of its seed and alpha)
+  WalkDeposit dep;               // the deposit records of the call's walk phases, or none
 };
 
 // Workspace of the sweep cut (sweep.cpp, kernels_sweep.hip; DESIGN.md §2 "Sweep cut"): allocated by the handle's first
@@ -544,6 +575,9 @@ struct pprhip_graph {
   bool pooled = false;
   bool has_col = false;
   uint32_t walk_waves = 0;  // waves per CU of the next walk kernels (0: the default)
+  // the last walk phase left records for walks [0, walk_dep_cap) if it had walk_dep_min walks or more (0, 0: atomics;
+  // read_dead_pops prices the phase by them)
+  unsigned long long walk_dep_cap = 0, walk_dep_min = 0;
   bool stream_open = false;  // a query stream's driver thread owns the handle (stream.cpp: pprhip_stream)
   void* stream_obj = nullptr;  // ... that stream (pprhip_graph_destroy closes a stream its owner forgot)
   hipEvent_t walk_ev[3] = {nullptr, nullptr, nullptr};  // slot: the events around its walk phase on the walk stream
@@ -718,7 +752,9 @@ int launch_mc_walk(pprhip_graph* g, double alpha, uint64_t seed, uint32_t stream
 int launch_mc_walk_indexed(pprhip_graph* g, const TerminalTable* ix, double alpha, uint64_t seed, double* target);
 // the walks of the latest plan (whole-graph FORA: stream 0, forced first hop) through the call's terminal cache: a walk
 // whose cell is filled deposits there at once, the others walk and fill their cells
-int launch_mc_walk_shared(pprhip_graph* g, const TerminalTable* ws, double alpha, uint64_t seed, double* target);
+// dep: the call's deposit records when this phase may use them (it runs on the walk stream), or null
+int launch_mc_walk_shared(pprhip_graph* g, const TerminalTable* ws, double alpha, uint64_t seed, double* target,
+                          const WalkDeposit* dep);
 // fills ix->term from ix->off (already in HBM): terminal j of node v = walk (seed, stream 0, v, j), forced first hop
 int launch_index_build(pprhip_graph* g, const TerminalTable* ix, unsigned long long* d_steps);
 // (rows of out-degree >= survival_heavy_degree() go in d_heavy: a workgroup each)

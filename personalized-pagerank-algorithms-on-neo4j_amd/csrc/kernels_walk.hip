@@ -323,8 +323,17 @@ __device__ __forceinline__ uint32_t plan_upper_bound(const WalkPlanRec* __restri
 // the deposit instead of ~6.7 gathered lines.  An empty cell: the walk runs as ever and stores its terminal with a
 // plain 4-byte store when it stops.  Nothing orders the store against other kernels' probes and nothing needs to: a
 // cell only goes from empty to the one value every writer writes, and a reader that still sees "empty" walks.  What
-// bounds a phase that is mostly served is its deposits: fp64 atomics on the terminals, the hubs among them hot.
+// bounds a phase that is mostly served is its deposits: fp64 atomics on the terminals, the hubs among them hot - which is
+// why a large phase of a batched call leaves records instead ("deposits by tile" below).
 enum WalkMode : int { kWalkPlain = 0, kWalkIndexed = 1, kWalkShared = 2 };
+// What a walk does with its increment: the fp64 atomic at the terminal; a record (terminal, increment) at the walk's own
+// index for the kernels under "deposits by tile" below, when the phase has dep.min_walks walks or more - a device-uniform
+// test on the plan's count that those kernels repeat - and the index lies below dep.cap (the others add atomically, in
+// the same phase); or nothing (libpprhip_hooks.so's measurement of what the deposits cost: the masses are wrong then).
+// Walk gidx is taken by one lane of one wave and deposits once, so positions [0, min(walks, cap)) are all written, the
+// lanes of a refill write consecutive ones, and no counter is needed.
+enum WalkDepositMode : int { kDepAtomic = 0, kDepBinned = 1, kDepNone = 2 };
+constexpr uint32_t kNoSlot = 0xFFFFFFFFu;  // (dep.cap < 2^31)
 template <int MODE>
 __global__ __launch_bounds__(64) void k_mc_walk(const WalkPlanRec* __restrict__ plan_rec,
                                                  const uint4* __restrict__ walk_rec, double* __restrict__ target,
@@ -332,7 +341,9 @@ __global__ __launch_bounds__(64) void k_mc_walk(const WalkPlanRec* __restrict__ 
                                                  int no_zero_hop, DevCounters* ctr, int parity,
                                                  const unsigned long long* __restrict__ idx_off,
                                                  uint32_t* share_term, uint32_t n_nodes,
-                                                 unsigned long long* __restrict__ share_usage) {
+                                                 unsigned long long* __restrict__ share_usage, int dep_mode,
+                                                 uint32_t* __restrict__ dep_key, double* __restrict__ dep_inc,
+                                                 unsigned long long dep_cap, unsigned long long dep_min) {
   constexpr bool INDEXED = MODE == kWalkIndexed;
   constexpr bool SHARED = MODE == kWalkShared;
   constexpr unsigned long long kNoCell = ~0ull;
@@ -345,6 +356,16 @@ __global__ __launch_bounds__(64) void k_mc_walk(const WalkPlanRec* __restrict__ 
     ctr->sources_total += n_src;
   }
   if (INDEXED && ctr->walks_over == 0ull) return;  // the index held every walk of the phase
+  const unsigned long long rec_cap = dep_mode == kDepBinned && n_walks >= dep_min ? dep_cap : 0ull;  // (wave-uniform)
+  uint32_t slot = kNoSlot;  // where this lane's walk leaves its record (kNoSlot: it adds at the terminal)
+  auto deposit = [&](uint32_t t, double x) {
+    if (slot != kNoSlot) {
+      dep_key[slot] = t;
+      dep_inc[slot] = x;
+    } else if (dep_mode != kDepNone) {
+      atomic_add_noret(&target[t], x);
+    }
+  };
   __shared__ WalkWindow S;
   const int lane = threadIdx.x;
   // this wave's share: whole groups of 64 walks, so that a short phase still spreads over the grid
@@ -436,17 +457,18 @@ __global__ __launch_bounds__(64) void k_mc_walk(const WalkPlanRec* __restrict__ 
         const unsigned long long sext = S.ext[j];
         const unsigned long long widx = gidx - S.woff[j];
         walker_init(w, start, sext, S.orig[j], widx, stream, no_zero_hop != 0);
+        slot = gidx < rec_cap ? (uint32_t)gidx : kNoSlot;
         bool stored = false;
         if (INDEXED) stored = widx < idx_off[start + 1] - idx_off[start];
         if (stored) {  // k_index_serve has deposited this walk's terminal
         } else if ((sext >> 32) == 0) {
-          atomic_add_noret(&target[start], inc);  // Monte_Carlo.java:70-72 / :106-108
+          deposit((uint32_t)start, inc);  // Monte_Carlo.java:70-72 / :106-108
         } else if (SHARED) {
           const unsigned long long o0 = idx_off[start];
           cell = widx < idx_off[start + 1] - o0 ? o0 + widx : kNoCell;
           const uint32_t t = cell != kNoCell ? share_term[cell] : kWalkShareEmpty;
           if (t < n_nodes) {  // (kWalkShareEmpty is no node)
-            atomic_add_noret(&target[t], inc);
+            deposit(t, inc);
             n_served++;
           } else {
             walking = true;
@@ -471,7 +493,7 @@ __global__ __launch_bounds__(64) void k_mc_walk(const WalkPlanRec* __restrict__ 
     if (walking) {
       stopped = walker_step(w, walk_rec, alpha, k0, k1);
       if (stopped) {
-        atomic_add_noret(&target[w.cur], inc);
+        deposit((uint32_t)w.cur, inc);
         steps_total += w.moves;
         walking = false;
         if (SHARED && cell != kNoCell) {
@@ -501,6 +523,153 @@ __global__ __launch_bounds__(64) void k_mc_walk(const WalkPlanRec* __restrict__ 
       atomic_add_u64(&ctr->share_stored, n_stored);
       atomic_add_u64(&share_usage[1], n_stored);
     }
+  }
+}
+
+// ------------------------------------------------------------------------------------------------
+// deposits by tile (engine.hpp: WalkDeposit)
+// What is left of a batched query's walk phase once the call's cache serves its walks is one fp64 atomic per walk at a
+// terminal: 64 lanes in 64 different lines per wave-instruction, executed at the memory side, the hubs' addresses hot.
+// Instead the walk kernel streams a 12-byte record per walk (above) and four kernels behind it on the same stream turn
+// the records into the same sums: k_dep_count counts the records per tile of 1 << tile_shift consecutive ids,
+// k_dep_items turns the counts into the tiles' runs and a table of work items (tile, slice of at most dep.slice
+// records: the first tile of an R-MAT holds a third of all records), k_dep_scatter moves the records into their runs (order
+// inside a run is free), and k_dep_sum adds an item's records into a tile of LDS and the tile to the vector: by
+// load-add-store when the item owns its tile, by atomics whose lanes are consecutive addresses when it shares it.
+// Nothing is sized on the host: grids are fixed, every kernel reads the phase's walk count from the plan's cell as the
+// walk kernel does, and all four return at once when the walk kernel kept its atomics.
+// ------------------------------------------------------------------------------------------------
+__device__ __forceinline__ unsigned long long dep_records(const DepositArgs& a, const DevCounters* ctr, int parity) {
+  const unsigned long long n_walks = ctr->mc_plan[parity] & kPackMask;
+  if (n_walks < a.min_walks) return 0ull;
+  return n_walks < a.cap ? n_walks : a.cap;
+}
+
+// this workgroup's share of the records: whole multiples of 256, so that a thread's loop is uniform per wave
+__device__ __forceinline__ void dep_share(unsigned long long n_rec, uint32_t* lo, uint32_t* hi) {
+  const unsigned long long per = ((n_rec + gridDim.x - 1) / gridDim.x + 255ull) / 256ull * 256ull;
+  const unsigned long long a = (unsigned long long)blockIdx.x * per, b = a + per;
+  *lo = (uint32_t)(a < n_rec ? a : n_rec);
+  *hi = (uint32_t)(b < n_rec ? b : n_rec);
+}
+
+__device__ __forceinline__ uint32_t dep_tile_of(const DepositArgs& a, uint32_t key) {
+  const uint32_t t = key >> a.tile_shift;
+  return t < a.n_tiles ? t : a.n_tiles - 1u;  // (a terminal is a node: the clamp only keeps a wrong record inside LDS)
+}
+
+__device__ __forceinline__ void dep_count_share(const DepositArgs& a, uint32_t lo, uint32_t hi, uint32_t* hist) {
+  for (uint32_t t = threadIdx.x; t < a.n_tiles; t += 256u) hist[t] = 0u;
+  __syncthreads();
+  for (uint32_t i = lo + threadIdx.x; i < hi; i += 256u) atomicAdd(&hist[dep_tile_of(a, a.key[i])], 1u);
+  __syncthreads();
+}
+
+__global__ __launch_bounds__(256) void k_dep_count(DepositArgs a, const DevCounters* ctr, int parity) {
+  const unsigned long long n_rec = dep_records(a, ctr, parity);
+  if (n_rec == 0) return;
+  __shared__ uint32_t hist[kDepMaxTiles];
+  uint32_t lo, hi;
+  dep_share(n_rec, &lo, &hi);
+  if (lo >= hi) return;
+  dep_count_share(a, lo, hi, hist);
+  for (uint32_t t = threadIdx.x; t < a.n_tiles; t += 256u) {  // (a wave's lanes: consecutive counters)
+    const uint32_t c = hist[t];
+    if (c) atomicAdd(&a.tile_cnt[t], c);
+  }
+}
+
+// One workgroup: thread i takes the tiles [i * per, (i + 1) * per), so the runs and the items are in tile order.
+__global__ __launch_bounds__(256) void k_dep_items(DepositArgs a, const DevCounters* ctr, int parity) {
+  const unsigned long long n_rec = dep_records(a, ctr, parity);
+  if (n_rec == 0) return;
+  __shared__ uint32_t s_scan[4];
+  const uint32_t per = (a.n_tiles + 255u) / 256u;
+  const uint32_t t_lo = threadIdx.x * per < a.n_tiles ? threadIdx.x * per : a.n_tiles;
+  const uint32_t t_hi = t_lo + per < a.n_tiles ? t_lo + per : a.n_tiles;
+  uint32_t recs = 0, its = 0;
+  for (uint32_t t = t_lo; t < t_hi; ++t) {
+    const uint32_t c = a.tile_cnt[t];
+    recs += c;
+    its += (c + a.slice - 1u) / a.slice;
+  }
+  uint32_t recs_all, its_all;
+  uint32_t base = block_excl_scan_256<uint32_t>(recs, s_scan, &recs_all);
+  uint32_t ib = block_excl_scan_256<uint32_t>(its, s_scan, &its_all);
+  for (uint32_t t = t_lo; t < t_hi; ++t) {
+    const uint32_t c = a.tile_cnt[t];
+    a.tile_cur[t] = base;
+    a.tile_cnt[t] = 0u;  // for the next phase
+    const uint32_t k_n = (c + a.slice - 1u) / a.slice;
+    for (uint32_t k = 0; k < k_n; ++k) {
+      const uint32_t first = k * a.slice;
+      const uint32_t len = c - first < a.slice ? c - first : a.slice;
+      if (ib + k < a.items_cap) a.items[ib + k] = make_uint4(t, base + first, len, k_n > 1u ? 1u : 0u);
+    }
+    base += c;
+    ib += k_n;
+  }
+  if (threadIdx.x == 0) {
+    const unsigned long long n_walks = ctr->mc_plan[parity] & kPackMask;
+    a.stat[0] = its_all < a.items_cap ? its_all : a.items_cap;  // (items_cap >= n_tiles + cap / slice: never short)
+    a.stat[1] += 1ull;
+    a.stat[2] += n_rec;
+    a.stat[3] += n_walks - n_rec;
+  }
+}
+
+__global__ __launch_bounds__(256) void k_dep_scatter(DepositArgs a, const DevCounters* ctr, int parity) {
+  const unsigned long long n_rec = dep_records(a, ctr, parity);
+  if (n_rec == 0) return;
+  __shared__ uint32_t hist[kDepMaxTiles];
+  uint32_t lo, hi;
+  dep_share(n_rec, &lo, &hi);
+  if (lo >= hi) return;
+  dep_count_share(a, lo, hi, hist);
+  for (uint32_t t = threadIdx.x; t < a.n_tiles; t += 256u) {  // this workgroup's piece of every run it has records for
+    const uint32_t c = hist[t];
+    hist[t] = c ? atomicAdd(&a.tile_cur[t], c) : 0u;
+  }
+  __syncthreads();
+  for (uint32_t i = lo + threadIdx.x; i < hi; i += 256u) {
+    const uint32_t key = a.key[i];
+    const double x = a.inc[i];
+    const uint32_t pos = atomicAdd(&hist[dep_tile_of(a, key)], 1u);
+    if (pos < n_rec) {
+      a.bkey[pos] = key;
+      a.binc[pos] = x;
+    }
+  }
+}
+
+__global__ __launch_bounds__(256) void k_dep_sum(DepositArgs a, const DevCounters* ctr, int parity,
+                                                  double* __restrict__ target) {
+  const unsigned long long n_rec = dep_records(a, ctr, parity);
+  if (n_rec == 0) return;
+  __shared__ double acc[1u << kDepTileShift];
+  const uint32_t n_items = (uint32_t)a.stat[0];
+  const uint32_t width = 1u << a.tile_shift;
+  for (uint32_t it = blockIdx.x; it < n_items; it += gridDim.x) {
+    const uint4 item = a.items[it];
+    const uint32_t v0 = item.x << a.tile_shift;
+    for (uint32_t j = threadIdx.x; j < width; j += 256u) acc[j] = 0.0;
+    __syncthreads();
+    for (uint32_t i = threadIdx.x; i < item.z; i += 256u) {
+      const unsigned long long p = (unsigned long long)item.y + i;
+      if (p >= n_rec) break;  // (never: the items cover the runs)
+      const uint32_t off = a.bkey[p] - v0;
+      if (off < width) (void)__hip_atomic_fetch_add(&acc[off], a.binc[p], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+    }
+    __syncthreads();
+    for (uint32_t j = threadIdx.x; j < width; j += 256u) {
+      const double x = acc[j];
+      const uint32_t v = v0 + j;
+      if (x != 0.0 && v < a.n) {
+        if (item.w) atomic_add_noret(&target[v], x);
+        else target[v] = target[v] + x;
+      }
+    }
+    __syncthreads();
   }
 }
 
@@ -967,7 +1136,8 @@ int launch_mc_walk(pprhip_graph* g, double alpha, uint64_t seed, uint32_t stream
   hipLaunchKernelGGL(k_mc_walk<kWalkPlain>, dim3(grid), dim3(64), 0, g->stream, plan_rec_of(g, g->mc_last_plan),
                      reinterpret_cast<const uint4*>(g->gr->walk_rec), target, alpha, (uint32_t)seed, (uint32_t)(seed >> 32), stream,
                      no_zero_hop, g->ctr, (int)(g->mc_last_plan % 3u), (const unsigned long long*)nullptr,
-                     (uint32_t*)nullptr, 0u, (unsigned long long*)nullptr);
+                     (uint32_t*)nullptr, 0u, (unsigned long long*)nullptr, (int)kDepAtomic, (uint32_t*)nullptr,
+                     (double*)nullptr, 0ull, 0ull);
   PPRHIP_CHECK_HIP(hipGetLastError());
   return PPRHIP_OK;
 }
@@ -983,18 +1153,34 @@ int launch_mc_walk_indexed(pprhip_graph* g, const TerminalTable* ix, double alph
   hipLaunchKernelGGL(k_mc_walk<kWalkIndexed>, dim3(grid), dim3(64), 0, g->stream, plan_rec_of(g, g->mc_last_plan),
                      reinterpret_cast<const uint4*>(g->gr->walk_rec), target, alpha, (uint32_t)seed, (uint32_t)(seed >> 32), 0u,
                      1, g->ctr, cell, (const unsigned long long*)ix->off, (uint32_t*)nullptr, 0u,
-                     (unsigned long long*)nullptr);
+                     (unsigned long long*)nullptr, (int)kDepAtomic, (uint32_t*)nullptr, (double*)nullptr, 0ull, 0ull);
   PPRHIP_CHECK_HIP(hipGetLastError());
   return PPRHIP_OK;
 }
 
-int launch_mc_walk_shared(pprhip_graph* g, const TerminalTable* ws, double alpha, uint64_t seed, double* target) {
+int launch_mc_walk_shared(pprhip_graph* g, const TerminalTable* ws, double alpha, uint64_t seed, double* target,
+                          const WalkDeposit* dep) {
   const uint32_t grid = mc_walk_grid(g);
+  // measurement switch, read per call: PPRHIP_WALK_DEPOSIT=none runs the phase without its deposits
+  const char* sw = hook_env("PPRHIP_WALK_DEPOSIT");
+  const int dep_mode = sw && sw[0] == 'n' ? kDepNone : dep && dep->on ? kDepBinned : kDepAtomic;
+  const DepositArgs none;
+  const DepositArgs& a = dep_mode == kDepBinned ? dep->a : none;
+  const int cell = (int)(g->mc_last_plan % 3u);
   hipLaunchKernelGGL(k_mc_walk<kWalkShared>, dim3(grid), dim3(64), 0, g->stream, plan_rec_of(g, g->mc_last_plan),
                      reinterpret_cast<const uint4*>(g->gr->walk_rec), target, alpha, (uint32_t)seed, (uint32_t)(seed >> 32), 0u,
-                     1, g->ctr, (int)(g->mc_last_plan % 3u), (const unsigned long long*)ws->off, (uint32_t*)ws->term, g->gr->n,
-                     ws->usage);
+                     1, g->ctr, cell, (const unsigned long long*)ws->off, (uint32_t*)ws->term, g->gr->n, ws->usage, dep_mode,
+                     a.key, a.inc, (unsigned long long)a.cap, (unsigned long long)a.min_walks);
   PPRHIP_CHECK_HIP(hipGetLastError());
+  if (dep_mode == kDepBinned) {
+    // one workgroup per CU: the sweeps on the other stream keep theirs (kernels_dense_batch.hip)
+    const uint32_t wg = (uint32_t)g->gr->n_cus;
+    hipLaunchKernelGGL(k_dep_count, dim3(wg), dim3(256), 0, g->stream, a, (const DevCounters*)g->ctr, cell);
+    hipLaunchKernelGGL(k_dep_items, dim3(1), dim3(256), 0, g->stream, a, (const DevCounters*)g->ctr, cell);
+    hipLaunchKernelGGL(k_dep_scatter, dim3(wg), dim3(256), 0, g->stream, a, (const DevCounters*)g->ctr, cell);
+    hipLaunchKernelGGL(k_dep_sum, dim3(wg), dim3(256), 0, g->stream, a, (const DevCounters*)g->ctr, cell, target);
+    PPRHIP_CHECK_HIP(hipGetLastError());
+  }
   return PPRHIP_OK;
 }
 

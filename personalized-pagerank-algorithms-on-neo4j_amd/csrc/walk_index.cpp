@@ -2,7 +2,9 @@
 // terminals of the walks a whole-graph FORA walk phase would draw from it, built once per (alpha, seed) and kept with
 // the lifted graph.  The kernels are in kernels_walk.hip (k_index_build, k_index_serve, k_mc_walk<kWalkIndexed>); the walk
 // phase picks the index in launch_walk_run (device_io.cpp).
+#include <algorithm>
 #include <cmath>
+#include <cstdlib>
 #include <cstring>
 #include <memory>
 #include <new>
@@ -117,9 +119,15 @@ void free_walk_index(GraphData* D) {
 }
 
 // ---- the call-scoped terminal cache (engine.hpp: WalkShare)
+static void free_walk_deposit(WalkDeposit& d) {
+  if (d.block) (void)hipFree(d.block);
+  d = WalkDeposit();
+}
+
 void free_walk_share(BatchState* B) {
   WalkShare* ws = B->share;
   if (!ws) return;
+  free_walk_deposit(ws->dep);
   table_free(*ws);
   if (ws->cleared) (void)hipEventDestroy(ws->cleared);
   delete ws;
@@ -135,6 +143,85 @@ static int walk_share_alloc(pprhip_graph* P, double density) {
   PPRHIP_CHECK_HIP(hipEventCreateWithFlags(&ws->cleared, hipEventDisableTiming));
   PPRHIP_CHECK_HIP(hipStreamSynchronize(P->stream));  // (h_off is pageable)
   return PPRHIP_OK;
+}
+
+// The deposit records of the call's walk phases (engine.hpp: WalkDeposit), decided and - on first use, or when the
+// call's bound differs - allocated where the call's cache is set up, queued on P->stream in front of the cache's clear
+// event.  cap: a query's walks from nodes with out-edges fit the cache's cells (the density bound), and a dead-end
+// start adds at most its own entry's walks, which n covers for all that was measured; a walk beyond cap adds
+// atomically, so the bound costs speed at worst.  More than a quarter of the free memory: as many records as fit.
+// Whatever fails, and a graph of more than kDepMaxTiles tiles, leaves the call with its atomics and is no error.
+static unsigned long long hook_number(const char* name, unsigned long long dflt) {
+  const char* e = hook_env(name);
+  return e && e[0] ? std::strtoull(e, nullptr, 10) : dflt;
+}
+
+static void walk_deposit_begin(pprhip_graph* P, WalkShare* ws) {
+  WalkDeposit& d = ws->dep;
+  d.on = false;
+  const char* sw = hook_env("PPRHIP_WALK_DEPOSIT");  // test switch: atomic = the walks add at their terminals
+  if (sw && sw[0] == 'a') return;
+  const uint32_t n = P->gr->n;
+  // test switches: a small tile (doubles, a power of two), slice and capacity, and the walk count binning starts from
+  uint32_t shift = 0;
+  for (unsigned long long t = hook_number("PPRHIP_WALK_DEPOSIT_TILE", 1ull << kDepTileShift); t > 1; t >>= 1) shift++;
+  if (shift < 4 || shift > kDepTileShift) shift = kDepTileShift;
+  const unsigned long long slice = std::min<unsigned long long>(
+      std::max<unsigned long long>(hook_number("PPRHIP_WALK_DEPOSIT_SLICE", kDepSlice), 16ull), kDepSlice);
+  unsigned long long cap = std::min<unsigned long long>(ws->total + n, (1ull << 31) - 1ull);
+  cap = std::min(cap, std::max<unsigned long long>(hook_number("PPRHIP_WALK_DEPOSIT_CAP", cap), 1ull));
+  const unsigned long long n_tiles = ((unsigned long long)n + (1ull << shift) - 1ull) >> shift;
+  if (n_tiles == 0 || n_tiles > kDepMaxTiles) return;
+  if (d.block && (d.want != cap || d.a.tile_shift != shift || d.a.slice != slice)) free_walk_deposit(d);
+  if (!d.block) {
+    auto up = [](size_t b) { return (b + 255) / 256 * 256; };
+    const size_t fixed = up(4 * n_tiles) * 2 + up(16 * (n_tiles + cap / slice + 1)) + up(4 * sizeof(unsigned long long));
+    size_t free_b = 0, total_b = 0;
+    if (hipMemGetInfo(&free_b, &total_b) != hipSuccess) {
+      (void)hipGetLastError();
+      return;
+    }
+    unsigned long long fit = cap;
+    if (fixed + 2 * (up(4 * fit) + up(8 * fit)) > free_b / 4) {
+      if (free_b / 4 < fixed + 4096) return;
+      fit = (free_b / 4 - fixed - 4096) / 24;
+    }
+    if (fit == 0) return;
+    const size_t bytes = fixed + 2 * (up(4 * fit) + up(8 * fit));
+    char* b = nullptr;
+    if (alloc_dev((void**)&b, bytes) != PPRHIP_OK) {
+      (void)hipGetLastError();
+      return;
+    }
+    d.block = b;
+    d.bytes = bytes;
+    d.want = cap;
+    DepositArgs& a = d.a;
+    a.cap = fit;
+    a.tile_shift = shift;
+    a.n_tiles = (uint32_t)n_tiles;
+    a.slice = (uint32_t)slice;
+    a.items_cap = (uint32_t)(n_tiles + cap / slice + 1);
+    a.n = n;
+    a.key = (uint32_t*)b;    b += up(4 * fit);
+    a.bkey = (uint32_t*)b;   b += up(4 * fit);
+    a.inc = (double*)b;      b += up(8 * fit);
+    a.binc = (double*)b;     b += up(8 * fit);
+    a.tile_cnt = (uint32_t*)b;  b += up(4 * n_tiles);
+    a.tile_cur = (uint32_t*)b;  b += up(4 * n_tiles);
+    a.items = (uint4*)b;     b += up(16 * (size_t)a.items_cap);
+    a.stat = (unsigned long long*)b;
+    // the counters start at zero (k_dep_items leaves tile_cnt so); the arrays of records need no clear
+    if (hipMemsetAsync(a.tile_cnt, 0, up(4 * n_tiles), P->stream) != hipSuccess ||
+        hipMemsetAsync(a.stat, 0, 4 * sizeof(unsigned long long), P->stream) != hipSuccess) {
+      (void)hipGetLastError();
+      (void)hipStreamSynchronize(P->stream);
+      free_walk_deposit(d);
+      return;
+    }
+  }
+  d.a.min_walks = hook_number("PPRHIP_WALK_DEPOSIT_MIN", kDepMinWalks);
+  d.on = true;
 }
 
 // Called where a batched whole-graph FORA call (or a stream's submission that finds the driver idle) is about to start
@@ -157,6 +244,7 @@ void walk_share_begin(pprhip_graph* P, int q, double alpha, double rmax, double 
   }
   WalkShare* ws = B->share;
   if (ws->total == 0) return;
+  walk_deposit_begin(P, ws);
   if (hipMemsetAsync(ws->term, 0xFF, sizeof(int32_t) * (size_t)ws->total, P->stream) != hipSuccess ||
       hipEventRecord(ws->cleared, P->stream) != hipSuccess) {
     (void)hipGetLastError();
@@ -302,6 +390,38 @@ int pprhip_hook_walk_share_fetch(pprhip_graph_t* g, int32_t node, int32_t* termi
     return PPRHIP_ERR_STATE;
   }
   return table_fetch_node(g, *ws, node, true, terminals_out, cap, count_out);
+}
+
+// ... and of the call's deposit records (engine.hpp: WalkDeposit): whether the handle holds them and the call in flight
+// (or the last one) uses them, their shape, and stat_out[4] = {items of the last binned phase; since the last reset:
+// binned phases, records, walks beyond the capacity}.
+int pprhip_hook_walk_deposit_info(pprhip_graph_t* g, int* present, int* on, uint64_t* cap, uint32_t* tile,
+                                  uint32_t* n_tiles, uint32_t* slice, uint64_t* bytes) {
+  PPRHIP_TRY(check_graph(g, "pprhip_hook_walk_deposit_info"));
+  const WalkShare* ws = g->batch ? g->batch->share : nullptr;
+  const WalkDeposit* d = ws && ws->dep.block ? &ws->dep : nullptr;
+  if (present) *present = d ? 1 : 0;
+  if (on) *on = d && d->on ? 1 : 0;
+  if (cap) *cap = d ? d->a.cap : 0;
+  if (tile) *tile = d ? 1u << d->a.tile_shift : 0;
+  if (n_tiles) *n_tiles = d ? d->a.n_tiles : 0;
+  if (slice) *slice = d ? d->a.slice : 0;
+  if (bytes) *bytes = d ? d->bytes : 0;
+  return PPRHIP_OK;
+}
+
+int pprhip_hook_walk_deposit_usage(pprhip_graph_t* g, uint64_t* stat_out, int reset) {
+  PPRHIP_TRY(check_graph(g, "pprhip_hook_walk_deposit_usage"));
+  const WalkShare* ws = g->batch ? g->batch->share : nullptr;
+  unsigned long long u[4] = {0ull, 0ull, 0ull, 0ull};
+  if (ws && ws->dep.block) {
+    PPRHIP_CHECK_HIP(hipDeviceSynchronize());  // (the walk stream as well)
+    PPRHIP_CHECK_HIP(hipMemcpy(u, ws->dep.a.stat, sizeof u, hipMemcpyDeviceToHost));
+    if (reset) PPRHIP_CHECK_HIP(hipMemset(ws->dep.a.stat, 0, sizeof u));
+  }
+  if (stat_out)
+    for (int i = 0; i < 4; ++i) stat_out[i] = u[i];
+  return PPRHIP_OK;
 }
 #endif
 
