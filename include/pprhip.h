@@ -747,12 +747,16 @@ int pprhip_local_cluster_seeds(pprhip_graph_t* g, const int32_t* seeds, const do
 
 /* ---------------------------------------------------------------- weighted relationships (beyond the reference)
  * Neo4j's PageRank takes a relationshipWeightProperty; the reference reads relationships as present or absent.  With
- * weights on the handle the four calls below run over the transition matrix
+ * weights on the handle the pprhip_weighted_* calls below run over the transition matrix
  *   P(u, v) = sum of w(u -> v) / W(u),   W(u) = the sum of u's out-weights,
  * and compute the restarting pi of pprhip_power_method with this P: the walk stops with probability alpha per step and
- * jumps back to its start at a dead end.  EVERY OTHER ENTRY POINT IGNORES THE WEIGHTS: seed sets, top-k rounds, the
- * batched calls and streams, backward push, pairs, targets, the walk index, All-Pair, the sweep cut (which ranks by the
- * relationship count, not by weighted degree), the multi-GPU calls; they give what they gave before pprhip_graph_set_weights.
+ * jumps back to its start at a dead end.  Both directions exist: forward (power method, forward push, walks, whole-graph
+ * FORA from one source) and backward (backward push, the survival vector, single targets / target sets, single pairs).
+ * Only the pprhip_weighted_* calls read the weights.  Every entry point without that prefix ignores them - the
+ * unweighted pprhip_backward_push, pprhip_ppr_targets and pprhip_ppr_pairs included - and so do the features that have
+ * no weighted form yet: seed sets, top-k rounds, the batched FORA calls and streams, the walk index, All-Pair, the sweep
+ * cut (which ranks by the relationship count, not by weighted degree), the multi-GPU calls; they give what they gave
+ * before pprhip_graph_set_weights.
  *
  * Weights: m doubles aligned with the out_col_idx given to pprhip_graph_create, every one finite and > 0 (a caller
  * drops relationships of weight <= 0 before the lift, so dead ends are exactly the unweighted dead ends), every row sum
@@ -802,6 +806,41 @@ int pprhip_weighted_random_walk_batch(pprhip_graph_t* g, const int32_t* starts, 
  * No threshold rounds and no cost model (the tuning constants were fitted on the unweighted kernels): rounds = 1. */
 int pprhip_weighted_fora(pprhip_graph_t* g, int32_t src, double eps, const pprhip_fora_conf_t* conf, uint64_t seed,
                          double rmax, double* reserve_out, pprhip_stats_t* stats);
+
+/* ---- the backward direction over the same P ("Weighted backward direction")
+ * Backward push: popping v with residue r credits reserve(v) += alpha r and deposits (c w(e)) / W(u) on r(u) along every
+ * in-edge e = (u -> v), c = (1 - alpha) r; with every weight equal to one power of two that is bit for bit the
+ * unweighted c / d_out(u).  u joins the next level when its residue crosses the unweighted backward test
+ * !(old > rmax) && new > rmax - strict, un-normalised, no degree in it, so nothing about it changes with the weights.
+ * Schedule: plain frontier-synchronous Jacobi levels; gs_blocks / gs_frac are ignored, dense_frac only picks the kernel
+ * of a level (sparse: one atomic per in-edge; dense: a pull over the out-rows, summed per row and divided by W once).
+ * Survival: S_w(u) = alpha + (1 - alpha) / W(u) * sum_{u -> v} w(u -> v) S_w(v), alpha at dead ends, by Jacobi from alpha
+ * until (1 - alpha) / alpha * max|dS| <= 1e-14; kept on the handle per alpha beside the unweighted S, freed with the
+ * weights (pprhip_graph_set_weights, also with NULL; PPRHIP_RELEASE_WEIGHTS; pprhip_graph_destroy).
+ * Targets: value(s) = p(s) / S_w(s) with 0 <= pi(s, T) - value(s) <= rmax, pi the restarting PPR over P.
+ * Pairs: value(s, t) = p_t(s) / S_w(s) + (1 / w) sum_{i < w} r_t(V_i), V_i the terminal of the weighted walk (seed,
+ * PPRHIP_PAIR_WALK_STREAM, s, i) without the forced first hop - pprhip_weighted_random_walk_batch's function; r_max and
+ * w are pprhip_pair_params', unchanged.  A pair's walk sums are formed without atomics in a fixed order.
+ * Weighted targets and pairs run one set / one distinct target after another on the handle's own workspace (the batched
+ * sweeps of the unweighted calls are not shared).  Checks as above: parameter ranges, the handle (an open query stream:
+ * PPRHIP_ERR_STATE), PPRHIP_ERR_STATE without weights, then ids and sets before any device work, the handle untouched. */
+/* the contract of pprhip_backward_push (in-degree 0: reserve(t) = 1 and no push); results stay in HBM for the getters,
+ * the sparse getters, pprhip_topk_select and pprhip_sweep_cut */
+int pprhip_weighted_backward_push(pprhip_graph_t* g, int32_t target, double alpha, double rmax, double* reserve_out,
+                                  double* residue_out, pprhip_stats_t* stats);
+/* the contract of pprhip_walk_survival */
+int pprhip_weighted_walk_survival(pprhip_graph_t* g, double alpha, double* survival_out /* may be NULL */);
+/* signature, checks, start rules (single target: r(t) = 1 and t pops, p(t) = alpha without in-edges; a set starts from
+ * r = w), delivery (keep, values_out, top-k rows padded -1 / 0) and stats of pprhip_ppr_targets; pprhip_get_reserve /
+ * _residue are undefined afterwards */
+int pprhip_weighted_ppr_targets(pprhip_graph_t* g, const int32_t* targets, const double* weights, const uint64_t* offsets,
+                                int q, double alpha, double rmax, pprhip_results_t* keep, double* values_out, int k,
+                                int32_t* ids_out, double* vals_out, int* n_out, pprhip_stats_t* per_query,
+                                pprhip_stats_t* stats_sum);
+/* signature, checks and stats of pprhip_ppr_pairs; a target without in-edges is exact and walks nothing */
+int pprhip_weighted_ppr_pairs(pprhip_graph_t* g, const int32_t* sources, const int32_t* targets, int q, double eps,
+                              const pprhip_fora_conf_t* conf, double rmax, uint64_t seed, double* values_out,
+                              pprhip_stats_t* stats_sum);
 
 /* ---------------------------------------------------------------- ground truth (a12) */
 /* Power_Method.computeWholeGraphPPR (Power_Method.java:44-101): `iters` synchronous sweeps. */

@@ -103,6 +103,8 @@ EXPORTS = [
     "pprhip_results_fetch_sparse_all",
     "pprhip_graph_set_weights", "pprhip_weights_info", "pprhip_weight_table_host", "pprhip_weighted_power_method",
     "pprhip_weighted_forward_push", "pprhip_weighted_random_walk_batch", "pprhip_weighted_fora",
+    "pprhip_weighted_backward_push", "pprhip_weighted_walk_survival", "pprhip_weighted_ppr_targets",
+    "pprhip_weighted_ppr_pairs",
 ]
 SPARSE_BY_ID, SPARSE_BY_VALUE = 0, 1  # PPRHIP_SPARSE_BY_*: the orders of the sparse getters
 RELEASE_SPARSE = 16  # PPRHIP_RELEASE_SPARSE
@@ -244,6 +246,10 @@ def lib():
     L.pprhip_weighted_forward_push.argtypes = [vp, i32, dbl, dbl, vp, vp, P(dbl), P(Stats)]
     L.pprhip_weighted_random_walk_batch.argtypes = [vp, vp, vp, u64, dbl, u64, u32, ci, vp, vp]
     L.pprhip_weighted_fora.argtypes = [vp, i32, dbl, P(ForaConf), u64, dbl, vp, P(Stats)]
+    L.pprhip_weighted_backward_push.argtypes = [vp, i32, dbl, dbl, vp, vp, P(Stats)]
+    L.pprhip_weighted_walk_survival.argtypes = [vp, dbl, vp]
+    L.pprhip_weighted_ppr_targets.argtypes = [vp, vp, vp, vp, ci, dbl, dbl, vp, vp, ci, vp, vp, vp, vp, P(Stats)]
+    L.pprhip_weighted_ppr_pairs.argtypes = [vp, vp, vp, ci, dbl, P(ForaConf), dbl, u64, vp, P(Stats)]
     _lib = L
     # the destroy entry points, reachable from destructors that run while the interpreter shuts down (the name `lib`
     # may already be None then: "TypeError: 'NoneType' object is not callable" out of Index.__del__, round 3)
@@ -1150,7 +1156,7 @@ class Graph:
         _check(lib().pprhip_walk_survival(self.h, alpha, _ptr(out)))
         return out
 
-    def ppr_pairs(self, sources, targets, eps, alpha, seed, rmax=0.0, conf=None):
+    def ppr_pairs(self, sources, targets, eps, alpha, seed, rmax=0.0, conf=None, _weighted=False):
         """pi(sources[i], targets[i]) for every i by the bidirectional estimator (pprhip_ppr_pairs); conf defaults to
         conf_whole_graph(n, m, alpha) (its alpha is the one used).  Returns (values, summed Stats)."""
         conf = conf or conf_whole_graph(self.n, self.m, alpha)
@@ -1160,14 +1166,15 @@ class Graph:
             raise ValueError("%d sources for %d targets" % (s.size, t.size))
         out = np.empty(s.size)
         st = Stats()
-        _check(lib().pprhip_ppr_pairs(self.h, _ptr(s), _ptr(t), s.size, eps, C.byref(conf), rmax, seed, _ptr(out),
-                                      C.byref(st)))
+        fn = lib().pprhip_weighted_ppr_pairs if _weighted else lib().pprhip_ppr_pairs
+        _check(fn(self.h, _ptr(s), _ptr(t), s.size, eps, C.byref(conf), rmax, seed, _ptr(out), C.byref(st)))
         return out, st
 
-    def _ppr_targets(self, t, w, offsets, q, alpha, rmax, k, keep, fetch):
+    def _ppr_targets(self, t, w, offsets, q, alpha, rmax, k, keep, fetch, weighted=False):
         values, ids, vals, nsel, pq = _batch_outputs(q, self.n, k, fetch, None, True)  # (always per-query stats)
         st = Stats()
-        _check(lib().pprhip_ppr_targets(
+        fn = lib().pprhip_weighted_ppr_targets if weighted else lib().pprhip_ppr_targets
+        _check(fn(
             self.h, _ptr(t), _ptr(w), _ptr(offsets), q, alpha, rmax, keep.h if keep is not None else None, _ptr(values),
             k, _ptr(ids), _ptr(vals), _ptr(nsel), C.cast(pq, C.c_void_p) if pq is not None else None, C.byref(st)))
         return values, ((ids, vals, nsel) if k > 0 else None), st, (list(pq) if pq is not None else [])
@@ -1256,3 +1263,33 @@ class Graph:
         st = Stats()
         _check(lib().pprhip_weighted_fora(self.h, src, eps, C.byref(conf), seed, rmax, _ptr(out), C.byref(st)))
         return out, st
+
+    # ---- the backward direction over the weights: the unweighted namesakes' arguments and return shapes
+    def weighted_backward_push(self, target, alpha, rmax):
+        """backward_push over the weighted transition matrix (pprhip_weighted_backward_push)."""
+        reserve = np.empty(self.n)
+        residue = np.empty(self.n)
+        st = Stats()
+        _check(lib().pprhip_weighted_backward_push(self.h, target, alpha, rmax, _ptr(reserve), _ptr(residue),
+                                                   C.byref(st)))
+        return reserve, residue, st
+
+    def weighted_walk_survival(self, alpha):
+        """S_w of the leaking walk over the weighted P at alpha (pprhip_weighted_walk_survival), n doubles by node id."""
+        out = np.empty(self.n)
+        _check(lib().pprhip_weighted_walk_survival(self.h, alpha, _ptr(out)))
+        return out
+
+    def weighted_ppr_targets(self, targets, alpha, rmax, k=0, keep=None, fetch=True):
+        """ppr_targets over the weighted P (pprhip_weighted_ppr_targets); the same return tuple."""
+        t = np.ascontiguousarray(np.atleast_1d(targets), dtype=np.int32).ravel()
+        return self._ppr_targets(t, None, None, int(t.size), alpha, rmax, k, keep, fetch, weighted=True)
+
+    def weighted_ppr_target_sets(self, sets, alpha, rmax, weights=None, k=0, keep=None, fetch=True):
+        """ppr_target_sets over the weighted P; the same return tuple."""
+        t, w, offsets = _seed_set_arrays(sets, weights)
+        return self._ppr_targets(t, w, offsets, int(offsets.size - 1), alpha, rmax, k, keep, fetch, weighted=True)
+
+    def weighted_ppr_pairs(self, sources, targets, eps, alpha, seed, rmax=0.0, conf=None):
+        """ppr_pairs over the weighted P with weighted walks (pprhip_weighted_ppr_pairs); (values, summed Stats)."""
+        return self.ppr_pairs(sources, targets, eps, alpha, seed, rmax, conf, _weighted=True)

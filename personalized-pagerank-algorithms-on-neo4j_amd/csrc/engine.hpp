@@ -501,6 +501,10 @@ struct GraphData {
   // aligned with in_ci and padded like it with 0.0.  24 m + 8 n bytes.
   double *out_w = nullptr, *out_cum = nullptr, *wsum = nullptr, *in_w = nullptr;
   uint64_t w_bytes = 0;  // what the four arrays hold in HBM (0: no weights)
+  // survival S_w of the leaking walk over the weighted P at wsurvival_alpha (weighted_bwd.cpp), beside `survival` and
+  // not instead of it; goes with the weights (free_weights)
+  double* wsurvival = nullptr;
+  double wsurvival_alpha = 0.0;
 };
 
 // The handle's batched-call state: the workspaces ("slots") of its batched queries and the arrays their dense levels
@@ -887,6 +891,25 @@ int launch_w_walk_batch(pprhip_graph* g, const int32_t* d_starts, const uint64_t
 // the weighted walks of the latest plan (launch_mc_plan): stream 0, forced first hop
 int launch_w_walk_plan(pprhip_graph* g, double alpha, uint64_t seed, double* target);
 int init_kernels_weighted();
+
+// ---- kernels_weighted_bwd.hip (the backward direction over the weights; weighted_bwd.cpp drives them)
+// step 1 of a backward level that starts from the list fbuf (nf entries): every entry gives up its residue; c =
+// (1 - alpha) r goes to cF[i], or (scatter_dense) to cdense[cbuf][node].  Clears *next_counter.
+int launch_wb_prepare(pprhip_graph* g, const PushArgs& a, int fbuf, uint32_t nf, bool scatter_dense, int cbuf,
+                      unsigned long long* next_counter);
+// step 2 of a sparse backward level: the list's ef in-edges (u -> v) deposit (c(v) * w) / W(u) on r(u); crossings are
+// appended to list fbuf ^ 1 with their in-degrees and counted into *next_counter (entries << 36 | in-edges)
+int launch_wb_push(pprhip_graph* g, const PushArgs& a, int fbuf, uint32_t nf, uint64_t ef, unsigned long long* next_counter);
+// one dense backward level over the out-CSR (ensure_bwd_layout first): cdense[cbuf] -> cdense[cbuf ^ 1], the frontier it
+// leaves counted into ctr->packed[out_slot]
+int launch_wb_dense_level(pprhip_graph* g, const PushArgs& a, int cbuf, int out_slot);
+// one Jacobi iteration of the weighted survival (the same edge sweep with x = s_old); dmax: nullptr, or the cell that
+// receives max |s_new - s_old| as a bit pattern (zero before)
+int launch_wb_survival_iter(pprhip_graph* g, const double* s_old, double* s_new, double alpha, unsigned long long* dmax);
+// launch_pair_walk with the weighted walker (chunk sums of g->residue at the terminals -> d_part)
+int launch_wb_pair_walk(pprhip_graph* g, const int32_t* d_src, uint32_t n_pairs, uint32_t chunks, uint64_t chunk_walks,
+                        uint64_t walks, double alpha, uint64_t seed, double* d_part, unsigned long long* d_steps);
+int init_kernels_weighted_bwd();
 
 // ---- kernels_select.hip
 int launch_select_hist(pprhip_graph* g, const double* x, uint32_t n, unsigned long long prefix, int prefix_bits,

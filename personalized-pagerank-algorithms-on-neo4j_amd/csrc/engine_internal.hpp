@@ -4,7 +4,7 @@
 // runs that push backward; sweep.cpp: sweep cut; sparse.cpp: sparse getters;
 // batch.cpp, batch_api.cpp, fetch_pipe.cpp, stream.cpp: the batched entry points; allpair.cpp:
 // All-Pair-Backward-Search; index.cpp: its inverted index; pairs.cpp, targets.cpp: single pairs and single targets;
-// weighted.cpp: relationship weights and the weighted calls).
+// weighted.cpp: relationship weights and the weighted calls; weighted_bwd.cpp: their backward direction).
 #pragma once
 
 #include <sys/mman.h>
@@ -252,7 +252,9 @@ void free_sweep(pprhip_graph* g);  // the handle's sweep-cut workspace, if it ha
 void free_sparse(pprhip_graph* g);  // the handle's workspace of the sparse getters, if it has one
 
 // ---- weighted.cpp
-void free_weights(GraphData* D);  // the lifted graph's relationship weights, if it has them
+void free_weights(GraphData* D);  // the lifted graph's relationship weights (and the weighted survival), if it has them
+int need_weights(const pprhip_graph* g, const char* fn);  // PPRHIP_ERR_STATE when the handle has no weights
+int fetch_packed(pprhip_graph* g, const unsigned long long* cell, uint32_t* nf, uint64_t* ef);  // a counter cell: entries << 36 | edges
 
 // ---- stream.cpp
 void stream_detach(void* stream_obj);  // ends a query stream's driver before its graph goes

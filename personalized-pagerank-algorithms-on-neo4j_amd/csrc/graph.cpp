@@ -49,6 +49,7 @@ int init_device_once(int device) {
   PPRHIP_TRY(init_kernels_host());
   PPRHIP_TRY(init_kernels_target());
   PPRHIP_TRY(init_kernels_weighted());
+  PPRHIP_TRY(init_kernels_weighted_bwd());
   if ((size_t)device >= g_dev_inited.size()) g_dev_inited.resize((size_t)device + 1, 0);
   g_dev_inited[device] = 1;
   return PPRHIP_OK;

@@ -51,14 +51,6 @@ int weight_table(uint32_t n, uint64_t m, const uint32_t* rp, const double* w, do
 
 size_t padded_in_edges(uint64_t m) { return ((size_t)m + kChunkPad - 1) / kChunkPad * kChunkPad + kChunkPad; }  // as in_ci
 
-int need_weights(const pprhip_graph* g, const char* fn) {
-  if (!g->gr->w_bytes) {
-    set_error("%s: the handle has no relationship weights (pprhip_graph_set_weights first)", fn);
-    return PPRHIP_ERR_STATE;
-  }
-  return PPRHIP_OK;
-}
-
 // ------------------------------------------------------------------ the level loop
 struct WLevels {
   int fcur = 0, ccur = 0, pslot = 0, dslot = 0;
@@ -66,14 +58,6 @@ struct WLevels {
   uint64_t ef = 0;
   bool prepared = false;  // the frontier is held as contributions in cdense[ccur] (after a dense level)
 };
-
-int fetch_packed(pprhip_graph* g, const unsigned long long* cell, uint32_t* nf, uint64_t* ef) {
-  unsigned long long pk = 0;
-  PPRHIP_TRY(fetch_small(g, cell, &pk, sizeof pk));
-  *nf = (uint32_t)(pk >> kPackShift);
-  *ef = pk & kPackMask;
-  return PPRHIP_OK;
-}
 
 // Runs levels from the list L.fcur until the frontier is empty.  A level is dense when nodes + edges of its frontier
 // reach dense_frac * m (the unweighted rule); the choice changes the order of fp64 additions and nothing else.
@@ -157,11 +141,28 @@ int weighted_push(pprhip_graph* g, int32_t src, double alpha, double rmax, pprhi
 namespace pprhip {
 namespace detail {
 
+int need_weights(const pprhip_graph* g, const char* fn) {
+  if (!g->gr->w_bytes) {
+    set_error("%s: the handle has no relationship weights (pprhip_graph_set_weights first)", fn);
+    return PPRHIP_ERR_STATE;
+  }
+  return PPRHIP_OK;
+}
+
+int fetch_packed(pprhip_graph* g, const unsigned long long* cell, uint32_t* nf, uint64_t* ef) {
+  unsigned long long pk = 0;
+  PPRHIP_TRY(fetch_small(g, cell, &pk, sizeof pk));
+  *nf = (uint32_t)(pk >> kPackShift);
+  *ef = pk & kPackMask;
+  return PPRHIP_OK;
+}
+
 void free_weights(GraphData* D) {
-  void* ptrs[] = {D->out_w, D->out_cum, D->wsum, D->in_w};
+  void* ptrs[] = {D->out_w, D->out_cum, D->wsum, D->in_w, D->wsurvival};
   for (void* p : ptrs)
     if (p) (void)hipFree(p);
-  D->out_w = D->out_cum = D->wsum = D->in_w = nullptr;
+  D->out_w = D->out_cum = D->wsum = D->in_w = D->wsurvival = nullptr;
+  D->wsurvival_alpha = 0.0;
   D->w_bytes = 0;
 }
 
