@@ -400,10 +400,12 @@ class _Gather:
         return full
 
 
-def push_fwd(host, src, alpha, rmax, B=1, side=None, mutant=None, max_levels=400):
+def push_fwd(host, src, alpha, rmax, B=1, side=None, mutant=None, max_levels=400, gather=None):
     """Frontier-synchronous forward push from src where every level is a dense pull: Jacobi (B = 1), or the twin's
     block sweeps (B > 1: the first in the entry state, the others in place; needs the forward side for its blocks).
     A mutant may never come to rest (mass that is counted twice grows): the push stops after max_levels.
+    gather: an object whose sums(P, b) gives the row sums of block pass b over original ids, in place of the plain
+    gathers (tests/sweep1_designs.py: the layout models of the single-query sweep).
     Returns (reserve, residue, levels, dead-end pops)."""
     n = host.n
     dout = np.diff(host.out_rp.astype(np.int64))
@@ -428,7 +430,8 @@ def push_fwd(host, src, alpha, rmax, B=1, side=None, mutant=None, max_levels=400
         members[-1] = np.concatenate([members[-1], rest])
     else:
         members = [np.arange(n)]
-    gather = _Gather(host, side, mutant, blocks)
+    if gather is None:
+        gather = _Gather(host, side, mutant, blocks)
     reserve[src] = alpha
     P = np.zeros(n)
     P[src] = (1.0 - alpha) / dout[src]
