@@ -1,8 +1,8 @@
 // bwd_runs.cpp — the three kinds of run that push backward (run.hpp): a backward search of All-Pair, the push and walks
 // of a pair call, the push and scaling of a single-target query.  They share the start of the push (backward_start,
 // which pprhip_backward_push uses too), its levels (bwd_step) and differ in what follows the push: the finishers below.
+// The walk blocks of a pair target (pair_walk_blocks) serve the weighted pair call (weighted_bwd.cpp) as well.
 #include <algorithm>
-#include <chrono>
 #include <cstring>
 
 #include "run.hpp"
@@ -68,10 +68,6 @@ int pair_begin(ForaRun& r, pprhip_graph* g, const PairPlan& pp, int32_t target_i
   return bwd_start_single(r, pp.alpha);
 }
 
-static double host_ms() {
-  return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch()).count();
-}
-
 // A single-target query (BatchJob kTargets, targets.cpp): the backward push from set i of the call's table at the
 // call's threshold, under the handle's tuning, then value = p / S in place of the reserve (k_target_finish), which the
 // batch driver delivers like a whole-graph vector (top-k, result store, values_out).  A single target starts as a
@@ -124,30 +120,32 @@ static int finish_search(ForaRun& r) {
   return PPRHIP_OK;
 }
 
-// kPairs: the walks of the target's sources and their values, in blocks of the plan's pairs per launch
+int pair_walk_blocks(pprhip_graph* g, const PairPlan& pp, uint32_t lo, uint32_t hi, double* part, bool lone,
+                     decltype(&launch_pair_walk) walk, pprhip_stats_t& st) {
+  const uint32_t chunks = lone ? 0u : pp.chunks;
+  ktimer().begin(PPRHIP_KERNEL_WALK, 0);
+  for (uint32_t b = lo; b < hi; b += pp.block_pairs) {
+    const uint32_t np = std::min(pp.block_pairs, hi - b);
+    if (chunks) PPRHIP_TRY(walk(g, pp.d_src + b, np, chunks, pp.chunk_walks, pp.walks, pp.alpha, pp.seed, part, pp.d_steps));
+    PPRHIP_TRY(launch_pair_reduce(g, pp.d_src + b, pp.d_pos + b, np, chunks, part, pp.walks, pp.survival, pp.d_values));
+  }
+  ktimer().end();
+  if (chunks) {
+    st.walks += pp.walks * (uint64_t)(hi - lo);
+    st.mc_sources += hi - lo;
+  }
+  return PPRHIP_OK;
+}
+
+// kPairs: the walks of the target's sources and their values, between the workspace's second and third event
 static int finish_pairs(ForaRun& r) {
   pprhip_graph* g = r.g;
   const PairPlan& pp = *r.pp;
   const int ws = g->ws_index;
   PPRHIP_CHECK_HIP(hipEventRecord(pp.ev[3 * ws + 1], g->stream));
-  // a target without in-edges left no residue: its values are exact, no walks
-  const uint32_t chunks = r.lone ? 0u : pp.chunks;
-  double* const part = pp.d_part + (size_t)ws * pp.part_cap;
-  ktimer().begin(PPRHIP_KERNEL_WALK, 0);
-  for (uint32_t lo = r.pair_lo; lo < r.pair_hi; lo += pp.block_pairs) {
-    const uint32_t np = std::min(pp.block_pairs, r.pair_hi - lo);
-    if (chunks)
-      PPRHIP_TRY(launch_pair_walk(g, pp.d_src + lo, np, chunks, pp.chunk_walks, pp.walks, pp.alpha, pp.seed, part,
-                                  pp.d_steps));
-    PPRHIP_TRY(launch_pair_reduce(g, pp.d_src + lo, pp.d_pos + lo, np, chunks, part, pp.walks, pp.survival,
-                                  pp.d_values));
-  }
-  ktimer().end();
+  PPRHIP_TRY(pair_walk_blocks(g, pp, r.pair_lo, r.pair_hi, pp.d_part + (size_t)ws * pp.part_cap, r.lone, launch_pair_walk,
+                              r.st));
   PPRHIP_CHECK_HIP(hipEventRecord(pp.ev[3 * ws + 2], g->stream));
-  if (chunks) {
-    r.st.walks += pp.walks * (uint64_t)(r.pair_hi - r.pair_lo);
-    r.st.mc_sources += r.pair_hi - r.pair_lo;
-  }
   r.st.rounds = 1;
   return PPRHIP_OK;
 }

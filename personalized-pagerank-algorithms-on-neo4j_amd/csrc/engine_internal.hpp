@@ -10,7 +10,9 @@
 #include <sys/mman.h>
 
 #include <atomic>
+#include <chrono>
 #include <condition_variable>
+#include <functional>
 #include <mutex>
 #include <new>
 #include <thread>
@@ -255,6 +257,15 @@ void free_sparse(pprhip_graph* g);  // the handle's workspace of the sparse gett
 void free_weights(GraphData* D);  // the lifted graph's relationship weights (and the weighted survival), if it has them
 int need_weights(const pprhip_graph* g, const char* fn);  // PPRHIP_ERR_STATE when the handle has no weights
 int fetch_packed(pprhip_graph* g, const unsigned long long* cell, uint32_t* nf, uint64_t* ef);  // a counter cell: entries << 36 | edges
+// The level loop of the weighted pushes, forward (kernels_weighted.hip) and backward (a.mode == kBackward:
+// kernels_weighted_bwd.hip, no dead-end mass: dslot goes unused): levels from the list L.fcur until the frontier is empty
+struct WLevels {
+  int fcur = 0, ccur = 0, pslot = 0, dslot = 0;
+  uint32_t nf = 0;
+  uint64_t ef = 0;
+  bool prepared = false;  // the frontier is held as contributions in cdense[ccur] (after a dense level)
+};
+int run_weighted_levels(pprhip_graph* g, const PushArgs& a, WLevels& L, pprhip_stats_t& st);
 
 // ---- stream.cpp
 void stream_detach(void* stream_obj);  // ends a query stream's driver before its graph goes
@@ -348,6 +359,10 @@ inline void fold_class_totals(pprhip_stats_t& st, const double tot[8], const uin
   st.dominant_kernel_launches = cnt[best];
 }
 
+inline double host_ms() {  // the host's steady clock
+  return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch()).count();
+}
+
 struct CallTimer {
   pprhip_graph* g;
   explicit CallTimer(pprhip_graph* g_) : g(g_) {
@@ -410,33 +425,47 @@ struct FetchPipe {
   void copier();
 };
 
-// A pair call (BatchJob kind kPairs, pairs.cpp): the pairs sorted by target; query i of the job is the i-th distinct target
-// (BatchJob::srcs) and covers the sorted pairs [first[i], first[i + 1]).  Device arrays of the call: the sources
-// (internal ids) and the call positions of the sorted pairs, the values by call position, per workspace (ws_index < kBatch)
-// a buffer of part_cap chunk sums and three events (push start, walks start, end).
+// A pair call (pairs.cpp: pair_plan / pair_upload / pair_collect): the pairs sorted by target; the i-th distinct target
+// covers the sorted pairs [first[i], first[i + 1]) - query i of a BatchJob kind kPairs (BatchJob::srcs = distinct).
+// Device arrays of the call, one block the plan owns: the sources (internal ids) and the call positions of the sorted
+// pairs, the values by call position, the steps counter, per workspace a buffer of part_cap chunk sums; and per
+// workspace (ws_index < kBatch) of the batched call three events (push start, walks start, end).
 struct PairPlan {
   std::vector<uint32_t> first;
+  std::vector<int32_t> distinct;      // the distinct targets, ascending (original ids)
+  std::vector<int32_t> h_src, order;  // the host halves of d_src / d_pos
   const int32_t* d_src = nullptr;
   const int32_t* d_pos = nullptr;
   double* d_values = nullptr;
-  double* d_part = nullptr;  // [kBatch][part_cap]
+  double* d_part = nullptr;  // [workspaces][part_cap]
   size_t part_cap = 0;
   unsigned long long* d_steps = nullptr;  // walk steps of the call
   uint64_t walks = 0;       // w per pair
   uint32_t chunks = 0;      // work items per pair ...
   uint64_t chunk_walks = 0; // ... of this many walks (the last one shorter)
   uint32_t block_pairs = 0; // pairs per walk launch (part_cap / chunks)
-  double alpha = 0.0, rmax = 0.0;
+  double alpha = 0.0, rmax = 0.0, omega = 0.0;
   uint64_t seed = 0;
   const double* survival = nullptr;
+  double t0 = 0.0;  // host clock when the call began its work (ms)
+  char* blob = nullptr;
   hipEvent_t ev[3 * kBatch] = {};
+  int n_ev = 0;
+  PairPlan() = default;
+  PairPlan(const PairPlan&) = delete;
+  PairPlan& operator=(const PairPlan&) = delete;
+  ~PairPlan() {
+    for (int e = 0; e < n_ev; ++e) (void)hipEventDestroy(ev[e]);
+    if (blob) (void)hipFree(blob);
+  }
 };
 
-// A single-target call (BatchJob kind kTargets, targets.cpp): query i is the backward push from set i of the table -
+// A single-target call (targets.cpp: target_plan): query i is the backward push from set i of the table -
 // members [first[i], first[i + 1]) of d_id / d_w (distinct internal ids, duplicates summed, zero weights dropped; every
 // set starts on a multiple of eight entries and is padded to one, kernels_target.hip) - and the division by S.
 // single[i]: one member of weight 1, started the pair call's way (r(t) = 1, t popped).  nf / ef: the first frontier of
 // a set as k_target_init lists it (members with in-edges over rmax, their in-edges), known to the host beforehand.
+// d_id / d_w lie in one device block that the plan owns.
 struct TargetPlan {
   std::vector<uint64_t> first;
   std::vector<uint32_t> count, nf;
@@ -447,6 +476,13 @@ struct TargetPlan {
   const double* d_w = nullptr;
   double alpha = 0.0, rmax = 0.0;
   const double* survival = nullptr;
+  char* blob = nullptr;
+  TargetPlan() = default;
+  TargetPlan(const TargetPlan&) = delete;
+  TargetPlan& operator=(const TargetPlan&) = delete;
+  ~TargetPlan() {
+    if (blob) (void)hipFree(blob);
+  }
 };
 
 // What a query of a batched job runs: whole-graph FORA, FORA top-k (seed + query index), a backward search of
@@ -491,6 +527,31 @@ struct BatchJob {
 
 // ---- pairs.cpp
 int ensure_survival(pprhip_graph* g, double alpha);  // S at alpha on the lifted graph (GraphData::survival), cached per alpha
+// The Jacobi iteration behind both survival vectors: from S0 = alpha, double-buffered, on the handle's stream, checked
+// every eighth iteration, until (1 - alpha) / alpha * max|dS| <= 1e-14 (the iteration contracts by 1 - alpha).  iter
+// queues one iteration s_old -> s_new; its third argument is nullptr or the zeroed cell that receives max|dS| as a bit
+// pattern.  both: S0 goes to both buffers (an iteration that leaves some rows unwritten); converged: nothing to
+// iterate.  *out: the vector, the caller's to free.  fn names the entry point in the messages.
+int survival_jacobi(pprhip_graph* g, double alpha, const char* fn, bool both, bool converged,
+                    const std::function<int(const double*, double*, unsigned long long*)>& iter, double** out);
+// The front of pprhip_ppr_pairs and pprhip_weighted_ppr_pairs (fn; weighted: the handle must have weights).
+// pair_plan: the checks in the documented order, r_max / w / omega, the stats_sum prologue, and for q > 0 the pairs
+// grouped by target and the chunk geometry.  pair_upload: the device block with `workspaces` buffers of chunk sums and
+// n_events events.  pair_collect: values and steps back to the host, stats_sum filled from sum.
+int pair_plan(pprhip_graph_t* g, const int32_t* sources, const int32_t* targets, int q, double eps,
+              const pprhip_fora_conf_t* conf, double rmax, uint64_t seed, const double* values_out,
+              pprhip_stats_t* stats_sum, const char* fn, bool weighted, PairPlan& pp);
+int pair_upload(pprhip_graph* g, PairPlan& pp, int workspaces, int n_events, const char* fn);
+int pair_collect(pprhip_graph* g, const PairPlan& pp, double* values_out, pprhip_stats_t& sum, pprhip_stats_t* stats_sum,
+                 const char* fn);
+
+// ---- targets.cpp
+// The front of pprhip_ppr_targets and pprhip_weighted_ppr_targets (fn; weighted: the handle must have weights): the
+// checks in the documented order, the stats_sum prologue, an empty call's keep->count = 0, and for q > 0 the set table
+// in tp, its ids and weights uploaded.  The caller returns at once when q == 0.
+int target_plan(pprhip_graph_t* g, const int32_t* targets, const double* weights, const uint64_t* offsets, int q,
+                double alpha, double rmax, pprhip_results* keep, int k, const int32_t* ids_out, const double* vals_out,
+                pprhip_stats_t* stats_sum, const char* fn, bool weighted, TargetPlan& tp);
 
 // ---- batch.cpp
 int batch_run(pprhip_graph_t* g, BatchJob& J, pprhip_stats_t* stats_sum);
@@ -521,6 +582,11 @@ int backward_search_whole(pprhip_graph_t* g, int32_t target_internal, double alp
 // the standard start (r(t) = 1, t popped) leaves there - p_t(t) = alpha and no residue.
 int backward_start(pprhip_graph* g, LevelCtx& L, PushArgs& a, int32_t target_internal, double alpha, double rmax,
                    double lone_value, bool* pushing);
+// The walks and values of the sorted pairs [lo, hi) of one target after its push, in blocks of the plan's pairs per
+// launch.  part: the workspace's chunk sums; lone: the target has no in-edges, so it left no residue and its values
+// are exact without walks; walk: launch_pair_walk or launch_wb_pair_walk.  Counts the walks into st.
+int pair_walk_blocks(pprhip_graph* g, const PairPlan& pp, uint32_t lo, uint32_t hi, double* part, bool lone,
+                     decltype(&launch_pair_walk) walk, pprhip_stats_t& st);
 
 // ---- index.cpp
 // the index over all n sources from entries on the host: bucketed by source, row order and k rule on the host's threads

@@ -1,7 +1,8 @@
 // targets.cpp — single-target PPR (beyond the reference): "who reaches t", for many targets and weighted target sets per
-// call (include/pprhip.h "single targets", DESIGN.md §2 "Single targets").  Argument checks, the call's set table
-// (duplicates merged, internal ids, in HBM) and the entry point.  The pushes run as BatchJob kind kTargets of the batch
-// driver (bwd_runs.cpp: target_begin / bwd_step), their start and the division by the survival vector S (pairs.cpp:
+// call (include/pprhip.h "single targets", DESIGN.md §2 "Single targets").  The front of a target call, which
+// pprhip_weighted_ppr_targets (weighted_bwd.cpp) shares - argument checks, the call's set table (duplicates merged,
+// internal ids, in HBM) - and the entry point.  The pushes run as BatchJob kind kTargets of the batch driver
+// (bwd_runs.cpp: target_begin / bwd_step), their start and the division by the survival vector S (pairs.cpp:
 // ensure_survival) are kernels_target.hip; top-k, the result store and values_out are the driver's own delivery.
 #include <algorithm>
 #include <cstdint>
@@ -11,26 +12,21 @@
 
 #include "engine_internal.hpp"
 
-using namespace pprhip;
-using namespace pprhip::detail;
-
-namespace {
+namespace pprhip {
+namespace detail {
 
 constexpr uint32_t kGroup = 8;  // a set starts on a multiple of this many table entries (kernels_target.hip: kTargetItems)
 
-}  // namespace
-
-extern "C" int pprhip_ppr_targets(pprhip_graph_t* g, const int32_t* targets, const double* weights,
-                                  const uint64_t* offsets, int q, double alpha, double rmax, pprhip_results_t* keep,
-                                  double* values_out, int k, int32_t* ids_out, double* vals_out, int* n_out,
-                                  pprhip_stats_t* per_query, pprhip_stats_t* stats_sum) {
-  static const char* fn = "pprhip_ppr_targets";
+int target_plan(pprhip_graph_t* g, const int32_t* targets, const double* weights, const uint64_t* offsets, int q,
+                double alpha, double rmax, pprhip_results* keep, int k, const int32_t* ids_out, const double* vals_out,
+                pprhip_stats_t* stats_sum, const char* fn, bool weighted, TargetPlan& tp) {
   PPRHIP_TRY(check_alpha(alpha, fn));
   if (!(rmax > 0.0 && rmax <= 1.0)) {  // (NaN fails both)
     set_error("%s: rmax = %g must be finite with 0 < rmax <= 1", fn, rmax);
     return PPRHIP_ERR_INVALID;
   }
   PPRHIP_TRY(check_graph(g, fn));
+  if (weighted) PPRHIP_TRY(need_weights(g, fn));
   if (q < 0 || k < 0 || (q > 0 && !targets) || (k > 0 && q > 0 && (!ids_out || !vals_out))) {
     set_error("%s: bad arguments (q=%d k=%d, targets %s)", fn, q, k, targets ? "given" : "NULL");
     return PPRHIP_ERR_INVALID;
@@ -47,7 +43,6 @@ extern "C" int pprhip_ppr_targets(pprhip_graph_t* g, const int32_t* targets, con
   }
 
   // the set table on the host: every set checked before anything runs
-  TargetPlan tp;
   tp.alpha = alpha;
   tp.rmax = rmax;
   std::vector<int32_t> h_id;
@@ -91,46 +86,57 @@ extern "C" int pprhip_ppr_targets(pprhip_graph_t* g, const int32_t* targets, con
     return PPRHIP_ERR_OOM;
   }
 
-  PPRHIP_TRY(ensure_survival(g, alpha));
-  tp.survival = g->gr->survival;
-  PPRHIP_TRY(ensure_batch(g));
   // one device block for the call: the ids, then the weights on a 256-byte boundary
   const size_t b_id = sizeof(int32_t) * h_id.size(), b_w = sizeof(double) * h_w.size();
   const size_t off_w = (b_id + 255) & ~(size_t)255;
-  char* blob = nullptr;
-  PPRHIP_TRY(alloc_dev((void**)&blob, off_w + b_w + 256));
-  tp.d_id = reinterpret_cast<const int32_t*>(blob);
-  tp.d_w = reinterpret_cast<const double*>(blob + off_w);
-  int rc = PPRHIP_OK;
-  if (hipMemcpyAsync(blob, h_id.data(), b_id, hipMemcpyHostToDevice, g->stream) != hipSuccess ||
-      hipMemcpyAsync(blob + off_w, h_w.data(), b_w, hipMemcpyHostToDevice, g->stream) != hipSuccess ||
+  PPRHIP_TRY(alloc_dev((void**)&tp.blob, off_w + b_w + 256));
+  tp.d_id = reinterpret_cast<const int32_t*>(tp.blob);
+  tp.d_w = reinterpret_cast<const double*>(tp.blob + off_w);
+  if (hipMemcpyAsync(tp.blob, h_id.data(), b_id, hipMemcpyHostToDevice, g->stream) != hipSuccess ||
+      hipMemcpyAsync(tp.blob + off_w, h_w.data(), b_w, hipMemcpyHostToDevice, g->stream) != hipSuccess ||
       hipStreamSynchronize(g->stream) != hipSuccess) {
     set_error("%s: upload of the target sets failed", fn);
-    rc = PPRHIP_ERR_HIP;
+    return PPRHIP_ERR_HIP;
   }
+  return PPRHIP_OK;
+}
+
+}  // namespace detail
+}  // namespace pprhip
+
+using namespace pprhip;
+using namespace pprhip::detail;
+
+extern "C" int pprhip_ppr_targets(pprhip_graph_t* g, const int32_t* targets, const double* weights,
+                                  const uint64_t* offsets, int q, double alpha, double rmax, pprhip_results_t* keep,
+                                  double* values_out, int k, int32_t* ids_out, double* vals_out, int* n_out,
+                                  pprhip_stats_t* per_query, pprhip_stats_t* stats_sum) {
+  static const char* fn = "pprhip_ppr_targets";
+  TargetPlan tp;
+  PPRHIP_TRY(target_plan(g, targets, weights, offsets, q, alpha, rmax, keep, k, ids_out, vals_out, stats_sum, fn, false, tp));
+  if (q == 0) return PPRHIP_OK;
+  PPRHIP_TRY(ensure_survival(g, alpha));
+  tp.survival = g->gr->survival;
+  PPRHIP_TRY(ensure_batch(g));
   pprhip_stats_t sum;
   std::memset(&sum, 0, sizeof sum);
-  if (rc == PPRHIP_OK) {
-    BatchJob J;
-    J.P = g;
-    J.kind = QueryKind::kTargets;
-    J.q = q;
-    J.reserve_out = values_out;
-    J.k = k;
-    J.ids_out = ids_out;
-    J.vals_out = vals_out;
-    J.n_out = n_out;
-    J.per_query = per_query;
-    J.alpha = alpha;
-    J.threshold = rmax;
-    J.targets = &tp;
-    J.keep = keep;
-    if (keep) keep->count = 0;
-    rc = batch_run(g, J, &sum);
-    if (rc == PPRHIP_OK && keep) keep->count = q;
-  }
-  (void)hipFree(blob);
-  if (rc != PPRHIP_OK) return rc;
+  BatchJob J;
+  J.P = g;
+  J.kind = QueryKind::kTargets;
+  J.q = q;
+  J.reserve_out = values_out;
+  J.k = k;
+  J.ids_out = ids_out;
+  J.vals_out = vals_out;
+  J.n_out = n_out;
+  J.per_query = per_query;
+  J.alpha = alpha;
+  J.threshold = rmax;
+  J.targets = &tp;
+  J.keep = keep;
+  if (keep) keep->count = 0;
+  PPRHIP_TRY(batch_run(g, J, &sum));
+  if (keep) keep->count = q;
   if (stats_sum) {
     sum.rmax_final = rmax;
     *stats_sum = sum;

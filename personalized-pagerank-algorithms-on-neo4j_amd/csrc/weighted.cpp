@@ -51,77 +51,6 @@ int weight_table(uint32_t n, uint64_t m, const uint32_t* rp, const double* w, do
 
 size_t padded_in_edges(uint64_t m) { return ((size_t)m + kChunkPad - 1) / kChunkPad * kChunkPad + kChunkPad; }  // as in_ci
 
-// ------------------------------------------------------------------ the level loop
-struct WLevels {
-  int fcur = 0, ccur = 0, pslot = 0, dslot = 0;
-  uint32_t nf = 0;
-  uint64_t ef = 0;
-  bool prepared = false;  // the frontier is held as contributions in cdense[ccur] (after a dense level)
-};
-
-// Runs levels from the list L.fcur until the frontier is empty.  A level is dense when nodes + edges of its frontier
-// reach dense_frac * m (the unweighted rule); the choice changes the order of fp64 additions and nothing else.
-int run_weighted_levels(pprhip_graph* g, const PushArgs& a, WLevels& L, pprhip_stats_t& st) {
-  const unsigned long long dense_thresh = (unsigned long long)std::ceil(g->tun.dense_frac * (double)g->gr->m);
-  const size_t nd = sizeof(double) * g->gr->n;
-  unsigned long long* const list_counter = &g->ctr->hist[1];
-  bool first_of_phase = false;
-  while (L.nf > 0) {
-    if ((unsigned long long)L.nf + L.ef >= dense_thresh) {
-      if (!L.prepared) {  // list form -> contributions in place
-        PPRHIP_CHECK_HIP(hipMemsetAsync(g->cdense[L.ccur], 0, nd, g->stream));
-        PPRHIP_CHECK_HIP(hipMemsetAsync(g->cdense[L.ccur ^ 1], 0, nd, g->stream));
-        PPRHIP_TRY(launch_w_prepare(g, a, L.fcur, L.nf, true, L.ccur, L.dslot, nullptr));
-        L.prepared = true;
-        first_of_phase = true;
-      }
-      const uint64_t bytes = 12ull * g->gr->m + 8ull * g->gr->m + 40ull * g->gr->n_nz;
-      ktimer().begin(PPRHIP_KERNEL_DENSE_PULL, bytes);
-      PPRHIP_TRY(launch_w_dense_level(g, a, L.ccur, L.pslot ^ 1, L.dslot));
-      ktimer().end();
-      // the sweep writes the contributions of the rows it applies only; a row without in-edges can hold one solely from
-      // the phase's seeding, so the seeded buffer is cleared right after its first level has consumed it
-      if (first_of_phase) PPRHIP_CHECK_HIP(hipMemsetAsync(g->cdense[L.ccur], 0, nd, g->stream));
-      first_of_phase = false;
-      st.dense_levels++;
-      st.levels++;
-      st.dense_nodes += L.nf;
-      st.dense_edges += L.ef;
-      st.push_bytes += bytes;
-      L.ccur ^= 1;
-      L.dslot ^= 1;
-      L.pslot ^= 1;
-      PPRHIP_TRY(fetch_packed(g, &g->ctr->packed[L.pslot], &L.nf, &L.ef));
-      st.enqueues += L.nf;
-      continue;
-    }
-    // ---- a sparse level
-    uint32_t nf_list = L.nf;
-    uint64_t ef_list = L.ef;
-    ktimer().begin(PPRHIP_KERNEL_SPARSE_PUSH, 44ull * L.nf + 36ull * L.ef);
-    if (L.prepared) {
-      // contributions in place -> list (dead-end nodes carry none: the list is recounted; it may be empty while their
-      // mass still has to land on the source, so the level runs whatever the recount says)
-      PPRHIP_CHECK_HIP(hipMemsetAsync(&g->ctr->hist[0], 0, 2 * sizeof(unsigned long long), g->stream));
-      PPRHIP_TRY(launch_compact_prepared(g, L.ccur, L.fcur, &g->ctr->hist[0], false));
-      PPRHIP_TRY(fetch_packed(g, &g->ctr->hist[0], &nf_list, &ef_list));
-      L.prepared = false;
-    } else {
-      PPRHIP_TRY(launch_w_prepare(g, a, L.fcur, L.nf, false, 0, L.dslot, list_counter));
-    }
-    PPRHIP_TRY(launch_w_push(g, a, L.fcur, nf_list, ef_list, L.dslot, list_counter));
-    ktimer().end();
-    st.pops += L.nf;
-    st.edge_pushes += L.ef;
-    st.levels++;
-    st.push_bytes += 44ull * L.nf + 36ull * L.ef;
-    L.fcur ^= 1;
-    PPRHIP_TRY(fetch_packed(g, list_counter, &L.nf, &L.ef));
-    st.enqueues += L.nf;
-  }
-  return PPRHIP_OK;
-}
-
 // one weighted push from src (internal id) at rmax, run to its end, on a workspace just reset; *rsum: the residue sum
 int weighted_push(pprhip_graph* g, int32_t src, double alpha, double rmax, pprhip_stats_t& st, double* rsum) {
   *rsum = 0.0;
@@ -154,6 +83,79 @@ int fetch_packed(pprhip_graph* g, const unsigned long long* cell, uint32_t* nf, 
   PPRHIP_TRY(fetch_small(g, cell, &pk, sizeof pk));
   *nf = (uint32_t)(pk >> kPackShift);
   *ef = pk & kPackMask;
+  return PPRHIP_OK;
+}
+
+// A level is dense when nodes + edges of its frontier reach dense_frac * m (the unweighted rule); the choice changes
+// the order of fp64 additions and nothing else.  Backward, a dense level sweeps the out-CSR (ensure_bwd_layout).
+int run_weighted_levels(pprhip_graph* g, const PushArgs& a, WLevels& L, pprhip_stats_t& st) {
+  const bool bwd = a.mode == kBackward;
+  const unsigned long long dense_thresh = (unsigned long long)std::ceil(g->tun.dense_frac * (double)g->gr->m);
+  const size_t nd = sizeof(double) * g->gr->n;
+  unsigned long long* const list_counter = &g->ctr->hist[1];
+  const uint64_t node_bytes = bwd ? 36 : 44, edge_bytes = bwd ? 44 : 36;  // of a sparse level, per list entry / edge
+  auto prepare = [&](bool dense, unsigned long long* counter) {
+    return bwd ? launch_wb_prepare(g, a, L.fcur, L.nf, dense, dense ? L.ccur : 0, counter)
+               : launch_w_prepare(g, a, L.fcur, L.nf, dense, dense ? L.ccur : 0, L.dslot, counter);
+  };
+  bool first_of_phase = false;
+  while (L.nf > 0) {
+    if ((unsigned long long)L.nf + L.ef >= dense_thresh) {
+      if (!L.prepared) {  // list form -> contributions in place
+        if (bwd) PPRHIP_TRY(ensure_bwd_layout(g));
+        PPRHIP_CHECK_HIP(hipMemsetAsync(g->cdense[L.ccur], 0, nd, g->stream));
+        PPRHIP_CHECK_HIP(hipMemsetAsync(g->cdense[L.ccur ^ 1], 0, nd, g->stream));
+        PPRHIP_TRY(prepare(true, nullptr));
+        L.prepared = true;
+        first_of_phase = true;
+      }
+      const uint64_t bytes = 12ull * g->gr->m + 8ull * g->gr->m + 40ull * (bwd ? g->gr->n_nz_o : g->gr->n_nz);
+      ktimer().begin(PPRHIP_KERNEL_DENSE_PULL, bytes);
+      PPRHIP_TRY(bwd ? launch_wb_dense_level(g, a, L.ccur, L.pslot ^ 1)
+                     : launch_w_dense_level(g, a, L.ccur, L.pslot ^ 1, L.dslot));
+      ktimer().end();
+      // the sweep writes the contributions of the rows it applies only; a row it skips (no in-edges forward, no
+      // out-edges backward) can hold one solely from the phase's seeding, so the seeded buffer is cleared right after
+      // its first level has consumed it
+      if (first_of_phase) PPRHIP_CHECK_HIP(hipMemsetAsync(g->cdense[L.ccur], 0, nd, g->stream));
+      first_of_phase = false;
+      st.dense_levels++;
+      st.levels++;
+      st.dense_nodes += L.nf;
+      st.dense_edges += L.ef;
+      st.push_bytes += bytes;
+      L.ccur ^= 1;
+      L.dslot ^= 1;
+      L.pslot ^= 1;
+      PPRHIP_TRY(fetch_packed(g, &g->ctr->packed[L.pslot], &L.nf, &L.ef));
+      st.enqueues += L.nf;
+      continue;
+    }
+    // ---- a sparse level
+    uint32_t nf_list = L.nf;
+    uint64_t ef_list = L.ef;
+    ktimer().begin(PPRHIP_KERNEL_SPARSE_PUSH, node_bytes * L.nf + edge_bytes * L.ef);
+    if (L.prepared) {
+      // contributions in place -> list (forward, dead-end nodes carry none: the list is recounted; it may be empty while
+      // their mass still has to land on the source, so the level runs whatever the recount says)
+      PPRHIP_CHECK_HIP(hipMemsetAsync(&g->ctr->hist[0], 0, 2 * sizeof(unsigned long long), g->stream));
+      PPRHIP_TRY(launch_compact_prepared(g, L.ccur, L.fcur, &g->ctr->hist[0], bwd));
+      PPRHIP_TRY(fetch_packed(g, &g->ctr->hist[0], &nf_list, &ef_list));
+      L.prepared = false;
+    } else {
+      PPRHIP_TRY(prepare(false, list_counter));
+    }
+    PPRHIP_TRY(bwd ? launch_wb_push(g, a, L.fcur, nf_list, ef_list, list_counter)
+                   : launch_w_push(g, a, L.fcur, nf_list, ef_list, L.dslot, list_counter));
+    ktimer().end();
+    st.pops += L.nf;
+    st.edge_pushes += L.ef;
+    st.levels++;
+    st.push_bytes += node_bytes * L.nf + edge_bytes * L.ef;
+    L.fcur ^= 1;
+    PPRHIP_TRY(fetch_packed(g, list_counter, &L.nf, &L.ef));
+    st.enqueues += L.nf;
+  }
   return PPRHIP_OK;
 }
 

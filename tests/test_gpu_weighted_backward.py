@@ -506,6 +506,72 @@ def test_state_errors_leave_the_handle(pkg, got):
         assert pv.size == 0 and st.walks == 0
 
 
+def test_bad_input_is_refused_alike_by_the_weighted_and_the_unweighted_call(pkg, got):
+    """pprhip_weighted_ppr_targets / _ppr_pairs refuse what pprhip_ppr_targets / _ppr_pairs refuse, on one handle that
+    has weights: the same return code, and the same message once the entry point's name is replaced.  Without weights
+    every weighted call is PPRHIP_ERR_STATE and the unweighted one succeeds."""
+    L = pkg.lib()
+    n = got.n
+    vp = lambda a: None if a is None else a.ctypes.data_as(C.c_void_p)
+    i32 = lambda *x: np.array(x, dtype=np.int32)
+    u64 = lambda *x: np.array(x, dtype=np.uint64)
+    f64 = lambda *x: np.array(x, dtype=np.float64)
+
+    def both(name, call):
+        """call(entry point) for the unweighted and the weighted one: ((rc, message), (rc, message))."""
+        res = []
+        for fn_name in ("pprhip_" + name, "pprhip_weighted_" + name):
+            rc = call(getattr(L, fn_name))
+            res.append((rc, L.pprhip_last_error().decode() if rc != pkg.OK else ""))
+        return res
+
+    def targets(t, w, off, q, k=0, ids=None, vals=None, keep=None, values=None):
+        st = pkg.Stats()
+        return lambda fn: fn(g.h, vp(t), vp(w), vp(off), q, ALPHA, 1e-4, keep, vp(values), k, vp(ids), vp(vals), None, None,
+                             C.byref(st))
+
+    def pairs(s, t, q, out, conf, rmax=0.0):
+        st = pkg.Stats()
+        return lambda fn: fn(g.h, vp(s), vp(t), q, 0.5, C.byref(conf), rmax, 3, vp(out), C.byref(st))
+
+    with pkg.Graph(got, device=0) as g, pkg.Graph(got, device=0) as other:
+        g.set_weights(_rand_w(got, 21))
+        conf = pkg.conf_whole_graph(got.n, got.m, ALPHA)
+        many = pkg.conf_whole_graph(got.n, got.m, ALPHA)
+        many.delta = 1e-16  # omega = 3 ln(2 / pfail) / (eps^2 delta) > 1e17 > 2^48 walks at rmax = 1
+        out4 = np.zeros(4)
+        with _closing(pkg.Results(other, 1)) as foreign:
+            bad = [
+                ("ppr_targets", "q < 0", targets(i32(0), None, None, -1), None),
+                ("ppr_targets", "k > 0 without ids_out", targets(i32(0), None, None, 1, k=3), None),
+                ("ppr_targets", "offsets[0] != 0", targets(i32(0, 1, 2), None, u64(1, 2, 3), 2), None),
+                ("ppr_targets", "descending offsets", targets(i32(0, 1, 2), None, u64(0, 2, 1, 3), 3), "set 1"),
+                ("ppr_targets", "an empty set", targets(i32(0, 1), None, u64(0, 1, 1, 2), 3), "set 1"),
+                ("ppr_targets", "id n", targets(i32(0, 1, n), None, u64(0, 1, 2, 3), 3), "set 2"),
+                ("ppr_targets", "negative weight", targets(i32(0, 1), f64(1.0, -0.5), None, 2), "set 1"),
+                ("ppr_targets", "NaN weight", targets(i32(0, 1), f64(1.0, np.nan), None, 2), "set 1"),
+                ("ppr_targets", "weights sum to 0", targets(i32(0, 1, 2), f64(1.0, 0.0, 0.0), u64(0, 1, 3), 2), "set 1"),
+                ("ppr_targets", "keep of another graph", targets(i32(0), None, None, 1, keep=foreign.h), None),
+                ("ppr_pairs", "NULL values_out", pairs(i32(0), i32(1), 1, None, conf), None),
+                ("ppr_pairs", "source -1", pairs(i32(-1, 0), i32(1, 1), 2, out4, conf), "pair 0"),
+                ("ppr_pairs", "target n", pairs(i32(0, 1, 2, 3), i32(1, 1, 1, n), 4, out4, conf), "pair 3"),
+                ("ppr_pairs", "more than 2^48 walks", pairs(i32(0), i32(1), 1, out4, many, rmax=1.0), "2^48"),
+            ]
+            for name, what, call, names in bad:
+                (rc_u, msg_u), (rc_w, msg_w) = both(name, call)
+                assert rc_u == rc_w == pkg.ERR_INVALID, (what, rc_u, rc_w, msg_u, msg_w)
+                assert msg_u.startswith("pprhip_%s: " % name), (what, msg_u)
+                assert msg_w.replace("pprhip_weighted_" + name, "pprhip_" + name) == msg_u, (what, msg_u, msg_w)
+                assert names is None or names in msg_u, (what, msg_u)
+        g.release(pkg.Graph.RELEASE_WEIGHTS)
+        values = np.zeros((1, n))
+        for name, call in (("ppr_targets", targets(i32(0), None, None, 1, values=values)),
+                           ("ppr_pairs", pairs(i32(0), i32(1), 1, out4, conf))):
+            (rc_u, _), (rc_w, msg_w) = both(name, call)
+            assert rc_u == pkg.OK and rc_w == pkg.ERR_STATE, (name, rc_u, rc_w, msg_w)
+            assert msg_w.startswith("pprhip_weighted_%s: " % name) and "no relationship weights" in msg_w
+
+
 def test_unweighted_backward_calls_ignore_the_weights(pkg, got):
     """backward_push, ppr_targets and ppr_pairs give what a weight-free handle gives, before and after weighted calls."""
     t = int(np.argmax(_indeg(got)))
