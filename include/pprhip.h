@@ -754,9 +754,9 @@ int pprhip_local_cluster_seeds(pprhip_graph_t* g, const int32_t* seeds, const do
  * FORA from one source) and backward (backward push, the survival vector, single targets / target sets, single pairs).
  * Only the pprhip_weighted_* calls read the weights.  Every entry point without that prefix ignores them - the
  * unweighted pprhip_backward_push, pprhip_ppr_targets and pprhip_ppr_pairs included - and so do the features that have
- * no weighted form yet: seed sets, top-k rounds, the batched FORA calls and streams, the walk index, All-Pair, the sweep
- * cut (which ranks by the relationship count, not by weighted degree), the multi-GPU calls; they give what they gave
- * before pprhip_graph_set_weights.
+ * no weighted form yet: the batched FORA calls and streams, the walk index, All-Pair, the sweep cut (which ranks by the
+ * relationship count, not by weighted degree), the multi-GPU calls; they give what they gave before
+ * pprhip_graph_set_weights.
  *
  * Weights: m doubles aligned with the out_col_idx given to pprhip_graph_create, every one finite and > 0 (a caller
  * drops relationships of weight <= 0 before the lift, so dead ends are exactly the unweighted dead ends), every row sum
@@ -806,6 +806,52 @@ int pprhip_weighted_random_walk_batch(pprhip_graph_t* g, const int32_t* starts, 
  * No threshold rounds and no cost model (the tuning constants were fitted on the unweighted kernels): rounds = 1. */
 int pprhip_weighted_fora(pprhip_graph_t* g, int32_t src, double eps, const pprhip_fora_conf_t* conf, uint64_t seed,
                          double rmax, double* reserve_out, pprhip_stats_t* stats);
+
+/* ---- weighted seed sets and top-k ("Weighted seed sets and top-k"): relationshipWeightProperty
+ * and sourceNodes in one query, and the reference's own top-k query over the weights.
+ * Seed set: seeds / weights / n_seeds exactly as pprhip_forward_push_seeds takes them - p = the weights over their sum
+ * (NULL: uniform), duplicates summed, zero weights dropped, the same refusals and messages - and p resolved for the
+ * dead-end seeds by the same closed form (with D = the weight of the dead-end seeds, mass x landing on p gives a live
+ * seed i the residue x q_i, q_i = p_i / (1 - (1 - alpha) D), and a dead-end seed j the reserve x alpha p_j / (1 - (1 -
+ * alpha) D)).  Nothing of this depends on the relationship weights: dead ends are the unweighted dead ends.
+ * Seeded push: the plain Jacobi levels of pprhip_weighted_forward_push with one change - a level's dead-end mass x lands
+ * on p instead of on the source, inside the same level: r(i) += x q_i for every live seed, tested with the same crossing
+ * rule, and x e_j into the reserve of every dead-end seed.  The first frontier is the set of live seeds; they pop
+ * unconditionally.  A set whose seeds are all dead ends leaves reserve = p and runs no push.  A set of one seed is
+ * pprhip_weighted_forward_push(s): the same levels and pops, vectors equal up to the order of additions.
+ * Top-k: Fora_Topk's schedule on delta, which does not depend on the weights - eps / 2, delta from conf->delta to
+ * max(min_delta, delta / 4) per round, the loop ends when kth >= (1 + eps / 2) delta or delta <= min_delta - over plain
+ * rounds.  Round j: rmax_j = the scaled push threshold of pprhip_fora_topk_params(delta), omega_j its omega; the first
+ * frontier is the live seeds (j = 0) or every node with r / d_out >= rmax_j (j > 0; possibly none); the levels above run
+ * at rmax_j to their end on the residues and the reserve the rounds before left; estimate := reserve; the walk plan of
+ * pprhip_fora_topk (rsum = (1 - alpha) * the residue sum, nrw = (long long)(omega_j rsum), an entry r starts ceil(r nrw)
+ * walks, each adding (r nrw / omega_i) / nrw); the walks are pprhip_weighted_random_walk_batch's (seed, stream j, node,
+ * index) without the forced first hop; then the selection of k and its k-th value (0 when fewer than k are positive).
+ * No parking or arming, no push ahead on a second stream, no cost model.  After every round no node is active at
+ * rmax_j.  No live seed: the estimate is p, rounds = 0, one selection.  The result is left as pprhip_fora_topk leaves it
+ * (pprhip_get_reserve, the sparse getters, pprhip_topk_select and pprhip_sweep_cut read the estimate); rows are padded
+ * -1 / 0; the stats are filled as by pprhip_fora_topk (rounds, levels, dense_levels, pops, walks, walk_steps,
+ * mc_sources, kth_value, rsum, rmax_final, omega, the times).
+ * Checks, in this order: the numeric parameters (the top-k calls: a top-k conf), the handle (an open query stream:
+ * PPRHIP_ERR_STATE), PPRHIP_ERR_STATE without weights, then ids and sets before any device work. */
+/* the contract of pprhip_forward_push_seeds, with the seeded weighted push */
+int pprhip_weighted_forward_push_seeds(pprhip_graph_t* g, const int32_t* seeds, const double* weights, int n_seeds,
+                                       double alpha, double rmax, double* reserve_out, double* residue_out,
+                                       double* rsum_out, pprhip_stats_t* stats);
+/* The seeded weighted push at rmax (0: rmax0), then pprhip_weighted_fora's walk phase unchanged: the whole-graph plan,
+ * stream 0, forced first hop, a walk restarts at its own start node at a dead end, rounds = 1.  No live seed: the
+ * estimate is p. */
+int pprhip_weighted_fora_seeds(pprhip_graph_t* g, const int32_t* seeds, const double* weights, int n_seeds, double eps,
+                               const pprhip_fora_conf_t* conf, uint64_t seed, double rmax, double* reserve_out,
+                               pprhip_stats_t* stats);
+/* signature and delivery of pprhip_fora_topk: the weighted top-k rounds from the set {src} with weight 1 */
+int pprhip_weighted_fora_topk(pprhip_graph_t* g, int32_t src, double eps, const pprhip_fora_conf_t* conf, uint64_t seed,
+                              int32_t* ids_out, double* vals_out, int cap, int* n_out, double* reserve_out,
+                              pprhip_stats_t* stats);
+/* signature and delivery of pprhip_fora_topk_seeds: the weighted top-k rounds from a seed set */
+int pprhip_weighted_fora_topk_seeds(pprhip_graph_t* g, const int32_t* seeds, const double* weights, int n_seeds,
+                                    double eps, const pprhip_fora_conf_t* conf, uint64_t seed, int32_t* ids_out,
+                                    double* vals_out, int cap, int* n_out, double* reserve_out, pprhip_stats_t* stats);
 
 /* ---- the backward direction over the same P ("Weighted backward direction")
  * Backward push: popping v with residue r credits reserve(v) += alpha r and deposits (c w(e)) / W(u) on r(u) along every

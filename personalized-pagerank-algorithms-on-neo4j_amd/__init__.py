@@ -105,6 +105,8 @@ EXPORTS = [
     "pprhip_weighted_forward_push", "pprhip_weighted_random_walk_batch", "pprhip_weighted_fora",
     "pprhip_weighted_backward_push", "pprhip_weighted_walk_survival", "pprhip_weighted_ppr_targets",
     "pprhip_weighted_ppr_pairs",
+    "pprhip_weighted_forward_push_seeds", "pprhip_weighted_fora_seeds", "pprhip_weighted_fora_topk",
+    "pprhip_weighted_fora_topk_seeds",
 ]
 SPARSE_BY_ID, SPARSE_BY_VALUE = 0, 1  # PPRHIP_SPARSE_BY_*: the orders of the sparse getters
 RELEASE_SPARSE = 16  # PPRHIP_RELEASE_SPARSE
@@ -246,6 +248,11 @@ def lib():
     L.pprhip_weighted_forward_push.argtypes = [vp, i32, dbl, dbl, vp, vp, P(dbl), P(Stats)]
     L.pprhip_weighted_random_walk_batch.argtypes = [vp, vp, vp, u64, dbl, u64, u32, ci, vp, vp]
     L.pprhip_weighted_fora.argtypes = [vp, i32, dbl, P(ForaConf), u64, dbl, vp, P(Stats)]
+    L.pprhip_weighted_forward_push_seeds.argtypes = [vp, vp, vp, ci, dbl, dbl, vp, vp, P(dbl), P(Stats)]
+    L.pprhip_weighted_fora_seeds.argtypes = [vp, vp, vp, ci, dbl, P(ForaConf), u64, dbl, vp, P(Stats)]
+    L.pprhip_weighted_fora_topk.argtypes = [vp, i32, dbl, P(ForaConf), u64, vp, vp, ci, P(ci), vp, P(Stats)]
+    L.pprhip_weighted_fora_topk_seeds.argtypes = [vp, vp, vp, ci, dbl, P(ForaConf), u64, vp, vp, ci, P(ci), vp,
+                                                  P(Stats)]
     L.pprhip_weighted_backward_push.argtypes = [vp, i32, dbl, dbl, vp, vp, P(Stats)]
     L.pprhip_weighted_walk_survival.argtypes = [vp, dbl, vp]
     L.pprhip_weighted_ppr_targets.argtypes = [vp, vp, vp, vp, ci, dbl, dbl, vp, vp, ci, vp, vp, vp, vp, P(Stats)]
@@ -1263,6 +1270,55 @@ class Graph:
         st = Stats()
         _check(lib().pprhip_weighted_fora(self.h, src, eps, C.byref(conf), seed, rmax, _ptr(out), C.byref(st)))
         return out, st
+
+    # ---- weighted seed sets and top-k: the return shapes of the unweighted / weighted namesakes
+    def weighted_forward_push_seeds(self, seeds, alpha, rmax, weights=None, fetch=True):
+        """forward_push_seeds over the weighted transition matrix (`weights`: the seeds' weights, None: uniform)."""
+        s, w = _seed_arrays(seeds, weights)
+        reserve = np.empty(self.n) if fetch else None
+        residue = np.empty(self.n) if fetch else None
+        rsum, st = C.c_double(), Stats()
+        _check(lib().pprhip_weighted_forward_push_seeds(self.h, _ptr(s), _ptr(w), s.size, alpha, rmax, _ptr(reserve),
+                                                        _ptr(residue), C.byref(rsum), C.byref(st)))
+        return reserve, residue, rsum.value, st
+
+    def weighted_fora_seeds(self, seeds, eps, alpha, seed, weights=None, rmax=0.0, conf=None, fetch=True):
+        """weighted_fora personalized to a seed set (`weights`: the seeds' weights, None: uniform)."""
+        s, w = _seed_arrays(seeds, weights)
+        conf = conf or conf_whole_graph(self.n, self.m, alpha)
+        out = np.empty(self.n) if fetch else None
+        st = Stats()
+        _check(lib().pprhip_weighted_fora_seeds(self.h, _ptr(s), _ptr(w), s.size, eps, C.byref(conf), seed, rmax,
+                                                _ptr(out), C.byref(st)))
+        return out, st
+
+    def weighted_fora_topk(self, src, eps, alpha, k, seed, cap=None, conf=None, fetch=False):
+        """fora_topk over the weighted transition matrix, in plain rounds; the same return shape."""
+        conf = conf or conf_topk(self.n, self.m, k, alpha)
+        cap = cap if cap is not None else k
+        ids = np.empty(max(cap, 1), dtype=np.int32)
+        vals = np.empty(max(cap, 1))
+        nsel, st = C.c_int(0), Stats()
+        out = np.empty(self.n) if fetch else None
+        _check(lib().pprhip_weighted_fora_topk(self.h, src, eps, C.byref(conf), seed, _ptr(ids), _ptr(vals), cap,
+                                               C.byref(nsel), _ptr(out), C.byref(st)))
+        w = min(nsel.value, cap)
+        return nsel.value, ids[:w].copy(), vals[:w].copy(), out, st
+
+    def weighted_fora_topk_seeds(self, seeds, eps, alpha, k, seed, weights=None, cap=None, conf=None, fetch=False):
+        """weighted_fora_topk personalized to a seed set; the return shape of fora_topk_seeds."""
+        s, w = _seed_arrays(seeds, weights)
+        conf = conf or conf_topk(self.n, self.m, k, alpha)
+        cap = cap if cap is not None else k
+        ids = np.empty(max(cap, 1), dtype=np.int32)
+        vals = np.empty(max(cap, 1))
+        nsel, st = C.c_int(0), Stats()
+        out = np.empty(self.n) if fetch else None
+        _check(lib().pprhip_weighted_fora_topk_seeds(self.h, _ptr(s), _ptr(w), s.size, eps, C.byref(conf), seed,
+                                                     _ptr(ids), _ptr(vals), cap, C.byref(nsel), _ptr(out),
+                                                     C.byref(st)))
+        w_ = min(nsel.value, cap)
+        return nsel.value, ids[:w_].copy(), vals[:w_].copy(), out, st
 
     # ---- the backward direction over the weights: the unweighted namesakes' arguments and return shapes
     def weighted_backward_push(self, target, alpha, rmax):

@@ -888,9 +888,22 @@ int launch_w_push(pprhip_graph* g, const PushArgs& a, int fbuf, uint32_t nf, uin
 int launch_w_dense_level(pprhip_graph* g, const PushArgs& a, int cbuf, int out_slot, int dead_slot);
 int launch_w_walk_batch(pprhip_graph* g, const int32_t* d_starts, const uint64_t* d_idx, uint64_t count, double alpha,
                         uint64_t seed, uint32_t stream, int no_zero_hop, int32_t* d_term, uint32_t* d_steps);
-// the weighted walks of the latest plan (launch_mc_plan): stream 0, forced first hop
-int launch_w_walk_plan(pprhip_graph* g, double alpha, uint64_t seed, double* target);
+// the weighted walks of the latest plan (launch_mc_plan) on `stream`, with or without the forced first hop
+// (pprhip_weighted_fora: 0, forced)
+int launch_w_walk_plan(pprhip_graph* g, double alpha, uint64_t seed, double* target, uint32_t stream, bool no_zero_hop);
 int init_kernels_weighted();
+
+// ---- kernels_weighted_query.hip (weighted seed sets and top-k rounds; weighted_query.cpp drives them)
+// between the two steps of a sparse level of a seeded push (g->seeds): the level's dead-end mass lands on p - the live
+// seeds' residues with the crossing test (crossers join list fbuf ^ 1, counted into *next_counter), the dead-end seeds'
+// reserves - and the cell is cleared before launch_w_push looks at it
+int launch_wq_land_sparse(pprhip_graph* g, const PushArgs& a, int fbuf, int dead_slot, unsigned long long* next_counter);
+// behind a seeded dense apply: the dead-end seeds' share of the level's dead-end mass, and the cell cleared
+int launch_wq_land_dense(pprhip_graph* g, int dead_slot);
+// a round's first frontier: the nodes active at rmax as list out_fbuf with the prefix of their out-degrees;
+// *d_counter: 0 before, entries << 36 | edges after
+int launch_wq_collect(pprhip_graph* g, double rmax, int out_fbuf, unsigned long long* d_counter);
+int init_kernels_weighted_query();
 
 // ---- kernels_weighted_bwd.hip (the backward direction over the weights; weighted_bwd.cpp drives them)
 // step 1 of a backward level that starts from the list fbuf (nf entries): every entry gives up its residue; c =

@@ -4,7 +4,8 @@
 // runs that push backward; sweep.cpp: sweep cut; sparse.cpp: sparse getters;
 // batch.cpp, batch_api.cpp, fetch_pipe.cpp, stream.cpp: the batched entry points; allpair.cpp:
 // All-Pair-Backward-Search; index.cpp: its inverted index; pairs.cpp, targets.cpp: single pairs and single targets;
-// weighted.cpp: relationship weights and the weighted calls; weighted_bwd.cpp: their backward direction).
+// weighted.cpp: relationship weights and the weighted calls; weighted_bwd.cpp: their backward direction;
+// weighted_query.cpp: weighted seed sets and top-k rounds).
 #pragma once
 
 #include <sys/mman.h>

@@ -12,7 +12,8 @@
 //           in-edges, 8 per lane, index and weight streams read once (non-temporal), gathers c[src], multiplies, sums
 //           by row with the segmented wave scan; row sums go to acc_nz.  k_w_dense_apply lands them (plus the dead-end
 //           mass on the source), tests the threshold with the relationship COUNT and prepares crossing rows for the
-//           next level; POWER: every row with mass pops.
+//           next level; POWER: every row with mass pops; SEEDED: the mass lands on a seed table instead
+//           (kernels_weighted_query.hip holds the rest of a seeded push).
 //   walks   one walk per lane, refilled in ballot order; the neighbour pick is a binary search over the row's
 //           inclusive weight prefix: x = (word * 2^-32) * W(cur), j = #{cum <= x} clamped to d - 1.
 //
@@ -66,16 +67,6 @@ __global__ __launch_bounds__(256) void k_w_prepare(const int32_t* __restrict__ F
 // ------------------------------------------------------------------------------------------------
 // sparse level, step 2: contributions land edge by edge
 // ------------------------------------------------------------------------------------------------
-// the unweighted push test: the relationship count, whatever the weights are
-__device__ __forceinline__ void w_push_finish(int32_t u, double add, double old, uint32_t du, WNewList* nl, double rmax) {
-  const double nw = old + add;
-  if (!active_fwd(old, du, rmax) && active_fwd(nw, du, rmax)) {
-    const uint32_t slot = atomicAdd(&nl->count, 1u);
-    nl->node[slot] = u;
-    nl->deg[slot] = du;
-  }
-}
-
 __global__ __launch_bounds__(256) void k_w_push(const int32_t* __restrict__ F, const double* __restrict__ cF,
                                                  const uint32_t* __restrict__ eoff, uint32_t nf, unsigned long long E,
                                                  const unsigned long long* __restrict__ out_ext,
@@ -253,7 +244,10 @@ __global__ __launch_bounds__(512) void k_w_dense_edges(const int32_t* __restrict
 // One thread per row with in-edges, plus one for a source without in-edges (it only ever receives returned dead-end
 // mass): lands the row sum, tests the threshold and prepares a crossing row for the next level in place
 // (k_dense_apply<kFwdWhole / kPower, false> with c = (1 - alpha) r / W).  POWER: every row with mass pops.
-template <bool POWER>
+// SEEDED (a seed set, src = -1): the level's dead-end mass x lands on p - a row takes x * seed_w[u] (q of a live seed,
+// zero elsewhere) before the test, the live seeds without in-edges are the extra rows, and the cell is left for
+// k_wq_land_dense, which credits the dead-end seeds and clears it.
+template <bool POWER, bool SEEDED>
 __global__ __launch_bounds__(256) void k_w_dense_apply(const int32_t* __restrict__ nz_rows, uint32_t n_nz,
                                                         double* __restrict__ acc_nz,
                                                         const unsigned long long* __restrict__ out_ext,
@@ -262,7 +256,8 @@ __global__ __launch_bounds__(256) void k_w_dense_apply(const int32_t* __restrict
                                                         DevCounters* ctr, unsigned long long* __restrict__ blk_pack,
                                                         double* __restrict__ blk_dead, uint32_t* __restrict__ blk_ndead,
                                                         int dead_slot, int src_extra, int32_t src, double alpha,
-                                                        double rmax) {
+                                                        double rmax, const double* __restrict__ seed_w,
+                                                        const int32_t* __restrict__ extra_rows) {
   __shared__ double s_red[4];
   __shared__ unsigned long long s_red2[4];
   const int tid = threadIdx.x;
@@ -276,13 +271,19 @@ __global__ __launch_bounds__(256) void k_w_dense_apply(const int32_t* __restrict
     acc_nz[j] = 0.0;
     have = true;
   } else if (j - n_nz < (uint32_t)src_extra) {
-    u = src;
+    u = SEEDED ? extra_rows[j - n_nz] : src;
     have = true;
   }
   double dead_next = 0.0;
   unsigned long long pack = 0, ndead = 0;
   if (have) {
-    if (u == src) {
+    if (SEEDED) {
+      const double q = seed_w[u];
+      if (q != 0.0) {
+        const double dd = ctr->dead[dead_slot];
+        if (dd > 0.0) acc += dd * q;
+      }
+    } else if (u == src) {
       const double dd = ctr->dead[dead_slot];
       if (dd > 0.0) {
         acc += dd;
@@ -375,11 +376,12 @@ __global__ __launch_bounds__(256) void k_w_walk_batch(const int32_t* __restrict_
 
 // The weighted walks of a plan (k_mc_plan<0> -> WalkPlanRec): one wave per workgroup with a contiguous share of the
 // phase's walks, a lane takes the wave's next walk when its own has stopped (ballot order) and finds the walk's entry
-// by binary search over the entries' walk offsets, from the entry of the wave's oldest open walk on.  Stream 0, forced
-// first hop; every walk adds its entry's increment at its terminal.
+// by binary search over the entries' walk offsets, from the entry of the wave's oldest open walk on.  The walks are
+// (seed, stream, node, index within the entry), with or without the forced first hop (whole-graph FORA: stream 0,
+// forced; a weighted top-k round: its round number, not forced); every walk adds its entry's increment at its terminal.
 __global__ __launch_bounds__(64) void k_w_walk_plan(const WalkPlanRec* __restrict__ plan_rec, WWalkGraph G,
                                                      double* __restrict__ target, double alpha, uint32_t k0, uint32_t k1,
-                                                     DevCounters* ctr, int parity) {
+                                                     uint32_t stream, int no_zero_hop, DevCounters* ctr, int parity) {
   const unsigned long long plan = ctr->mc_plan[parity];
   const uint32_t n_src = (uint32_t)(plan >> kPackShift);
   const unsigned long long n_walks = plan & kPackMask;
@@ -415,7 +417,7 @@ __global__ __launch_bounds__(64) void k_w_walk_plan(const WalkPlanRec* __restric
         e = a - 1u;
         const WalkPlanRec r = plan_rec[e];
         inc = r.inc;
-        w_walker_init(w, r.node, r.ext, r.orig, gidx - r.woff, 0u, true);
+        w_walker_init(w, r.node, r.ext, r.orig, gidx - r.woff, stream, no_zero_hop != 0);
         if ((r.ext >> 32) == 0)
           atomic_add_noret(&target[r.node], inc);  // a dead-end start is its own terminal
         else
@@ -467,8 +469,10 @@ int launch_w_push(pprhip_graph* g, const PushArgs& a, int fbuf, uint32_t nf, uin
 
 int launch_w_dense_level(pprhip_graph* g, const PushArgs& a, int cbuf, int out_slot, int dead_slot) {
   const GraphData* D = g->gr;
-  // a source without in-edges still receives returned dead-end mass: one extra apply thread
-  const int src_extra = (a.src >= 0 && D->h_in_rp[a.src + 1] == D->h_in_rp[a.src]) ? 1 : 0;
+  // a source without in-edges still receives returned dead-end mass: one extra apply thread (a seed set: one per live
+  // seed without in-edges, and the live seeds' landing weights go to the apply kernel)
+  const SeedTable* sd = (g->seed_on && a.mode != kPower) ? g->seeds : nullptr;
+  const int src_extra = sd ? (int)sd->n_zin : (a.src >= 0 && D->h_in_rp[a.src + 1] == D->h_in_rp[a.src]) ? 1 : 0;
   if (D->n_chunks) {
     constexpr uint32_t kWaves = 8;  // per workgroup of 512 threads
     const uint32_t want = (D->n_chunks + kWaves - 1) / kWaves;
@@ -480,12 +484,16 @@ int launch_w_dense_level(pprhip_graph* g, const PushArgs& a, int cbuf, int out_s
   const uint32_t rows = D->n_nz + (uint32_t)src_extra;
   const uint32_t grid = (rows + 255) / 256;
   if (grid) {
-    const auto apply = a.mode == kPower ? &k_w_dense_apply<true> : &k_w_dense_apply<false>;
+    const auto apply = a.mode == kPower ? &k_w_dense_apply<true, false>
+                       : sd             ? &k_w_dense_apply<false, true>
+                                        : &k_w_dense_apply<false, false>;
     apply<<<dim3(grid), dim3(256), 0, g->stream>>>(D->nz_rows, D->n_nz, g->acc_nz, D->out_ext, D->wsum, g->cdense[cbuf ^ 1],
                                                    g->residue, g->reserve, g->ctr, g->blk_pack, g->blk_dead, g->blk_ndead,
-                                                   dead_slot, src_extra, a.src, a.alpha, a.rmax);
+                                                   dead_slot, src_extra, a.src, a.alpha, a.rmax, sd ? sd->w_node : nullptr,
+                                                   sd ? sd->zin : nullptr);
     PPRHIP_CHECK_HIP(hipGetLastError());
   }
+  if (sd) PPRHIP_TRY(launch_wq_land_dense(g, dead_slot));
   return reduce_partials(g, grid, out_slot, dead_slot ^ 1, true);
 }
 
@@ -502,7 +510,7 @@ int launch_w_walk_batch(pprhip_graph* g, const int32_t* d_starts, const uint64_t
   return PPRHIP_OK;
 }
 
-int launch_w_walk_plan(pprhip_graph* g, double alpha, uint64_t seed, double* target) {
+int launch_w_walk_plan(pprhip_graph* g, double alpha, uint64_t seed, double* target, uint32_t stream, bool no_zero_hop) {
   // a fixed grid of waves, each with an equal share of whatever the plan holds; the host's bound of the walk count
   // (g->walk_hint) only trims the grid of a short phase (kernels_walk.hip: mc_walk_grid)
   uint32_t grid = (uint32_t)g->gr->n_cus * 16u;
@@ -510,7 +518,8 @@ int launch_w_walk_plan(pprhip_graph* g, double alpha, uint64_t seed, double* tar
   g->walk_hint = 0;
   const WalkPlanRec* rec = (g->mc_plan_rec2 && (g->mc_last_plan & 1u)) ? g->mc_plan_rec2 : g->mc_plan_rec;
   k_w_walk_plan<<<dim3(grid), dim3(64), 0, g->stream>>>(rec, walk_graph(g->gr), target, alpha, (uint32_t)seed,
-                                                        (uint32_t)(seed >> 32), g->ctr, (int)(g->mc_last_plan % 3u));
+                                                        (uint32_t)(seed >> 32), stream, no_zero_hop ? 1 : 0, g->ctr,
+                                                        (int)(g->mc_last_plan % 3u));
   PPRHIP_CHECK_HIP(hipGetLastError());
   return PPRHIP_OK;
 }

@@ -90,6 +90,7 @@ int fetch_packed(pprhip_graph* g, const unsigned long long* cell, uint32_t* nf, 
 // the order of fp64 additions and nothing else.  Backward, a dense level sweeps the out-CSR (ensure_bwd_layout).
 int run_weighted_levels(pprhip_graph* g, const PushArgs& a, WLevels& L, pprhip_stats_t& st) {
   const bool bwd = a.mode == kBackward;
+  const bool seeded = g->seed_on && !bwd;
   const unsigned long long dense_thresh = (unsigned long long)std::ceil(g->tun.dense_frac * (double)g->gr->m);
   const size_t nd = sizeof(double) * g->gr->n;
   unsigned long long* const list_counter = &g->ctr->hist[1];
@@ -145,6 +146,9 @@ int run_weighted_levels(pprhip_graph* g, const PushArgs& a, WLevels& L, pprhip_s
     } else {
       PPRHIP_TRY(prepare(false, list_counter));
     }
+    // a seeded push (SeedScope; a.src is -1): the level's dead-end mass lands on p here, and launch_w_push finds the
+    // cell empty
+    if (seeded) PPRHIP_TRY(launch_wq_land_sparse(g, a, L.fcur, L.dslot, list_counter));
     PPRHIP_TRY(bwd ? launch_wb_push(g, a, L.fcur, nf_list, ef_list, list_counter)
                    : launch_w_push(g, a, L.fcur, nf_list, ef_list, L.dslot, list_counter));
     ktimer().end();
@@ -461,7 +465,7 @@ int pprhip_weighted_fora(pprhip_graph_t* g, int32_t src, double eps, const pprhi
     const long long nrw = (nrw_d == nrw_d && nrw_d > 0.0) ? (long long)nrw_d : 0;
     PPRHIP_TRY(launch_walk_plan(g, 0, alpha, rsum, nrw, g->reserve, 0.0));
     ktimer().begin(PPRHIP_KERNEL_WALK, 0);
-    PPRHIP_TRY(launch_w_walk_plan(g, alpha, seed, g->reserve));
+    PPRHIP_TRY(launch_w_walk_plan(g, alpha, seed, g->reserve, 0u, true));
     ktimer().end();
   }
   tm.mark(2);

@@ -15,6 +15,17 @@ struct WNewList {  // crossings of the current tile, collected in LDS
   uint32_t count;
 };
 
+// the unweighted push test on (old, old + add): the relationship count, whatever the weights are; a crossing joins the
+// tile's list
+__device__ __forceinline__ void w_push_finish(int32_t u, double add, double old, uint32_t du, WNewList* nl, double rmax) {
+  const double nw = old + add;
+  if (!active_fwd(old, du, rmax) && active_fwd(nw, du, rmax)) {
+    const uint32_t slot = atomicAdd(&nl->count, 1u);
+    nl->node[slot] = u;
+    nl->deg[slot] = du;
+  }
+}
+
 // Appends the tile's crossings to the next frontier: one packed atomic reserves list slots and the edge range, a
 // workgroup scan turns the degrees into edge offsets (kernels_push.hip: flush_new).
 __device__ __forceinline__ void w_flush_new(WNewList* nl, int32_t* __restrict__ Fn, uint32_t* __restrict__ eoffn,
