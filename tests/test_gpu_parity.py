@@ -927,7 +927,9 @@ def test_sparse_levels_all_modes(pkg, orc, rmat15, dev_rmat15, got, dev_got):
     """Batches of sparse levels (prepare + push per level, eight levels per host round trip) in every push mode: same
     levels, same counters, same vectors as the twin - the forward push (sparse levels only, and mixed with sweeps), the
     resumable top-k push round by round, and the backward search; on GOT (levels of a handful of edges) and R-MAT 15
-    (levels of 10^5 edges)."""
+    (levels of 10^5 edges).  Which edge of the kernels a level meets here is chance: the designed edges (tile, staging,
+    batch, one-workgroup cap, grid bounds, LDS table, level shapes), held bit for bit, live in
+    tests/test_gpu_sparse_level_designs.py."""
     for host, dev, rmaxes in ((got, dev_got, (7.554e-4, 1e-8)), (rmat15, dev_rmat15, (1e-5, 1e-7))):
         og = to_oracle(orc, host)
         od = np.diff(host.out_rp)
