@@ -349,26 +349,38 @@ constexpr uint32_t kWalkShareEmpty = 0xFFFFFFFFu;
 constexpr int kWalkShareMinQueries = 32;  // calls of fewer queries run without the cache
 // Deposit records of a batched call's walk phases (kernels_walk.hip "deposits by tile"): walk
 // gidx < cap of a phase stores (terminal, increment) at position gidx instead of adding at the terminal; the records are
-// binned by tile of `1 << tile_shift` consecutive ids, summed per tile in LDS and added to the vector in runs.  One set
-// per handle: the phases that use it run one after another on the batch state's walk stream.  Lives and dies with the
-// call's terminal cache (WalkShare), under the same memory rule.
+// binned by tile of `1 << tile_shift` consecutive ids, summed per tile in LDS and added to the vector in runs.  The
+// records reach their tile's run in two passes that store whole lines: into the run of their coarse bin (`bin`
+// consecutive tiles) in bkey/binc, then from there into the tile's run, back in key/inc.  One set per handle: the
+// phases that use it run one after another on the batch state's walk stream.  Lives and dies with the call's terminal
+// cache (WalkShare), under the same memory rule.
 constexpr uint32_t kDepTileShift = 11;     // 2 048 doubles: 16 KB of LDS in the sum kernel
 constexpr uint32_t kDepMaxTiles = 4096;    // more tiles than this (16 KB of counters in LDS): the walks keep their atomics
 constexpr uint32_t kDepSlice = 16384;      // records of a work item: a hot tile is summed by several workgroups
 constexpr unsigned long long kDepMinWalks = 1ull << 18;  // a phase of fewer walks keeps its atomics
+constexpr uint32_t kDepBin = 32;           // tiles of a coarse bin: 64 bins on R-MAT 22
+constexpr uint32_t kDepMaxBin = 64;        // (a pass sorts into at most kDepMaxBins runs: a counter per thread)
+constexpr uint32_t kDepMaxBins = 256;      // more bins than this: the bin grows (4 096 tiles: 16 tiles at the least)
+constexpr uint32_t kDepChunk = 2048;       // records a workgroup of a binning pass sorts in LDS at a time (24 KB)
 struct DepositArgs {  // what the kernels take, by value
-  uint32_t* key = nullptr;   // [cap] terminal of walk gidx (internal id) ...
+  uint32_t* key = nullptr;   // [cap] terminal of walk gidx (internal id) ...; after the second pass: in per-tile runs
   double* inc = nullptr;     // [cap] ... and what it adds there
-  uint32_t* bkey = nullptr;  // [cap] the same records in per-tile runs
+  uint32_t* bkey = nullptr;  // [cap] the same records in per-bin runs
   double* binc = nullptr;
   uint32_t* tile_cnt = nullptr;  // [n_tiles] records per tile: counted, turned into items and zeroed again per phase
   uint32_t* tile_cur = nullptr;  // [n_tiles] next free position of every tile's run
+  uint32_t* bin_cur = nullptr;   // [n_bins + 1] next free position of every bin's run; [n_bins]: units of the phase
   uint4* items = nullptr;        // [items_cap] {tile, first record, records, the tile has other items}
+  uint4* units = nullptr;        // [units_cap] second pass: {bin, first record of the bin's run, records, 0}
   // [0] items of the phase in flight; since the last reset: [1] binned phases, [2] records, [3] walks beyond cap
   unsigned long long* stat = nullptr;
   unsigned long long cap = 0, min_walks = 0;
   uint32_t tile_shift = 0, n_tiles = 0, slice = 0, items_cap = 0, n = 0;
+  uint32_t bin = 0, n_bins = 0, units_cap = 0;  // tiles per coarse bin, bins (<= kDepMaxBins)
+  // hooks library only (PPRHIP_WALK_DEPOSIT_SKIP): the pass that keeps its loads and arithmetic but stores nothing
+  uint32_t skip = 0;
 };
+enum { kDepSkipNone = 0, kDepSkipCount = 1, kDepSkipScatter = 2, kDepSkipSum = 3 };  // (scatter: both binning passes)
 struct WalkDeposit {
   DepositArgs a;
   void* block = nullptr;  // the one allocation behind the arrays

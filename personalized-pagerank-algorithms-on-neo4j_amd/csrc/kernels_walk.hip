@@ -530,14 +530,20 @@ __global__ __launch_bounds__(64) void k_mc_walk(const WalkPlanRec* __restrict__ 
 // deposits by tile (engine.hpp: WalkDeposit)
 // What is left of a batched query's walk phase once the call's cache serves its walks is one fp64 atomic per walk at a
 // terminal: 64 lanes in 64 different lines per wave-instruction, executed at the memory side, the hubs' addresses hot.
-// Instead the walk kernel streams a 12-byte record per walk (above) and four kernels behind it on the same stream turn
+// Instead the walk kernel streams a 12-byte record per walk (above) and five kernels behind it on the same stream turn
 // the records into the same sums: k_dep_count counts the records per tile of 1 << tile_shift consecutive ids,
 // k_dep_items turns the counts into the tiles' runs and a table of work items (tile, slice of at most dep.slice
-// records: the first tile of an R-MAT holds a third of all records), k_dep_scatter moves the records into their runs (order
-// inside a run is free), and k_dep_sum adds an item's records into a tile of LDS and the tile to the vector: by
-// load-add-store when the item owns its tile, by atomics whose lanes are consecutive addresses when it shares it.
+// records: the first tile of an R-MAT holds a third of all records), k_dep_bin and k_dep_tile move the records into
+// their runs (order inside a run is free), and k_dep_sum adds an item's records into a tile of LDS and the tile to the
+// vector: by load-add-store when the item owns its tile, by atomics whose lanes are consecutive addresses when it
+// shares it.  The records move in two radix passes (dep_move) so that a store instruction's lanes write consecutive
+// positions: storing a record straight at its tile's cursor put a wave's 64 lanes into up to 64 lines of each array,
+// with 2 048 tiles x 2 arrays open per workgroup, which no cache merges.  k_dep_bin sorts a workgroup's share into the
+// runs of coarse bins of dep.bin consecutive tiles (runs are in tile order: a bin's run is its tiles' runs on end),
+// key/inc -> bkey/binc; k_dep_tile sorts a unit (bin, slice of the bin's run) into the bin's tile runs, bkey/binc ->
+// key/inc, which are dead by then.
 // Nothing is sized on the host: grids are fixed, every kernel reads the phase's walk count from the plan's cell as the
-// walk kernel does, and all four return at once when the walk kernel kept its atomics.
+// walk kernel does, and all five return at once when the walk kernel kept its atomics.
 // ------------------------------------------------------------------------------------------------
 __device__ __forceinline__ unsigned long long dep_records(const DepositArgs& a, const DevCounters* ctr, int parity) {
   const unsigned long long n_walks = ctr->mc_plan[parity] & kPackMask;
@@ -551,6 +557,13 @@ __device__ __forceinline__ void dep_share(unsigned long long n_rec, uint32_t* lo
   const unsigned long long a = (unsigned long long)blockIdx.x * per, b = a + per;
   *lo = (uint32_t)(a < n_rec ? a : n_rec);
   *hi = (uint32_t)(b < n_rec ? b : n_rec);
+}
+
+// Measurement switch of the hooks library (PPRHIP_WALK_DEPOSIT_SKIP, a.skip; 0 in the product): the named pass keeps
+// its loads, histograms and index arithmetic and stores nothing.  `never` is a condition on the loaded value that no
+// record meets: it keeps the compiler from dropping the loads with the store.
+__device__ __forceinline__ bool dep_stores(const DepositArgs& a, uint32_t pass, bool never) {
+  return a.skip != pass || never;
 }
 
 __device__ __forceinline__ uint32_t dep_tile_of(const DepositArgs& a, uint32_t key) {
@@ -575,7 +588,7 @@ __global__ __launch_bounds__(256) void k_dep_count(DepositArgs a, const DevCount
   dep_count_share(a, lo, hi, hist);
   for (uint32_t t = threadIdx.x; t < a.n_tiles; t += 256u) {  // (a wave's lanes: consecutive counters)
     const uint32_t c = hist[t];
-    if (c) atomicAdd(&a.tile_cnt[t], c);
+    if (c && dep_stores(a, kDepSkipCount, c == 0xFFFFFFFFu)) atomicAdd(&a.tile_cnt[t], c);
   }
 }
 
@@ -584,6 +597,7 @@ __global__ __launch_bounds__(256) void k_dep_items(DepositArgs a, const DevCount
   const unsigned long long n_rec = dep_records(a, ctr, parity);
   if (n_rec == 0) return;
   __shared__ uint32_t s_scan[4];
+  __shared__ uint32_t s_bin[kDepMaxBins + 1];  // where every bin's run starts, and the end of the last
   const uint32_t per = (a.n_tiles + 255u) / 256u;
   const uint32_t t_lo = threadIdx.x * per < a.n_tiles ? threadIdx.x * per : a.n_tiles;
   const uint32_t t_hi = t_lo + per < a.n_tiles ? t_lo + per : a.n_tiles;
@@ -599,6 +613,7 @@ __global__ __launch_bounds__(256) void k_dep_items(DepositArgs a, const DevCount
   for (uint32_t t = t_lo; t < t_hi; ++t) {
     const uint32_t c = a.tile_cnt[t];
     a.tile_cur[t] = base;
+    if (t % a.bin == 0u) s_bin[t / a.bin] = base;  // a bin's run starts where its first tile's does
     a.tile_cnt[t] = 0u;  // for the next phase
     const uint32_t k_n = (c + a.slice - 1u) / a.slice;
     for (uint32_t k = 0; k < k_n; ++k) {
@@ -609,7 +624,23 @@ __global__ __launch_bounds__(256) void k_dep_items(DepositArgs a, const DevCount
     base += c;
     ib += k_n;
   }
+  // the bins' cursors and the units of k_dep_tile (bin, slice of at most a.slice records of its run), in bin order
+  if (threadIdx.x == 0) s_bin[a.n_bins] = recs_all;
+  __syncthreads();
+  const uint32_t b = threadIdx.x;  // (n_bins <= kDepMaxBins = 256: a bin per thread)
+  const uint32_t b_first = b < a.n_bins ? s_bin[b] : 0u;
+  const uint32_t b_len = b < a.n_bins ? s_bin[b + 1u] - b_first : 0u;
+  const uint32_t u_n = (b_len + a.slice - 1u) / a.slice;
+  uint32_t units_all;
+  const uint32_t ub = block_excl_scan_256<uint32_t>(u_n, s_scan, &units_all);
+  if (b < a.n_bins) a.bin_cur[b] = b_first;
+  for (uint32_t k = 0; k < u_n; ++k) {
+    const uint32_t first = k * a.slice;
+    const uint32_t len = b_len - first < a.slice ? b_len - first : a.slice;
+    if (ub + k < a.units_cap) a.units[ub + k] = make_uint4(b, b_first + first, len, 0u);
+  }
   if (threadIdx.x == 0) {
+    a.bin_cur[a.n_bins] = units_all < a.units_cap ? units_all : a.units_cap;  // (units_cap >= n_bins + cap / slice)
     const unsigned long long n_walks = ctr->mc_plan[parity] & kPackMask;
     a.stat[0] = its_all < a.items_cap ? its_all : a.items_cap;  // (items_cap >= n_tiles + cap / slice: never short)
     a.stat[1] += 1ull;
@@ -618,27 +649,120 @@ __global__ __launch_bounds__(256) void k_dep_items(DepositArgs a, const DevCount
   }
 }
 
-__global__ __launch_bounds__(256) void k_dep_scatter(DepositArgs a, const DevCounters* ctr, int parity) {
+// One radix pass of a workgroup over the records [lo, hi) of src: into the runs of n_cls <= 256 classes of dst, class
+// = (tile - t0) / div, whose cursors are cur[].  The workgroup sorts kDepChunk records at a time by class in LDS (a
+// rank from an LDS counter, a scan over the classes) and stores them from there: LDS position p of a class goes to its
+// piece's cursor plus p's place in the class, so consecutive lanes write consecutive positions and a class's records
+// leave as whole lines but for the piece's two ends.  WHOLE: the workgroup first counts all its records per class and
+// reserves one piece per run (one atomic per class; k_dep_bin, where a chunk has some 32 records per bin and the pieces
+// of one workgroup follow each other); otherwise every chunk reserves its own pieces (k_dep_tile: one atomic per tile
+// and chunk, no second read of the keys).  27 KB of LDS.
+struct DepMoveLds {
+  uint32_t pos[kDepMaxBins];  // next position of every class's piece in dst
+  uint32_t cnt[kDepMaxBins];  // of the chunk: records per class; then: dst position minus LDS position of the class
+  uint32_t off[kDepMaxBins];  // of the chunk: where the class's records start in LDS
+  uint32_t scan[4];
+  uint32_t key[kDepChunk];
+  double inc[kDepChunk];
+};
+
+__device__ __forceinline__ uint32_t dep_class_of(const DepositArgs& a, uint32_t key, uint32_t t0, uint32_t div,
+                                                 uint32_t n_cls) {
+  const uint32_t c = (dep_tile_of(a, key) - t0) / div;
+  return c < n_cls ? c : n_cls - 1u;  // (never: the clamp only keeps a wrong record inside LDS)
+}
+
+template <bool WHOLE>
+__device__ __forceinline__ void dep_move(const DepositArgs& a, const uint32_t* __restrict__ src_key,
+                                         const double* __restrict__ src_inc, uint32_t* __restrict__ dst_key,
+                                         double* __restrict__ dst_inc, uint32_t lo, uint32_t hi, uint32_t n_rec,
+                                         uint32_t t0, uint32_t div, uint32_t n_cls, uint32_t* cur, DepMoveLds& s) {
+  constexpr uint32_t kPer = kDepChunk / 256u;
+  const uint32_t tid = threadIdx.x;
+  if (WHOLE) {
+    s.pos[tid] = 0u;
+    __syncthreads();
+    for (uint32_t i = lo + tid; i < hi; i += 256u) atomicAdd(&s.pos[dep_class_of(a, src_key[i], t0, div, n_cls)], 1u);
+    __syncthreads();
+    // this workgroup's piece of every run it has records for (thread c keeps the cursor of class c from here on)
+    const uint32_t c = s.pos[tid];
+    s.pos[tid] = tid < n_cls && c ? atomicAdd(&cur[tid], c) : 0u;
+  }
+  for (uint32_t c0 = lo; c0 < hi; c0 += kDepChunk) {
+    s.cnt[tid] = 0u;
+    __syncthreads();
+    uint32_t key[kPer], at[kPer];  // at: class << 16 | rank among the chunk's records of the class
+    double x[kPer];
+#pragma unroll
+    for (uint32_t k = 0; k < kPer; ++k) {
+      const uint32_t i = c0 + k * 256u + tid;
+      key[k] = i < hi ? src_key[i] : 0u;
+      x[k] = i < hi ? src_inc[i] : 0.0;
+    }
+#pragma unroll
+    for (uint32_t k = 0; k < kPer; ++k) {
+      const uint32_t cls = dep_class_of(a, key[k], t0, div, n_cls);
+      if (c0 + k * 256u + tid < hi) at[k] = cls << 16 | atomicAdd(&s.cnt[cls], 1u);
+    }
+    __syncthreads();
+    const uint32_t mine = s.cnt[tid];
+    uint32_t total;
+    const uint32_t off = block_excl_scan_256<uint32_t>(mine, s.scan, &total);
+    uint32_t piece;
+    if (WHOLE) {
+      piece = s.pos[tid];
+      s.pos[tid] = piece + mine;
+    } else {
+      piece = tid < n_cls && mine ? atomicAdd(&cur[tid], mine) : 0u;
+    }
+    s.off[tid] = off;
+    s.cnt[tid] = piece - off;
+    __syncthreads();
+#pragma unroll
+    for (uint32_t k = 0; k < kPer; ++k)
+      if (c0 + k * 256u + tid < hi) {
+        const uint32_t p = s.off[at[k] >> 16] + (at[k] & 0xFFFFu);
+        if (p < kDepChunk) {  // (always: the ranks and the scan count the same records)
+          s.key[p] = key[k];
+          s.inc[p] = x[k];
+        }
+      }
+    __syncthreads();
+    for (uint32_t p = tid; p < total; p += 256u) {
+      const uint32_t k = s.key[p];
+      const double y = s.inc[p];
+      const uint32_t dst = s.cnt[dep_class_of(a, k, t0, div, n_cls)] + p;
+      if (dst < n_rec && dep_stores(a, kDepSkipScatter, y < -1e300)) {
+        dst_key[dst] = k;
+        dst_inc[dst] = y;
+      }
+    }
+    __syncthreads();
+  }
+}
+
+__global__ __launch_bounds__(256) void k_dep_bin(DepositArgs a, const DevCounters* ctr, int parity) {
   const unsigned long long n_rec = dep_records(a, ctr, parity);
   if (n_rec == 0) return;
-  __shared__ uint32_t hist[kDepMaxTiles];
+  __shared__ DepMoveLds s;
   uint32_t lo, hi;
   dep_share(n_rec, &lo, &hi);
   if (lo >= hi) return;
-  dep_count_share(a, lo, hi, hist);
-  for (uint32_t t = threadIdx.x; t < a.n_tiles; t += 256u) {  // this workgroup's piece of every run it has records for
-    const uint32_t c = hist[t];
-    hist[t] = c ? atomicAdd(&a.tile_cur[t], c) : 0u;
-  }
-  __syncthreads();
-  for (uint32_t i = lo + threadIdx.x; i < hi; i += 256u) {
-    const uint32_t key = a.key[i];
-    const double x = a.inc[i];
-    const uint32_t pos = atomicAdd(&hist[dep_tile_of(a, key)], 1u);
-    if (pos < n_rec) {
-      a.bkey[pos] = key;
-      a.binc[pos] = x;
-    }
+  dep_move<true>(a, a.key, a.inc, a.bkey, a.binc, lo, hi, (uint32_t)n_rec, 0u, a.bin, a.n_bins, a.bin_cur, s);
+}
+
+__global__ __launch_bounds__(256) void k_dep_tile(DepositArgs a, const DevCounters* ctr, int parity) {
+  const unsigned long long n_rec = dep_records(a, ctr, parity);
+  if (n_rec == 0) return;
+  __shared__ DepMoveLds s;
+  const uint32_t n_units = a.bin_cur[a.n_bins];
+  for (uint32_t u = blockIdx.x; u < n_units; u += gridDim.x) {
+    const uint4 unit = a.units[u];
+    const uint32_t t0 = unit.x * a.bin;
+    if (t0 >= a.n_tiles || unit.y >= n_rec) continue;  // (never: the units cover the bins' runs)
+    const uint32_t n_cls = a.n_tiles - t0 < a.bin ? a.n_tiles - t0 : a.bin;
+    const uint32_t hi = unit.z < (uint32_t)n_rec - unit.y ? unit.y + unit.z : (uint32_t)n_rec;
+    dep_move<false>(a, a.bkey, a.binc, a.key, a.inc, unit.y, hi, (uint32_t)n_rec, t0, 1u, n_cls, a.tile_cur + t0, s);
   }
 }
 
@@ -657,14 +781,14 @@ __global__ __launch_bounds__(256) void k_dep_sum(DepositArgs a, const DevCounter
     for (uint32_t i = threadIdx.x; i < item.z; i += 256u) {
       const unsigned long long p = (unsigned long long)item.y + i;
       if (p >= n_rec) break;  // (never: the items cover the runs)
-      const uint32_t off = a.bkey[p] - v0;
-      if (off < width) (void)__hip_atomic_fetch_add(&acc[off], a.binc[p], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+      const uint32_t off = a.key[p] - v0;
+      if (off < width) (void)__hip_atomic_fetch_add(&acc[off], a.inc[p], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
     }
     __syncthreads();
     for (uint32_t j = threadIdx.x; j < width; j += 256u) {
       const double x = acc[j];
       const uint32_t v = v0 + j;
-      if (x != 0.0 && v < a.n) {
+      if (x != 0.0 && v < a.n && dep_stores(a, kDepSkipSum, x < -1e300)) {
         if (item.w) atomic_add_noret(&target[v], x);
         else target[v] = target[v] + x;
       }
@@ -1164,8 +1288,12 @@ int launch_mc_walk_shared(pprhip_graph* g, const TerminalTable* ws, double alpha
   // measurement switch, read per call: PPRHIP_WALK_DEPOSIT=none runs the phase without its deposits
   const char* sw = hook_env("PPRHIP_WALK_DEPOSIT");
   const int dep_mode = sw && sw[0] == 'n' ? kDepNone : dep && dep->on ? kDepBinned : kDepAtomic;
-  const DepositArgs none;
-  const DepositArgs& a = dep_mode == kDepBinned ? dep->a : none;
+  DepositArgs a;
+  if (dep_mode == kDepBinned) a = dep->a;
+  // measurement switch, read per call: PPRHIP_WALK_DEPOSIT_SKIP=count|scatter|sum, the pass that stores nothing
+  const char* skip = hook_env("PPRHIP_WALK_DEPOSIT_SKIP");
+  a.skip = !skip ? kDepSkipNone : skip[0] == 'c' ? kDepSkipCount : skip[0] == 's' && skip[1] == 'c' ? kDepSkipScatter
+         : skip[0] == 's' && skip[1] == 'u' ? kDepSkipSum : kDepSkipNone;
   const int cell = (int)(g->mc_last_plan % 3u);
   hipLaunchKernelGGL(k_mc_walk<kWalkShared>, dim3(grid), dim3(64), 0, g->stream, plan_rec_of(g, g->mc_last_plan),
                      reinterpret_cast<const uint4*>(g->gr->walk_rec), target, alpha, (uint32_t)seed, (uint32_t)(seed >> 32), 0u,
@@ -1177,7 +1305,8 @@ int launch_mc_walk_shared(pprhip_graph* g, const TerminalTable* ws, double alpha
     const uint32_t wg = (uint32_t)g->gr->n_cus;
     hipLaunchKernelGGL(k_dep_count, dim3(wg), dim3(256), 0, g->stream, a, (const DevCounters*)g->ctr, cell);
     hipLaunchKernelGGL(k_dep_items, dim3(1), dim3(256), 0, g->stream, a, (const DevCounters*)g->ctr, cell);
-    hipLaunchKernelGGL(k_dep_scatter, dim3(wg), dim3(256), 0, g->stream, a, (const DevCounters*)g->ctr, cell);
+    hipLaunchKernelGGL(k_dep_bin, dim3(wg), dim3(256), 0, g->stream, a, (const DevCounters*)g->ctr, cell);
+    hipLaunchKernelGGL(k_dep_tile, dim3(wg), dim3(256), 0, g->stream, a, (const DevCounters*)g->ctr, cell);
     hipLaunchKernelGGL(k_dep_sum, dim3(wg), dim3(256), 0, g->stream, a, (const DevCounters*)g->ctr, cell, target);
     PPRHIP_CHECK_HIP(hipGetLastError());
   }

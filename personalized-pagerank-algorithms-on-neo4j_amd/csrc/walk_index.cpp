@@ -162,7 +162,8 @@ static void walk_deposit_begin(pprhip_graph* P, WalkShare* ws) {
   const char* sw = hook_env("PPRHIP_WALK_DEPOSIT");  // test switch: atomic = the walks add at their terminals
   if (sw && sw[0] == 'a') return;
   const uint32_t n = P->gr->n;
-  // test switches: a small tile (doubles, a power of two), slice and capacity, and the walk count binning starts from
+  // test switches: a small tile (doubles, a power of two), slice, capacity and coarse bin (tiles), and the walk count
+  // binning starts from
   uint32_t shift = 0;
   for (unsigned long long t = hook_number("PPRHIP_WALK_DEPOSIT_TILE", 1ull << kDepTileShift); t > 1; t >>= 1) shift++;
   if (shift < 4 || shift > kDepTileShift) shift = kDepTileShift;
@@ -172,10 +173,17 @@ static void walk_deposit_begin(pprhip_graph* P, WalkShare* ws) {
   cap = std::min(cap, std::max<unsigned long long>(hook_number("PPRHIP_WALK_DEPOSIT_CAP", cap), 1ull));
   const unsigned long long n_tiles = ((unsigned long long)n + (1ull << shift) - 1ull) >> shift;
   if (n_tiles == 0 || n_tiles > kDepMaxTiles) return;
-  if (d.block && (d.want != cap || d.a.tile_shift != shift || d.a.slice != slice)) free_walk_deposit(d);
+  // tiles per coarse bin: at most kDepMaxBin, and as many as keep the bins within kDepMaxBins
+  unsigned long long bin = std::min<unsigned long long>(
+      std::max<unsigned long long>(hook_number("PPRHIP_WALK_DEPOSIT_BIN", kDepBin), 1ull), kDepMaxBin);
+  bin = std::max(bin, (n_tiles + kDepMaxBins - 1ull) / kDepMaxBins);
+  const unsigned long long n_bins = (n_tiles + bin - 1ull) / bin;
+  if (d.block && (d.want != cap || d.a.tile_shift != shift || d.a.slice != slice || d.a.bin != bin))
+    free_walk_deposit(d);
   if (!d.block) {
     auto up = [](size_t b) { return (b + 255) / 256 * 256; };
-    const size_t fixed = up(4 * n_tiles) * 2 + up(16 * (n_tiles + cap / slice + 1)) + up(4 * sizeof(unsigned long long));
+    const size_t fixed = up(4 * n_tiles) * 2 + up(4 * (n_bins + 1)) + up(16 * (n_tiles + cap / slice + 1)) +
+                         up(16 * (n_bins + cap / slice + 1)) + up(4 * sizeof(unsigned long long));
     size_t free_b = 0, total_b = 0;
     if (hipMemGetInfo(&free_b, &total_b) != hipSuccess) {
       (void)hipGetLastError();
@@ -202,6 +210,9 @@ static void walk_deposit_begin(pprhip_graph* P, WalkShare* ws) {
     a.n_tiles = (uint32_t)n_tiles;
     a.slice = (uint32_t)slice;
     a.items_cap = (uint32_t)(n_tiles + cap / slice + 1);
+    a.bin = (uint32_t)bin;
+    a.n_bins = (uint32_t)n_bins;
+    a.units_cap = (uint32_t)(n_bins + cap / slice + 1);
     a.n = n;
     a.key = (uint32_t*)b;    b += up(4 * fit);
     a.bkey = (uint32_t*)b;   b += up(4 * fit);
@@ -209,7 +220,9 @@ static void walk_deposit_begin(pprhip_graph* P, WalkShare* ws) {
     a.binc = (double*)b;     b += up(8 * fit);
     a.tile_cnt = (uint32_t*)b;  b += up(4 * n_tiles);
     a.tile_cur = (uint32_t*)b;  b += up(4 * n_tiles);
+    a.bin_cur = (uint32_t*)b;   b += up(4 * (n_bins + 1));
     a.items = (uint4*)b;     b += up(16 * (size_t)a.items_cap);
+    a.units = (uint4*)b;     b += up(16 * (size_t)a.units_cap);
     a.stat = (unsigned long long*)b;
     // the counters start at zero (k_dep_items leaves tile_cnt so); the arrays of records need no clear
     if (hipMemsetAsync(a.tile_cnt, 0, up(4 * n_tiles), P->stream) != hipSuccess ||
