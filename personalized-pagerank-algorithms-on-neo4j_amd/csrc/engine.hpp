@@ -529,6 +529,11 @@ struct BatchState {
   double* acc8 = nullptr;  // [row ordinal][kBatch] row sums
   int acc8_dir = 0;        // layout the row sums were last written in (0 forward, 1 backward)
   unsigned long long* prep_bits = nullptr;  // [kBatch][tiles]: rows holding a contribution after the last sweep
+  // what the batched apply kernel needs of a row besides its sums, per row ordinal of a sweep side (0 forward,
+  // 1 backward; rows with edges first, then the rows carried behind them): {node, out-degree, in-degree (backward
+  // side only, else 0), 0}, padded with node = -1 to apply_meta_rows().  Built on the device from the side's row
+  // lists (ensure_apply_meta: the forward side with the batch state, the backward side with its layout).
+  uint4* apply_meta[2] = {nullptr, nullptr};
   SlotArgs* d_slot_args = nullptr;
   SlotArgs* h_slot_args = nullptr;  // pinned
   unsigned long long* sweep_out = nullptr;    // [kBatch] frontier counters a sweep produced
@@ -719,6 +724,11 @@ int init_kernels_dense();
 constexpr uint32_t kApplyBlocks8 = 2048;  // workgroups of the batched apply kernel (per-slot partials each)
 // slot arguments already staged in parent->batch->h_slot_args; blocks: Gauss-Seidel blocks (nullptr / 1: one launch)
 int launch_dense_level_b8(pprhip_graph* parent, bool backward, const pprhip::GsBlock* blocks = nullptr, int n_blocks = 1);
+// records of BatchState::apply_meta for a side of n_rows rows: a trip reads the records of both its tiles without
+// asking where the rows end, so the array runs to the end of the tile pair behind the last tile
+static inline size_t apply_meta_rows(uint32_t n_rows) { return ((size_t)n_rows / 128 + 2) * 128; }
+// fills parent->batch->apply_meta[backward] (allocated, apply_meta_rows records) from the side's row lists
+int launch_build_apply_meta(pprhip_graph* parent, bool backward);
 #ifdef PPRHIP_TEST_HOOKS
 int launch_sweep_edges_only(pprhip_graph* parent, const pprhip::GsBlock& B);
 int launch_count_live_lines(pprhip_graph* P, unsigned long long* d_out);

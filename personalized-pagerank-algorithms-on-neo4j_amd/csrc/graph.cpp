@@ -314,6 +314,19 @@ int ensure_workspaces(pprhip_graph* P, int count) {
   return PPRHIP_OK;
 }
 
+// The apply kernel's row records of one sweep side (BatchState::apply_meta), built once: with the batch state for the
+// forward side, and for the backward side as soon as both the batch state and the layout over the out-CSR exist.
+static int ensure_apply_meta(pprhip_graph* P, bool backward) {
+  BatchState* B = P->batch;
+  const GraphData* D = P->gr;
+  if (!B || B->apply_meta[backward] || (backward && !D->start_flags_o)) return PPRHIP_OK;
+  const uint32_t n_rows = backward ? D->n_nz_o + D->n_z_o : D->n_nz + D->n_zin;
+  PPRHIP_TRY(alloc_dev((void**)&B->apply_meta[backward], sizeof(uint4) * apply_meta_rows(n_rows)));
+  PPRHIP_TRY(launch_build_apply_meta(P, backward));
+  PPRHIP_CHECK_HIP(hipStreamSynchronize(P->stream));
+  return PPRHIP_OK;
+}
+
 // Batch slots and the interleaved dense-level arrays, created on the first batched call.
 static int build_batch(pprhip_graph* P) {
   BatchState* B = P->batch;
@@ -333,6 +346,8 @@ static int build_batch(pprhip_graph* P) {
   PPRHIP_TRY(alloc_dev((void**)&B->blk_pack8, sizeof(unsigned long long) * kBatch * kApplyBlocks8));
   PPRHIP_TRY(alloc_dev((void**)&B->blk_dead8, sizeof(double) * kBatch * kApplyBlocks8));
   PPRHIP_TRY(alloc_dev((void**)&B->blk_ndead8, sizeof(uint32_t) * kBatch * kApplyBlocks8));
+  PPRHIP_TRY(ensure_apply_meta(P, false));
+  PPRHIP_TRY(ensure_apply_meta(P, true));
   for (int s = 0; s < kBatch; ++s) {
     B->col_owner[s] = -1;
     PPRHIP_TRY(make_slot(P, s));
@@ -363,7 +378,7 @@ void free_batch(pprhip_graph* P) {
   if (B->slot_stream) (void)hipStreamDestroy(B->slot_stream);
   for (pprhip_graph* S : B->slots) drop_slot(S);
   void* dev[] = {B->c8[0], B->c8[1], B->acc8, B->prep_bits, B->d_slot_args, B->sweep_out, B->blk_pack8, B->blk_dead8,
-                 B->blk_ndead8};
+                 B->blk_ndead8, B->apply_meta[0], B->apply_meta[1]};
   for (void* p : dev)
     if (p) (void)hipFree(p);
   if (B->h_slot_args) (void)hipHostFree(B->h_slot_args);
@@ -375,7 +390,7 @@ void free_batch(pprhip_graph* P) {
 // sweep layout over the out-CSR for batched backward searches (the forward one is built at graph lift)
 int ensure_bwd_layout(pprhip_graph* P) {
   GraphData* D = P->gr;
-  if (D->start_flags_o) return PPRHIP_OK;
+  if (D->start_flags_o) return ensure_apply_meta(P, true);
   const uint32_t n = D->n;
   const uint64_t m = D->m;
   const std::vector<uint32_t>& rp = D->h_out_rp;
@@ -410,7 +425,7 @@ int ensure_bwd_layout(pprhip_graph* P) {
   PPRHIP_TRY(upload((void**)&D->z_rows_o, zr.data(), sizeof(int32_t) * zr.size()));
   PPRHIP_TRY(upload((void**)&D->cross_bits_o, cross.data(), sizeof(unsigned long long) * cross.size()));
   PPRHIP_TRY(upload((void**)&D->start_flags_o, flags.data(), flags.size()));
-  return PPRHIP_OK;
+  return ensure_apply_meta(P, true);
 }
 
 }  // namespace detail

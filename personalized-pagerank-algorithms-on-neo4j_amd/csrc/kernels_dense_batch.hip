@@ -214,11 +214,67 @@ constexpr int kApplyGroups = 2;  // tiles of kApplyRows rows a workgroup carries
 constexpr int kApplyThreads = 512;  // 8 waves, 2 slots each: few enough slot arguments to stay in SGPRs
 constexpr int kSlotsPerWave = kBatch / (kApplyThreads / 64);
 
-__global__ __launch_bounds__(kApplyThreads) void k_dense_apply_batch(const int32_t* __restrict__ nz_rows, uint32_t n_nz,
-                                                            const int32_t* __restrict__ zin_rows, uint32_t n_zin,
-                                                            double* __restrict__ acc8,
-                                                            const uint32_t* __restrict__ out_rp,
-                                                            const uint32_t* __restrict__ in_rp_bwd,
+// The slot vectors' pointers come out of SlotArgs in memory, so the compiler takes them for generic pointers and uses
+// flat_* instructions, which also count on lgkmcnt; they are device memory.
+template <class T>
+__device__ __forceinline__ T __attribute__((address_space(1)))* slot_vec(T* p) {
+  return (T __attribute__((address_space(1)))*)p;
+}
+// take_armed (push_device.hpp) on a slot's armed bits
+__device__ __forceinline__ bool take_armed_slot(uint32_t* armed_generic, int32_t u) {
+  auto armed = slot_vec(armed_generic);
+  const uint32_t bit = 1u << ((uint32_t)u & 31u);
+  if (!(armed[(uint32_t)u >> 5] & bit)) return false;
+  return (__hip_atomic_fetch_and(&armed[(uint32_t)u >> 5], ~bit, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) & bit) != 0;
+}
+
+constexpr int kApplyPerThread = kApplyRows * kBatch / kApplyThreads;  // row sums of a tile a thread moves
+
+// What a trip needs from memory before its first barrier, loaded in one flight: no load below depends on another or
+// stands behind a branch (a row behind the last with edges reads row 0's sums, a tile behind tile_hi what is there,
+// and the trip counts both as 0.0; the records behind the last row hold node -1), so a trip waits for memory once
+// where it used to wait for every row sum and then for nz_rows -> out_rp.
+struct ApplyFlight {
+  double v[kApplyGroups][kApplyPerThread];  // row sums, as the tile's [row][slot] lines (out of range: row 0's)
+  uint4 md;                                 // threads below kApplyRows * kApplyGroups: the record of row tid of the trip
+  unsigned long long cw[kApplyGroups];      // cross bits of the tiles
+};
+__device__ __forceinline__ void apply_flight(ApplyFlight& f, uint32_t tl0, uint32_t n_nz, const double* acc8,
+                                             const uint4* __restrict__ meta,
+                                             const unsigned long long* __restrict__ cross_bits, int tid) {
+  if (tid < kApplyRows * kApplyGroups) f.md = meta[(size_t)tl0 * kApplyRows + tid];  // (whole waves take the branch)
+#pragma unroll
+  for (int g = 0; g < kApplyGroups; ++g) {
+    const uint32_t tl = tl0 + g;  // (at most the tile behind the last: cross_bits has a word for it)
+    f.cw[g] = cross_bits[tl];
+#pragma unroll
+    for (int i = 0; i < kApplyPerThread; ++i) {
+      const uint32_t idx = (uint32_t)i * (uint32_t)kApplyThreads + tid;
+      const uint32_t j = tl * kApplyRows + idx / kBatch;
+      f.v[g][i] = __builtin_nontemporal_load(&acc8[(size_t)(j < n_nz ? j : 0u) * kBatch + idx % kBatch]);
+    }
+  }
+}
+
+// records of the apply kernel's rows on one sweep side (BatchState::apply_meta), n_pad of them
+__global__ __launch_bounds__(256) void k_build_apply_meta(const int32_t* __restrict__ nz_rows, uint32_t n_nz,
+                                                          const int32_t* __restrict__ z_rows, uint32_t n_z,
+                                                          const uint32_t* __restrict__ out_rp,
+                                                          const uint32_t* __restrict__ in_rp_bwd, uint4* __restrict__ meta,
+                                                          uint32_t n_pad) {
+  const uint32_t j = blockIdx.x * 256u + threadIdx.x;
+  if (j >= n_pad) return;
+  const int32_t u = j < n_nz ? nz_rows[j] : (j < n_nz + n_z ? z_rows[j - n_nz] : -1);
+  uint4 r = make_uint4((uint32_t)u, 0u, 0u, 0u);
+  if (u >= 0) {
+    r.y = out_rp[u + 1] - out_rp[u];
+    if (in_rp_bwd) r.z = in_rp_bwd[u + 1] - in_rp_bwd[u];
+  }
+  meta[j] = r;
+}
+
+__global__ __launch_bounds__(kApplyThreads) void k_dense_apply_batch(const uint4* __restrict__ meta, uint32_t n_nz,
+                                                            uint32_t n_zin, double* __restrict__ acc8,
                                                             double* __restrict__ c8_cur, double* __restrict__ c8_next,
                                                             uint32_t tile_lo, uint32_t tile_hi, uint32_t gs_mask,
                                                             uint32_t entry_mask,
@@ -252,50 +308,52 @@ __global__ __launch_bounds__(kApplyThreads) void k_dense_apply_batch(const int32
     pack[i] = 0;
     ndead[i] = 0;
   }
-  // kApplyGroups tiles of 64 rows per trip: every phase below issues the loads of all of them before the barrier that
-  // ends it (the waves of a workgroup spent four fifths of their cycles at those barriers with one tile per trip)
+  // kApplyGroups tiles of 64 rows per trip (the waves of a workgroup spent four fifths of their cycles at the barriers
+  // with one tile per trip).  A trip waits for memory three times: for its first phase's flight (ApplyFlight), for
+  // the entry staging's loads, issued together, and for the residue / reserve loads of the wave's slots.
   for (uint32_t tl0 = tile_lo + blockIdx.x * kApplyGroups; tl0 < tile_hi; tl0 += gridDim.x * kApplyGroups) {
+    ApplyFlight f;
+    apply_flight(f, tl0, n_nz, acc8, meta, cross_bits, tid);
 #pragma unroll
     for (int g = 0; g < kApplyGroups; ++g) {
-      const uint32_t tl = tl0 + g;
-      const bool in = tl < tile_hi;
-      const uint32_t row0 = tl * kApplyRows;
-      // rows inside one 512-edge chunk are rewritten by plain stores every sweep; only the rows that
-      // cross a chunk boundary are summed with atomics and have to be cleared for the next sweep
-      const unsigned long long cw = in ? cross_bits[tl] : 0ull;
 #pragma unroll
-      for (int i = 0; i < kApplyRows * kBatch / kApplyThreads; ++i) {
+      for (int i = 0; i < kApplyPerThread; ++i) {
         const uint32_t idx = (uint32_t)i * (uint32_t)kApplyThreads + tid;
         const uint32_t r = idx / kBatch, s = idx % kBatch;
-        const uint32_t j = row0 + r;
-        double v = 0.0;
-        if (in && j < n_nz) {
-          const size_t t = (size_t)j * kBatch + s;
-          v = __builtin_nontemporal_load(&acc8[t]);
-          if (v != 0.0 && ((cw >> r) & 1ull)) acc8[t] = 0.0;
-        }
+        // rows inside one 512-edge chunk are rewritten by plain stores every sweep; only the rows that
+        // cross a chunk boundary are summed with atomics and have to be cleared for the next sweep
+        const uint32_t j = (tl0 + g) * kApplyRows + r;
+        const double v = (tl0 + g < tile_hi && j < n_nz) ? f.v[g][i] : 0.0;  // (nothing looks at a value in flight)
+        if (v != 0.0 && ((f.cw[g] >> r) & 1ull)) acc8[(size_t)j * kBatch + s] = 0.0;
         tile[g][r][s] = v;
       }
     }
     if (tid < kApplyRows * kApplyGroups) {
       const uint32_t g = tid / kApplyRows, r = tid % kApplyRows;
-      const uint32_t tl = tl0 + g;
-      const uint32_t j = tl * kApplyRows + r;
-      const int32_t u = tl >= tile_hi ? -1 : (j < n_nz ? nz_rows[j] : (j < n_rows ? zin_rows[j - n_nz] : -1));
-      s_u[g][r] = u;
-      s_d[g][r] = u >= 0 ? out_rp[u + 1] - out_rp[u] : 0u;
-      s_din[g][r] = (u >= 0 && in_rp_bwd) ? in_rp_bwd[u + 1] - in_rp_bwd[u] : 0u;
+      const bool in = tl0 + g < tile_hi;
+      s_u[g][r] = in ? (int32_t)f.md.x : -1;
+      s_d[g][r] = in ? f.md.y : 0u;
+      s_din[g][r] = in ? f.md.z : 0u;
     }
     __syncthreads();
     if (entry_mask) {  // entry sweeps add to the row's own pending contribution: stage it (whole lines)
+      double p[kApplyGroups][kApplyPerThread];
 #pragma unroll
       for (int g = 0; g < kApplyGroups; ++g) {
 #pragma unroll
-        for (int i = 0; i < kApplyRows * kBatch / kApplyThreads; ++i) {
+        for (int i = 0; i < kApplyPerThread; ++i) {
+          const uint32_t idx = (uint32_t)i * (uint32_t)kApplyThreads + tid;
+          const int32_t ur = s_u[g][idx / kBatch];
+          p[g][i] = c8_cur[(size_t)(ur >= 0 ? ur : 0) * kBatch + idx % kBatch];  // (an absent row reads row 0)
+        }
+      }
+#pragma unroll
+      for (int g = 0; g < kApplyGroups; ++g) {
+#pragma unroll
+        for (int i = 0; i < kApplyPerThread; ++i) {
           const uint32_t idx = (uint32_t)i * (uint32_t)kApplyThreads + tid;
           const uint32_t r = idx / kBatch, s = idx % kBatch;
-          const int32_t ur = s_u[g][r];
-          tile_p[g][r][s] = (ur >= 0 && (entry_mask >> s & 1u)) ? c8_cur[(size_t)ur * kBatch + s] : 0.0;
+          tile_p[g][r][s] = (s_u[g][r] >= 0 && (entry_mask >> s & 1u)) ? p[g][i] : 0.0;
         }
       }
       __syncthreads();
@@ -341,8 +399,9 @@ __global__ __launch_bounds__(kApplyThreads) void k_dense_apply_batch(const int32
     for (int g = 0; g < kApplyGroups; ++g) {
 #pragma unroll
       for (int i = 0; i < kSlotsPerWave; ++i) {
-        oldv[g][i] = live[g][i] ? a[i].res[u[g]] : 0.0;
-        rsvv[g][i] = live[g][i] ? a[i].reserve[u[g]] : 0.0;  // needed when the row crosses, which most rows of a dense level do
+        oldv[g][i] = live[g][i] ? slot_vec(a[i].res)[u[g]] : 0.0;
+        // (the reserve is needed when the row crosses, which most rows of a dense level do)
+        rsvv[g][i] = live[g][i] ? slot_vec(a[i].reserve)[u[g]] : 0.0;
       }
     }
 #pragma unroll
@@ -357,24 +416,24 @@ __global__ __launch_bounds__(kApplyThreads) void k_dense_apply_batch(const int32
           const double old = oldv[g][i];
           const double nw = old + accv[g][i] / (double)d[g];
           if (!(old > a[i].rmax) && nw > a[i].rmax) {
-            a[i].reserve[u[g]] = rsvv[g][i] + nw * a[i].alpha;
-            if (oldv[g][i] != 0.0) a[i].res[u[g]] = 0.0;  // (rows that cross every sweep hold zero already)
+            slot_vec(a[i].reserve)[u[g]] = rsvv[g][i] + nw * a[i].alpha;
+            if (oldv[g][i] != 0.0) slot_vec(a[i].res)[u[g]] = 0.0;  // (rows that cross every sweep hold zero already)
             cn = (1.0 - a[i].alpha) * nw;
             pack[i] += (1ull << kPackShift) | (unsigned long long)din[g];
           } else {
-            a[i].res[u[g]] = nw;
+            slot_vec(a[i].res)[u[g]] = nw;
           }
         } else if (live[g][i]) {
           const double old = oldv[g][i];
           const double nw = old + accv[g][i];
           bool crossing = !active_fwd(old, d[g], a[i].rmax) && active_fwd(nw, d[g], a[i].rmax);
           if (a[i].mode == kFwdTopk) {
-            if (a[i].rmax < a[i].min_rmax && active_fwd(old, d[g], a[i].rmax)) crossing = take_armed(a[i].armed, u[g]);
-            if (active_fwd(nw, d[g], a[i].min_rmax)) a[i].flags[u[g]] = 1;
+            if (a[i].rmax < a[i].min_rmax && active_fwd(old, d[g], a[i].rmax)) crossing = take_armed_slot(a[i].armed, u[g]);
+            if (active_fwd(nw, d[g], a[i].min_rmax)) slot_vec(a[i].flags)[u[g]] = 1;
           }
           if (crossing) {  // becomes a frontier node of the next level: prepare it right here
-            a[i].reserve[u[g]] = rsvv[g][i] + nw * a[i].alpha;
-            if (oldv[g][i] != 0.0) a[i].res[u[g]] = 0.0;  // (rows that cross every sweep hold zero already)
+            slot_vec(a[i].reserve)[u[g]] = rsvv[g][i] + nw * a[i].alpha;
+            if (oldv[g][i] != 0.0) slot_vec(a[i].res)[u[g]] = 0.0;  // (rows that cross every sweep hold zero already)
             if (d[g] == 0) {
               dead_next[i] += nw * (1.0 - a[i].alpha);
               ndead[i]++;
@@ -383,7 +442,7 @@ __global__ __launch_bounds__(kApplyThreads) void k_dense_apply_batch(const int32
             }
             pack[i] += (1ull << kPackShift) | (unsigned long long)d[g];
           } else {
-            a[i].res[u[g]] = nw;
+            slot_vec(a[i].res)[u[g]] = nw;
           }
         }
         tile[g][lane][s] = cn;
@@ -402,7 +461,7 @@ __global__ __launch_bounds__(kApplyThreads) void k_dense_apply_batch(const int32
 #pragma unroll
     for (int g = 0; g < kApplyGroups; ++g) {
 #pragma unroll
-      for (int i = 0; i < kApplyRows * kBatch / kApplyThreads; ++i) {
+      for (int i = 0; i < kApplyPerThread; ++i) {
         const uint32_t idx = (uint32_t)i * (uint32_t)kApplyThreads + tid;
         const uint32_t r = idx / kBatch, s = idx % kBatch;
         const int32_t ur = s_u[g][r];
@@ -547,6 +606,17 @@ int launch_sweep_edges_only(pprhip_graph* P, const GsBlock& B) {
 }
 #endif
 
+int launch_build_apply_meta(pprhip_graph* P, bool backward) {
+  const GraphData* D = P->gr;
+  const SweepSide S = sweep_side(D, backward);
+  const uint32_t n_pad = (uint32_t)apply_meta_rows(S.n_nz + S.n_z);
+  k_build_apply_meta<<<dim3((n_pad + 255) / 256), dim3(256), 0, P->stream>>>(
+      S.nz_rows, S.n_nz, S.z_rows, S.n_z, D->out_rp, backward ? D->in_rp : nullptr, P->batch->apply_meta[backward], n_pad);
+  PPRHIP_CHECK_HIP(hipGetLastError());
+  return PPRHIP_OK;
+}
+
+static_assert(kApplyRows * kApplyGroups == 128, "apply_meta_rows (engine.hpp) pads the records to pairs of 64-row tiles");
 static_assert(kApplyRows == kTileRows, "launch_compact_prepared (kernels_frontier.hip) finds a slot's prep_bits by kTileRows");
 
 int launch_dense_level_b8(pprhip_graph* P, bool backward, const GsBlock* gs_blocks, int n_gs_blocks) {
@@ -555,6 +625,11 @@ int launch_dense_level_b8(pprhip_graph* P, bool backward, const GsBlock* gs_bloc
   PPRHIP_CHECK_HIP(hipMemcpyAsync(bs->d_slot_args, bs->h_slot_args, sizeof(SlotArgs) * kBatch, hipMemcpyHostToDevice,
                                   P->stream));
   const SweepSide S = sweep_side(D, backward);
+  const uint4* meta = bs->apply_meta[backward];
+  if (!meta) {
+    set_error("batched sweep: no row records for the %s side", backward ? "backward" : "forward");
+    return PPRHIP_ERR_INVALID;
+  }
   // slots whose sweep state writes the current contribution array in place; without any, one launch serves the
   // whole sweep (Jacobi rows do not care in which order the blocks run)
   uint32_t gs_mask = 0, entry_mask = 0;
@@ -581,9 +656,13 @@ int launch_dense_level_b8(pprhip_graph* P, bool backward, const GsBlock* gs_bloc
     const uint32_t t_hi = (b == nb - 1) ? n_tiles : B.j_hi / kApplyRows;
     if (t_hi <= t_lo) continue;
     const uint32_t quota = kApplyBlocks8 / (uint32_t)nb;
-    const uint32_t grid = std::max(1u, std::min((t_hi - t_lo + kApplyGroups - 1) / kApplyGroups, quota));
+    uint32_t grid = std::max(1u, std::min((t_hi - t_lo + kApplyGroups - 1) / kApplyGroups, quota));
+    // PPRHIP_APPLY_GRID (test switch, read at every launch): at most so many workgroups, so that a graph of a few
+    // hundred rows gives a workgroup a second and a third trip
+    if (const char* e = hook_env("PPRHIP_APPLY_GRID"))
+      if (atol(e) > 0) grid = (uint32_t)std::min<long>(grid, atol(e));
     k_dense_apply_batch<<<dim3(grid), dim3(kApplyThreads), 0, P->stream>>>(
-          S.nz_rows, S.n_nz, S.z_rows, S.n_z, bs->acc8, D->out_rp, backward ? D->in_rp : nullptr, bs->c8[bs->c8cur],
+          meta, S.n_nz, S.n_z, bs->acc8, bs->c8[bs->c8cur],
           bs->c8[bs->c8cur ^ 1], t_lo, t_hi, b == nb - 1 ? 0u : gs_mask, b == nb - 1 ? 0u : entry_mask, bs->d_slot_args,
           S.cross_bits, bs->prep_bits, bs->blk_pack8, bs->blk_dead8, bs->blk_ndead8, part_base, kApplyBlocks8);
     PPRHIP_CHECK_HIP(hipGetLastError());
