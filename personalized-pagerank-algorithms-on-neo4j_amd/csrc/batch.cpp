@@ -773,6 +773,24 @@ void BatchSync::sweeper() {
 }  // namespace pprhip
 
 // runs a prepared job on the handle's slots (both batched entry points)
+#ifdef PPRHIP_TEST_HOOKS
+// PPRHIP_APPLY_COUNT_RES=1 (hooks library): what the batched apply counted on dead-end tiles since the last look, in the
+// unused class 7 of a call's statistics - class_bytes: the non-zero residues it met (it takes them for zero without the
+// switch: DESIGN.md §5), class_launches: the residues it loaded to see, class_ms: the dead-end tiles an entry sweep came
+// by.  On the sweeps' stream, behind the sweeps launched so far.
+int pprhip::detail::take_apply_counts(pprhip_graph* g, pprhip_stats_t& sum) {
+  if (!hook_env("PPRHIP_APPLY_COUNT_RES") || !g->batch || !g->batch->apply_res_count) return PPRHIP_OK;
+  unsigned long long c[3] = {0, 0, 0};
+  PPRHIP_CHECK_HIP(hipMemcpyAsync(c, g->batch->apply_res_count, sizeof c, hipMemcpyDeviceToHost, g->stream));
+  PPRHIP_CHECK_HIP(hipMemsetAsync(g->batch->apply_res_count, 0, sizeof c, g->stream));
+  PPRHIP_CHECK_HIP(hipStreamSynchronize(g->stream));
+  sum.class_bytes[7] = c[0];
+  sum.class_launches[7] = (uint32_t)std::min<unsigned long long>(c[1], 0xffffffffull);
+  sum.class_ms[7] = (double)c[2];
+  return PPRHIP_OK;
+}
+#endif
+
 int pprhip::detail::batch_run(pprhip_graph_t* g, BatchJob& J, pprhip_stats_t* stats_sum) {
   PPRHIP_TRY(ensure_batch(g));
   if (pushes_backward(J.kind)) PPRHIP_TRY(ensure_bwd_layout(g));
@@ -865,6 +883,9 @@ int pprhip::detail::batch_run(pprhip_graph_t* g, BatchJob& J, pprhip_stats_t* st
   pprhip_stats_t& sum = J.sum;
   sum.total_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
   fold_class_totals(sum, tot, bytes, cnt);
+#ifdef PPRHIP_TEST_HOOKS
+  PPRHIP_TRY(take_apply_counts(g, sum));
+#endif
   if (stats_sum) *stats_sum = sum;
   return PPRHIP_OK;
 }

@@ -532,10 +532,26 @@ struct BatchState {
   // what the batched apply kernel needs of a row besides its sums, per row ordinal of a sweep side (0 forward,
   // 1 backward; rows with edges first, then the rows carried behind them): {node, out-degree, in-degree (backward
   // side only, else 0), 0}, padded with node = -1 to apply_meta_rows().  Built on the device from the side's row
-  // lists (ensure_apply_meta: the forward side with the batch state, the backward side with its layout).
+  // lists (ensure_apply_meta: the forward side with the batch state, the backward side with its layout).  The fourth
+  // word is the class of the row's 64-row tile (ApplyTileClass; the backward side: plain everywhere).
   uint4* apply_meta[2] = {nullptr, nullptr};
+  // kBatch SlotArgs, then kApplyListMax tile numbers (the tiles of rows without in-edges a forward sweep visits): one
+  // block, one copy per sweep
   SlotArgs* d_slot_args = nullptr;
   SlotArgs* h_slot_args = nullptr;  // pinned
+  // Forward sweeps leave the tiles that hold rows without in-edges only alone, except those with the source of a
+  // column in the sweep and those of the two sweeps before (DESIGN.md §5 "Rows the apply skips"): the sources' tiles of
+  // those two sweeps, and the sweeps that still run over every tile because that history does not say enough (a new
+  // batch state, a backward sweep or a seeded column among the last three).  Those sweeps also store the dead-end
+  // tiles, on whose rows a backward call's entry preparation may have left a contribution.
+  uint32_t zin_hist[2][kBatch];
+  int zin_hist_n[2] = {0, 0};
+  int zin_full_left = 2;
+#ifdef PPRHIP_TEST_HOOKS
+  // PPRHIP_APPLY_COUNT_RES, on dead-end tiles: [0] non-zero residues met, [1] residues loaded, [2] tiles an entry sweep
+  // came by (take_apply_counts hands them out)
+  unsigned long long* apply_res_count = nullptr;
+#endif
   unsigned long long* sweep_out = nullptr;    // [kBatch] frontier counters a sweep produced
   unsigned long long* h_sweep_out = nullptr;  // pinned
   unsigned long long* blk_pack8 = nullptr;  // [kBatch][kApplyBlocks8]
@@ -722,6 +738,12 @@ int init_kernels_dense();
 
 // ---- kernels_dense_batch.hip
 constexpr uint32_t kApplyBlocks8 = 2048;  // workgroups of the batched apply kernel (per-slot partials each)
+// class of a 64-row tile of the forward side, in the fourth word of its rows' records (k_build_apply_meta).  A mixed
+// tile is plain.  Dead end: every row has in-edges and out-degree 0 - it never holds a contribution and, at a dense
+// level, never a residue.  No in-edges: every row lies behind the rows with in-edges (or behind the last row).
+enum ApplyTileClass : uint32_t { kTilePlain = 0, kTileDeadEnd = 1, kTileNoIn = 2 };
+constexpr uint32_t kApplyListMax = 3 * kBatch;  // tiles without in-edges a sweep visits: sixteen sources, three sweeps
+static inline size_t slot_args_bytes() { return sizeof(SlotArgs) * kBatch + sizeof(uint32_t) * kApplyListMax; }
 // slot arguments already staged in parent->batch->h_slot_args; blocks: Gauss-Seidel blocks (nullptr / 1: one launch)
 int launch_dense_level_b8(pprhip_graph* parent, bool backward, const pprhip::GsBlock* blocks = nullptr, int n_blocks = 1);
 // records of BatchState::apply_meta for a side of n_rows rows: a trip reads the records of both its tiles without

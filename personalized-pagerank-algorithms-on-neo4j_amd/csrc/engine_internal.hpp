@@ -556,6 +556,9 @@ int target_plan(pprhip_graph_t* g, const int32_t* targets, const double* weights
 
 // ---- batch.cpp
 int batch_run(pprhip_graph_t* g, BatchJob& J, pprhip_stats_t* stats_sum);
+#ifdef PPRHIP_TEST_HOOKS
+int take_apply_counts(pprhip_graph* g, pprhip_stats_t& sum);  // batch.cpp
+#endif
 
 // ---- allpair.cpp
 // where the entries of All-Pair's backward searches go: an HBM record store, which the single-GPU call hands to the index

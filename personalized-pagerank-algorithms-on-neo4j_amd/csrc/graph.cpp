@@ -339,8 +339,13 @@ static int build_batch(pprhip_graph* P) {
   PPRHIP_CHECK_HIP(hipMemsetAsync(B->acc8, 0, sizeof(double) * (n + 1) * kBatch, P->stream));
   PPRHIP_TRY(alloc_dev((void**)&B->prep_bits, sizeof(unsigned long long) * kBatch * (n / 64 + 2)));
   PPRHIP_CHECK_HIP(hipMemsetAsync(B->prep_bits, 0, sizeof(unsigned long long) * kBatch * (n / 64 + 2), P->stream));
-  PPRHIP_TRY(alloc_dev((void**)&B->d_slot_args, sizeof(SlotArgs) * kBatch));
-  PPRHIP_TRY(alloc_pinned((void**)&B->h_slot_args, sizeof(SlotArgs) * kBatch, hipHostMallocDefault));
+  PPRHIP_TRY(alloc_dev((void**)&B->d_slot_args, slot_args_bytes()));
+  PPRHIP_TRY(alloc_pinned((void**)&B->h_slot_args, slot_args_bytes(), hipHostMallocDefault));
+  std::memset(B->h_slot_args, 0, slot_args_bytes());
+#ifdef PPRHIP_TEST_HOOKS
+  PPRHIP_TRY(alloc_dev((void**)&B->apply_res_count, sizeof(unsigned long long) * 3));
+  PPRHIP_CHECK_HIP(hipMemsetAsync(B->apply_res_count, 0, sizeof(unsigned long long) * 3, P->stream));
+#endif
   PPRHIP_TRY(alloc_dev((void**)&B->sweep_out, sizeof(unsigned long long) * kBatch));
   PPRHIP_TRY(alloc_pinned((void**)&B->h_sweep_out, sizeof(unsigned long long) * kBatch, hipHostMallocDefault));
   PPRHIP_TRY(alloc_dev((void**)&B->blk_pack8, sizeof(unsigned long long) * kBatch * kApplyBlocks8));
@@ -381,6 +386,9 @@ void free_batch(pprhip_graph* P) {
                  B->blk_ndead8, B->apply_meta[0], B->apply_meta[1]};
   for (void* p : dev)
     if (p) (void)hipFree(p);
+#ifdef PPRHIP_TEST_HOOKS
+  if (B->apply_res_count) (void)hipFree(B->apply_res_count);
+#endif
   if (B->h_slot_args) (void)hipHostFree(B->h_slot_args);
   if (B->h_sweep_out) (void)hipHostFree(B->h_sweep_out);
   delete B;

@@ -213,6 +213,16 @@ constexpr int kApplyRows = 64;
 constexpr int kApplyGroups = 2;  // tiles of kApplyRows rows a workgroup carries through its phases together
 constexpr int kApplyThreads = 512;  // 8 waves, 2 slots each: few enough slot arguments to stay in SGPRs
 constexpr int kSlotsPerWave = kBatch / (kApplyThreads / 64);
+// flags of a launch: the tiles' classes count; (hooks library) the residues of dead-end tiles are loaded and counted;
+// dead-end tiles are staged and stored as plain ones are (their residues still count as zero)
+constexpr uint32_t kApplyLean = 1u;
+#ifdef PPRHIP_TEST_HOOKS
+constexpr uint32_t kApplyCountRes = 2u;
+#endif
+constexpr uint32_t kApplyStoreDead = 4u;
+// a dead-end tile of a launch with kApplyStoreDead, inside the kernel only (bit 0: the rows are dead ends)
+constexpr uint32_t kTileDeadEndStored = 3u;
+static_assert((kTileDeadEnd & 1u) && !(kTilePlain & 1u) && !(kTileNoIn & 1u), "bit 0 of a class says dead end");
 
 // The slot vectors' pointers come out of SlotArgs in memory, so the compiler takes them for generic pointers and uses
 // flat_* instructions, which also count on lgkmcnt; they are device memory.
@@ -263,12 +273,18 @@ __global__ __launch_bounds__(256) void k_build_apply_meta(const int32_t* __restr
                                                           const uint32_t* __restrict__ in_rp_bwd, uint4* __restrict__ meta,
                                                           uint32_t n_pad) {
   const uint32_t j = blockIdx.x * 256u + threadIdx.x;
-  if (j >= n_pad) return;
+  if (j >= n_pad) return;  // (n_pad is a multiple of 128: whole waves, i.e. whole tiles, return)
   const int32_t u = j < n_nz ? nz_rows[j] : (j < n_nz + n_z ? z_rows[j - n_nz] : -1);
   uint4 r = make_uint4((uint32_t)u, 0u, 0u, 0u);
   if (u >= 0) {
     r.y = out_rp[u + 1] - out_rp[u];
     if (in_rp_bwd) r.z = in_rp_bwd[u + 1] - in_rp_bwd[u];
+  }
+  // the tile's class (engine.hpp: ApplyTileClass), from the records themselves: a wave holds one tile
+  if (!in_rp_bwd) {
+    const bool dead_end = u >= 0 && j < n_nz && r.y == 0u;
+    if (__ballot(dead_end) == ~0ull) r.w = kTileDeadEnd;
+    if (__ballot(j >= n_nz) == ~0ull) r.w = kTileNoIn;
   }
   meta[j] = r;
 }
@@ -284,10 +300,24 @@ __global__ __launch_bounds__(kApplyThreads) void k_dense_apply_batch(const uint4
                                                             unsigned long long* __restrict__ blk_pack8,
                                                             double* __restrict__ blk_dead8,
                                                             uint32_t* __restrict__ blk_ndead8, uint32_t part_base,
-                                                            uint32_t part_stride) {
-  // tiles [tile_lo, tile_hi) of one block of the sweep.  gs_mask: slots whose state writes the current array in place
-  // (entry / in-place / flush, engine.hpp: GsState); entry_mask: those of them that add to what it holds.
+                                                            uint32_t part_stride,
+                                                            const uint32_t* __restrict__ tile_list, uint32_t n_list,
+                                                            uint32_t flags, unsigned long long* res_count) {
+  // tiles [tile_lo, tile_hi) of one block of the sweep, two per trip, and behind them the n_list tiles of tile_list
+  // (tiles of rows without in-edges that lie behind tile_hi), one per trip.  gs_mask: slots whose state writes the
+  // current array in place (entry / in-place / flush, engine.hpp: GsState); entry_mask: those of them that add to what
+  // it holds.  The tiles' classes (ApplyTileClass): a tile without in-edges gets the bits of every column, the columns
+  // outside the sweep included (zeros), because the sweeps behind this one may not come by - also without kApplyLean,
+  // where the kernel before the classes wrote only the active columns' words (zeros over zeros).  With kApplyLean in flags
+  // a dead-end tile's rows are taken for what they are: no residue at a dense level, so it counts as 0
+  // without the load; and no forward sweep leaves a contribution on them, so their lines of c8_next and c8_cur are
+  // neither staged nor stored.  A backward call does leave one there (the entry preparation of a target without
+  // out-edges), and only a store clears it: the launcher sets kApplyStoreDead for the forward sweeps behind a backward
+  // one, which stage and store these tiles as plain ones.  Without kApplyLean a dead-end tile is a plain one.
+  // res_count (hooks library, kApplyCountRes): [0] non-zero residues met on dead-end tiles, [1] residues loaded there,
+  // [2] dead-end tiles an entry sweep came by.
   __shared__ double tile[kApplyGroups][kApplyRows][kBatch + 1];
+  __shared__ uint32_t s_cls[kApplyGroups];
   __shared__ double tile_p[kApplyGroups][kApplyRows][kBatch + 1];  // what the rows leave in the current array (slots in gs_mask)
   __shared__ int32_t s_u[kApplyGroups][kApplyRows];
   __shared__ uint32_t s_d[kApplyGroups][kApplyRows];
@@ -311,7 +341,12 @@ __global__ __launch_bounds__(kApplyThreads) void k_dense_apply_batch(const uint4
   // kApplyGroups tiles of 64 rows per trip (the waves of a workgroup spent four fifths of their cycles at the barriers
   // with one tile per trip).  A trip waits for memory three times: for its first phase's flight (ApplyFlight), for
   // the entry staging's loads, issued together, and for the residue / reserve loads of the wave's slots.
-  for (uint32_t tl0 = tile_lo + blockIdx.x * kApplyGroups; tl0 < tile_hi; tl0 += gridDim.x * kApplyGroups) {
+  const uint32_t pair_trips = tile_hi > tile_lo ? (tile_hi - tile_lo + kApplyGroups - 1) / kApplyGroups : 0u;
+  for (uint32_t trip = blockIdx.x; trip < pair_trips + n_list; trip += gridDim.x) {
+    // a listed tile travels alone: the trip's second tile counts as one behind the end
+    const bool listed = trip >= pair_trips;
+    const uint32_t tl0 = listed ? tile_list[trip - pair_trips] : tile_lo + trip * kApplyGroups;
+    const uint32_t hi = listed ? tl0 + 1u : tile_hi;
     ApplyFlight f;
     apply_flight(f, tl0, n_nz, acc8, meta, cross_bits, tid);
 #pragma unroll
@@ -323,19 +358,32 @@ __global__ __launch_bounds__(kApplyThreads) void k_dense_apply_batch(const uint4
         // rows inside one 512-edge chunk are rewritten by plain stores every sweep; only the rows that
         // cross a chunk boundary are summed with atomics and have to be cleared for the next sweep
         const uint32_t j = (tl0 + g) * kApplyRows + r;
-        const double v = (tl0 + g < tile_hi && j < n_nz) ? f.v[g][i] : 0.0;  // (nothing looks at a value in flight)
+        const double v = (tl0 + g < hi && j < n_nz) ? f.v[g][i] : 0.0;  // (nothing looks at a value in flight)
         if (v != 0.0 && ((f.cw[g] >> r) & 1ull)) acc8[(size_t)j * kBatch + s] = 0.0;
         tile[g][r][s] = v;
       }
     }
     if (tid < kApplyRows * kApplyGroups) {
       const uint32_t g = tid / kApplyRows, r = tid % kApplyRows;
-      const bool in = tl0 + g < tile_hi;
+      const bool in = tl0 + g < hi;
       s_u[g][r] = in ? (int32_t)f.md.x : -1;
       s_d[g][r] = in ? f.md.y : 0u;
       s_din[g][r] = in ? f.md.z : 0u;
+      if (r == 0) {
+        uint32_t c = in ? f.md.w : (uint32_t)kTilePlain;
+        if (c == kTileDeadEnd) c = !(flags & kApplyLean) ? (uint32_t)kTilePlain : ((flags & kApplyStoreDead) ? kTileDeadEndStored : c);
+        s_cls[g] = c;
+      }
     }
     __syncthreads();
+    uint32_t cls[kApplyGroups];  // (the same for every thread: kept in SGPRs)
+#pragma unroll
+    for (int g = 0; g < kApplyGroups; ++g) cls[g] = __builtin_amdgcn_readfirstlane(s_cls[g]);
+#ifdef PPRHIP_TEST_HOOKS
+    if ((flags & kApplyCountRes) && entry_mask && tid == 0)
+      for (int g = 0; g < kApplyGroups; ++g)
+        if (cls[g] & 1u) atomicAdd(res_count + 2, 1ull);
+#endif
     if (entry_mask) {  // entry sweeps add to the row's own pending contribution: stage it (whole lines)
       double p[kApplyGroups][kApplyPerThread];
 #pragma unroll
@@ -344,7 +392,8 @@ __global__ __launch_bounds__(kApplyThreads) void k_dense_apply_batch(const uint4
         for (int i = 0; i < kApplyPerThread; ++i) {
           const uint32_t idx = (uint32_t)i * (uint32_t)kApplyThreads + tid;
           const int32_t ur = s_u[g][idx / kBatch];
-          p[g][i] = c8_cur[(size_t)(ur >= 0 ? ur : 0) * kBatch + idx % kBatch];  // (an absent row reads row 0)
+          p[g][i] = 0.0;  // (a dead-end tile's lines are zero and are not written below, unless kApplyStoreDead)
+          if (cls[g] != kTileDeadEnd) p[g][i] = c8_cur[(size_t)(ur >= 0 ? ur : 0) * kBatch + idx % kBatch];  // (an absent row reads row 0)
         }
       }
 #pragma unroll
@@ -399,7 +448,15 @@ __global__ __launch_bounds__(kApplyThreads) void k_dense_apply_batch(const uint4
     for (int g = 0; g < kApplyGroups; ++g) {
 #pragma unroll
       for (int i = 0; i < kSlotsPerWave; ++i) {
-        oldv[g][i] = live[g][i] ? slot_vec(a[i].res)[u[g]] : 0.0;
+        // (a dead end that holds mass is in the frontier, so the level's preparation has taken it: zero without the load)
+        oldv[g][i] = live[g][i] && !(cls[g] & 1u) ? slot_vec(a[i].res)[u[g]] : 0.0;
+#ifdef PPRHIP_TEST_HOOKS
+        if ((flags & kApplyCountRes) && (cls[g] & 1u) && live[g][i]) {  // load it all the same, and count
+          oldv[g][i] = slot_vec(a[i].res)[u[g]];
+          atomicAdd(res_count + 1, 1ull);
+          if (oldv[g][i] != 0.0) atomicAdd(res_count, 1ull);
+        }
+#endif
         // (the reserve is needed when the row crosses, which most rows of a dense level do)
         rsvv[g][i] = live[g][i] ? slot_vec(a[i].reserve)[u[g]] : 0.0;
       }
@@ -453,13 +510,15 @@ __global__ __launch_bounds__(kApplyThreads) void k_dense_apply_batch(const uint4
         }
         // rows of this tile that hold a contribution for the slot's next level (read when the slot
         // goes back to list form)
-        const unsigned long long bits = __ballot(cn > 0.0);
-        if (lane == 0 && a[i].active && tl0 + g < tile_hi) prep_bits[(size_t)s * n_tiles + tl0 + g] = bits;
+        const unsigned long long bits = (cls[g] & 1u) ? 0ull : __ballot(cn > 0.0);
+        const bool wr = a[i].active || cls[g] == kTileNoIn;  // (a column outside the sweep has cn = 0 everywhere)
+        if (lane == 0 && wr && tl0 + g < hi) prep_bits[(size_t)s * n_tiles + tl0 + g] = bits;
       }
     }
     __syncthreads();
 #pragma unroll
     for (int g = 0; g < kApplyGroups; ++g) {
+      if (cls[g] == kTileDeadEnd) continue;  // zeros over zeros (kTileDeadEndStored: over what a backward call left)
 #pragma unroll
       for (int i = 0; i < kApplyPerThread; ++i) {
         const uint32_t idx = (uint32_t)i * (uint32_t)kApplyThreads + tid;
@@ -621,9 +680,7 @@ static_assert(kApplyRows == kTileRows, "launch_compact_prepared (kernels_frontie
 
 int launch_dense_level_b8(pprhip_graph* P, bool backward, const GsBlock* gs_blocks, int n_gs_blocks) {
   const GraphData* D = P->gr;
-  const BatchState* bs = P->batch;
-  PPRHIP_CHECK_HIP(hipMemcpyAsync(bs->d_slot_args, bs->h_slot_args, sizeof(SlotArgs) * kBatch, hipMemcpyHostToDevice,
-                                  P->stream));
+  BatchState* bs = P->batch;
   const SweepSide S = sweep_side(D, backward);
   const uint4* meta = bs->apply_meta[backward];
   if (!meta) {
@@ -645,30 +702,7 @@ int launch_dense_level_b8(pprhip_graph* P, bool backward, const GsBlock* gs_bloc
   const bool cut = gs_mask && gs_blocks && n_gs_blocks > 1 && !backward;
   const GsBlock* blocks = cut ? gs_blocks : &whole;
   const int nb = cut ? n_gs_blocks : 1;
-  uint32_t part_base = 0;
-  for (int b = 0; b < nb; ++b) {
-    const GsBlock& B = blocks[b];
-    PPRHIP_TRY(launch_dense_edges_bG<kBatch>(P, S.ci, S.start_flags, S.chunk_starts, bs->c8[bs->c8cur], bs->acc8, B));
-    // block boundaries are multiples of 256 row ordinals, so tiles never straddle; the rows without in-edges
-    // follow the last block.  The last block's rows are read by nobody again in this sweep (the next sweep reads the
-    // other array), so only the blocks before it write the current array in place.
-    const uint32_t t_lo = B.j_lo / kApplyRows;
-    const uint32_t t_hi = (b == nb - 1) ? n_tiles : B.j_hi / kApplyRows;
-    if (t_hi <= t_lo) continue;
-    const uint32_t quota = kApplyBlocks8 / (uint32_t)nb;
-    uint32_t grid = std::max(1u, std::min((t_hi - t_lo + kApplyGroups - 1) / kApplyGroups, quota));
-    // PPRHIP_APPLY_GRID (test switch, read at every launch): at most so many workgroups, so that a graph of a few
-    // hundred rows gives a workgroup a second and a third trip
-    if (const char* e = hook_env("PPRHIP_APPLY_GRID"))
-      if (atol(e) > 0) grid = (uint32_t)std::min<long>(grid, atol(e));
-    k_dense_apply_batch<<<dim3(grid), dim3(kApplyThreads), 0, P->stream>>>(
-          meta, S.n_nz, S.n_z, bs->acc8, bs->c8[bs->c8cur],
-          bs->c8[bs->c8cur ^ 1], t_lo, t_hi, b == nb - 1 ? 0u : gs_mask, b == nb - 1 ? 0u : entry_mask, bs->d_slot_args,
-          S.cross_bits, bs->prep_bits, bs->blk_pack8, bs->blk_dead8, bs->blk_ndead8, part_base, kApplyBlocks8);
-    PPRHIP_CHECK_HIP(hipGetLastError());
-    part_base += grid;
-  }
-  // seed sets: the dead-end seeds of every seeded column, and their dead-mass cells cleared
+  // seed sets: the dead-end seeds of every seeded column (landed behind the last apply block)
   uint32_t seed_dead_max = 0;
   bool seeded = false;
   for (int s = 0; s < kBatch; ++s) {
@@ -677,6 +711,90 @@ int launch_dense_level_b8(pprhip_graph* P, bool backward, const GsBlock* gs_bloc
       seeded = true;
       seed_dead_max = std::max(seed_dead_max, sa.seed_n_all - sa.seed_n_live);
     }
+  }
+  // Rows the apply skips.  The tiles from z_lo on hold rows without in-edges only: their row sums are 0
+  // by construction, so a column is live there on the row of its source alone (returned dead-end mass), and what a
+  // sweep would write everywhere else - zeros into the array it fills, zero bits - is there already.  The sweep visits
+  // the tiles of its columns' sources and those of the two sweeps before (the arrays ping-pong: an entry written in
+  // sweep k sits in the array that sweep k + 2 fills again; a column's bits are rewritten by the next sweep that comes
+  // by, whether the column is in it or not).  A seeded column lands mass on any row, a backward sweep has another
+  // layout and without the relabeling a row's ordinal is not its node: such a sweep and the two behind it run over
+  // every tile, as the first two of a batch state do.  Those sweeps also stage and store the dead-end tiles
+  // (kApplyStoreDead): the entry preparation of a backward call leaves a contribution on a target without out-edges,
+  // in the array its sweep reads, and the call may end before a backward sweep has filled that array again.  The first
+  // forward sweep behind it does, as every forward sweep did before the classes.  PPRHIP_APPLY_ALL_ROWS=1 (test
+  // switch, read at every launch): every tile, every load and every store, as before the classes - but for the bits
+  // of the columns outside the sweep on tiles without in-edges, which are written all the same (zeros over zeros).
+  const char* const all_rows_env = hook_env("PPRHIP_APPLY_ALL_ROWS");
+  const bool all_rows = all_rows_env && all_rows_env[0] == '1';
+  const uint32_t z_lo = (S.n_nz + kApplyRows - 1) / kApplyRows;
+  uint32_t now[kBatch];
+  int n_now = 0;
+  auto add_unique = [](uint32_t* v, int& n, uint32_t t) {
+    for (int i = 0; i < n; ++i)
+      if (v[i] == t) return;
+    v[n++] = t;
+  };
+  if (backward || seeded || !D->relabeled) {
+    bs->zin_full_left = 3;
+  } else {
+    for (int s = 0; s < kBatch; ++s) {
+      const SlotArgs& sa = bs->h_slot_args[s];
+      if (!sa.active || sa.src < 0) continue;
+      const uint32_t t = (uint32_t)sa.src / kApplyRows;  // (relabeled: a row's ordinal is its node)
+      if (t >= z_lo && t < n_tiles) add_unique(now, n_now, t);
+    }
+  }
+  const bool full = all_rows || bs->zin_full_left > 0;
+  if (bs->zin_full_left > 0) bs->zin_full_left--;
+  uint32_t* list = reinterpret_cast<uint32_t*>(bs->h_slot_args + kBatch);
+  int n_list = 0;
+  if (!full) {
+    for (int i = 0; i < n_now; ++i) add_unique(list, n_list, now[i]);
+    for (int h = 0; h < 2; ++h)
+      for (int i = 0; i < bs->zin_hist_n[h]; ++i) add_unique(list, n_list, bs->zin_hist[h][i]);
+  }
+  std::copy(bs->zin_hist[0], bs->zin_hist[0] + bs->zin_hist_n[0], bs->zin_hist[1]);
+  bs->zin_hist_n[1] = bs->zin_hist_n[0];
+  std::copy(now, now + n_now, bs->zin_hist[0]);
+  bs->zin_hist_n[0] = n_now;
+  // the slots' arguments and the tile list in one block: no further command on the sweep's stream
+  PPRHIP_CHECK_HIP(hipMemcpyAsync(bs->d_slot_args, bs->h_slot_args, slot_args_bytes(), hipMemcpyHostToDevice, P->stream));
+  const uint32_t* d_list = reinterpret_cast<const uint32_t*>(bs->d_slot_args + kBatch);
+  uint32_t flags = all_rows ? 0u : (full ? kApplyLean | kApplyStoreDead : kApplyLean);
+  unsigned long long* res_count = nullptr;
+#ifdef PPRHIP_TEST_HOOKS
+  // PPRHIP_APPLY_COUNT_RES=1 (test switch): the residues of dead-end tiles are loaded all the same and the non-zero ones
+  // counted (batch_run hands the count out in the call's statistics)
+  res_count = bs->apply_res_count;
+  if (hook_env("PPRHIP_APPLY_COUNT_RES") && flags) flags |= kApplyCountRes;
+#endif
+  uint32_t part_base = 0;
+  for (int b = 0; b < nb; ++b) {
+    const GsBlock& B = blocks[b];
+    const bool last = b == nb - 1;
+    PPRHIP_TRY(launch_dense_edges_bG<kBatch>(P, S.ci, S.start_flags, S.chunk_starts, bs->c8[bs->c8cur], bs->acc8, B));
+    // block boundaries are multiples of 256 row ordinals, so tiles never straddle; the rows without in-edges
+    // follow the last block.  The last block's rows are read by nobody again in this sweep (the next sweep reads the
+    // other array), so only the blocks before it write the current array in place.
+    const uint32_t t_lo = B.j_lo / kApplyRows;
+    const uint32_t t_hi = last ? (full ? n_tiles : z_lo) : B.j_hi / kApplyRows;
+    const uint32_t nl = last && !full ? (uint32_t)n_list : 0u;
+    const uint32_t trips = (t_hi > t_lo ? (t_hi - t_lo + kApplyGroups - 1) / kApplyGroups : 0u) + nl;
+    if (!trips) continue;
+    const uint32_t quota = kApplyBlocks8 / (uint32_t)nb;
+    uint32_t grid = std::max(1u, std::min(trips, quota));
+    // PPRHIP_APPLY_GRID (test switch, read at every launch): at most so many workgroups, so that a graph of a few
+    // hundred rows gives a workgroup a second and a third trip
+    if (const char* e = hook_env("PPRHIP_APPLY_GRID"))
+      if (atol(e) > 0) grid = (uint32_t)std::min<long>(grid, atol(e));
+    k_dense_apply_batch<<<dim3(grid), dim3(kApplyThreads), 0, P->stream>>>(
+          meta, S.n_nz, S.n_z, bs->acc8, bs->c8[bs->c8cur],
+          bs->c8[bs->c8cur ^ 1], t_lo, t_hi, last ? 0u : gs_mask, last ? 0u : entry_mask, bs->d_slot_args,
+          S.cross_bits, bs->prep_bits, bs->blk_pack8, bs->blk_dead8, bs->blk_ndead8, part_base, kApplyBlocks8, d_list, nl,
+          flags, res_count);
+    PPRHIP_CHECK_HIP(hipGetLastError());
+    part_base += grid;
   }
   if (seeded) {
     k_seed_land_dense_batch<<<dim3(grid_for(seed_dead_max, 256, 1024), kBatch), dim3(256), 0, P->stream>>>(

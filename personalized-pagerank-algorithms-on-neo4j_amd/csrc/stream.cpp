@@ -112,6 +112,9 @@ void stream_driver(pprhip_stream* s) {
     std::lock_guard<std::mutex> lk(s->mu);
     if (++J->finished == J->q) {
       J->sum.total_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - J->t0).count();
+#ifdef PPRHIP_TEST_HOOKS
+      (void)take_apply_counts(P, J->sum);  // (test switch: what the sweeps up to here counted on dead-end tiles)
+#endif
       J->done = true;
       s->cv_done.notify_all();
     }
