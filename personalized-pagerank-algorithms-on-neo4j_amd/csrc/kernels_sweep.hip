@@ -265,9 +265,17 @@ __global__ __launch_bounds__(256) void k_sweep_best_final(const double* __restri
 }
 
 // ------------------------------------------------------------------ launchers
+// PPRHIP_SWEEP_ITEM_GRID / PPRHIP_SWEEP_EDGE_GRID (test switches, read at every launch): at most so many workgroups, so
+// that a graph of a few thousand nodes and a few tiles gives a workgroup a second and a third turn of its stride loop
+static uint32_t sweep_grid_cap(const char* name, uint32_t grid) {
+  if (const char* e = hook_env(name))
+    if (atol(e) > 0) grid = (uint32_t)std::min<long>((long)grid, atol(e));
+  return grid;
+}
+
 static uint32_t sweep_grid(uint64_t items, uint32_t cap) {
   const uint64_t b = (items + 255) / 256;
-  return (uint32_t)(b < 1 ? 1 : (b > cap ? cap : b));
+  return sweep_grid_cap("PPRHIP_SWEEP_ITEM_GRID", (uint32_t)(b < 1 ? 1 : (b > cap ? cap : b)));
 }
 
 int launch_sweep_support(pprhip_graph* g, SweepWs* w, const double* x, int normalize) {
@@ -357,7 +365,8 @@ int launch_sweep_edges(pprhip_graph* g, SweepWs* w, uint32_t profiled, hipEvent_
   PPRHIP_CHECK_HIP(hipEventRecord(before, g->stream));
   PPRHIP_CHECK_HIP(hipMemsetAsync(w->delta, 0, sizeof(long long) * (size_t)profiled, g->stream));
   // 32 KB of LDS per workgroup: five of them share a CU
-  const uint32_t grid = (uint32_t)std::min<uint64_t>(max_tiles, (uint64_t)D->n_cus * 5u);
+  const uint32_t grid =
+      sweep_grid_cap("PPRHIP_SWEEP_EDGE_GRID", (uint32_t)std::min<uint64_t>(max_tiles, (uint64_t)D->n_cus * 5u));
   hipLaunchKernelGGL(k_sweep_edges, dim3(grid), dim3(256), 0, g->stream, w->volx, profiled, w->tile_node, w->rec, w->rank,
                      D->out_ci, D->in_ci, w->delta);
   PPRHIP_CHECK_HIP(hipGetLastError());

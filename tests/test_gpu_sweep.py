@@ -100,6 +100,7 @@ def test_got_sources_seed_sets_and_bounds(pkg, got, dev_cache):
 
 
 # ------------------------------------------------------------------ tile edges without knowing the tile
+# (graphs built for the tile, the turns and the stride loops: test_gpu_sweep_cut_designs.py)
 def stars_host(pkg, j):
     """A 3-cycle (ids 0, 1, 2), then three hubs (3, 4, 5) with 2^j - 1, 2^j and 2^j + 1 leaves each, hub <-> leaf in both
     directions: in slot space some hub ends before, on and after every power-of-two boundary up to 2^(j + 1)."""
