@@ -754,7 +754,7 @@ int pprhip_local_cluster_seeds(pprhip_graph_t* g, const int32_t* seeds, const do
  * FORA from one source) and backward (backward push, the survival vector, single targets / target sets, single pairs).
  * Only the pprhip_weighted_* calls read the weights.  Every entry point without that prefix ignores them - the
  * unweighted pprhip_backward_push, pprhip_ppr_targets and pprhip_ppr_pairs included - and so do the features that have
- * no weighted form yet: the batched FORA calls and streams, the walk index, All-Pair, the sweep cut (which ranks by the
+ * no weighted form yet: the batched FORA calls and streams, All-Pair, the sweep cut (which ranks by the
  * relationship count, not by weighted degree), the multi-GPU calls; they give what they gave before
  * pprhip_graph_set_weights.
  *
@@ -852,6 +852,36 @@ int pprhip_weighted_fora_topk(pprhip_graph_t* g, int32_t src, double eps, const 
 int pprhip_weighted_fora_topk_seeds(pprhip_graph_t* g, const int32_t* seeds, const double* weights, int n_seeds,
                                     double eps, const pprhip_fora_conf_t* conf, uint64_t seed, int32_t* ids_out,
                                     double* vals_out, int cap, int* n_out, double* reserve_out, pprhip_stats_t* stats);
+
+/* ---- weighted walk index (FORA+ for pprhip_weighted_fora and pprhip_weighted_fora_seeds; DESIGN.md section 2,
+ * "Weighted walk index"): the walk index above, over the weighted walks.  Both weighted whole-graph calls plan with the
+ * unweighted plan and draw the weighted walks (seed, stream 0, v, 0 .. omega_v - 1) with the forced first hop for a
+ * residue node v; the weighted push test keeps the relationship count, so cap(v) = ceil(d_out(v) * density) with
+ * pprhip_walk_index_density's density covers every such call whose threshold is <= rmax, as it does unweighted.
+ * Terminal j of node v = the terminal of pprhip_weighted_random_walk_batch(start = v, walk_idx = j, alpha, seed,
+ * stream = 0, no_zero_hop = 1).
+ * Use rule: the walk phase of pprhip_weighted_fora / pprhip_weighted_fora_seeds on a handle whose weighted index was
+ * built at the call's alpha (bit for bit) and seed reads walk i of residue node v from it when i < cap(v) and walks it
+ * live, with its own index i, otherwise (every walk of a dead-end start is walked: its capacity is 0); the result is
+ * the same vector up to fp64 addition order.  With another alpha or seed, or without the index, the phase runs as
+ * before.  The weighted top-k rounds, pprhip_weighted_ppr_pairs and pprhip_weighted_random_walk_batch never touch it.
+ * Statistics of a served phase: walks and mc_sources as without the index, walk_steps counts the live walks only.
+ * The two indexes coexist on a handle and neither is ever read by the other family of calls:
+ * PPRHIP_RELEASE_WALK_INDEX and pprhip_walk_index_drop leave the weighted index alone.  It is built from the weights:
+ * pprhip_graph_set_weights (new weights or NULL) and pprhip_graph_release(PPRHIP_RELEASE_WEIGHTS) drop it before the
+ * weights change (a refused pprhip_graph_set_weights changes nothing and leaves it); pprhip_graph_destroy frees it.
+ * The five calls take the arguments of their unweighted namesakes, check them in the same order with the same
+ * messages under their own names, and fill the same statistics; _build returns PPRHIP_ERR_STATE on a handle without
+ * weights (after the checks of the numbers and of the handle). */
+#define PPRHIP_RELEASE_WEIGHTED_WALK_INDEX 256u /* the weighted walk index: as pprhip_weighted_walk_index_drop */
+int pprhip_weighted_walk_index_build(pprhip_graph_t* g, double alpha, uint64_t seed, double density,
+                                     pprhip_stats_t* stats);
+int pprhip_weighted_walk_index_drop(pprhip_graph_t* g);
+int pprhip_weighted_walk_index_info(const pprhip_graph_t* g, int* present, double* alpha, uint64_t* seed,
+                                    double* density, uint64_t* terminals, uint64_t* bytes);
+int pprhip_weighted_walk_index_fetch(pprhip_graph_t* g, int32_t node, int32_t* terminals_out, uint64_t cap,
+                                     uint64_t* count_out);
+int pprhip_weighted_walk_index_usage(pprhip_graph_t* g, uint64_t* served, uint64_t* walked, int reset);
 
 /* ---- the backward direction over the same P ("Weighted backward direction")
  * Backward push: popping v with residue r credits reserve(v) += alpha r and deposits (c w(e)) / W(u) on r(u) along every

@@ -107,10 +107,13 @@ EXPORTS = [
     "pprhip_weighted_ppr_pairs",
     "pprhip_weighted_forward_push_seeds", "pprhip_weighted_fora_seeds", "pprhip_weighted_fora_topk",
     "pprhip_weighted_fora_topk_seeds",
+    "pprhip_weighted_walk_index_build", "pprhip_weighted_walk_index_drop", "pprhip_weighted_walk_index_info",
+    "pprhip_weighted_walk_index_fetch", "pprhip_weighted_walk_index_usage",
 ]
 SPARSE_BY_ID, SPARSE_BY_VALUE = 0, 1  # PPRHIP_SPARSE_BY_*: the orders of the sparse getters
 RELEASE_SPARSE = 16  # PPRHIP_RELEASE_SPARSE
 RELEASE_WEIGHTS = 128  # PPRHIP_RELEASE_WEIGHTS
+RELEASE_WEIGHTED_WALK_INDEX = 256  # PPRHIP_RELEASE_WEIGHTED_WALK_INDEX
 PAIR_WALK_STREAM = 0xFFFF  # PPRHIP_PAIR_WALK_STREAM: the walk stream of every single-pair walk
 COMM_ID_BYTES = 128
 
@@ -230,6 +233,11 @@ def lib():
     L.pprhip_walk_index_info.argtypes = [vp, P(ci), P(dbl), P(u64), P(dbl), P(u64), P(u64)]
     L.pprhip_walk_index_fetch.argtypes = [vp, i32, vp, u64, P(u64)]
     L.pprhip_walk_index_usage.argtypes = [vp, P(u64), P(u64), ci]
+    L.pprhip_weighted_walk_index_build.argtypes = [vp, dbl, u64, dbl, P(Stats)]
+    L.pprhip_weighted_walk_index_drop.argtypes = [vp]
+    L.pprhip_weighted_walk_index_info.argtypes = [vp, P(ci), P(dbl), P(u64), P(dbl), P(u64), P(u64)]
+    L.pprhip_weighted_walk_index_fetch.argtypes = [vp, i32, vp, u64, P(u64)]
+    L.pprhip_weighted_walk_index_usage.argtypes = [vp, P(u64), P(u64), ci]
     L.pprhip_tuning_indexed.argtypes = [P(Tuning)]
     L.pprhip_tuning_indexed.restype = None
     L.pprhip_tuning_indexed_batch.argtypes = [P(Tuning)]
@@ -895,6 +903,7 @@ class Graph:
 
     RELEASE_ALL_PAIR, RELEASE_BATCH, RELEASE_WALK_INDEX, RELEASE_SWEEP, RELEASE_SPARSE = 1, 2, 4, 8, 16
     RELEASE_WEIGHTS = 128
+    RELEASE_WEIGHTED_WALK_INDEX = 256
 
     def release(self, what):
         """Hands the workspaces of the named entry points back (pprhip_graph_release); they come back on next use."""
@@ -996,43 +1005,46 @@ class Graph:
                                               int(no_zero_hop), _ptr(term), _ptr(steps)))
         return term, steps
 
-    def build_walk_index(self, alpha, seed, density=None, eps=0.5, conf=None):
+    def build_walk_index(self, alpha, seed, density=None, eps=0.5, conf=None, _weighted=False):
         """Builds the FORA+ walk index of (alpha, seed) on the handle (pprhip_walk_index_build): ceil(d_out(v) * density)
         stored walk terminals per node, which every whole-graph FORA call at that alpha and seed then reads instead of
         walking.  density None: the density at rmax0 of eps and conf (walk_index_density).  Returns the build's Stats."""
         if density is None:
             density = walk_index_density(conf or conf_whole_graph(self.n, self.m, alpha), eps)
         st = Stats()
-        _check(lib().pprhip_walk_index_build(self.h, alpha, seed, density, C.byref(st)))
+        build = lib().pprhip_weighted_walk_index_build if _weighted else lib().pprhip_walk_index_build
+        _check(build(self.h, alpha, seed, density, C.byref(st)))
         return st
 
     def drop_walk_index(self):
         _check(lib().pprhip_walk_index_drop(self.h))
 
-    def walk_index_info(self):
+    def walk_index_info(self, _weighted=False):
         """None without an index, else dict(alpha, seed, density, terminals, bytes)."""
         present, a, s, d = C.c_int(), C.c_double(), C.c_uint64(), C.c_double()
         t, b = C.c_uint64(), C.c_uint64()
-        _check(lib().pprhip_walk_index_info(self.h, C.byref(present), C.byref(a), C.byref(s), C.byref(d), C.byref(t),
-                                            C.byref(b)))
+        info = lib().pprhip_weighted_walk_index_info if _weighted else lib().pprhip_walk_index_info
+        _check(info(self.h, C.byref(present), C.byref(a), C.byref(s), C.byref(d), C.byref(t), C.byref(b)))
         if not present.value:
             return None
         return dict(alpha=a.value, seed=s.value, density=d.value, terminals=t.value, bytes=b.value)
 
-    def walk_index_terminals(self, node):
+    def walk_index_terminals(self, node, _weighted=False):
         """The stored terminals of one node (original ids), in walk-index order."""
         cnt = C.c_uint64()
-        _check(lib().pprhip_walk_index_fetch(self.h, node, None, 0, C.byref(cnt)))
+        fetch = lib().pprhip_weighted_walk_index_fetch if _weighted else lib().pprhip_walk_index_fetch
+        _check(fetch(self.h, node, None, 0, C.byref(cnt)))
         out = np.empty(cnt.value, dtype=np.int32)
         if cnt.value:
-            _check(lib().pprhip_walk_index_fetch(self.h, node, _ptr(out), cnt.value, C.byref(cnt)))
+            _check(fetch(self.h, node, _ptr(out), cnt.value, C.byref(cnt)))
         return out
 
-    def walk_index_usage(self, reset=False):
+    def walk_index_usage(self, reset=False, _weighted=False):
         """(served, walked): walks of whole-graph FORA phases read from the index / walked live in those phases, since
         the build or the last reset."""
         s, w = C.c_uint64(), C.c_uint64()
-        _check(lib().pprhip_walk_index_usage(self.h, C.byref(s), C.byref(w), int(bool(reset))))
+        usage = lib().pprhip_weighted_walk_index_usage if _weighted else lib().pprhip_walk_index_usage
+        _check(usage(self.h, C.byref(s), C.byref(w), int(bool(reset))))
         return s.value, w.value
 
     def fora_single_source(self, src, eps, alpha, seed, n_rounds=0, conf=None, fetch=True):
@@ -1272,6 +1284,27 @@ class Graph:
         return out, st
 
     # ---- weighted seed sets and top-k: the return shapes of the unweighted / weighted namesakes
+    def build_weighted_walk_index(self, alpha, seed, density=None, eps=0.5, conf=None):
+        """build_walk_index over the weighted walks (pprhip_weighted_walk_index_build): weighted_fora and
+        weighted_fora_seeds at that alpha and seed then read the stored terminals instead of walking.  It lives beside
+        the unweighted index and goes with the weights (set_weights, RELEASE_WEIGHTS)."""
+        return self.build_walk_index(alpha, seed, density, eps, conf, _weighted=True)
+
+    def drop_weighted_walk_index(self):
+        _check(lib().pprhip_weighted_walk_index_drop(self.h))
+
+    def weighted_walk_index_info(self):
+        """walk_index_info of the weighted walk index."""
+        return self.walk_index_info(_weighted=True)
+
+    def weighted_walk_index_terminals(self, node):
+        """walk_index_terminals of the weighted walk index."""
+        return self.walk_index_terminals(node, _weighted=True)
+
+    def weighted_walk_index_usage(self, reset=False):
+        """(served, walked) of the weighted whole-graph FORA phases that used the weighted walk index."""
+        return self.walk_index_usage(reset, _weighted=True)
+
     def weighted_forward_push_seeds(self, seeds, alpha, rmax, weights=None, fetch=True):
         """forward_push_seeds over the weighted transition matrix (`weights`: the seeds' weights, None: uniform)."""
         s, w = _seed_arrays(seeds, weights)

@@ -259,4 +259,17 @@ __device__ __forceinline__ void block_tile_compact(const bool (&take)[ITEMS], co
     }
 }
 
+// Walk index (k_index_build, k_w_index_build): the node whose terminals hold index position p - the largest v in [a, b]
+// with off[v] <= p (off[a] <= p is given; nodes of capacity 0 share their offset with the node behind them and are
+// passed over)
+__device__ __forceinline__ uint32_t index_node_of(const unsigned long long* __restrict__ off, uint32_t a, uint32_t b,
+                                                  unsigned long long p) {
+  while (a < b) {
+    const uint32_t mid = a + (b - a + 1u) / 2u;
+    if (off[mid] <= p) a = mid;
+    else b = mid - 1u;
+  }
+  return a;
+}
+
 }  // namespace pprhip

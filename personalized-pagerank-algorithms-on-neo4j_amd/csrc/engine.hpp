@@ -517,6 +517,10 @@ struct GraphData {
   // not instead of it; goes with the weights (free_weights)
   double* wsurvival = nullptr;
   double wsurvival_alpha = 0.0;
+  // the weighted walk index, or none (pprhip_weighted_walk_index_build / _drop): terminals of weighted walks, beside
+  // `widx` and never read by the unweighted calls, as `widx` is never read by the weighted ones; built from the weights
+  // and dropped before they change (walk_index.cpp: free_weighted_walk_index)
+  WalkIndex* widx_w = nullptr;
 };
 
 // The handle's batched-call state: the workspaces ("slots") of its batched queries and the arrays their dense levels
@@ -798,6 +802,9 @@ int launch_mc_walk(pprhip_graph* g, double alpha, uint64_t seed, uint32_t stream
 // the walks of the latest plan with the index `ix`: k_index_serve deposits the stored terminals, k_mc_walk<kWalkIndexed> walks
 // what the index does not hold (walk idx >= cap of its node, dead-end starts) with the walks' own indices
 int launch_mc_walk_indexed(pprhip_graph* g, const TerminalTable* ix, double alpha, uint64_t seed, double* target);
+// its first half alone, on a grid the caller sized: k_index_serve reads the plan and the table only, so it serves a
+// weighted walk phase from the weighted walk index as well (kernels_weighted.hip: launch_w_walk_run)
+int launch_index_serve(pprhip_graph* g, const TerminalTable* ix, double* target, uint32_t grid);
 // the walks of the latest plan (whole-graph FORA: stream 0, forced first hop) through the call's terminal cache: a walk
 // whose cell is filled deposits there at once, the others walk and fill their cells
 // dep: the call's deposit records when this phase may use them (it runs on the walk stream), or null
@@ -932,9 +939,13 @@ int launch_w_push(pprhip_graph* g, const PushArgs& a, int fbuf, uint32_t nf, uin
 int launch_w_dense_level(pprhip_graph* g, const PushArgs& a, int cbuf, int out_slot, int dead_slot);
 int launch_w_walk_batch(pprhip_graph* g, const int32_t* d_starts, const uint64_t* d_idx, uint64_t count, double alpha,
                         uint64_t seed, uint32_t stream, int no_zero_hop, int32_t* d_term, uint32_t* d_steps);
-// the weighted walks of the latest plan (launch_mc_plan) on `stream`, with or without the forced first hop
-// (pprhip_weighted_fora: 0, forced)
-int launch_w_walk_plan(pprhip_graph* g, double alpha, uint64_t seed, double* target, uint32_t stream, bool no_zero_hop);
+// The weighted walks of the latest plan (launch_mc_plan) on `stream`, with or without the forced first hop
+// (pprhip_weighted_fora: 0, forced).  A phase of stream 0 with the forced hop on a handle whose weighted walk index
+// (GraphData::widx_w) was built at this alpha, bit for bit, and this seed reads the stored terminals (k_index_serve) and
+// walks only what the index does not hold (k_w_walk_plan<true>); every other phase runs k_w_walk_plan<false>.
+int launch_w_walk_run(pprhip_graph* g, double alpha, uint64_t seed, double* target, uint32_t stream, bool no_zero_hop);
+// fills ix->term from ix->off (already in HBM): terminal j of node v = weighted walk (seed, stream 0, v, j), forced hop
+int launch_w_index_build(pprhip_graph* g, const TerminalTable* ix, unsigned long long* d_steps);
 int init_kernels_weighted();
 
 // ---- kernels_weighted_query.hip (weighted seed sets and top-k rounds; weighted_query.cpp drives them)

@@ -243,7 +243,7 @@ int lift_host(uint32_t n, uint64_t m, const uint32_t* out_rp, const int32_t* out
 unsigned host_threads();  // CPU affinity and cgroup quota of the process, at most 64 (PPRHIP_HOST_THREADS overrides)
 
 // ---- walk_index.cpp
-void free_walk_index(GraphData* D);  // the lifted graph's walk index, if it has one
+void free_walk_index(WalkIndex*& slot);  // a walk index of the lifted graph (GraphData::widx / widx_w), if it has one
 // the call-scoped terminal cache of the batched whole-graph FORA paths (engine.hpp: WalkShare)
 void walk_share_begin(pprhip_graph* P, int q, double alpha, double rmax, double omega, uint64_t seed);
 void free_walk_share(BatchState* B);
@@ -255,7 +255,9 @@ void free_sweep(pprhip_graph* g);  // the handle's sweep-cut workspace, if it ha
 void free_sparse(pprhip_graph* g);  // the handle's workspace of the sparse getters, if it has one
 
 // ---- weighted.cpp
-void free_weights(GraphData* D);  // the lifted graph's relationship weights (and the weighted survival), if it has them
+// the lifted graph's relationship weights (and what was built from them: the weighted survival, the weighted walk
+// index), if it has them
+void free_weights(GraphData* D);
 int need_weights(const pprhip_graph* g, const char* fn);  // PPRHIP_ERR_STATE when the handle has no weights
 int fetch_packed(pprhip_graph* g, const unsigned long long* cell, uint32_t* nf, uint64_t* ef);  // a counter cell: entries << 36 | edges
 // The level loop of the weighted pushes, forward (kernels_weighted.hip) and backward (a.mode == kBackward:

@@ -547,8 +547,8 @@ int pprhip_graph_create(uint32_t n, uint64_t m, const uint32_t* out_rp, const in
 
 // the lifted graph and every layout built from it (pprhip_graph_destroy, after everything that uses it)
 static void free_graph_data(GraphData* D) {
-  free_walk_index(D);
-  free_weights(D);
+  free_walk_index(D->widx);
+  free_weights(D);  // (the weighted walk index with them)
   void* ptrs[] = {D->walk_rec, D->out_ext, D->out_rp, D->out_ci, D->in_rp, D->in_ci, D->new2old, D->old2new, D->start_flags,
                   D->chunk_starts, D->nz_rows, D->zin_rows, D->cross_bits, D->start_flags_o, D->chunk_starts_o,
                   D->nz_rows_o, D->z_rows_o, D->cross_bits_o, D->survival};
@@ -583,7 +583,7 @@ static void free_all_pair(pprhip_graph* g) {
 int pprhip_graph_release(pprhip_graph_t* g, unsigned what) {
   PPRHIP_TRY(check_graph(g, "pprhip_graph_release"));
   if (what & ~(PPRHIP_RELEASE_ALL_PAIR | PPRHIP_RELEASE_BATCH | PPRHIP_RELEASE_WALK_INDEX | PPRHIP_RELEASE_SWEEP |
-               PPRHIP_RELEASE_SPARSE | PPRHIP_RELEASE_WEIGHTS)) {
+               PPRHIP_RELEASE_SPARSE | PPRHIP_RELEASE_WEIGHTS | PPRHIP_RELEASE_WEIGHTED_WALK_INDEX)) {
     set_error("pprhip_graph_release: unknown flag in %u", what);
     return PPRHIP_ERR_INVALID;
   }
@@ -593,6 +593,7 @@ int pprhip_graph_release(pprhip_graph_t* g, unsigned what) {
   if (what & PPRHIP_RELEASE_WALK_INDEX) PPRHIP_TRY(pprhip_walk_index_drop(g));
   if (what & PPRHIP_RELEASE_SWEEP) free_sweep(g);
   if (what & PPRHIP_RELEASE_SPARSE) free_sparse(g);
+  if (what & PPRHIP_RELEASE_WEIGHTED_WALK_INDEX) PPRHIP_TRY(pprhip_weighted_walk_index_drop(g));
   if (what & PPRHIP_RELEASE_WEIGHTS) free_weights(g->gr);
   return PPRHIP_OK;
 }

@@ -800,18 +800,7 @@ __global__ __launch_bounds__(256) void k_dep_sum(DepositArgs a, const DevCounter
 // ------------------------------------------------------------------------------------------------
 // walk index (FORA+, DESIGN.md §2 "Walk index"): build and serve
 // ------------------------------------------------------------------------------------------------
-// the node whose terminals hold index position p: the largest v in [a, b] with off[v] <= p (off[a] <= p is given; nodes
-// of capacity 0 share their offset with the node behind them and are passed over)
-__device__ __forceinline__ uint32_t index_node_of(const unsigned long long* __restrict__ off, uint32_t a, uint32_t b,
-                                                  unsigned long long p) {
-  while (a < b) {
-    const uint32_t mid = a + (b - a + 1u) / 2u;
-    if (off[mid] <= p) a = mid;
-    else b = mid - 1u;
-  }
-  return a;
-}
-
+// (index_node_of, the node of an index position, is in device_utils.hpp: k_w_index_build shares it)
 // A wave takes a contiguous range of index positions; a lane whose walk has stopped stores its terminal (internal id)
 // and takes the range's next position (refill in ballot order, as k_pair_walk).  Position p of node v is walk
 // (seed, stream 0, v, p - off[v]) with the forced first hop: what k_mc_walk would run for walk p - off[v] of a residue
@@ -1268,12 +1257,17 @@ int launch_mc_walk(pprhip_graph* g, double alpha, uint64_t seed, uint32_t stream
 
 // The same grid for both kernels: the serve kernel's share of a wave is a stream of terminals, the walk kernel behind
 // it returns at once unless the serve kernel counted walks the index does not hold.
+int launch_index_serve(pprhip_graph* g, const TerminalTable* ix, double* target, uint32_t grid) {
+  hipLaunchKernelGGL(k_index_serve, dim3(grid), dim3(64), 0, g->stream, plan_rec_of(g, g->mc_last_plan), ix->off, ix->term,
+                     target, g->ctr, (int)(g->mc_last_plan % 3u), ix->usage);
+  PPRHIP_CHECK_HIP(hipGetLastError());
+  return PPRHIP_OK;
+}
+
 int launch_mc_walk_indexed(pprhip_graph* g, const TerminalTable* ix, double alpha, uint64_t seed, double* target) {
   const uint32_t grid = mc_walk_grid(g);
   const int cell = (int)(g->mc_last_plan % 3u);
-  hipLaunchKernelGGL(k_index_serve, dim3(grid), dim3(64), 0, g->stream, plan_rec_of(g, g->mc_last_plan), ix->off, ix->term,
-                     target, g->ctr, cell, ix->usage);
-  PPRHIP_CHECK_HIP(hipGetLastError());
+  PPRHIP_TRY(launch_index_serve(g, ix, target, grid));
   hipLaunchKernelGGL(k_mc_walk<kWalkIndexed>, dim3(grid), dim3(64), 0, g->stream, plan_rec_of(g, g->mc_last_plan),
                      reinterpret_cast<const uint4*>(g->gr->walk_rec), target, alpha, (uint32_t)seed, (uint32_t)(seed >> 32), 0u,
                      1, g->ctr, cell, (const unsigned long long*)ix->off, (uint32_t*)nullptr, 0u,

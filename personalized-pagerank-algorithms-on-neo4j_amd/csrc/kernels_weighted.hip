@@ -16,9 +16,15 @@
 //           (kernels_weighted_query.hip holds the rest of a seeded push).
 //   walks   one walk per lane, refilled in ballot order; the neighbour pick is a binary search over the row's
 //           inclusive weight prefix: x = (word * 2^-32) * W(cur), j = #{cum <= x} clamped to d - 1.
+//   index   k_w_index_build stores the terminals of the walks a whole-graph weighted FORA phase draws per node (the
+//           weighted walk index); a phase at the index's alpha and seed is served by kernels_walk.hip's k_index_serve
+//           and k_w_walk_plan<true> walks only what the index does not hold.
 //
 // All arithmetic is IEEE double with -ffp-contract=off: each product / quotient rounds on its own, so that a host
 // restatement of these rules (tests/weighted_ref.py) takes the same decisions.
+#include <cstring>
+#include <type_traits>
+
 #include "weighted_device.hpp"
 
 namespace pprhip {
@@ -379,9 +385,20 @@ __global__ __launch_bounds__(256) void k_w_walk_batch(const int32_t* __restrict_
 // by binary search over the entries' walk offsets, from the entry of the wave's oldest open walk on.  The walks are
 // (seed, stream, node, index within the entry), with or without the forced first hop (whole-graph FORA: stream 0,
 // forced; a weighted top-k round: its round number, not forced); every walk adds its entry's increment at its terminal.
+// INDEXED (idx_off: the offsets of the weighted walk index; k_mc_walk<kWalkIndexed>'s rule): k_index_serve has deposited
+// the stored terminals of this plan and counted the walks the index does not hold into ctr->walks_over.  None: the
+// kernel returns at once.  Otherwise a walk whose index lies below its node's capacity is passed over, the others - an
+// entry's tail [cap, omega_i), every walk of a dead-end start - run with their own indices.  The plain instantiation is
+// the kernel as it was, argument block included: its last argument is an empty struct, which takes no bytes there.
+struct WNoIndex {};
+template <bool INDEXED>
+using WIndexOffsets = std::conditional_t<INDEXED, const unsigned long long*, WNoIndex>;
+
+template <bool INDEXED>
 __global__ __launch_bounds__(64) void k_w_walk_plan(const WalkPlanRec* __restrict__ plan_rec, WWalkGraph G,
                                                      double* __restrict__ target, double alpha, uint32_t k0, uint32_t k1,
-                                                     uint32_t stream, int no_zero_hop, DevCounters* ctr, int parity) {
+                                                     uint32_t stream, int no_zero_hop, DevCounters* ctr, int parity,
+                                                     WIndexOffsets<INDEXED> idx_off) {
   const unsigned long long plan = ctr->mc_plan[parity];
   const uint32_t n_src = (uint32_t)(plan >> kPackShift);
   const unsigned long long n_walks = plan & kPackMask;
@@ -389,6 +406,7 @@ __global__ __launch_bounds__(64) void k_w_walk_plan(const WalkPlanRec* __restric
     ctr->walks_total += n_walks;
     ctr->sources_total += n_src;
   }
+  if (INDEXED && ctr->walks_over == 0ull) return;  // the index held every walk of the phase
   const int lane = threadIdx.x;
   const unsigned long long groups = (n_walks + 63) / 64;
   const unsigned long long per = (groups + gridDim.x - 1) / gridDim.x * 64;
@@ -422,6 +440,8 @@ __global__ __launch_bounds__(64) void k_w_walk_plan(const WalkPlanRec* __restric
           atomic_add_noret(&target[r.node], inc);  // a dead-end start is its own terminal
         else
           walking = true;
+        if constexpr (INDEXED)  // k_index_serve has deposited this walk's terminal (never a dead-end start's: capacity 0)
+          if (gidx - r.woff < idx_off[r.node + 1] - idx_off[r.node]) walking = false;
       }
       // the walk of the first refilled lane is the oldest one the wave has not placed yet
       e_lo = (uint32_t)__shfl((int)e, __builtin_ctzll(need));
@@ -440,6 +460,57 @@ __global__ __launch_bounds__(64) void k_w_walk_plan(const WalkPlanRec* __restric
   }
   steps_total = wave_sum_u64(steps_total);
   if (lane == 0 && steps_total) atomic_add_u64(&ctr->walk_steps, steps_total);
+}
+
+// The weighted walk index (DESIGN.md §2 "Weighted walk index"): k_index_build's loop with the weighted walker.  A wave
+// takes a contiguous range of index positions; a lane whose walk has stopped stores its terminal (internal id) and takes
+// the range's next position (refill in ballot order).  Position p of node v is the weighted walk (seed, stream 0, v,
+// p - off[v]) with the forced first hop: what k_w_walk_plan runs for walk p - off[v] of a residue entry v.  Only nodes
+// with out-edges have positions.
+__global__ __launch_bounds__(64) void k_w_index_build(const unsigned long long* __restrict__ off, uint32_t n,
+                                                       unsigned long long total, WWalkGraph G,
+                                                       const int32_t* __restrict__ new2old, double alpha, uint32_t k0,
+                                                       uint32_t k1, int32_t* __restrict__ term,
+                                                       unsigned long long* __restrict__ steps_out) {
+  const int lane = threadIdx.x;
+  const unsigned long long groups = (total + 63) / 64;
+  const unsigned long long per = (groups + gridDim.x - 1) / gridDim.x * 64;
+  const unsigned long long lo = (unsigned long long)blockIdx.x * per;
+  if (lo >= total) return;
+  const unsigned long long hi = lo + per < total ? lo + per : total;
+  const uint32_t va = index_node_of(off, 0u, n - 1u, lo);
+  const uint32_t vb = index_node_of(off, va, n - 1u, hi - 1ull);
+  unsigned long long cursor = lo, pos = 0, steps = 0;
+  WWalker w;
+  bool walking = false;
+  for (;;) {
+    const unsigned long long need = __ballot(!walking);
+    if (need && cursor < hi) {
+      const unsigned long long avail = hi - cursor;
+      const uint32_t rank = __popcll(need & ((1ull << lane) - 1ull));
+      if (!walking && rank < avail) {
+        pos = cursor + rank;
+        const uint32_t v = index_node_of(off, va, vb, pos);
+        const unsigned long long sext = G.out_ext[v];
+        w_walker_init(w, (int32_t)v, sext, new2old[v], pos - off[v], 0u, true);
+        if ((sext >> 32) == 0) term[pos] = (int32_t)v;  // (no node without out-edges has a position)
+        else walking = true;
+      }
+      const unsigned long long want = __popcll(need);
+      cursor += want < avail ? want : avail;
+    }
+    if (__ballot(walking) == 0) {
+      if (cursor >= hi) break;
+      continue;
+    }
+    if (walking && w_walker_step(w, G, alpha, k0, k1)) {
+      term[pos] = w.cur;
+      steps += w.moves;
+      walking = false;
+    }
+  }
+  steps = wave_sum_u64(steps);
+  if (lane == 0 && steps) atomic_add_u64(steps_out, steps);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -510,16 +581,41 @@ int launch_w_walk_batch(pprhip_graph* g, const int32_t* d_starts, const uint64_t
   return PPRHIP_OK;
 }
 
-int launch_w_walk_plan(pprhip_graph* g, double alpha, uint64_t seed, double* target, uint32_t stream, bool no_zero_hop) {
+int launch_w_walk_run(pprhip_graph* g, double alpha, uint64_t seed, double* target, uint32_t stream, bool no_zero_hop) {
   // a fixed grid of waves, each with an equal share of whatever the plan holds; the host's bound of the walk count
   // (g->walk_hint) only trims the grid of a short phase (kernels_walk.hip: mc_walk_grid)
   uint32_t grid = (uint32_t)g->gr->n_cus * 16u;
   if (g->walk_hint) grid = (uint32_t)std::min<unsigned long long>(grid, std::max<unsigned long long>((g->walk_hint + 63) / 64, 1ull));
   g->walk_hint = 0;
   const WalkPlanRec* rec = (g->mc_plan_rec2 && (g->mc_last_plan & 1u)) ? g->mc_plan_rec2 : g->mc_plan_rec;
-  k_w_walk_plan<<<dim3(grid), dim3(64), 0, g->stream>>>(rec, walk_graph(g->gr), target, alpha, (uint32_t)seed,
-                                                        (uint32_t)(seed >> 32), stream, no_zero_hop ? 1 : 0, g->ctr,
-                                                        (int)(g->mc_last_plan % 3u));
+  const int cell = (int)(g->mc_last_plan % 3u);
+  // Whole-graph weighted FORA walks (stream 0, forced first hop, walk indices 0 .. omega_i - 1 per residue node; their
+  // plan is k_mc_plan<0>, which clears ctr->walks_over) are read from the handle's weighted walk index when it was built
+  // at this alpha and seed, bit for bit: the serve kernel on the same grid, then the walker for what the index does not
+  // hold.  Everything else - the top-k rounds among it (stream = round, no forced hop) - walks.
+  const WalkIndex* ix = g->gr->widx_w;
+  if (ix && stream == 0u && no_zero_hop && std::memcmp(&ix->alpha, &alpha, sizeof alpha) == 0 && ix->seed == seed) {
+    PPRHIP_TRY(launch_index_serve(g, ix, target, grid));
+    k_w_walk_plan<true><<<dim3(grid), dim3(64), 0, g->stream>>>(rec, walk_graph(g->gr), target, alpha, (uint32_t)seed,
+                                                                (uint32_t)(seed >> 32), 0u, 1, g->ctr, cell,
+                                                                (const unsigned long long*)ix->off);
+  } else {
+    k_w_walk_plan<false><<<dim3(grid), dim3(64), 0, g->stream>>>(rec, walk_graph(g->gr), target, alpha, (uint32_t)seed,
+                                                                 (uint32_t)(seed >> 32), stream, no_zero_hop ? 1 : 0, g->ctr,
+                                                                 cell, WNoIndex{});
+  }
+  PPRHIP_CHECK_HIP(hipGetLastError());
+  return PPRHIP_OK;
+}
+
+int launch_w_index_build(pprhip_graph* g, const TerminalTable* ix, unsigned long long* d_steps) {
+  if (ix->total == 0) return PPRHIP_OK;
+  const uint64_t cap = (uint64_t)g->gr->n_cus * 16u;  // launch_w_walk_run's waves
+  const uint64_t groups = (ix->total + 63) / 64;
+  const uint32_t grid = (uint32_t)(groups < cap ? groups : cap);
+  k_w_index_build<<<dim3(grid), dim3(64), 0, g->stream>>>(ix->off, g->gr->n, (unsigned long long)ix->total,
+                                                          walk_graph(g->gr), g->gr->new2old, ix->alpha,
+                                                          (uint32_t)ix->seed, (uint32_t)(ix->seed >> 32), ix->term, d_steps);
   PPRHIP_CHECK_HIP(hipGetLastError());
   return PPRHIP_OK;
 }

@@ -1,7 +1,9 @@
 // walk_index.cpp — the FORA+ walk index (include/pprhip.h "walk index"; DESIGN.md §2 "Walk index"): per node the
 // terminals of the walks a whole-graph FORA walk phase would draw from it, built once per (alpha, seed) and kept with
 // the lifted graph.  The kernels are in kernels_walk.hip (k_index_build, k_index_serve, k_mc_walk<kWalkIndexed>); the walk
-// phase picks the index in launch_walk_run (device_io.cpp).
+// phase picks the index in launch_walk_run (device_io.cpp).  The weighted walk index (include/pprhip.h "weighted walk
+// index") is the same table in a second slot of the lifted graph, filled with weighted walks (kernels_weighted.hip:
+// k_w_index_build) and picked by launch_w_walk_run; the entry points of both are one set of functions here.
 #include <algorithm>
 #include <cmath>
 #include <cstdlib>
@@ -113,9 +115,9 @@ static void destroy_index(WalkIndex* ix) {
   delete ix;
 }
 
-void free_walk_index(GraphData* D) {
-  destroy_index(D->widx);
-  D->widx = nullptr;
+void free_walk_index(WalkIndex*& slot) {
+  destroy_index(slot);
+  slot = nullptr;
 }
 
 // ---- the call-scoped terminal cache (engine.hpp: WalkShare)
@@ -291,8 +293,10 @@ int pprhip_walk_index_density(const pprhip_fora_conf_t* conf, double eps, double
   return PPRHIP_OK;
 }
 
-int pprhip_walk_index_build(pprhip_graph_t* g, double alpha, uint64_t seed, double density, pprhip_stats_t* stats) {
-  static const char* fn = "pprhip_walk_index_build";
+// ---- the two walk indexes of a lifted graph: GraphData::widx (unweighted walks) and GraphData::widx_w (weighted walks).
+// The five entry points of each are these functions with the slot, the build kernel and the name messages carry.
+static int index_build(pprhip_graph_t* g, bool weighted, const char* fn, double alpha, uint64_t seed, double density,
+                       pprhip_stats_t* stats) {
   PPRHIP_TRY(check_alpha(alpha, fn));
   PPRHIP_TRY(check_positive(density, fn, "density"));
   PPRHIP_TRY(check_graph(g, fn));
@@ -300,6 +304,7 @@ int pprhip_walk_index_build(pprhip_graph_t* g, double alpha, uint64_t seed, doub
     set_error("%s: not a graph handle", fn);
     return PPRHIP_ERR_INVALID;
   }
+  if (weighted) PPRHIP_TRY(need_weights(g, fn));
   GraphData* D = g->gr;
   // (the new index is complete before the old one goes: whatever fails below frees it and leaves the handle as it was)
   std::unique_ptr<WalkIndex, void (*)(WalkIndex*)> ix(new (std::nothrow) WalkIndex(), destroy_index);
@@ -308,7 +313,7 @@ int pprhip_walk_index_build(pprhip_graph_t* g, double alpha, uint64_t seed, doub
   ix->seed = seed;
   PPRHIP_TRY(table_alloc(*ix, D, density, 3, false, g->stream, fn));
   PPRHIP_CHECK_HIP(hipEventRecord(g->ev[0], g->stream));
-  PPRHIP_TRY(launch_index_build(g, ix.get(), ix->usage + 2));
+  PPRHIP_TRY(weighted ? launch_w_index_build(g, ix.get(), ix->usage + 2) : launch_index_build(g, ix.get(), ix->usage + 2));
   PPRHIP_CHECK_HIP(hipEventRecord(g->ev[1], g->stream));
   unsigned long long steps = 0;
   PPRHIP_CHECK_HIP(hipMemcpyAsync(&steps, ix->usage + 2, sizeof steps, hipMemcpyDeviceToHost, g->stream));
@@ -321,26 +326,28 @@ int pprhip_walk_index_build(pprhip_graph_t* g, double alpha, uint64_t seed, doub
     stats->mc_bytes = 12ull * steps + 4ull * ix->total + 8ull * ((uint64_t)D->n + 1);
   }
   PPRHIP_CHECK_HIP(hipDeviceSynchronize());  // nothing reads the old index any more
-  free_walk_index(D);
-  D->widx = ix.release();
+  WalkIndex*& slot = weighted ? D->widx_w : D->widx;
+  free_walk_index(slot);
+  slot = ix.release();
   return PPRHIP_OK;
 }
 
-int pprhip_walk_index_drop(pprhip_graph_t* g) {
-  PPRHIP_TRY(check_graph(g, "pprhip_walk_index_drop"));
-  if (!g->gr->widx) return PPRHIP_OK;
+static int index_drop(pprhip_graph_t* g, bool weighted, const char* fn) {
+  PPRHIP_TRY(check_graph(g, fn));
+  WalkIndex*& slot = weighted ? g->gr->widx_w : g->gr->widx;
+  if (!slot) return PPRHIP_OK;
   PPRHIP_CHECK_HIP(hipDeviceSynchronize());
-  free_walk_index(g->gr);
+  free_walk_index(slot);
   return PPRHIP_OK;
 }
 
-int pprhip_walk_index_info(const pprhip_graph_t* g, int* present, double* alpha, uint64_t* seed, double* density,
-                           uint64_t* terminals, uint64_t* bytes) {
+static int index_info(const pprhip_graph_t* g, bool weighted, const char* fn, int* present, double* alpha, uint64_t* seed,
+                      double* density, uint64_t* terminals, uint64_t* bytes) {
   if (!g) {
-    set_error("pprhip_walk_index_info: null graph handle");
+    set_error("%s: null graph handle", fn);
     return PPRHIP_ERR_INVALID;
   }
-  const WalkIndex* ix = g->gr->widx;
+  const WalkIndex* ix = weighted ? g->gr->widx_w : g->gr->widx;
   if (present) *present = ix ? 1 : 0;
   if (alpha) *alpha = ix ? ix->alpha : 0.0;
   if (seed) *seed = ix ? ix->seed : 0;
@@ -350,13 +357,13 @@ int pprhip_walk_index_info(const pprhip_graph_t* g, int* present, double* alpha,
   return PPRHIP_OK;
 }
 
-int pprhip_walk_index_fetch(pprhip_graph_t* g, int32_t node, int32_t* terminals_out, uint64_t cap, uint64_t* count_out) {
-  static const char* fn = "pprhip_walk_index_fetch";
+static int index_fetch(pprhip_graph_t* g, bool weighted, const char* fn, int32_t node, int32_t* terminals_out, uint64_t cap,
+                       uint64_t* count_out) {
   PPRHIP_TRY(check_graph(g, fn));
   PPRHIP_TRY(check_node(g, node, fn));
-  const WalkIndex* ix = g->gr->widx;
+  const WalkIndex* ix = weighted ? g->gr->widx_w : g->gr->widx;
   if (!ix) {
-    set_error("%s: the handle has no walk index", fn);
+    set_error(weighted ? "%s: the handle has no weighted walk index" : "%s: the handle has no walk index", fn);
     return PPRHIP_ERR_STATE;
   }
   if (cap && !terminals_out) {
@@ -366,9 +373,46 @@ int pprhip_walk_index_fetch(pprhip_graph_t* g, int32_t node, int32_t* terminals_
   return table_fetch_node(g, *ix, node, false, terminals_out, cap, count_out);
 }
 
+int pprhip_walk_index_build(pprhip_graph_t* g, double alpha, uint64_t seed, double density, pprhip_stats_t* stats) {
+  return index_build(g, false, "pprhip_walk_index_build", alpha, seed, density, stats);
+}
+
+int pprhip_walk_index_drop(pprhip_graph_t* g) { return index_drop(g, false, "pprhip_walk_index_drop"); }
+
+int pprhip_walk_index_info(const pprhip_graph_t* g, int* present, double* alpha, uint64_t* seed, double* density,
+                           uint64_t* terminals, uint64_t* bytes) {
+  return index_info(g, false, "pprhip_walk_index_info", present, alpha, seed, density, terminals, bytes);
+}
+
+int pprhip_walk_index_fetch(pprhip_graph_t* g, int32_t node, int32_t* terminals_out, uint64_t cap, uint64_t* count_out) {
+  return index_fetch(g, false, "pprhip_walk_index_fetch", node, terminals_out, cap, count_out);
+}
+
 int pprhip_walk_index_usage(pprhip_graph_t* g, uint64_t* served, uint64_t* walked, int reset) {
   PPRHIP_TRY(check_graph(g, "pprhip_walk_index_usage"));
   return table_usage(g->gr->widx, served, walked, reset);
+}
+
+int pprhip_weighted_walk_index_build(pprhip_graph_t* g, double alpha, uint64_t seed, double density,
+                                     pprhip_stats_t* stats) {
+  return index_build(g, true, "pprhip_weighted_walk_index_build", alpha, seed, density, stats);
+}
+
+int pprhip_weighted_walk_index_drop(pprhip_graph_t* g) { return index_drop(g, true, "pprhip_weighted_walk_index_drop"); }
+
+int pprhip_weighted_walk_index_info(const pprhip_graph_t* g, int* present, double* alpha, uint64_t* seed, double* density,
+                                    uint64_t* terminals, uint64_t* bytes) {
+  return index_info(g, true, "pprhip_weighted_walk_index_info", present, alpha, seed, density, terminals, bytes);
+}
+
+int pprhip_weighted_walk_index_fetch(pprhip_graph_t* g, int32_t node, int32_t* terminals_out, uint64_t cap,
+                                     uint64_t* count_out) {
+  return index_fetch(g, true, "pprhip_weighted_walk_index_fetch", node, terminals_out, cap, count_out);
+}
+
+int pprhip_weighted_walk_index_usage(pprhip_graph_t* g, uint64_t* served, uint64_t* walked, int reset) {
+  PPRHIP_TRY(check_graph(g, "pprhip_weighted_walk_index_usage"));
+  return table_usage(g->gr->widx_w, served, walked, reset);
 }
 
 #ifdef PPRHIP_TEST_HOOKS

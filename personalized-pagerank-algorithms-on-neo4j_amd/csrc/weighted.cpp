@@ -164,6 +164,10 @@ int run_weighted_levels(pprhip_graph* g, const PushArgs& a, WLevels& L, pprhip_s
 }
 
 void free_weights(GraphData* D) {
+  if (D->widx_w) {  // built from these weights: it goes before they change (its readers are the handle's weighted calls)
+    (void)hipDeviceSynchronize();
+    free_walk_index(D->widx_w);
+  }
   void* ptrs[] = {D->out_w, D->out_cum, D->wsum, D->in_w, D->wsurvival};
   for (void* p : ptrs)
     if (p) (void)hipFree(p);
@@ -465,7 +469,7 @@ int pprhip_weighted_fora(pprhip_graph_t* g, int32_t src, double eps, const pprhi
     const long long nrw = (nrw_d == nrw_d && nrw_d > 0.0) ? (long long)nrw_d : 0;
     PPRHIP_TRY(launch_walk_plan(g, 0, alpha, rsum, nrw, g->reserve, 0.0));
     ktimer().begin(PPRHIP_KERNEL_WALK, 0);
-    PPRHIP_TRY(launch_w_walk_plan(g, alpha, seed, g->reserve, 0u, true));
+    PPRHIP_TRY(launch_w_walk_run(g, alpha, seed, g->reserve, 0u, true));
     ktimer().end();
   }
   tm.mark(2);

@@ -95,7 +95,7 @@ int topk_drive(pprhip_graph* g, SeedTable& plan, double eps, const pprhip_fora_c
       PPRHIP_TRY(launch_walk_plan(g, 1, alpha, 0.0, 0, g->est, omega_j, g->reserve, g->est));
       tm.mark(2);
       ktimer().begin(PPRHIP_KERNEL_WALK, 0);  // (its bytes are added when the counters are read)
-      PPRHIP_TRY(launch_w_walk_plan(g, alpha, seed, g->est, round, false));
+      PPRHIP_TRY(launch_w_walk_run(g, alpha, seed, g->est, round, false));
       ktimer().end();
       tm.mark(3);
       round++;
@@ -210,7 +210,7 @@ int pprhip_weighted_fora_seeds(pprhip_graph_t* g, const int32_t* seeds, const do
     const long long nrw = (nrw_d == nrw_d && nrw_d > 0.0) ? (long long)nrw_d : 0;
     PPRHIP_TRY(launch_walk_plan(g, 0, alpha, rsum, nrw, g->reserve, 0.0));
     ktimer().begin(PPRHIP_KERNEL_WALK, 0);
-    PPRHIP_TRY(launch_w_walk_plan(g, alpha, seed, g->reserve, 0u, true));
+    PPRHIP_TRY(launch_w_walk_run(g, alpha, seed, g->reserve, 0u, true));
     ktimer().end();
   }
   tm.mark(2);
