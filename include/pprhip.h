@@ -287,7 +287,7 @@ void pprhip_lift_destroy(pprhip_lift_t* lift);
  * 80 GB).  pprhip_graph_release hands them back between phases of a job; the next call of that entry point allocates
  * them again.  The CSR pair, the walk records and the single-query workspace stay.  Not to be called while another
  * thread uses the handle. */
-#define PPRHIP_RELEASE_ALL_PAIR 1u
+#define PPRHIP_RELEASE_ALL_PAIR 1u /* also the weighted All-Pair edge records (16 bytes per relationship) */
 #define PPRHIP_RELEASE_BATCH 2u
 #define PPRHIP_RELEASE_WALK_INDEX 4u /* the walk index (pprhip_walk_index_build): as pprhip_walk_index_drop */
 #define PPRHIP_RELEASE_SWEEP 8u      /* the sweep cut's workspace (pprhip_sweep_cut: ranks, sort buffers, the profile) */
@@ -917,6 +917,27 @@ int pprhip_weighted_ppr_targets(pprhip_graph_t* g, const int32_t* targets, const
 int pprhip_weighted_ppr_pairs(pprhip_graph_t* g, const int32_t* sources, const int32_t* targets, int q, double eps,
                               const pprhip_fora_conf_t* conf, double rmax, uint64_t seed, double* values_out,
                               pprhip_stats_t* stats_sum);
+
+/* ---- All-Pair backward search over the same P ("Weighted All-Pair")
+ * pprhip_all_pair_backward's index over the weighted transition matrix: signature, k rule, target ranges, the
+ * index type (pprhip_index_merge / _arrays / _write_dir work on it unchanged) and the meaning of every stats field are
+ * the unweighted call's.  One search per target t is the frontier-synchronous weighted backward push with the start rule
+ * of pprhip_weighted_backward_push at rmax = threshold: t pops first whatever the threshold; a popped v credits alpha r
+ * to its reserve and holds c = (1 - alpha) r; every in-edge e = (u -> v) deposits c * p(e) on r(u), p(e) = w(e) / W(u)
+ * rounded ONCE when the edge records are built; u joins the next level iff !(old > threshold) && new > threshold; a
+ * target without in-edges yields {t: 1.0}; entries with reserve > 0 and reserve >= threshold are emitted.  A deposit
+ * c * (w / W) may differ by an ulp from pprhip_weighted_backward_push's (c * w) / W; with power-of-two row sums both are
+ * exact.  The searches that the table and dense tiers give up run as pprhip_weighted_backward_push's whole-vector search
+ * (deposits (c * w) / W), one after another, whatever their number.
+ * Checks: alpha, threshold, the handle, PPRHIP_ERR_STATE without weights, then the target range.
+ * The edge records {source, p} (16 bytes per relationship) are built on the first call and kept beside the weights:
+ * pprhip_weights_info counts them from then on; pprhip_graph_set_weights (also with NULL), PPRHIP_RELEASE_WEIGHTS and
+ * PPRHIP_RELEASE_ALL_PAIR free them.  The workspaces are shared with pprhip_all_pair_backward; the two calls may be
+ * interleaved on one handle.
+ * Not offered over the weights: pprhip_all_pair_backward_multi / _sharded and the comm entry points (target ranges plus
+ * pprhip_index_merge shard by hand), the ppr command line and the JNI binding. */
+int pprhip_weighted_all_pair_backward(pprhip_graph_t* g, double alpha, double threshold, int k, uint32_t t_begin,
+                                      uint32_t t_end, pprhip_index_t** index_out, pprhip_stats_t* stats);
 
 /* ---------------------------------------------------------------- ground truth (a12) */
 /* Power_Method.computeWholeGraphPPR (Power_Method.java:44-101): `iters` synchronous sweeps. */

@@ -104,7 +104,7 @@ EXPORTS = [
     "pprhip_graph_set_weights", "pprhip_weights_info", "pprhip_weight_table_host", "pprhip_weighted_power_method",
     "pprhip_weighted_forward_push", "pprhip_weighted_random_walk_batch", "pprhip_weighted_fora",
     "pprhip_weighted_backward_push", "pprhip_weighted_walk_survival", "pprhip_weighted_ppr_targets",
-    "pprhip_weighted_ppr_pairs",
+    "pprhip_weighted_ppr_pairs", "pprhip_weighted_all_pair_backward",
     "pprhip_weighted_forward_push_seeds", "pprhip_weighted_fora_seeds", "pprhip_weighted_fora_topk",
     "pprhip_weighted_fora_topk_seeds",
     "pprhip_weighted_walk_index_build", "pprhip_weighted_walk_index_drop", "pprhip_weighted_walk_index_info",
@@ -205,6 +205,7 @@ def lib():
     L.pprhip_index_from_entries.argtypes = [u32, vp, vp, vp, u64, ci, P(vp)]
     L.pprhip_backward_push.argtypes = [vp, i32, dbl, dbl, vp, vp, P(Stats)]
     L.pprhip_all_pair_backward.argtypes = [vp, dbl, dbl, ci, u32, u32, P(vp), P(Stats)]
+    L.pprhip_weighted_all_pair_backward.argtypes = [vp, dbl, dbl, ci, u32, u32, P(vp), P(Stats)]
     L.pprhip_index_merge.argtypes = [P(vp), ci, ci, P(vp)]
     L.pprhip_index_from_arrays.argtypes = [u32, vp, vp, vp, P(vp)]
     L.pprhip_format_double.argtypes = [dbl, C.c_char_p, C.c_size_t]
@@ -1362,6 +1363,14 @@ class Graph:
         _check(lib().pprhip_weighted_backward_push(self.h, target, alpha, rmax, _ptr(reserve), _ptr(residue),
                                                    C.byref(st)))
         return reserve, residue, st
+
+    def weighted_all_pair_backward(self, alpha, threshold, k, t_begin=0, t_end=None):
+        """all_pair_backward over the weighted transition matrix (pprhip_weighted_all_pair_backward): (Index, Stats)."""
+        t_end = self.n if t_end is None else t_end
+        out, st = C.c_void_p(), Stats()
+        _check(lib().pprhip_weighted_all_pair_backward(self.h, alpha, threshold, k, t_begin, t_end, C.byref(out),
+                                                       C.byref(st)))
+        return Index(out), st
 
     def weighted_walk_survival(self, alpha):
         """S_w of the leaking walk over the weighted P at alpha (pprhip_weighted_walk_survival), n doubles by node id."""

@@ -1,6 +1,8 @@
 // allpair.cpp — All-Pair-Backward-Search (Base_Whole_Graph.preprocessing): the record store the searches' entries are
-// collected in on the device, the driver of the search tiers (all_pair_collect; the tiers: kernels_apbs.hip) and
-// pprhip_all_pair_backward.  The index the entries end up in is index.cpp's.
+// collected in on the device, the driver of the search tiers (all_pair_collect; the tiers: kernels_apbs.hip),
+// pprhip_all_pair_backward and pprhip_weighted_all_pair_backward.  The index the entries end up in is index.cpp's.
+// The weighted call is the same driver with ApbsCall::weighted set: the table and dense tiers read the weighted in-edge
+// records, and every search they give up is a whole-vector weighted backward push (the batch slots are unweighted).
 #include <algorithm>
 #include <chrono>
 #include <condition_variable>
@@ -76,6 +78,7 @@ struct ApbsCall {
   TripleStore& store;
   pprhip_stats_t& st;
   bool debug;  // developer switch PPRHIP_APBS_DEBUG: phase times and per-workgroup timers on stderr
+  bool weighted;  // the searches run over P(u, v) = w / W(u) (GraphData::in_wrec, weighted_backward_search_whole)
   ApbsBuffers B;
   unsigned long long h_cells[kApCells];
   std::vector<int32_t> h_ovf;
@@ -130,7 +133,7 @@ int run_tier(ApbsCall& c, bool dense_tier, std::vector<int32_t> list, bool use_r
     if (dense_tier)  // every board entry closed, nothing posted
       PPRHIP_CHECK_HIP(hipMemsetAsync(B.board, 0, apbs_board_bytes(B.ws_blocks), g->stream));
     ktimer().begin(PPRHIP_KERNEL_BACKWARD_BATCH, 0);
-    PPRHIP_TRY(launch_apbs(g, dense_tier, use_range ? nullptr : d_list, c.t_begin, cnt, c.alpha, c.threshold, B));
+    PPRHIP_TRY(launch_apbs(g, c.weighted, dense_tier, use_range ? nullptr : d_list, c.t_begin, cnt, c.alpha, c.threshold, B));
     ktimer().end();
     PPRHIP_CHECK_HIP(hipMemcpyAsync(c.h_cells, B.cells, sizeof c.h_cells, hipMemcpyDeviceToHost, g->stream));
     PPRHIP_CHECK_HIP(hipStreamSynchronize(g->stream));
@@ -141,7 +144,8 @@ int run_tier(ApbsCall& c, bool dense_tier, std::vector<int32_t> list, bool use_r
     const unsigned long long valid = std::min(std::min(h_cells[kApOutCount], h_cells[kApOutValid]), B.out_cap);
     st.pops += h_cells[kApPops];
     st.edge_pushes += h_cells[kApEdges];
-    const uint64_t bytes = 44ull * h_cells[kApPops] + 28ull * h_cells[kApEdges] + 16ull * valid;
+    // (an edge: its record - 8 bytes, 16 with a weight - and the read-modify-write of a residue)
+    const uint64_t bytes = 44ull * h_cells[kApPops] + (c.weighted ? 36ull : 28ull) * h_cells[kApEdges] + 16ull * valid;
     st.push_bytes += bytes;
     if (!ktimer().recs.empty()) ktimer().recs.back().bytes = bytes;
     if (valid) PPRHIP_TRY(c.store.take_device(g, B.out_rec, valid));
@@ -183,6 +187,21 @@ int ensure_in_rec(pprhip_graph* g) {
   PPRHIP_TRY(alloc_dev(&rec, sizeof(unsigned long long) * std::max<uint64_t>(1, g->gr->m)));
   PPRHIP_TRY(launch_build_in_rec(g, rec));
   g->in_rec = rec;
+  rec = nullptr;
+  return PPRHIP_OK;
+}
+
+// ... and their weighted twin {source, w / W(source)} (16 B per edge; stays with the lifted graph's weights)
+int ensure_weighted_in_rec(pprhip_graph* g) {
+  GraphData* D = g->gr;
+  if (D->in_wrec) return PPRHIP_OK;
+  void* rec = nullptr;
+  FreeOnExit<void> rec_guard{rec};
+  const uint64_t bytes = 16ull * std::max<uint64_t>(1, D->m);
+  PPRHIP_TRY(alloc_dev(&rec, bytes));
+  PPRHIP_TRY(launch_build_in_rec_w(g, rec));
+  D->in_wrec = rec;
+  D->in_wrec_bytes = 16ull * D->m;
   rec = nullptr;
   return PPRHIP_OK;
 }
@@ -385,12 +404,13 @@ int dense_tier(ApbsCall& c, std::vector<int32_t>& list, std::vector<int32_t>& to
 // pushes - pprhip_backward_push's path.  Measured (tools/exp/apbs_big_searches.py): 2.5 ms of device time for that
 // target against 158 ms in the full-size pass below, where one workgroup owns the search and the others help with its
 // levels at the rate of memory-side atomics.  The entries go from the reserve vector into records on the device.
-int whole_searches(ApbsCall& c, std::vector<int32_t>& to_tier3) {
+// every: whatever their number (the weighted call's last tier: what the dense and full-size passes gave up)
+int whole_searches(ApbsCall& c, std::vector<int32_t>& to_tier3, bool every) {
   pprhip_graph* g = c.g;
   pprhip_stats_t& st = c.st;
   const char* whole_env = hook_env("PPRHIP_APBS_WHOLE");
   const size_t whole_max = whole_env ? (size_t)std::max(0, atoi(whole_env)) : 256;
-  const bool run = !to_tier3.empty() && to_tier3.size() <= whole_max;
+  const bool run = !to_tier3.empty() && (every || to_tier3.size() <= whole_max);
   if (!run) return PPRHIP_OK;
   TripleRec* d_rec = nullptr;
   unsigned long long* d_cnt = nullptr;
@@ -403,7 +423,9 @@ int whole_searches(ApbsCall& c, std::vector<int32_t>& to_tier3) {
   for (int32_t t_old : to_tier3) {
     pprhip_stats_t s1;
     std::memset(&s1, 0, sizeof s1);
-    PPRHIP_TRY(backward_search_whole(g, g->gr->relabeled ? o2n[t_old] : t_old, c.alpha, c.threshold, s1));
+    const int32_t t = g->gr->relabeled ? o2n[t_old] : t_old;
+    PPRHIP_TRY(c.weighted ? weighted_backward_search_whole(g, t, c.alpha, c.threshold, s1)
+                          : backward_search_whole(g, t, c.alpha, c.threshold, s1));
     PPRHIP_CHECK_HIP(hipMemsetAsync(d_cnt, 0, sizeof(unsigned long long), g->stream));
     PPRHIP_TRY(launch_emit_reserve(g, g->reserve, g->gr->n, c.threshold, t_old, d_rec, cap, d_cnt));
     unsigned long long cnt = 0;
@@ -490,15 +512,17 @@ struct PhaseClock {  // wall time since the phase before (PPRHIP_APBS_DEBUG's "[
 // quarter of the job; since tier 1 routes its targets by in-degree it is a seventh of it, and the tiers one after the
 // other are as fast or faster - R-MAT 22: 655 against 670 ms, R-MAT 24: 1 894 against 1 910 ms - with one pass of each
 // tier instead of three.  The side-by-side form was taken out.)
+// weighted: the searches of pprhip_weighted_all_pair_backward - the tiers read the weighted records, and what the dense
+// and full-size passes give up runs as whole-vector weighted pushes whatever its number (tier 3's slots are unweighted).
 int all_pair_collect(pprhip_graph_t* g, double alpha, double threshold, uint32_t t_begin, uint32_t t_end,
-                     TripleStore& store, pprhip_stats_t& st) {
+                     TripleStore& store, pprhip_stats_t& st, bool weighted) {
   g->topk_active = false;
   CallTimer tm(g);
   // PPRHIP_APBS_TIER = 2 / 3 starts at a later tier (tests exercise every tier that way)
   const int first_tier = hook_env("PPRHIP_APBS_TIER") ? atoi(hook_env("PPRHIP_APBS_TIER")) : 1;
-  ApbsCall c{g, alpha, threshold, t_begin, t_end - t_begin, store, st, hook_env("PPRHIP_APBS_DEBUG") != nullptr};
+  ApbsCall c{g, alpha, threshold, t_begin, t_end - t_begin, store, st, hook_env("PPRHIP_APBS_DEBUG") != nullptr, weighted};
   PPRHIP_TRY(c.alloc_buffers());
-  PPRHIP_TRY(ensure_in_rec(g));
+  PPRHIP_TRY(weighted ? ensure_weighted_in_rec(g) : ensure_in_rec(g));
   // the sweep layout over the out-CSR that the whole-vector searches' dense levels need: built with the handle's other
   // first-use work, not inside a later call's searches
   PPRHIP_TRY(ensure_bwd_layout(g));
@@ -513,15 +537,20 @@ int all_pair_collect(pprhip_graph_t* g, double alpha, double threshold, uint32_t
   if (!to_tier2.empty()) {
     PPRHIP_TRY(dense_tier(c, to_tier2, to_tier3));
     st.xl_targets = (uint32_t)to_tier3.size();  // searches that outgrew a workspace's lists
-    PPRHIP_TRY(whole_searches(c, to_tier3));
+    PPRHIP_TRY(whole_searches(c, to_tier3, false));
     PPRHIP_TRY(xl_pass(c, to_tier2.size(), to_tier3));
   }
   if (c.debug) fprintf(stderr, "[apbs host] tier 2 (%zu targets): %.1f ms\n", to_tier2.size(), clock.lap_ms());
   c.free_buffers();  // (up to 2 GB of records: the batch slots need the room)
   pprhip_stats_t st3;
   std::memset(&st3, 0, sizeof st3);
-  PPRHIP_TRY(batch_tier(c, to_tier3, st3));
-  if (c.debug) fprintf(stderr, "[apbs host] tier 3 (%zu targets): %.1f ms\n", to_tier3.size(), clock.lap_ms());
+  const size_t n_tier3 = to_tier3.size();
+  if (weighted) {
+    PPRHIP_TRY(whole_searches(c, to_tier3, true));
+  } else {
+    PPRHIP_TRY(batch_tier(c, to_tier3, st3));
+  }
+  if (c.debug) fprintf(stderr, "[apbs host] tier 3 (%zu targets): %.1f ms\n", n_tier3, clock.lap_ms());
   tm.mark(1);
   tm.finish(st);
   for (int i = 0; i < 8; ++i) {
@@ -532,22 +561,24 @@ int all_pair_collect(pprhip_graph_t* g, double alpha, double threshold, uint32_t
   st.push_ms = CallTimer::ms(g->ev[0], g->ev[1]);
   st.rmax_final = threshold;
   st.rounds = (uint32_t)(to_tier2.size());      // targets that needed the dense tier
-  st.dense_nodes = (uint64_t)to_tier3.size();   // targets that needed the whole-vector path
+  st.dense_nodes = (uint64_t)n_tier3;           // targets that needed the whole-vector path
   return PPRHIP_OK;
 }
 
 }  // namespace detail
 }  // namespace pprhip
 
-extern "C" {
+namespace {
 
-int pprhip_all_pair_backward(pprhip_graph_t* g, double alpha, double threshold, int k, uint32_t t_begin, uint32_t t_end,
-                             pprhip_index_t** index_out, pprhip_stats_t* stats) {
-  PPRHIP_TRY(check_alpha(alpha, "pprhip_all_pair_backward"));
-  PPRHIP_TRY(check_threshold(threshold, "pprhip_all_pair_backward", "threshold"));
-  PPRHIP_TRY(check_graph(g, "pprhip_all_pair_backward"));
+// both entry points: the checks, the searches, the index finalisation
+int all_pair_index(pprhip_graph_t* g, double alpha, double threshold, int k, uint32_t t_begin, uint32_t t_end,
+                   pprhip_index_t** index_out, pprhip_stats_t* stats, const char* fn, bool weighted) {
+  PPRHIP_TRY(check_alpha(alpha, fn));
+  PPRHIP_TRY(check_threshold(threshold, fn, "threshold"));
+  PPRHIP_TRY(check_graph(g, fn));
+  if (weighted) PPRHIP_TRY(need_weights(g, fn));
   if (!index_out || t_begin > t_end || t_end > g->gr->n) {
-    set_error("pprhip_all_pair_backward: bad target range [%u, %u) for n=%u", t_begin, t_end, g->gr->n);
+    set_error("%s: bad target range [%u, %u) for n=%u", fn, t_begin, t_end, g->gr->n);
     return PPRHIP_ERR_INVALID;
   }
   pprhip_stats_t st;
@@ -568,14 +599,14 @@ int pprhip_all_pair_backward(pprhip_graph_t* g, double alpha, double threshold, 
   // room for the entries a range of this size usually yields (a dozen per target at the thresholds the thesis uses):
   // the store then does not grow - allocate, copy, free - while the searches run
   if (t_end - t_begin >= (1u << 18)) (void)sink.reserve(g, 12ull * (unsigned long long)(t_end - t_begin));
-  const int crc = all_pair_collect(g, alpha, threshold, t_begin, t_end, sink, st);
+  const int crc = all_pair_collect(g, alpha, threshold, t_begin, t_end, sink, st, weighted);
   if (pin.joinable()) pin.join();
   PPRHIP_TRY(crc);
   const auto t1 = std::chrono::steady_clock::now();
   try {  // (the index arrays are host allocations of hundreds of megabytes: no exception leaves the C ABI)
     PPRHIP_TRY(index_from_device(g, sink.rec, sink.count, k, 0u, g->gr->n, index_out));
   } catch (const std::exception& e) {
-    set_error("pprhip_all_pair_backward: index finalisation: %s", e.what());
+    set_error("%s: index finalisation: %s", fn, e.what());
     return PPRHIP_ERR_OOM;
   }
   if (hook_env("PPRHIP_APBS_DEBUG"))
@@ -584,6 +615,21 @@ int pprhip_all_pair_backward(pprhip_graph_t* g, double alpha, double threshold, 
             std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t1).count());
   if (stats) *stats = st;
   return PPRHIP_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int pprhip_all_pair_backward(pprhip_graph_t* g, double alpha, double threshold, int k, uint32_t t_begin, uint32_t t_end,
+                             pprhip_index_t** index_out, pprhip_stats_t* stats) {
+  return all_pair_index(g, alpha, threshold, k, t_begin, t_end, index_out, stats, "pprhip_all_pair_backward", false);
+}
+
+int pprhip_weighted_all_pair_backward(pprhip_graph_t* g, double alpha, double threshold, int k, uint32_t t_begin,
+                                      uint32_t t_end, pprhip_index_t** index_out, pprhip_stats_t* stats) {
+  return all_pair_index(g, alpha, threshold, k, t_begin, t_end, index_out, stats, "pprhip_weighted_all_pair_backward",
+                        true);
 }
 
 }  // extern "C"

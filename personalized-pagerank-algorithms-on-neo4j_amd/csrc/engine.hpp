@@ -517,6 +517,11 @@ struct GraphData {
   // not instead of it; goes with the weights (free_weights)
   double* wsurvival = nullptr;
   double wsurvival_alpha = 0.0;
+  // the weighted All-Pair searches' in-edge records {source, w / W(source)} (16 B per edge, aligned with in_ci; built on
+  // the first pprhip_weighted_all_pair_backward, allpair.cpp); goes with the weights (free_weights) and with
+  // PPRHIP_RELEASE_ALL_PAIR.  in_wrec_bytes: what it holds in HBM, counted by pprhip_weights_info while it exists
+  void* in_wrec = nullptr;
+  uint64_t in_wrec_bytes = 0;
   // the weighted walk index, or none (pprhip_weighted_walk_index_build / _drop): terminals of weighted walks, beside
   // `widx` and never read by the unweighted calls, as `widx` is never read by the weighted ones; built from the weights
   // and dropped before they change (walk_index.cpp: free_weighted_walk_index)
@@ -874,8 +879,10 @@ size_t apbs_dense_bytes(uint32_t n, unsigned long long m, uint32_t cap_t, uint32
 uint32_t apbs_default_chunk();
 size_t apbs_board_bytes(uint32_t blocks);
 int launch_build_in_rec(pprhip_graph* g, void* rec);                  // rec: m records of 8 bytes
-int launch_apbs(pprhip_graph* g, bool dense_tier, const int32_t* d_targets, uint32_t t_begin, uint32_t n_targets,
-                double alpha, double rmax, ApbsBuffers& b);
+int launch_build_in_rec_w(pprhip_graph* g, void* rec);                // rec: m records of 16 bytes, from in_ci / in_w / wsum
+// weighted: the searches run over the weighted records (GraphData::in_wrec) instead of the handle's in_rec
+int launch_apbs(pprhip_graph* g, bool weighted, bool dense_tier, const int32_t* d_targets, uint32_t t_begin,
+                uint32_t n_targets, double alpha, double rmax, ApbsBuffers& b);
 // entries >= rmax of a reserve vector (internal ids [0, n)) as records of target t_old; *count counts them all, also
 // beyond cap
 int launch_emit_reserve(pprhip_graph* g, const double* reserve, uint32_t n, double rmax, int32_t t_old, TripleRec* out,

@@ -258,6 +258,7 @@ void free_sparse(pprhip_graph* g);  // the handle's workspace of the sparse gett
 // the lifted graph's relationship weights (and what was built from them: the weighted survival, the weighted walk
 // index), if it has them
 void free_weights(GraphData* D);
+void free_weighted_in_rec(GraphData* D);  // the weighted All-Pair records alone (PPRHIP_RELEASE_ALL_PAIR)
 int need_weights(const pprhip_graph* g, const char* fn);  // PPRHIP_ERR_STATE when the handle has no weights
 int fetch_packed(pprhip_graph* g, const unsigned long long* cell, uint32_t* nf, uint64_t* ef);  // a counter cell: entries << 36 | edges
 // The level loop of the weighted pushes, forward (kernels_weighted.hip) and backward (a.mode == kBackward:
@@ -575,10 +576,13 @@ struct TripleStore {
 };
 // the searches of the targets [t_begin, t_end), tier by tier; their entries >= threshold are added to `store`
 int all_pair_collect(pprhip_graph_t* g, double alpha, double threshold, uint32_t t_begin, uint32_t t_end,
-                     TripleStore& store, pprhip_stats_t& st);
+                     TripleStore& store, pprhip_stats_t& st, bool weighted = false);
 // Backward_Search.backward_search_whole_graph on the handle's own vectors (internal id); reserve / residue stay in HBM
 // (engine.cpp)
 int backward_search_whole(pprhip_graph_t* g, int32_t target_internal, double alpha, double rmax, pprhip_stats_t& st);
+// ... and its weighted form: pprhip_weighted_backward_push's search (weighted_bwd.cpp)
+int weighted_backward_search_whole(pprhip_graph_t* g, int32_t target_internal, double alpha, double rmax,
+                                   pprhip_stats_t& st);
 
 // ---- bwd_runs.cpp
 // The start of every backward push from one target (internal id), on a workspace the caller has just reset: a and L for

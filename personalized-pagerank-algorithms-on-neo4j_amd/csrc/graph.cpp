@@ -575,6 +575,7 @@ static void free_all_pair(pprhip_graph* g) {
     if (p) (void)hipFree(p);
   g->apbs_dense = g->apbs_xl = pprhip::ApbsWorkspace{};  // (allpair.cpp sizes and allocates the workspaces it does not find)
   g->apbs_board = g->in_rec = nullptr;
+  free_weighted_in_rec(g->gr);
   if (g->ix_stage) (void)hipHostFree(g->ix_stage);
   g->ix_stage = nullptr;
   g->ix_stage_bytes = 0;

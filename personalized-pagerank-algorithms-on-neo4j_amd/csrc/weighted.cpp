@@ -174,6 +174,13 @@ void free_weights(GraphData* D) {
   D->out_w = D->out_cum = D->wsum = D->in_w = D->wsurvival = nullptr;
   D->wsurvival_alpha = 0.0;
   D->w_bytes = 0;
+  free_weighted_in_rec(D);
+}
+
+void free_weighted_in_rec(GraphData* D) {
+  if (D->in_wrec) (void)hipFree(D->in_wrec);
+  D->in_wrec = nullptr;
+  D->in_wrec_bytes = 0;
 }
 
 }  // namespace detail
@@ -303,7 +310,7 @@ int pprhip_weights_info(const pprhip_graph_t* g, int* present, uint64_t* bytes) 
     return PPRHIP_ERR_INVALID;
   }
   if (present) *present = g->gr->w_bytes ? 1 : 0;
-  if (bytes) *bytes = g->gr->w_bytes;
+  if (bytes) *bytes = g->gr->w_bytes + g->gr->in_wrec_bytes;  // (the weighted All-Pair records once they exist)
   return PPRHIP_OK;
 }
 

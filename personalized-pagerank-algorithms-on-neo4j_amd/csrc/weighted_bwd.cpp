@@ -53,6 +53,14 @@ int ensure_weighted_survival(pprhip_graph* g, double alpha) {
 
 }  // namespace
 
+// (All-Pair's whole-vector searches over the weights, allpair.cpp)
+int pprhip::detail::weighted_backward_search_whole(pprhip_graph_t* g, int32_t target, double alpha, double rmax,
+                                                   pprhip_stats_t& st) {
+  PPRHIP_TRY(reset_query_state(g, false, target));
+  bool lone = false;
+  return weighted_bwd_single(g, target, alpha, rmax, 1.0, st, &lone);
+}
+
 extern "C" {
 
 int pprhip_weighted_backward_push(pprhip_graph_t* g, int32_t target, double alpha, double rmax, double* reserve_out,
