@@ -292,6 +292,12 @@ def _seed_arrays(seeds, weights):
     return s, w
 
 
+def _seed_start(seeds, weights):
+    """The leading arguments of a seed-set call (Graph._push_call and its like): ids, weights | None, count."""
+    s, w = _seed_arrays(seeds, weights)
+    return s, w, s.size
+
+
 def _batch_outputs(q, n, k, fetch, out, per_query):
     """The output arrays of a batched call of q queries: (vectors[q, n] | None, ids[q, k] | None, vals[q, k] | None,
     n_sel[q] | None, Stats array | None).  out: the caller's array for the vectors (with fetch), checked here."""
@@ -981,13 +987,53 @@ class Graph:
         k = min(cap, info.best_size)
         return (members[:k].copy() if cap else np.zeros(0, dtype=np.int32)), info, st
 
-    def forward_push(self, src, alpha, rmax, fetch=True):
+    # ---- the forward single-query calls, weighted and unweighted: one helper per return shape.  call: the C function;
+    # start: the arguments that name where the query starts - (src,) or _seed_start(seeds, weights)
+    def _push_call(self, call, start, alpha, rmax, fetch):
+        """(reserve | None, residue | None, rsum, Stats)"""
         reserve = np.empty(self.n) if fetch else None
         residue = np.empty(self.n) if fetch else None
         rsum, st = C.c_double(), Stats()
-        _check(lib().pprhip_forward_push(self.h, src, alpha, rmax, _ptr(reserve), _ptr(residue), C.byref(rsum),
-                                         C.byref(st)))
+        _check(call(self.h, *self._start(start), alpha, rmax, _ptr(reserve), _ptr(residue), C.byref(rsum), C.byref(st)))
         return reserve, residue, rsum.value, st
+
+    def _fora_call(self, call, start, eps, alpha, seed, knob, conf, fetch):
+        """(estimate | None, Stats); knob: n_rounds of the unweighted calls, rmax of the weighted ones"""
+        conf = conf or conf_whole_graph(self.n, self.m, alpha)
+        out = np.empty(self.n) if fetch else None
+        st = Stats()
+        _check(call(self.h, *self._start(start), eps, C.byref(conf), seed, knob, _ptr(out), C.byref(st)))
+        return out, st
+
+    def _topk_call(self, call, start, eps, alpha, k, seed, cap, conf, fetch):
+        """(nsel, ids, vals, estimate | None, Stats)"""
+        conf = conf or conf_topk(self.n, self.m, k, alpha)
+        cap = cap if cap is not None else k
+        ids = np.empty(max(cap, 1), dtype=np.int32)
+        vals = np.empty(max(cap, 1))
+        nsel, st = C.c_int(0), Stats()
+        out = np.empty(self.n) if fetch else None
+        _check(call(self.h, *self._start(start), eps, C.byref(conf), seed, _ptr(ids), _ptr(vals), cap, C.byref(nsel),
+                    _ptr(out), C.byref(st)))
+        w = min(nsel.value, cap)
+        return nsel.value, ids[:w].copy(), vals[:w].copy(), out, st
+
+    def _walk_call(self, call, starts, idx, alpha, seed, stream, no_zero_hop):
+        """(terminals, steps)"""
+        starts = np.ascontiguousarray(starts, dtype=np.int32)
+        idx = np.ascontiguousarray(idx, dtype=np.uint64)
+        term = np.empty(starts.size, dtype=np.int32)
+        steps = np.empty(starts.size, dtype=np.uint32)
+        _check(call(self.h, _ptr(starts), _ptr(idx), starts.size, alpha, seed, stream, int(no_zero_hop), _ptr(term),
+                    _ptr(steps)))
+        return term, steps
+
+    @staticmethod
+    def _start(start):
+        return [_ptr(a) if a is None or isinstance(a, np.ndarray) else a for a in start]
+
+    def forward_push(self, src, alpha, rmax, fetch=True):
+        return self._push_call(lib().pprhip_forward_push, (src,), alpha, rmax, fetch)
 
     def topk_push_reset(self, src, alpha):
         _check(lib().pprhip_fwdpush_topk_reset(self.h, src, alpha))
@@ -998,13 +1044,7 @@ class Graph:
         return rsum.value, st
 
     def random_walks(self, starts, idx, alpha, seed, stream=0, no_zero_hop=False):
-        starts = np.ascontiguousarray(starts, dtype=np.int32)
-        idx = np.ascontiguousarray(idx, dtype=np.uint64)
-        term = np.empty(starts.size, dtype=np.int32)
-        steps = np.empty(starts.size, dtype=np.uint32)
-        _check(lib().pprhip_random_walk_batch(self.h, _ptr(starts), _ptr(idx), starts.size, alpha, seed, stream,
-                                              int(no_zero_hop), _ptr(term), _ptr(steps)))
-        return term, steps
+        return self._walk_call(lib().pprhip_random_walk_batch, starts, idx, alpha, seed, stream, no_zero_hop)
 
     def build_walk_index(self, alpha, seed, density=None, eps=0.5, conf=None, _weighted=False):
         """Builds the FORA+ walk index of (alpha, seed) on the handle (pprhip_walk_index_build): ceil(d_out(v) * density)
@@ -1049,58 +1089,24 @@ class Graph:
         return s.value, w.value
 
     def fora_single_source(self, src, eps, alpha, seed, n_rounds=0, conf=None, fetch=True):
-        conf = conf or conf_whole_graph(self.n, self.m, alpha)
-        out = np.empty(self.n) if fetch else None
-        st = Stats()
-        _check(lib().pprhip_fora_single_source(self.h, src, eps, C.byref(conf), seed, n_rounds, _ptr(out),
-                                               C.byref(st)))
-        return out, st
+        return self._fora_call(lib().pprhip_fora_single_source, (src,), eps, alpha, seed, n_rounds, conf, fetch)
 
     def forward_push_seeds(self, seeds, alpha, rmax, weights=None, fetch=True):
         """forward_push personalized to a seed set (weights None: uniform); the same return shape."""
-        s, w = _seed_arrays(seeds, weights)
-        reserve = np.empty(self.n) if fetch else None
-        residue = np.empty(self.n) if fetch else None
-        rsum, st = C.c_double(), Stats()
-        _check(lib().pprhip_forward_push_seeds(self.h, _ptr(s), _ptr(w), s.size, alpha, rmax, _ptr(reserve),
-                                               _ptr(residue), C.byref(rsum), C.byref(st)))
-        return reserve, residue, rsum.value, st
+        return self._push_call(lib().pprhip_forward_push_seeds, _seed_start(seeds, weights), alpha, rmax, fetch)
 
     def fora_seeds(self, seeds, eps, alpha, seed, weights=None, n_rounds=0, conf=None, fetch=True):
         """fora_single_source personalized to a seed set (weights None: uniform); the same return shape."""
-        s, w = _seed_arrays(seeds, weights)
-        conf = conf or conf_whole_graph(self.n, self.m, alpha)
-        out = np.empty(self.n) if fetch else None
-        st = Stats()
-        _check(lib().pprhip_fora_seeds(self.h, _ptr(s), _ptr(w), s.size, eps, C.byref(conf), seed, n_rounds,
-                                       _ptr(out), C.byref(st)))
-        return out, st
+        return self._fora_call(lib().pprhip_fora_seeds, _seed_start(seeds, weights), eps, alpha, seed, n_rounds, conf,
+                               fetch)
 
     def fora_topk_seeds(self, seeds, eps, alpha, k, seed, weights=None, cap=None, conf=None, fetch=False):
         """fora_topk personalized to a seed set (weights None: uniform); the same return shape."""
-        s, w = _seed_arrays(seeds, weights)
-        conf = conf or conf_topk(self.n, self.m, k, alpha)
-        cap = cap if cap is not None else k
-        ids = np.empty(max(cap, 1), dtype=np.int32)
-        vals = np.empty(max(cap, 1))
-        nsel, st = C.c_int(0), Stats()
-        out = np.empty(self.n) if fetch else None
-        _check(lib().pprhip_fora_topk_seeds(self.h, _ptr(s), _ptr(w), s.size, eps, C.byref(conf), seed, _ptr(ids),
-                                            _ptr(vals), cap, C.byref(nsel), _ptr(out), C.byref(st)))
-        w_ = min(nsel.value, cap)
-        return nsel.value, ids[:w_].copy(), vals[:w_].copy(), out, st
+        return self._topk_call(lib().pprhip_fora_topk_seeds, _seed_start(seeds, weights), eps, alpha, k, seed, cap, conf,
+                               fetch)
 
     def fora_topk(self, src, eps, alpha, k, seed, cap=None, conf=None, fetch=False):
-        conf = conf or conf_topk(self.n, self.m, k, alpha)
-        cap = cap if cap is not None else k
-        ids = np.empty(max(cap, 1), dtype=np.int32)
-        vals = np.empty(max(cap, 1))
-        nsel, st = C.c_int(0), Stats()
-        out = np.empty(self.n) if fetch else None
-        _check(lib().pprhip_fora_topk(self.h, src, eps, C.byref(conf), seed, _ptr(ids), _ptr(vals), cap,
-                                      C.byref(nsel), _ptr(out), C.byref(st)))
-        w = min(nsel.value, cap)
-        return nsel.value, ids[:w].copy(), vals[:w].copy(), out, st
+        return self._topk_call(lib().pprhip_fora_topk, (src,), eps, alpha, k, seed, cap, conf, fetch)
 
     def topk_select(self, k, cap=None):
         cap = cap if cap is not None else k
@@ -1258,31 +1264,16 @@ class Graph:
 
     def weighted_forward_push(self, src, alpha, rmax, fetch=True):
         """forward_push over the weighted transition matrix; the same return shape."""
-        reserve = np.empty(self.n) if fetch else None
-        residue = np.empty(self.n) if fetch else None
-        rsum, st = C.c_double(), Stats()
-        _check(lib().pprhip_weighted_forward_push(self.h, src, alpha, rmax, _ptr(reserve), _ptr(residue), C.byref(rsum),
-                                                  C.byref(st)))
-        return reserve, residue, rsum.value, st
+        return self._push_call(lib().pprhip_weighted_forward_push, (src,), alpha, rmax, fetch)
 
     def weighted_random_walks(self, starts, idx, alpha, seed, stream=0, no_zero_hop=False):
         """random_walks with the weighted neighbour pick; the same return shape."""
-        starts = np.ascontiguousarray(starts, dtype=np.int32)
-        idx = np.ascontiguousarray(idx, dtype=np.uint64)
-        term = np.empty(starts.size, dtype=np.int32)
-        steps = np.empty(starts.size, dtype=np.uint32)
-        _check(lib().pprhip_weighted_random_walk_batch(self.h, _ptr(starts), _ptr(idx), starts.size, alpha, seed, stream,
-                                                       int(no_zero_hop), _ptr(term), _ptr(steps)))
-        return term, steps
+        return self._walk_call(lib().pprhip_weighted_random_walk_batch, starts, idx, alpha, seed, stream, no_zero_hop)
 
     def weighted_fora(self, src, eps, alpha, seed, rmax=0.0, conf=None, fetch=True):
         """One weighted push at rmax (0: rmax0 of conf and eps), then the whole-graph FORA walk phase with weighted
         walks (pprhip_weighted_fora).  Returns (estimate | None, Stats)."""
-        conf = conf or conf_whole_graph(self.n, self.m, alpha)
-        out = np.empty(self.n) if fetch else None
-        st = Stats()
-        _check(lib().pprhip_weighted_fora(self.h, src, eps, C.byref(conf), seed, rmax, _ptr(out), C.byref(st)))
-        return out, st
+        return self._fora_call(lib().pprhip_weighted_fora, (src,), eps, alpha, seed, rmax, conf, fetch)
 
     # ---- weighted seed sets and top-k: the return shapes of the unweighted / weighted namesakes
     def build_weighted_walk_index(self, alpha, seed, density=None, eps=0.5, conf=None):
@@ -1308,51 +1299,21 @@ class Graph:
 
     def weighted_forward_push_seeds(self, seeds, alpha, rmax, weights=None, fetch=True):
         """forward_push_seeds over the weighted transition matrix (`weights`: the seeds' weights, None: uniform)."""
-        s, w = _seed_arrays(seeds, weights)
-        reserve = np.empty(self.n) if fetch else None
-        residue = np.empty(self.n) if fetch else None
-        rsum, st = C.c_double(), Stats()
-        _check(lib().pprhip_weighted_forward_push_seeds(self.h, _ptr(s), _ptr(w), s.size, alpha, rmax, _ptr(reserve),
-                                                        _ptr(residue), C.byref(rsum), C.byref(st)))
-        return reserve, residue, rsum.value, st
+        return self._push_call(lib().pprhip_weighted_forward_push_seeds, _seed_start(seeds, weights), alpha, rmax, fetch)
 
     def weighted_fora_seeds(self, seeds, eps, alpha, seed, weights=None, rmax=0.0, conf=None, fetch=True):
         """weighted_fora personalized to a seed set (`weights`: the seeds' weights, None: uniform)."""
-        s, w = _seed_arrays(seeds, weights)
-        conf = conf or conf_whole_graph(self.n, self.m, alpha)
-        out = np.empty(self.n) if fetch else None
-        st = Stats()
-        _check(lib().pprhip_weighted_fora_seeds(self.h, _ptr(s), _ptr(w), s.size, eps, C.byref(conf), seed, rmax,
-                                                _ptr(out), C.byref(st)))
-        return out, st
+        return self._fora_call(lib().pprhip_weighted_fora_seeds, _seed_start(seeds, weights), eps, alpha, seed, rmax, conf,
+                               fetch)
 
     def weighted_fora_topk(self, src, eps, alpha, k, seed, cap=None, conf=None, fetch=False):
         """fora_topk over the weighted transition matrix, in plain rounds; the same return shape."""
-        conf = conf or conf_topk(self.n, self.m, k, alpha)
-        cap = cap if cap is not None else k
-        ids = np.empty(max(cap, 1), dtype=np.int32)
-        vals = np.empty(max(cap, 1))
-        nsel, st = C.c_int(0), Stats()
-        out = np.empty(self.n) if fetch else None
-        _check(lib().pprhip_weighted_fora_topk(self.h, src, eps, C.byref(conf), seed, _ptr(ids), _ptr(vals), cap,
-                                               C.byref(nsel), _ptr(out), C.byref(st)))
-        w = min(nsel.value, cap)
-        return nsel.value, ids[:w].copy(), vals[:w].copy(), out, st
+        return self._topk_call(lib().pprhip_weighted_fora_topk, (src,), eps, alpha, k, seed, cap, conf, fetch)
 
     def weighted_fora_topk_seeds(self, seeds, eps, alpha, k, seed, weights=None, cap=None, conf=None, fetch=False):
         """weighted_fora_topk personalized to a seed set; the return shape of fora_topk_seeds."""
-        s, w = _seed_arrays(seeds, weights)
-        conf = conf or conf_topk(self.n, self.m, k, alpha)
-        cap = cap if cap is not None else k
-        ids = np.empty(max(cap, 1), dtype=np.int32)
-        vals = np.empty(max(cap, 1))
-        nsel, st = C.c_int(0), Stats()
-        out = np.empty(self.n) if fetch else None
-        _check(lib().pprhip_weighted_fora_topk_seeds(self.h, _ptr(s), _ptr(w), s.size, eps, C.byref(conf), seed,
-                                                     _ptr(ids), _ptr(vals), cap, C.byref(nsel), _ptr(out),
-                                                     C.byref(st)))
-        w_ = min(nsel.value, cap)
-        return nsel.value, ids[:w_].copy(), vals[:w_].copy(), out, st
+        return self._topk_call(lib().pprhip_weighted_fora_topk_seeds, _seed_start(seeds, weights), eps, alpha, k, seed,
+                               cap, conf, fetch)
 
     # ---- the backward direction over the weights: the unweighted namesakes' arguments and return shapes
     def weighted_backward_push(self, target, alpha, rmax):

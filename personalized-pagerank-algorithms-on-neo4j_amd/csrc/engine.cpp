@@ -1,10 +1,11 @@
-// engine.cpp — the single-query C ABI of the pprhip engine: kernel timing, tuning and conf functions, forward push,
-// top-k push rounds, the walker exposure, top-k select, Monte-Carlo, backward push and the power method, with the
-// parameter checks every entry point runs and the top-k push session.  Everything numerical runs in the HIP kernels;
-// the host only sequences launches on the handle's stream.  The handle's lifecycle lives in graph.cpp, the level loop
-// in levels.cpp, the selection driver in select.cpp, read-backs and walk launchers in device_io.cpp, FORA runs in
-// fora.cpp, the runs that push backward in bwd_runs.cpp, the batched entry points in batch.cpp, batch_api.cpp and
-// stream.cpp, All-Pair in allpair.cpp and its index in index.cpp (shared declarations: engine_internal.hpp).
+// engine.cpp — the single-query C ABI of the pprhip engine: kernel timing, tuning and conf functions, top-k push
+// rounds, top-k select, Monte-Carlo, backward push and the power method, with the parameter checks every entry point
+// runs and the top-k push session.  Everything numerical runs in the HIP kernels; the host only sequences launches on
+// the handle's stream.  The forward push and walk-batch calls live in forward_calls.cpp, the handle's lifecycle in
+// graph.cpp, the level loop in levels.cpp, the selection driver in select.cpp, read-backs and walk launchers in
+// device_io.cpp, FORA runs in fora.cpp, the runs that push backward in bwd_runs.cpp, the batched entry points in
+// batch.cpp, batch_api.cpp and stream.cpp, All-Pair in allpair.cpp and its index in index.cpp (shared declarations:
+// engine_internal.hpp).
 #include <algorithm>
 #include <climits>
 #include <cmath>
@@ -49,7 +50,7 @@ int check_graph(const pprhip_graph* g, const char* fn) {
 }
 
 int check_node(const pprhip_graph* g, int32_t v, const char* fn) {
-  if (v < 0 || (uint32_t)v >= g->gr->n) {
+  if (!node_in_range(g, v)) {
     set_error("%s: node id %d outside [0, %u)", fn, v, g->gr->n);
     return PPRHIP_ERR_INVALID;
   }
@@ -95,6 +96,15 @@ int check_conf(const pprhip_fora_conf_t* c, const char* fn, bool topk) {
     return PPRHIP_ERR_INVALID;
   }
   return check_positive(c->min_delta, fn, "conf->min_delta");
+}
+
+bool topk_args_ok(const pprhip_fora_conf_t* conf, double eps, int cap, const int32_t* ids_out, const double* vals_out,
+                  const char* fn) {
+  if (!conf || conf->k < 1 || !(eps > 0.0) || cap < 0 || (cap > 0 && (!ids_out || !vals_out))) {
+    set_error("%s: bad arguments", fn);
+    return false;
+  }
+  return true;
 }
 
 int check_set_offsets(const uint64_t* offsets, int q, const char* fn) {
@@ -341,44 +351,6 @@ int pprhip_fora_topk_params(const pprhip_fora_conf_t* c, double eps, double delt
   return PPRHIP_OK;
 }
 
-// ------------------------------------------------------------------ forward push (a1)
-int pprhip_forward_push(pprhip_graph_t* g, int32_t src, double alpha, double rmax, double* reserve_out,
-                        double* residue_out, double* rsum_out, pprhip_stats_t* stats) {
-  PPRHIP_TRY(check_alpha(alpha, "pprhip_forward_push"));
-  PPRHIP_TRY(check_threshold(rmax, "pprhip_forward_push", "rmax"));
-  PPRHIP_TRY(check_graph(g, "pprhip_forward_push"));
-  PPRHIP_TRY(check_node(g, src, "pprhip_forward_push"));
-  src = g->gr->h_old2new[src];  // internal (degree-sorted) id
-  pprhip_stats_t st;
-  std::memset(&st, 0, sizeof st);
-  g->topk_active = false;
-  PPRHIP_TRY(reset_query_state(g, false, src));
-  CallTimer tm(g);
-  double rsum = 0.0;
-  if (hdeg_out(g, src) == 0) {  // Forward_Push.java:72-76
-    PPRHIP_TRY(launch_set_f64(g, g->reserve, (uint32_t)src, 1.0));
-  } else {
-    PushArgs a{alpha, rmax, 0.0, src, kFwdWhole};
-    LevelCtx L;
-    PPRHIP_TRY(launch_set_f64(g, g->residue, (uint32_t)src, 1.0));
-    PPRHIP_TRY(seed_single(g, L, src, hdeg_out(g, src)));
-    PPRHIP_TRY(run_levels(g, a, L, st, nullptr));
-    PPRHIP_TRY(device_sum(g, g->residue, &rsum));
-    PPRHIP_TRY(read_dead_pops(g, st));
-  }
-  tm.mark(1);
-  tm.finish(st);
-  st.push_ms = CallTimer::ms(g->ev[0], g->ev[1]);
-  st.rsum = rsum;
-  st.rmax_final = rmax;
-  st.rounds = 1;
-  if (rsum_out) *rsum_out = rsum;
-  PPRHIP_TRY(copy_out(g, g->reserve, reserve_out));
-  PPRHIP_TRY(copy_out(g, g->residue, residue_out));
-  if (stats) *stats = st;
-  return PPRHIP_OK;
-}
-
 // ------------------------------------------------------------------ resumable top-k push (a2)
 int pprhip_fwdpush_topk_reset(pprhip_graph_t* g, int32_t src, double alpha) {
   PPRHIP_TRY(check_alpha(alpha, "pprhip_fwdpush_topk_reset"));
@@ -420,53 +392,6 @@ int pprhip_fwdpush_topk_round(pprhip_graph_t* g, double min_rmax, double rmax, d
   if (rsum_out) *rsum_out = g->topk_rsum;
   if (stats) *stats = st;
   return PPRHIP_OK;
-}
-
-// ------------------------------------------------------------------ walker exposure (a3, a4)
-int pprhip_random_walk_batch(pprhip_graph_t* g, const int32_t* starts, const uint64_t* walk_idx, uint64_t count,
-                             double alpha, uint64_t seed, uint32_t stream, int no_zero_hop, int32_t* terminals_out,
-                             uint32_t* steps_out) {
-  PPRHIP_TRY(check_alpha(alpha, "pprhip_random_walk_batch"));
-  PPRHIP_TRY(check_graph(g, "pprhip_random_walk_batch"));
-  if ((!starts || !walk_idx || !terminals_out) && count) {
-    set_error("pprhip_random_walk_batch: null argument");
-    return PPRHIP_ERR_INVALID;
-  }
-  if (stream >= 65536) {
-    set_error("pprhip_random_walk_batch: stream must be < 65536");
-    return PPRHIP_ERR_INVALID;
-  }
-  for (uint64_t i = 0; i < count; ++i) PPRHIP_TRY(check_node(g, starts[i], "pprhip_random_walk_batch"));
-  if (count == 0) return PPRHIP_OK;
-  int32_t *d_s = nullptr, *d_t = nullptr;
-  uint64_t* d_i = nullptr;
-  uint32_t* d_n = nullptr;
-  auto done = [&](int code) {
-    (void)hipFree(d_s); (void)hipFree(d_t); (void)hipFree(d_i); (void)hipFree(d_n);
-    return code;
-  };
-  int rc = PPRHIP_OK;
-  if ((rc = alloc_dev((void**)&d_s, sizeof(int32_t) * count)) || (rc = alloc_dev((void**)&d_t, sizeof(int32_t) * count)) ||
-      (rc = alloc_dev((void**)&d_i, sizeof(uint64_t) * count)) || (rc = alloc_dev((void**)&d_n, sizeof(uint32_t) * count)))
-    return done(rc);
-  std::vector<int32_t> mapped(count);
-  for (uint64_t i = 0; i < count; ++i) mapped[i] = g->gr->h_old2new[starts[i]];
-  if (hipMemcpy(d_s, mapped.data(), sizeof(int32_t) * count, hipMemcpyHostToDevice) != hipSuccess ||
-      hipMemcpyAsync(d_i, walk_idx, sizeof(uint64_t) * count, hipMemcpyHostToDevice, g->stream) != hipSuccess) {
-    set_error("pprhip_random_walk_batch: upload failed");
-    return done(PPRHIP_ERR_HIP);
-  }
-  rc = launch_walk_batch(g, d_s, d_i, count, alpha, seed, stream, no_zero_hop, d_t, d_n);
-  if (rc) return done(rc);
-  if (hipMemcpyAsync(terminals_out, d_t, sizeof(int32_t) * count, hipMemcpyDeviceToHost, g->stream) != hipSuccess ||
-      (steps_out &&
-       hipMemcpyAsync(steps_out, d_n, sizeof(uint32_t) * count, hipMemcpyDeviceToHost, g->stream) != hipSuccess) ||
-      hipStreamSynchronize(g->stream) != hipSuccess) {
-    set_error("pprhip_random_walk_batch: download failed: %s", hipGetErrorString(hipGetLastError()));
-    return done(PPRHIP_ERR_HIP);
-  }
-  for (uint64_t i = 0; i < count; ++i) terminals_out[i] = g->gr->h_new2old[terminals_out[i]];
-  return done(PPRHIP_OK);
 }
 
 // ------------------------------------------------------------------ top-k select (a7)

@@ -1,11 +1,12 @@
 // engine_internal.hpp — declarations shared by the engine's translation units (engine.cpp: single-query
-// entry points; graph.cpp: graph lifecycle and workspaces; levels.cpp: level loop; select.cpp: top-k selection;
+// entry points and the parameter checks; forward_calls.cpp: the forward push, walk-batch and weighted FORA calls;
+// graph.cpp: graph lifecycle and workspaces; levels.cpp: level loop; select.cpp: top-k selection;
 // device_io.cpp: read-backs, scopes, walk launchers; fora.cpp: resumable FORA / top-k runs; bwd_runs.cpp: the resumable
 // runs that push backward; sweep.cpp: sweep cut; sparse.cpp: sparse getters;
 // batch.cpp, batch_api.cpp, fetch_pipe.cpp, stream.cpp: the batched entry points; allpair.cpp:
 // All-Pair-Backward-Search; index.cpp: its inverted index; pairs.cpp, targets.cpp: single pairs and single targets;
-// weighted.cpp: relationship weights and the weighted calls; weighted_bwd.cpp: their backward direction;
-// weighted_query.cpp: weighted seed sets and top-k rounds).
+// weighted.cpp: relationship weights, the weighted level loop and power method; weighted_bwd.cpp: the backward
+// direction over the weights; weighted_query.cpp: the weighted top-k rounds).
 #pragma once
 
 #include <sys/mman.h>
@@ -327,12 +328,16 @@ int select_topk(pprhip_graph* g, const double* x, int k, int32_t* ids_out, doubl
 // ---- engine.cpp
 int copy_out(pprhip_graph* g, const double* dev, double* host);
 int check_graph(const pprhip_graph* g, const char* fn);
-int check_node(const pprhip_graph* g, int32_t v, const char* fn);
+inline bool node_in_range(const pprhip_graph* g, int32_t v) { return v >= 0 && (uint32_t)v < g->gr->n; }
+int check_node(const pprhip_graph* g, int32_t v, const char* fn);  // PPRHIP_ERR_INVALID unless node_in_range
 // parameter ranges (include/pprhip.h): alpha in (0, 1); eps, delta, pfail finite and > 0; thresholds finite and >= 0
 int check_alpha(double alpha, const char* fn, const char* name = "alpha");
 int check_positive(double v, const char* fn, const char* name);
 int check_threshold(double v, const char* fn, const char* name);
 int check_conf(const pprhip_fora_conf_t* c, const char* fn, bool topk);
+// what every FORA top-k entry point asks of its conf, eps and output row (the message, "fn: bad arguments", is set)
+bool topk_args_ok(const pprhip_fora_conf_t* conf, double eps, int cap, const int32_t* ids_out, const double* vals_out,
+                  const char* fn);
 // q sets described like a CSR: offsets[0] = 0, ascending, no set of more than INT32_MAX members (the message names the set)
 int check_set_offsets(const uint64_t* offsets, int q, const char* fn);
 // a batched call's result store (NULL: none) belongs to the call's graph and holds its q queries
@@ -620,6 +625,7 @@ int seed_plan_sets(pprhip_graph* g, const int32_t* seeds, const double* weights,
                    double alpha, const char* fn, std::vector<SeedTable>& plans);
 int seed_upload(pprhip_graph* g, SeedTable& plan);  // plan -> g->seeds (HBM; allocated on first use, grown)
 int seed_start(pprhip_graph* g, LevelCtx& L);       // r = p resolved, the live seeds as L's frontier
+int seed_start(pprhip_graph* g, WLevels& L);        // ... of a weighted push
 void seed_free(pprhip_graph* g);
 // the push levels of the calling query land dead-end mass on the seed table while the scope lasts
 struct SeedScope {

@@ -557,15 +557,6 @@ int pprhip_fora_seeds(pprhip_graph_t* g, const int32_t* seeds, const double* wei
 }
 
 // ------------------------------------------------------------------ FORA top-k (a6)
-static bool fora_topk_args_ok(const pprhip_fora_conf_t* conf, double eps, int cap, const int32_t* ids_out,
-                              const double* vals_out, const char* fn) {
-  if (!conf || conf->k < 1 || !(eps > 0.0) || cap < 0 || (cap > 0 && (!ids_out || !vals_out))) {
-    set_error("%s: bad arguments", fn);
-    return false;
-  }
-  return true;
-}
-
 // Fora_Topk.computeTopKPPR for one query, without yielding, on the run topk_begin* has just started.  A round's walks
 // and selection do not touch what the next round's push works on (residue, reserve, frontier lists, parked flags: the
 // plan has read the residues and the estimate is a copy of the reserve by then), and the next threshold is known
@@ -622,7 +613,7 @@ int pprhip_fora_topk(pprhip_graph_t* g, int32_t src, double eps, const pprhip_fo
   PPRHIP_TRY(check_conf(conf, "pprhip_fora_topk", true));
   PPRHIP_TRY(check_graph(g, "pprhip_fora_topk"));
   PPRHIP_TRY(check_node(g, src, "pprhip_fora_topk"));
-  if (!fora_topk_args_ok(conf, eps, cap, ids_out, vals_out, "pprhip_fora_topk")) return PPRHIP_ERR_INVALID;
+  if (!topk_args_ok(conf, eps, cap, ids_out, vals_out, "pprhip_fora_topk")) return PPRHIP_ERR_INVALID;
   ForaRun r;
   PPRHIP_TRY(topk_begin(r, g, g->gr->h_old2new[src], eps, conf, seed, ids_out, vals_out, cap));
   return fora_topk_drive(r, n_out, reserve_out, stats);
@@ -636,7 +627,7 @@ int pprhip_fora_topk_seeds(pprhip_graph_t* g, const int32_t* seeds, const double
   PPRHIP_TRY(check_positive(eps, fn, "eps"));
   PPRHIP_TRY(check_conf(conf, fn, true));
   PPRHIP_TRY(check_graph(g, fn));
-  if (!fora_topk_args_ok(conf, eps, cap, ids_out, vals_out, fn)) return PPRHIP_ERR_INVALID;
+  if (!topk_args_ok(conf, eps, cap, ids_out, vals_out, fn)) return PPRHIP_ERR_INVALID;
   SeedTable plan;
   PPRHIP_TRY(seed_plan(g, seeds, weights, n_seeds, conf->alpha, fn, plan));
   ForaRun r;

@@ -1,7 +1,7 @@
 // seeds.cpp — queries personalized to a weighted node set (Neo4j PageRank's sourceNodes, which the reference only ever
 // passes one node: Neo4j_Method.java:73-77): the caller's arrays normalized into p, p resolved for the dead-end seeds,
-// the seed table in HBM, and the forward push from p (FORA: fora.cpp, top-k: engine.cpp).  DESIGN.md §2 "Seed sets"
-// states the rule.
+// the seed table in HBM, and the first frontier of a push from p (the forward push calls: forward_calls.cpp, FORA:
+// fora.cpp, top-k: engine.cpp, the weighted top-k rounds: weighted_query.cpp).  DESIGN.md §2 "Seed sets" states the rule.
 #include <algorithm>
 #include <cstdint>
 #include <cstring>
@@ -145,15 +145,23 @@ int seed_upload(pprhip_graph* g, SeedTable& plan) {
   return PPRHIP_OK;
 }
 
-int seed_start(pprhip_graph* g, LevelCtx& L) {
+// r = q on the live seeds, reserve = e on the dead-end seeds (p itself when no seed is live), the live seeds - they pop
+// unconditionally - as the list fbuf
+static int seed_frontier(pprhip_graph* g, int fbuf, uint32_t* nf, uint64_t* ef) {
   const SeedTable& t = *g->seeds;
-  if (t.n_live + t.n_dead) PPRHIP_TRY(launch_seed_init(g, L.fcur));
-  L.nf = t.n_live;
-  L.ef = t.e_live;
-  L.dense_prepared = false;
-  L.gs_dirty = false;
+  if (t.n_live + t.n_dead) PPRHIP_TRY(launch_seed_init(g, fbuf));
+  *nf = t.n_live;
+  *ef = t.e_live;
   return PPRHIP_OK;
 }
+
+int seed_start(pprhip_graph* g, LevelCtx& L) {
+  L.dense_prepared = false;
+  L.gs_dirty = false;
+  return seed_frontier(g, L.fcur, &L.nf, &L.ef);
+}
+
+int seed_start(pprhip_graph* g, WLevels& L) { return seed_frontier(g, L.fcur, &L.nf, &L.ef); }
 
 void seed_free(pprhip_graph* g) {
   if (!g->seeds) return;
@@ -168,52 +176,12 @@ void seed_free(pprhip_graph* g) {
 }  // namespace detail
 }  // namespace pprhip
 
+#ifdef PPRHIP_TEST_HOOKS
 using namespace pprhip;
 using namespace pprhip::detail;
 
 extern "C" {
 
-int pprhip_forward_push_seeds(pprhip_graph_t* g, const int32_t* seeds, const double* weights, int n_seeds,
-                              double alpha, double rmax, double* reserve_out, double* residue_out, double* rsum_out,
-                              pprhip_stats_t* stats) {
-  static const char* fn = "pprhip_forward_push_seeds";
-  PPRHIP_TRY(check_alpha(alpha, fn));
-  PPRHIP_TRY(check_threshold(rmax, fn, "rmax"));
-  PPRHIP_TRY(check_graph(g, fn));
-  SeedTable plan;
-  PPRHIP_TRY(seed_plan(g, seeds, weights, n_seeds, alpha, fn, plan));
-  pprhip_stats_t st;
-  std::memset(&st, 0, sizeof st);
-  g->topk_active = false;
-  PPRHIP_TRY(reset_query_state(g, false, plan.max_id));
-  PPRHIP_TRY(seed_upload(g, plan));
-  CallTimer tm(g);
-  double rsum = 0.0;
-  {
-    SeedScope scope(g);
-    PushArgs a{alpha, rmax, 0.0, -1, kFwdWhole};
-    LevelCtx L;
-    PPRHIP_TRY(seed_start(g, L));
-    if (L.nf) {
-      PPRHIP_TRY(run_levels(g, a, L, st, nullptr));
-      PPRHIP_TRY(device_sum(g, g->residue, &rsum));
-      PPRHIP_TRY(read_dead_pops(g, st));
-    }
-  }
-  tm.mark(1);
-  tm.finish(st);
-  st.push_ms = CallTimer::ms(g->ev[0], g->ev[1]);
-  st.rsum = rsum;
-  st.rmax_final = rmax;
-  st.rounds = 1;
-  if (rsum_out) *rsum_out = rsum;
-  PPRHIP_TRY(copy_out(g, g->reserve, reserve_out));
-  PPRHIP_TRY(copy_out(g, g->residue, residue_out));
-  if (stats) *stats = st;
-  return PPRHIP_OK;
-}
-
-#ifdef PPRHIP_TEST_HOOKS
 // Test hook (libpprhip_hooks.so only): the parser behind the seed sets and behind the target sets of pprhip_ppr_targets,
 // without a device, as `fn` would call it: `noun` "seed" or "target", the weights divided by their sum (normalize != 0)
 // or as given.  ids_out / w_out hold `count` entries; *count_out receives the distinct ids of non-zero weight.
@@ -236,6 +204,6 @@ int pprhip_hook_seed_normalize(uint32_t n, const int32_t* seeds, const double* w
   return pprhip_hook_parse_weighted_set(n, seeds, weights, n_seeds, 1, "seed", "pprhip_hook_seed_normalize", ids_out,
                                         p_out, count_out);
 }
-#endif
 
 }  // extern "C"
+#endif

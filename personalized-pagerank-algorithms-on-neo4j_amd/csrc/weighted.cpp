@@ -1,9 +1,9 @@
 // weighted.cpp — weighted relationships (include/pprhip.h "weighted relationships"): the weights on the
-// lifted graph (validation, the prefix rule, the in-row copy), and the four calls that run over P(u, v) = w / W(u) -
-// power method, forward push, walks, FORA - as a small driver of their own over kernels_weighted.hip.  The level loop
-// is plain frontier-synchronous Jacobi: one level per host round trip, sparse or dense by the handle's dense_frac,
-// no Gauss-Seidel blocks, no level batches, no cost model.  Everything the unweighted engine offers around a query is
-// reused as it is: the workspace and its reset, the list builders, the sums, the walk plan, the getters.
+// lifted graph (validation, the prefix rule, the in-row copy), the level loop of every push over P(u, v) = w / W(u),
+// and the weighted power method, over kernels_weighted.hip.  The level loop is plain frontier-synchronous Jacobi: one
+// level per host round trip, sparse or dense by the handle's dense_frac, no Gauss-Seidel blocks, no level batches, no
+// cost model.  The weighted forward push, walk-batch and FORA calls are in forward_calls.cpp, the weighted top-k rounds
+// in weighted_query.cpp, the backward direction in weighted_bwd.cpp.
 #include <algorithm>
 #include <cmath>
 #include <cstring>
@@ -50,20 +50,6 @@ int weight_table(uint32_t n, uint64_t m, const uint32_t* rp, const double* w, do
 }
 
 size_t padded_in_edges(uint64_t m) { return ((size_t)m + kChunkPad - 1) / kChunkPad * kChunkPad + kChunkPad; }  // as in_ci
-
-// one weighted push from src (internal id) at rmax, run to its end, on a workspace just reset; *rsum: the residue sum
-int weighted_push(pprhip_graph* g, int32_t src, double alpha, double rmax, pprhip_stats_t& st, double* rsum) {
-  *rsum = 0.0;
-  if (hdeg_out(g, src) == 0) return launch_set_f64(g, g->reserve, (uint32_t)src, 1.0);  // as the unweighted push
-  const PushArgs a{alpha, rmax, 0.0, src, kFwdWhole};
-  WLevels L;
-  PPRHIP_TRY(launch_set_f64(g, g->residue, (uint32_t)src, 1.0));
-  PPRHIP_TRY(launch_seed_one(g, L.fcur, src));  // the source is pushed unconditionally first
-  L.nf = 1;
-  L.ef = hdeg_out(g, src);
-  PPRHIP_TRY(run_weighted_levels(g, a, L, st));
-  return device_sum(g, g->residue, rsum);
-}
 
 }  // namespace
 
@@ -314,36 +300,6 @@ int pprhip_weights_info(const pprhip_graph_t* g, int* present, uint64_t* bytes) 
   return PPRHIP_OK;
 }
 
-int pprhip_weighted_forward_push(pprhip_graph_t* g, int32_t src, double alpha, double rmax, double* reserve_out,
-                                 double* residue_out, double* rsum_out, pprhip_stats_t* stats) {
-  const char* fn = "pprhip_weighted_forward_push";
-  PPRHIP_TRY(check_alpha(alpha, fn));
-  PPRHIP_TRY(check_threshold(rmax, fn, "rmax"));
-  PPRHIP_TRY(check_graph(g, fn));
-  PPRHIP_TRY(need_weights(g, fn));
-  PPRHIP_TRY(check_node(g, src, fn));
-  src = g->gr->h_old2new[src];  // internal id
-  pprhip_stats_t st;
-  std::memset(&st, 0, sizeof st);
-  g->topk_active = false;
-  PPRHIP_TRY(reset_query_state(g, false, src));
-  CallTimer tm(g);
-  double rsum = 0.0;
-  PPRHIP_TRY(weighted_push(g, src, alpha, rmax, st, &rsum));
-  PPRHIP_TRY(read_dead_pops(g, st));
-  tm.mark(1);
-  tm.finish(st);
-  st.push_ms = CallTimer::ms(g->ev[0], g->ev[1]);
-  st.rsum = rsum;
-  st.rmax_final = rmax;
-  st.rounds = 1;
-  if (rsum_out) *rsum_out = rsum;
-  PPRHIP_TRY(copy_out(g, g->reserve, reserve_out));
-  PPRHIP_TRY(copy_out(g, g->residue, residue_out));
-  if (stats) *stats = st;
-  return PPRHIP_OK;
-}
-
 int pprhip_weighted_power_method(pprhip_graph_t* g, int32_t src, double alpha, int iters, double* reserve_out,
                                  pprhip_stats_t* stats) {
   const char* fn = "pprhip_weighted_power_method";
@@ -391,103 +347,6 @@ int pprhip_weighted_power_method(pprhip_graph_t* g, int32_t src, double alpha, i
   tm.finish(st);
   st.push_ms = CallTimer::ms(g->ev[0], g->ev[1]);
   st.rounds = (uint32_t)iters;
-  PPRHIP_TRY(copy_out(g, g->reserve, reserve_out));
-  if (stats) *stats = st;
-  return PPRHIP_OK;
-}
-
-int pprhip_weighted_random_walk_batch(pprhip_graph_t* g, const int32_t* starts, const uint64_t* walk_idx, uint64_t count,
-                                      double alpha, uint64_t seed, uint32_t stream, int no_zero_hop, int32_t* terminals_out,
-                                      uint32_t* steps_out) {
-  const char* fn = "pprhip_weighted_random_walk_batch";
-  PPRHIP_TRY(check_alpha(alpha, fn));
-  PPRHIP_TRY(check_graph(g, fn));
-  PPRHIP_TRY(need_weights(g, fn));
-  if ((!starts || !walk_idx || !terminals_out) && count) {
-    set_error("%s: null argument", fn);
-    return PPRHIP_ERR_INVALID;
-  }
-  if (stream >= 65536) {
-    set_error("%s: stream must be < 65536", fn);
-    return PPRHIP_ERR_INVALID;
-  }
-  for (uint64_t i = 0; i < count; ++i) PPRHIP_TRY(check_node(g, starts[i], fn));
-  if (count == 0) return PPRHIP_OK;
-  int32_t *d_s = nullptr, *d_t = nullptr;
-  uint64_t* d_i = nullptr;
-  uint32_t* d_n = nullptr;
-  auto done = [&](int code) {
-    (void)hipFree(d_s); (void)hipFree(d_t); (void)hipFree(d_i); (void)hipFree(d_n);
-    return code;
-  };
-  int rc = PPRHIP_OK;
-  if ((rc = alloc_dev((void**)&d_s, sizeof(int32_t) * count)) || (rc = alloc_dev((void**)&d_t, sizeof(int32_t) * count)) ||
-      (rc = alloc_dev((void**)&d_i, sizeof(uint64_t) * count)) || (rc = alloc_dev((void**)&d_n, sizeof(uint32_t) * count)))
-    return done(rc);
-  std::vector<int32_t> mapped(count);
-  for (uint64_t i = 0; i < count; ++i) mapped[i] = g->gr->h_old2new[starts[i]];
-  if (hipMemcpy(d_s, mapped.data(), sizeof(int32_t) * count, hipMemcpyHostToDevice) != hipSuccess ||
-      hipMemcpy(d_i, walk_idx, sizeof(uint64_t) * count, hipMemcpyHostToDevice) != hipSuccess) {
-    set_error("%s: upload failed", fn);
-    return done(PPRHIP_ERR_HIP);
-  }
-  rc = launch_w_walk_batch(g, d_s, d_i, count, alpha, seed, stream, no_zero_hop, d_t, d_n);
-  if (rc) return done(rc);
-  if (hipStreamSynchronize(g->stream) != hipSuccess ||
-      hipMemcpy(terminals_out, d_t, sizeof(int32_t) * count, hipMemcpyDeviceToHost) != hipSuccess ||
-      (steps_out && hipMemcpy(steps_out, d_n, sizeof(uint32_t) * count, hipMemcpyDeviceToHost) != hipSuccess)) {
-    set_error("%s: download failed: %s", fn, hipGetErrorString(hipGetLastError()));
-    return done(PPRHIP_ERR_HIP);
-  }
-  for (uint64_t i = 0; i < count; ++i) terminals_out[i] = g->gr->h_new2old[terminals_out[i]];
-  return done(PPRHIP_OK);
-}
-
-int pprhip_weighted_fora(pprhip_graph_t* g, int32_t src, double eps, const pprhip_fora_conf_t* conf, uint64_t seed,
-                         double rmax, double* reserve_out, pprhip_stats_t* stats) {
-  const char* fn = "pprhip_weighted_fora";
-  PPRHIP_TRY(check_positive(eps, fn, "eps"));
-  PPRHIP_TRY(check_conf(conf, fn, false));
-  PPRHIP_TRY(check_threshold(rmax, fn, "rmax"));
-  if (!conf) {
-    set_error("%s: null conf", fn);
-    return PPRHIP_ERR_INVALID;
-  }
-  PPRHIP_TRY(check_graph(g, fn));
-  PPRHIP_TRY(need_weights(g, fn));
-  PPRHIP_TRY(check_node(g, src, fn));
-  src = g->gr->h_old2new[src];  // internal id
-  double rmax0 = 0.0, omega = 0.0;
-  PPRHIP_TRY(pprhip_fora_whole_params(conf, eps, &rmax0, &omega));
-  if (rmax == 0.0) rmax = rmax0;
-  const double alpha = conf->alpha;
-  pprhip_stats_t st;
-  std::memset(&st, 0, sizeof st);
-  g->topk_active = false;
-  PPRHIP_TRY(reset_query_state(g, false, src));
-  CallTimer tm(g);
-  double sum = 0.0;
-  PPRHIP_TRY(weighted_push(g, src, alpha, rmax, st, &sum));
-  tm.mark(1);
-  const double rsum = sum * (1 - alpha);
-  if (hdeg_out(g, src) != 0) {
-    // the walk plan of the unweighted whole-graph FORA, unchanged (k_mc_plan<0>); the walks are weighted
-    const double nrw_d = omega * rsum;
-    const long long nrw = (nrw_d == nrw_d && nrw_d > 0.0) ? (long long)nrw_d : 0;
-    PPRHIP_TRY(launch_walk_plan(g, 0, alpha, rsum, nrw, g->reserve, 0.0));
-    ktimer().begin(PPRHIP_KERNEL_WALK, 0);
-    PPRHIP_TRY(launch_w_walk_run(g, alpha, seed, g->reserve, 0u, true));
-    ktimer().end();
-  }
-  tm.mark(2);
-  PPRHIP_TRY(read_dead_pops(g, st));
-  st.rounds = 1;
-  st.rsum = rsum;
-  st.rmax_final = rmax;
-  st.omega = omega;
-  tm.finish(st);
-  st.push_ms = CallTimer::ms(g->ev[0], g->ev[1]);
-  st.mc_ms = CallTimer::ms(g->ev[1], g->ev[2]);
   PPRHIP_TRY(copy_out(g, g->reserve, reserve_out));
   if (stats) *stats = st;
   return PPRHIP_OK;

@@ -1,9 +1,9 @@
-// weighted_query.cpp — weighted seed sets and weighted FORA top-k (include/pprhip.h "weighted seed sets and top-k",
-// DESIGN.md §2): pprhip_weighted_forward_push_seeds, pprhip_weighted_fora_seeds, pprhip_weighted_fora_topk and
-// pprhip_weighted_fora_topk_seeds.  All four share one thing: a weighted push that starts from a seed table (a single
-// source is the set {s} with weight 1), lands dead-end mass on p, and can be resumed at a lower threshold.  The driver
-// is a small loop of its own over run_weighted_levels (weighted.cpp): plain rounds, no parking or arming, no push
-// ahead, no cost model.  The seed table, the walk plan, the selection and the getters are the unweighted engine's.
+// weighted_query.cpp — weighted FORA top-k (include/pprhip.h "weighted seed sets and top-k"):
+// pprhip_weighted_fora_topk and pprhip_weighted_fora_topk_seeds.  Both run one loop: a weighted push that starts from
+// a seed table (here a single source is the set {s} with weight 1), lands dead-end mass on p, and is resumed at a
+// lower threshold round after round.  The driver is a small loop of its own over run_weighted_levels (weighted.cpp):
+// plain rounds, no parking or arming, no push ahead, no cost model.  The seed table, the walk plan, the selection and
+// the getters are the unweighted engine's.  The weighted seed-set push and FORA calls are in forward_calls.cpp.
 #include <cstring>
 
 #include "run.hpp"
@@ -13,18 +13,6 @@ using namespace pprhip::detail;
 
 namespace {
 
-// The start of a seeded weighted push on a workspace just reset: r = q on the live seeds, reserve = e on the dead-end
-// seeds (p itself when no seed is live), the live seeds as the first frontier - they pop unconditionally.
-int seeded_start(pprhip_graph* g, SeedTable& plan, WLevels& L) {
-  PPRHIP_TRY(reset_query_state(g, false, plan.max_id));
-  PPRHIP_TRY(seed_upload(g, plan));
-  const SeedTable& t = *g->seeds;
-  if (t.n_live + t.n_dead) PPRHIP_TRY(launch_seed_init(g, L.fcur));
-  L.nf = t.n_live;
-  L.ef = t.e_live;
-  return PPRHIP_OK;
-}
-
 // levels at rmax from L's frontier to their end, dead-end mass landing on the seed table
 int seeded_levels(pprhip_graph* g, double alpha, double rmax, WLevels& L, pprhip_stats_t& st) {
   SeedScope scope(g);
@@ -32,18 +20,16 @@ int seeded_levels(pprhip_graph* g, double alpha, double rmax, WLevels& L, pprhip
   return run_weighted_levels(g, a, L, st);
 }
 
-// the set {src} with weight 1 as a seed plan (src: the caller's id, checked)
-int single_plan(pprhip_graph* g, int32_t src, double alpha, const char* fn, SeedTable& plan) {
-  return seed_plan(g, &src, nullptr, 1, alpha, fn, plan);
-}
-
-bool topk_args_ok(const pprhip_fora_conf_t* conf, double eps, int cap, const int32_t* ids_out, const double* vals_out,
-                  const char* fn) {
-  if (!conf || conf->k < 1 || !(eps > 0.0) || cap < 0 || (cap > 0 && (!ids_out || !vals_out))) {
-    set_error("%s: bad arguments", fn);
-    return false;
-  }
-  return true;
+// The checks of both entry points up to the start, in their order.  src: the caller's single source, checked between
+// the weights and the output row (NULL: a seed set, which the caller parses after them).
+int topk_checks(pprhip_graph* g, const int32_t* src, double eps, const pprhip_fora_conf_t* conf, int cap,
+                const int32_t* ids_out, const double* vals_out, const char* fn) {
+  PPRHIP_TRY(check_positive(eps, fn, "eps"));
+  PPRHIP_TRY(check_conf(conf, fn, true));
+  PPRHIP_TRY(check_graph(g, fn));
+  PPRHIP_TRY(need_weights(g, fn));
+  if (src) PPRHIP_TRY(check_node(g, *src, fn));
+  return topk_args_ok(conf, eps, cap, ids_out, vals_out, fn) ? PPRHIP_OK : PPRHIP_ERR_INVALID;
 }
 
 // The weighted top-k loop on delta (Fora_Topk.java's schedule: nothing in it depends on the weights) from the seed
@@ -55,8 +41,10 @@ int topk_drive(pprhip_graph* g, SeedTable& plan, double eps, const pprhip_fora_c
   pprhip_stats_t st;
   std::memset(&st, 0, sizeof st);
   g->topk_active = false;
+  PPRHIP_TRY(reset_query_state(g, false, plan.max_id));
+  PPRHIP_TRY(seed_upload(g, plan));
   WLevels L0;
-  PPRHIP_TRY(seeded_start(g, plan, L0));
+  PPRHIP_TRY(seed_start(g, L0));
   const size_t nd = sizeof(double) * (size_t)act_n(g);  // (est beyond the query's scan bound is zero and stays so)
   CallTimer tm(g);
   double push_ms = 0.0, mc_ms = 0.0, sel_ms = 0.0;
@@ -136,109 +124,13 @@ int topk_drive(pprhip_graph* g, SeedTable& plan, double eps, const pprhip_fora_c
 
 extern "C" {
 
-int pprhip_weighted_forward_push_seeds(pprhip_graph_t* g, const int32_t* seeds, const double* weights, int n_seeds,
-                                       double alpha, double rmax, double* reserve_out, double* residue_out,
-                                       double* rsum_out, pprhip_stats_t* stats) {
-  static const char* fn = "pprhip_weighted_forward_push_seeds";
-  PPRHIP_TRY(check_alpha(alpha, fn));
-  PPRHIP_TRY(check_threshold(rmax, fn, "rmax"));
-  PPRHIP_TRY(check_graph(g, fn));
-  PPRHIP_TRY(need_weights(g, fn));
-  SeedTable plan;
-  PPRHIP_TRY(seed_plan(g, seeds, weights, n_seeds, alpha, fn, plan));
-  pprhip_stats_t st;
-  std::memset(&st, 0, sizeof st);
-  g->topk_active = false;
-  WLevels L;
-  PPRHIP_TRY(seeded_start(g, plan, L));
-  CallTimer tm(g);
-  double rsum = 0.0;
-  if (L.nf) {
-    PPRHIP_TRY(seeded_levels(g, alpha, rmax, L, st));
-    PPRHIP_TRY(device_sum(g, g->residue, &rsum));
-    PPRHIP_TRY(read_dead_pops(g, st));
-  }
-  tm.mark(1);
-  tm.finish(st);
-  st.push_ms = CallTimer::ms(g->ev[0], g->ev[1]);
-  st.rsum = rsum;
-  st.rmax_final = rmax;
-  st.rounds = 1;
-  if (rsum_out) *rsum_out = rsum;
-  PPRHIP_TRY(copy_out(g, g->reserve, reserve_out));
-  PPRHIP_TRY(copy_out(g, g->residue, residue_out));
-  if (stats) *stats = st;
-  return PPRHIP_OK;
-}
-
-int pprhip_weighted_fora_seeds(pprhip_graph_t* g, const int32_t* seeds, const double* weights, int n_seeds, double eps,
-                               const pprhip_fora_conf_t* conf, uint64_t seed, double rmax, double* reserve_out,
-                               pprhip_stats_t* stats) {
-  static const char* fn = "pprhip_weighted_fora_seeds";
-  PPRHIP_TRY(check_positive(eps, fn, "eps"));
-  PPRHIP_TRY(check_conf(conf, fn, false));
-  PPRHIP_TRY(check_threshold(rmax, fn, "rmax"));
-  if (!conf) {
-    set_error("%s: null conf", fn);
-    return PPRHIP_ERR_INVALID;
-  }
-  PPRHIP_TRY(check_graph(g, fn));
-  PPRHIP_TRY(need_weights(g, fn));
-  SeedTable plan;
-  PPRHIP_TRY(seed_plan(g, seeds, weights, n_seeds, conf->alpha, fn, plan));
-  double rmax0 = 0.0, omega = 0.0;
-  PPRHIP_TRY(pprhip_fora_whole_params(conf, eps, &rmax0, &omega));
-  if (rmax == 0.0) rmax = rmax0;
-  const double alpha = conf->alpha;
-  pprhip_stats_t st;
-  std::memset(&st, 0, sizeof st);
-  g->topk_active = false;
-  WLevels L;
-  PPRHIP_TRY(seeded_start(g, plan, L));
-  CallTimer tm(g);
-  double rsum = 0.0;
-  const bool live = L.nf != 0;
-  if (live) {
-    double sum = 0.0;
-    PPRHIP_TRY(seeded_levels(g, alpha, rmax, L, st));
-    PPRHIP_TRY(device_sum(g, g->residue, &sum));
-    rsum = sum * (1 - alpha);
-  }
-  tm.mark(1);
-  if (live) {  // pprhip_weighted_fora's walk phase, unchanged
-    const double nrw_d = omega * rsum;
-    const long long nrw = (nrw_d == nrw_d && nrw_d > 0.0) ? (long long)nrw_d : 0;
-    PPRHIP_TRY(launch_walk_plan(g, 0, alpha, rsum, nrw, g->reserve, 0.0));
-    ktimer().begin(PPRHIP_KERNEL_WALK, 0);
-    PPRHIP_TRY(launch_w_walk_run(g, alpha, seed, g->reserve, 0u, true));
-    ktimer().end();
-  }
-  tm.mark(2);
-  PPRHIP_TRY(read_dead_pops(g, st));
-  st.rounds = 1;
-  st.rsum = rsum;
-  st.rmax_final = rmax;
-  st.omega = omega;
-  tm.finish(st);
-  st.push_ms = CallTimer::ms(g->ev[0], g->ev[1]);
-  st.mc_ms = CallTimer::ms(g->ev[1], g->ev[2]);
-  PPRHIP_TRY(copy_out(g, g->reserve, reserve_out));
-  if (stats) *stats = st;
-  return PPRHIP_OK;
-}
-
 int pprhip_weighted_fora_topk(pprhip_graph_t* g, int32_t src, double eps, const pprhip_fora_conf_t* conf, uint64_t seed,
                               int32_t* ids_out, double* vals_out, int cap, int* n_out, double* reserve_out,
                               pprhip_stats_t* stats) {
   static const char* fn = "pprhip_weighted_fora_topk";
-  PPRHIP_TRY(check_positive(eps, fn, "eps"));
-  PPRHIP_TRY(check_conf(conf, fn, true));
-  PPRHIP_TRY(check_graph(g, fn));
-  PPRHIP_TRY(need_weights(g, fn));
-  PPRHIP_TRY(check_node(g, src, fn));
-  if (!topk_args_ok(conf, eps, cap, ids_out, vals_out, fn)) return PPRHIP_ERR_INVALID;
+  PPRHIP_TRY(topk_checks(g, &src, eps, conf, cap, ids_out, vals_out, fn));
   SeedTable plan;
-  PPRHIP_TRY(single_plan(g, src, conf->alpha, fn, plan));
+  PPRHIP_TRY(seed_plan(g, &src, nullptr, 1, conf->alpha, fn, plan));  // the set {src} with weight 1
   return topk_drive(g, plan, eps, conf, seed, ids_out, vals_out, cap, n_out, reserve_out, stats);
 }
 
@@ -246,11 +138,7 @@ int pprhip_weighted_fora_topk_seeds(pprhip_graph_t* g, const int32_t* seeds, con
                                     double eps, const pprhip_fora_conf_t* conf, uint64_t seed, int32_t* ids_out,
                                     double* vals_out, int cap, int* n_out, double* reserve_out, pprhip_stats_t* stats) {
   static const char* fn = "pprhip_weighted_fora_topk_seeds";
-  PPRHIP_TRY(check_positive(eps, fn, "eps"));
-  PPRHIP_TRY(check_conf(conf, fn, true));
-  PPRHIP_TRY(check_graph(g, fn));
-  PPRHIP_TRY(need_weights(g, fn));
-  if (!topk_args_ok(conf, eps, cap, ids_out, vals_out, fn)) return PPRHIP_ERR_INVALID;
+  PPRHIP_TRY(topk_checks(g, nullptr, eps, conf, cap, ids_out, vals_out, fn));
   SeedTable plan;
   PPRHIP_TRY(seed_plan(g, seeds, weights, n_seeds, conf->alpha, fn, plan));
   return topk_drive(g, plan, eps, conf, seed, ids_out, vals_out, cap, n_out, reserve_out, stats);
