@@ -25,7 +25,8 @@
  * Environment.  libpprhip.so reads these six variables and no others:
  *   PPRHIP_HOST_THREADS=<n>      host threads of the graph lift and the index finalisation (default: the CPU affinity /
  *                                cgroup quota of the process, at most 64)
- *   PPRHIP_BATCH_WORKSPACES=<n>  query workspaces of the batch driver, 16-48 (default 32; 0.33 GB each at R-MAT 22)
+ *   PPRHIP_BATCH_WORKSPACES=<n>  query workspaces of the batch driver, 16-48 (default 32; 0.33 GB each at R-MAT 22);
+ *                                the batched weighted FORA calls: queries in flight, 1-16 (default 16)
  *   PPRHIP_BATCH_THREADS=0|1     batched top-k / All-Pair's third tier: one host thread per slot (default 1) or one in all
  *   PPRHIP_SHARD_CUT=count|work  target ranges of the sharded All-Pair: equal counts, or cut by measured work (default:
  *                                by work when equal counts would leave a rank more than 1.15 x the mean)
@@ -852,6 +853,34 @@ int pprhip_weighted_fora_topk(pprhip_graph_t* g, int32_t src, double eps, const 
 int pprhip_weighted_fora_topk_seeds(pprhip_graph_t* g, const int32_t* seeds, const double* weights, int n_seeds,
                                     double eps, const pprhip_fora_conf_t* conf, uint64_t seed, int32_t* ids_out,
                                     double* vals_out, int cap, int* n_out, double* reserve_out, pprhip_stats_t* stats);
+
+/* ---- batched weighted FORA ("Batched weighted FORA"): q weighted whole-graph queries in one call,
+ * up to 16 of them in flight on the handle's batch workspaces (PPRHIP_BATCH_WORKSPACES: fewer), their dense levels
+ * sharing one sweep over the interleaved contributions.  Query i runs as pprhip_weighted_fora(srcs[i], eps, conf, seed,
+ * rmax) / pprhip_weighted_fora_seeds(set i, ...) would: the same dense / sparse rule on its own frontier, the same
+ * thresholds, the same walk plan, the same walks (every query walks with the call's seed, stream 0, forced first hop),
+ * served from the weighted walk index where the single call is.  Batching changes the order of fp64 additions and
+ * nothing else.  A dead-end source runs no push and no walks (reserve = e_s), a set without a live seed neither
+ * (reserve = p).  Terminals are not shared between the queries of a call.
+ * rmax (0: rmax0 of conf and eps) as in pprhip_weighted_fora; every other argument and output means what it means in
+ * pprhip_fora_batch_single_source_resident / pprhip_fora_batch_seeds: keep (NULL: none) receives every vector,
+ * reserve_out (NULL: none) q x n doubles, k > 0 the top-k of every vector (rows padded -1 / 0, n_out[i] as there),
+ * per_query (NULL: none) q statistics as pprhip_weighted_fora fills them - levels, dense_levels, pops, dense_nodes,
+ * edge_pushes, walks, walk_steps, dead_end_pops, rsum, rmax_final, omega, rounds = 1; push_ms and mc_ms on the host's
+ * clock - and stats_sum their sums with the call's kernel classes (the sweeps are class PPRHIP_KERNEL_DENSE_PULL_BATCH).
+ * Checks, in this order, all before anything runs: the numeric parameters (pprhip_weighted_fora's), the handle,
+ * PPRHIP_ERR_STATE without weights, q / k / the top-k rows, keep, then every source / every set.  q = 0 is
+ * PPRHIP_OK with keep->count = 0.  An error on any workspace ends the call; the handle stays usable. */
+int pprhip_weighted_fora_batch(pprhip_graph_t* g, const int32_t* srcs, int q, double eps, const pprhip_fora_conf_t* conf,
+                               uint64_t seed, double rmax, pprhip_results_t* keep, double* reserve_out, int k,
+                               int32_t* ids_out, double* vals_out, int* n_out, pprhip_stats_t* per_query,
+                               pprhip_stats_t* stats_sum);
+/* ... over q seed sets described like a CSR (pprhip_fora_batch_seeds): set i = seeds / weights [offsets[i], offsets[i + 1]) */
+int pprhip_weighted_fora_batch_seeds(pprhip_graph_t* g, const int32_t* seeds, const double* weights,
+                                     const uint64_t* offsets, int q, double eps, const pprhip_fora_conf_t* conf,
+                                     uint64_t seed, double rmax, pprhip_results_t* keep, double* reserve_out, int k,
+                                     int32_t* ids_out, double* vals_out, int* n_out, pprhip_stats_t* per_query,
+                                     pprhip_stats_t* stats_sum);
 
 /* ---- weighted walk index (FORA+ for pprhip_weighted_fora and pprhip_weighted_fora_seeds; DESIGN.md section 2,
  * "Weighted walk index"): the walk index above, over the weighted walks.  Both weighted whole-graph calls plan with the

@@ -109,6 +109,7 @@ EXPORTS = [
     "pprhip_weighted_fora_topk_seeds",
     "pprhip_weighted_walk_index_build", "pprhip_weighted_walk_index_drop", "pprhip_weighted_walk_index_info",
     "pprhip_weighted_walk_index_fetch", "pprhip_weighted_walk_index_usage",
+    "pprhip_weighted_fora_batch", "pprhip_weighted_fora_batch_seeds",
 ]
 SPARSE_BY_ID, SPARSE_BY_VALUE = 0, 1  # PPRHIP_SPARSE_BY_*: the orders of the sparse getters
 RELEASE_SPARSE = 16  # PPRHIP_RELEASE_SPARSE
@@ -262,6 +263,9 @@ def lib():
     L.pprhip_weighted_fora_topk.argtypes = [vp, i32, dbl, P(ForaConf), u64, vp, vp, ci, P(ci), vp, P(Stats)]
     L.pprhip_weighted_fora_topk_seeds.argtypes = [vp, vp, vp, ci, dbl, P(ForaConf), u64, vp, vp, ci, P(ci), vp,
                                                   P(Stats)]
+    L.pprhip_weighted_fora_batch.argtypes = [vp, vp, ci, dbl, P(ForaConf), u64, dbl, vp, vp, ci, vp, vp, vp, vp, P(Stats)]
+    L.pprhip_weighted_fora_batch_seeds.argtypes = [vp, vp, vp, vp, ci, dbl, P(ForaConf), u64, dbl, vp, vp, ci, vp, vp, vp,
+                                                   vp, P(Stats)]
     L.pprhip_weighted_backward_push.argtypes = [vp, i32, dbl, dbl, vp, vp, P(Stats)]
     L.pprhip_weighted_walk_survival.argtypes = [vp, dbl, vp]
     L.pprhip_weighted_ppr_targets.argtypes = [vp, vp, vp, vp, ci, dbl, dbl, vp, vp, ci, vp, vp, vp, vp, P(Stats)]
@@ -1314,6 +1318,37 @@ class Graph:
         """weighted_fora_topk personalized to a seed set; the return shape of fora_topk_seeds."""
         return self._topk_call(lib().pprhip_weighted_fora_topk_seeds, _seed_start(seeds, weights), eps, alpha, k, seed,
                                cap, conf, fetch)
+
+    # ---- batched weighted FORA: the return tuple of fora_batch_single_source
+    def weighted_fora_batch(self, srcs, eps, alpha, seed, rmax=0.0, k=0, conf=None, fetch=False, per_query=False,
+                            keep=None, out=None):
+        """q weighted_fora queries in one call, BATCH of them in flight, their dense levels in one shared sweep
+        (pprhip_weighted_fora_batch): query i is weighted_fora(srcs[i], eps, alpha, seed, rmax).  Returns what
+        fora_batch_single_source returns."""
+        srcs = np.ascontiguousarray(srcs, dtype=np.int32)
+        q = int(srcs.size)
+        conf = conf or conf_whole_graph(self.n, self.m, alpha)
+        out, ids, vals, nsel, pq = _batch_outputs(q, self.n, k, fetch, out, per_query)
+        st = Stats()
+        _check(lib().pprhip_weighted_fora_batch(
+            self.h, _ptr(srcs), q, eps, C.byref(conf), seed, rmax, keep.h if keep is not None else None, _ptr(out), k,
+            _ptr(ids), _ptr(vals), _ptr(nsel), C.cast(pq, C.c_void_p) if pq is not None else None, C.byref(st)))
+        return out, ids, vals, nsel, (list(pq) if pq is not None else None), st
+
+    def weighted_fora_batch_seeds(self, sets, eps, alpha, seed, weights=None, rmax=0.0, k=0, conf=None, fetch=False,
+                                  per_query=False, keep=None, out=None):
+        """weighted_fora_batch over seed sets: query i is weighted_fora_seeds(sets[i], ..., weights[i]); sets and weights
+        as fora_batch_seeds takes them; the same return tuple."""
+        s, w, offsets = _seed_set_arrays(sets, weights)
+        q = int(offsets.size - 1)
+        conf = conf or conf_whole_graph(self.n, self.m, alpha)
+        out, ids, vals, nsel, pq = _batch_outputs(q, self.n, k, fetch, out, per_query)
+        st = Stats()
+        _check(lib().pprhip_weighted_fora_batch_seeds(
+            self.h, _ptr(s), _ptr(w), _ptr(offsets), q, eps, C.byref(conf), seed, rmax,
+            keep.h if keep is not None else None, _ptr(out), k, _ptr(ids), _ptr(vals), _ptr(nsel),
+            C.cast(pq, C.c_void_p) if pq is not None else None, C.byref(st)))
+        return out, ids, vals, nsel, (list(pq) if pq is not None else None), st
 
     # ---- the backward direction over the weights: the unweighted namesakes' arguments and return shapes
     def weighted_backward_push(self, target, alpha, rmax):

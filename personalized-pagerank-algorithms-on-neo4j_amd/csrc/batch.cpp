@@ -133,8 +133,9 @@ static int run_sweep(pprhip_graph* P, ForaRun* runs, const bool* active, int n_a
   return collect_sweep(P, runs, T);
 }
 
-// The vector, the selection and the per-query stats of a finished whole-graph FORA or top-k query
-static int deliver_vector(BatchJob& J, ForaRun& r) {
+// The vector, the selection and the per-query stats of a finished whole-graph FORA or top-k query (and of a query of the
+// batched weighted FORA calls, weighted_batch.cpp)
+int deliver_vector(BatchJob& J, ForaRun& r) {
   pprhip_graph* S = r.g;
   const int i = r.query;
   const bool topk = r.kind == QueryKind::kTopk;

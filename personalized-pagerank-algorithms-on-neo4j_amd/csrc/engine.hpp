@@ -967,6 +967,25 @@ int launch_wq_land_dense(pprhip_graph* g, int dead_slot);
 int launch_wq_collect(pprhip_graph* g, double rmax, int out_fbuf, unsigned long long* d_counter);
 int init_kernels_weighted_query();
 
+// ---- kernels_weighted_batch.hip (the dense level of kBatch weighted queries at once; weighted_batch.cpp drives them)
+// S: a batch slot whose column of the parent's c8 arrays is slot_index; its kernels run on S->stream.
+// launch_w_prepare with the contributions of list fbuf (nf entries) scattered into S's column of c8[c8cur] (all-zero
+// before); the list's dead-end mass goes to ctr->dead[dead_slot]
+int launch_wbat_scatter(pprhip_graph* S, const PushArgs& a, int fbuf, uint32_t nf, int dead_slot);
+// S's column of c8[c8cur] back to list form: F / eoff [out_fbuf] and cF, the column handed back all-zero;
+// *d_counter: 0 before, entries << 36 | edges after
+int launch_wbat_compact(pprhip_graph* S, int out_fbuf, unsigned long long* d_counter);
+// S leaves its column: the rows outside the sweep's rows that its query visits (src: PushArgs::src - the source without
+// in-edges, or -1: the live seeds without in-edges of S->seeds) are zeroed in both arrays
+int launch_wbat_leave(pprhip_graph* S, int32_t src);
+// one batched weighted sweep of the columns staged as active in parent->batch->h_slot_args (res, reserve, ctr, alpha,
+// rmax, src, dead_slot, out_slot, seed_w): c8[c8cur] -> c8[c8cur ^ 1], c8cur flipped; an active column's new frontier
+// counter goes to its ctr->packed[out_slot] and to sweep_out[column], its next dead-end mass to ctr->dead[dead_slot ^ 1]
+int launch_wbat_sweep(pprhip_graph* parent);
+// sweep_out[s] = *cells[s] for every non-null cell: the counters of a driver round side by side, for one read-back
+int launch_wbat_collect(pprhip_graph* parent, const unsigned long long* const* cells);
+int init_kernels_weighted_batch();
+
 // ---- kernels_weighted_bwd.hip (the backward direction over the weights; weighted_bwd.cpp drives them)
 // step 1 of a backward level that starts from the list fbuf (nf entries): every entry gives up its residue; c =
 // (1 - alpha) r goes to cF[i], or (scatter_dense) to cdense[cbuf][node].  Clears *next_counter.

@@ -6,7 +6,8 @@
 // batch.cpp, batch_api.cpp, fetch_pipe.cpp, stream.cpp: the batched entry points; allpair.cpp:
 // All-Pair-Backward-Search; index.cpp: its inverted index; pairs.cpp, targets.cpp: single pairs and single targets;
 // weighted.cpp: relationship weights, the weighted level loop and power method; weighted_bwd.cpp: the backward
-// direction over the weights; weighted_query.cpp: the weighted top-k rounds).
+// direction over the weights; weighted_query.cpp: the weighted top-k rounds; weighted_batch.cpp: the batched weighted
+// FORA calls).
 #pragma once
 
 #include <sys/mman.h>
@@ -564,6 +565,12 @@ int target_plan(pprhip_graph_t* g, const int32_t* targets, const double* weights
 
 // ---- batch.cpp
 int batch_run(pprhip_graph_t* g, BatchJob& J, pprhip_stats_t* stats_sum);
+// delivery of query r.query of J, finished on the workspace r.g with the statistics r.st: the vector into the result
+// store and / or the caller's array, the top-J.k selection, the per-query statistics
+int deliver_vector(BatchJob& J, ForaRun& r);
+
+// ---- forward_calls.cpp
+int check_weighted_fora_params(double eps, const pprhip_fora_conf_t* conf, double rmax, const char* fn);
 #ifdef PPRHIP_TEST_HOOKS
 int take_apply_counts(pprhip_graph* g, pprhip_stats_t& sum);  // batch.cpp
 #endif

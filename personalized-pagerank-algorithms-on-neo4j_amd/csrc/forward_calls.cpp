@@ -87,18 +87,6 @@ int forward_push(pprhip_graph* g, const Start& s, bool weighted, double alpha, d
   return PPRHIP_OK;
 }
 
-// The checks both weighted FORA calls run before they look at the handle.
-int check_weighted_fora_params(double eps, const pprhip_fora_conf_t* conf, double rmax, const char* fn) {
-  PPRHIP_TRY(check_positive(eps, fn, "eps"));
-  PPRHIP_TRY(check_conf(conf, fn, false));
-  PPRHIP_TRY(check_threshold(rmax, fn, "rmax"));
-  if (!conf) {
-    set_error("%s: null conf", fn);
-    return PPRHIP_ERR_INVALID;
-  }
-  return PPRHIP_OK;
-}
-
 // Both weighted whole-graph FORA calls behind their checks: one push at rmax (0: rmax0), then the walk plan of the
 // unweighted whole-graph FORA, unchanged (k_mc_plan<0>), with weighted walks - where something was pushed.
 int weighted_fora(pprhip_graph* g, const Start& s, double eps, const pprhip_fora_conf_t* conf, uint64_t seed, double rmax,
@@ -186,6 +174,18 @@ int walk_batch(pprhip_graph* g, bool weighted, const int32_t* starts, const uint
 }
 
 }  // namespace
+
+// The checks the weighted FORA calls (and their batched forms, weighted_batch.cpp) run before they look at the handle.
+int pprhip::detail::check_weighted_fora_params(double eps, const pprhip_fora_conf_t* conf, double rmax, const char* fn) {
+  PPRHIP_TRY(check_positive(eps, fn, "eps"));
+  PPRHIP_TRY(check_conf(conf, fn, false));
+  PPRHIP_TRY(check_threshold(rmax, fn, "rmax"));
+  if (!conf) {
+    set_error("%s: null conf", fn);
+    return PPRHIP_ERR_INVALID;
+  }
+  return PPRHIP_OK;
+}
 
 extern "C" {
 
