@@ -755,9 +755,9 @@ int pprhip_local_cluster_seeds(pprhip_graph_t* g, const int32_t* seeds, const do
  * FORA from one source) and backward (backward push, the survival vector, single targets / target sets, single pairs).
  * Only the pprhip_weighted_* calls read the weights.  Every entry point without that prefix ignores them - the
  * unweighted pprhip_backward_push, pprhip_ppr_targets and pprhip_ppr_pairs included - and so do the features that have
- * no weighted form yet: the batched FORA calls and streams, All-Pair, the sweep cut (which ranks by the
- * relationship count, not by weighted degree), the multi-GPU calls; they give what they gave before
- * pprhip_graph_set_weights.
+ * no weighted form: the query streams and the multi-GPU calls; they give what they gave before
+ * pprhip_graph_set_weights.  pprhip_sweep_cut ranks by the relationship count whatever the weights are; the sweep by
+ * weighted degree is pprhip_weighted_sweep_cut ("weighted local clustering" below).
  *
  * Weights: m doubles aligned with the out_col_idx given to pprhip_graph_create, every one finite and > 0 (a caller
  * drops relationships of weight <= 0 before the lift, so dead ends are exactly the unweighted dead ends), every row sum
@@ -967,6 +967,67 @@ int pprhip_weighted_ppr_pairs(pprhip_graph_t* g, const int32_t* sources, const i
  * pprhip_index_merge shard by hand), the ppr command line and the JNI binding. */
 int pprhip_weighted_all_pair_backward(pprhip_graph_t* g, double alpha, double threshold, int k, uint32_t t_begin,
                                       uint32_t t_end, pprhip_index_t** index_out, pprhip_stats_t* stats);
+
+/* ---- weighted local clustering ("Weighted sweep cut"): the sweep cut by relationship weight,
+ * PageRank-Nibble on the weighted graph.  The graph is read as pprhip_sweep_cut reads it - undirected, a node's
+ * adjacency its out-row followed by its in-row, every relationship once, parallel relationships each, a self loop never
+ * cuts and adds its weight twice to the degree - and the order of the steps, the outputs and `cap` are that call's.
+ * Quanta: the weights enter as integers in fixed point, so that every sum is a 64-bit integer and the result the same
+ * words every run (sums of fp64 weights depend on the order of addition).  With wmax the largest of the m weights,
+ * e the exponent of frexp(wmax) (wmax = f 2^e, 0.5 <= f < 1) and L the smallest integer with m <= 2^L, the shift is
+ * s = 61 - e - L and the quantum of relationship e is q(e) = max(1, llrint(ldexp(w(e), s))), rounded to nearest, ties to
+ * even: a weight below half a quantum counts as one quantum, no relationship vanishes.  q(e) <= 2^(61 - L), the sum of
+ * all q <= 2^61, the total volume <= 2^62.  One weight unit is 2^s quanta.  The rule depends on wmax and m only.
+ * pprhip_weight_quantum gives s for a weight array as a pure host function, with the validation of
+ * pprhip_weight_table_host (a weight that is not finite and > 0 is PPRHIP_ERR_INVALID, the message names the edge);
+ * weights may be NULL when m == 0, and s = 0 then.
+ *   qdeg(v) = the sum of q over v's out-row plus its in-row; vol_q(S) = sum of qdeg over S; total_vol_q = 2 sum q;
+ *   cut_q(S) = the sum of q over relationships (a -> b), a != b, with exactly one endpoint in S;
+ *   phi(S) = (double)cut_q / (double)min(vol_q, total_vol_q - vol_q): two conversions uint64 -> fp64 to nearest and one
+ *   division; a prefix whose denominator is 0 is not a candidate.
+ * Node v is ranked when x(v) > 0 and it has at least one adjacency slot (then qdeg(v) >= 1).  Score: x(v) /
+ * (double)qdeg(v) with normalize = 1, x(v) with normalize = 0; order: score descending, ties by original id ascending.
+ * max_size as in pprhip_sweep_cut.  max_vol is a double in weight units, finite and >= 0, 0: no bound; a prefix is
+ * admitted when vol_q <= min(2^63 - 1, floor(ldexp(max_vol, s))), a limit formed on the host.  Best prefix: the
+ * smallest phi, ties to the shortest; without a candidate best_size = best_cut_q = best_vol_q = 0, best_conductance =
+ * +inf.  The input is whatever result vector is in HBM, whichever call put it there; it is not modified.
+ * Checks, in this order: normalize outside {0, 1}, a null info, a buffer with cap == 0, a max_vol that is negative, NaN
+ * or infinite (the one-call form: then alpha and rmax) are PPRHIP_ERR_INVALID before the handle is looked at, the
+ * message naming the entry point and the parameter; then the handle (an open query stream: PPRHIP_ERR_STATE); then
+ * PPRHIP_ERR_STATE when the handle has no weights.
+ * Memory: qdeg (8 n bytes), s and total_vol_q are built by the first weighted sweep after pprhip_graph_set_weights (one
+ * pass over the 16 m bytes of the two weight arrays) and kept beside the weights: pprhip_weights_info counts the 8 n
+ * bytes while they exist; pprhip_graph_set_weights (also with NULL), PPRHIP_RELEASE_WEIGHTS and pprhip_graph_destroy
+ * free them.  The sweep workspace of pprhip_sweep_cut is shared; the first weighted sweep adds 8 (n + 1) bytes to it
+ * (the volume in quanta), freed with it by PPRHIP_RELEASE_SWEEP and pprhip_graph_destroy.  Weighted and unweighted sweeps
+ * may be interleaved on one handle; a handle that never runs a weighted sweep pays nothing. */
+typedef struct pprhip_wsweep {
+  uint64_t support;      /* ranked nodes */
+  uint64_t profiled;     /* prefixes whose vol_q / cut_q were computed (== support unless cut short by max_size) */
+  uint64_t best_size, best_cut_q, best_vol_q;  /* the best prefix, cut and volume in quanta */
+  double best_conductance;
+  uint64_t total_vol_q;  /* 2 sum q */
+  int32_t shift;         /* s: one weight unit is 2^s quanta */
+  int32_t reserved;
+  uint64_t edge_slots;   /* adjacency entries scanned (the count, as in pprhip_sweep_t) */
+  double sort_ms, scan_ms, total_ms;  /* as in pprhip_sweep_t; the one-off build of qdeg lies before total_ms begins */
+} pprhip_wsweep_t;
+
+int pprhip_weight_quantum(uint64_t m, const double* weights, int* shift_out);
+/* over the vector pprhip_get_reserve would return; order_out / vol_q_out / cut_q_out and cap as in pprhip_sweep_cut */
+int pprhip_weighted_sweep_cut(pprhip_graph_t* g, int normalize, uint64_t max_size, double max_vol, int32_t* order_out,
+                              uint64_t* vol_q_out, uint64_t* cut_q_out, uint64_t cap, pprhip_wsweep_t* info);
+/* the same over vector i of a device-resident store */
+int pprhip_results_weighted_sweep_cut(pprhip_results_t* r, int i, int normalize, uint64_t max_size, double max_vol,
+                                      int32_t* order_out, uint64_t* vol_q_out, uint64_t* cut_q_out, uint64_t cap,
+                                      pprhip_wsweep_t* info);
+/* pprhip_weighted_forward_push_seeds(seeds, weights, alpha, rmax) with its outputs left in HBM, then the weighted sweep:
+ * the counterpart of pprhip_local_cluster_seeds.  members_out: the first min(cap, best_size) nodes of the order.  alpha,
+ * rmax and the seed set follow that call's rules (a bad set leaves the handle untouched); push_stats may be NULL. */
+int pprhip_weighted_local_cluster_seeds(pprhip_graph_t* g, const int32_t* seeds, const double* weights, int n_seeds,
+                                        double alpha, double rmax, int normalize, uint64_t max_size, double max_vol,
+                                        int32_t* members_out, uint64_t cap, pprhip_wsweep_t* info,
+                                        pprhip_stats_t* push_stats);
 
 /* ---------------------------------------------------------------- ground truth (a12) */
 /* Power_Method.computeWholeGraphPPR (Power_Method.java:44-101): `iters` synchronous sweeps. */

@@ -60,6 +60,17 @@ class Sweep(C.Structure):
         return {k: getattr(self, k) for k, _ in self._fields_}
 
 
+class WeightedSweep(C.Structure):
+    """pprhip_wsweep_t: what a weighted sweep cut found; cut and volume in quanta, one weight unit being 2**shift quanta."""
+    _fields_ = [("support", C.c_uint64), ("profiled", C.c_uint64), ("best_size", C.c_uint64),
+                ("best_cut_q", C.c_uint64), ("best_vol_q", C.c_uint64), ("best_conductance", C.c_double),
+                ("total_vol_q", C.c_uint64), ("shift", C.c_int32), ("reserved", C.c_int32), ("edge_slots", C.c_uint64),
+                ("sort_ms", C.c_double), ("scan_ms", C.c_double), ("total_ms", C.c_double)]
+
+    def as_dict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_ if k != "reserved"}
+
+
 class Tuning(C.Structure):
     _fields_ = [("c_walk_ns", C.c_double), ("c_edge_ns", C.c_double), ("c_pop_ns", C.c_double),
                 ("c_level_ns", C.c_double), ("c_dense_edge_ns", C.c_double), ("c_dense_node_ns", C.c_double),
@@ -110,6 +121,8 @@ EXPORTS = [
     "pprhip_weighted_walk_index_build", "pprhip_weighted_walk_index_drop", "pprhip_weighted_walk_index_info",
     "pprhip_weighted_walk_index_fetch", "pprhip_weighted_walk_index_usage",
     "pprhip_weighted_fora_batch", "pprhip_weighted_fora_batch_seeds",
+    "pprhip_weight_quantum", "pprhip_weighted_sweep_cut", "pprhip_results_weighted_sweep_cut",
+    "pprhip_weighted_local_cluster_seeds",
 ]
 SPARSE_BY_ID, SPARSE_BY_VALUE = 0, 1  # PPRHIP_SPARSE_BY_*: the orders of the sparse getters
 RELEASE_SPARSE = 16  # PPRHIP_RELEASE_SPARSE
@@ -270,6 +283,11 @@ def lib():
     L.pprhip_weighted_walk_survival.argtypes = [vp, dbl, vp]
     L.pprhip_weighted_ppr_targets.argtypes = [vp, vp, vp, vp, ci, dbl, dbl, vp, vp, ci, vp, vp, vp, vp, P(Stats)]
     L.pprhip_weighted_ppr_pairs.argtypes = [vp, vp, vp, ci, dbl, P(ForaConf), dbl, u64, vp, P(Stats)]
+    L.pprhip_weight_quantum.argtypes = [u64, vp, P(ci)]
+    L.pprhip_weighted_sweep_cut.argtypes = [vp, ci, u64, dbl, vp, vp, vp, u64, P(WeightedSweep)]
+    L.pprhip_results_weighted_sweep_cut.argtypes = [vp, ci, ci, u64, dbl, vp, vp, vp, u64, P(WeightedSweep)]
+    L.pprhip_weighted_local_cluster_seeds.argtypes = [vp, vp, vp, ci, dbl, dbl, ci, u64, dbl, vp, u64, P(WeightedSweep),
+                                                      P(Stats)]
     _lib = L
     # the destroy entry points, reachable from destructors that run while the interpreter shuts down (the name `lib`
     # may already be None then: "TypeError: 'NoneType' object is not callable" out of Index.__del__, round 3)
@@ -341,14 +359,14 @@ def _seed_set_arrays(sets, weights):
     return np.ascontiguousarray(seeds), np.ascontiguousarray(wv), offsets
 
 
-def _sweep_call(n, max_size, cap, call):
+def _sweep_call(n, max_size, cap, call, info_type=None):
     """The output arrays of a sweep cut for `cap` positions (None: everything profiled), the call, the filled parts."""
     room = n if not max_size else min(n, int(max_size))
     cap = room if cap is None else min(int(cap), room)
     order = np.empty(cap, dtype=np.int32) if cap else None
     vol = np.empty(cap, dtype=np.uint64) if cap else None
     cut = np.empty(cap, dtype=np.uint64) if cap else None
-    info = Sweep()
+    info = (info_type or Sweep)()
     _check(call(_ptr(order), _ptr(vol), _ptr(cut), cap, C.byref(info)))
     k = min(cap, info.profiled)
     if not cap:
@@ -430,6 +448,16 @@ def weight_table_host(out_rp, weights):
     cum, ws = np.empty(m), np.empty(max(n, 1))
     _check(lib().pprhip_weight_table_host(n, m, _ptr(rp), _ptr(w), _ptr(cum), _ptr(ws)))
     return cum, ws[:n]
+
+
+def weight_quantum(weights):
+    """The shift s of the weighted sweep cut's quantum rule for a weight array, without a device
+    (pprhip_weight_quantum): relationship e counts q(e) = max(1, rint(w(e) * 2**s)) quanta.  The validation of
+    Graph.set_weights: PprhipError(ERR_INVALID) names the edge."""
+    w = np.ascontiguousarray(weights, dtype=np.float64).ravel()
+    s = C.c_int()
+    _check(lib().pprhip_weight_quantum(w.size, _ptr(w), C.byref(s)))
+    return s.value
 
 
 class HostCsr:
@@ -826,6 +854,11 @@ class Results:
         """Graph.sweep_cut over vector i of the store (pprhip_results_sweep_cut)."""
         return _sweep_call(self.n, max_size, cap, lambda o, v, c, k, info: lib().pprhip_results_sweep_cut(
             self.h, int(i), int(bool(normalize)), int(max_size), int(max_vol), o, v, c, k, info))
+
+    def weighted_sweep_cut(self, i, normalize=True, max_size=0, max_vol=0.0, cap=None):
+        """Graph.weighted_sweep_cut over vector i of the store (pprhip_results_weighted_sweep_cut)."""
+        return _sweep_call(self.n, max_size, cap, lambda o, v, c, k, info: lib().pprhip_results_weighted_sweep_cut(
+            self.h, int(i), int(bool(normalize)), int(max_size), float(max_vol), o, v, c, k, info), WeightedSweep)
 
     def sum(self, i):
         s = C.c_double()
@@ -1349,6 +1382,30 @@ class Graph:
             keep.h if keep is not None else None, _ptr(out), k, _ptr(ids), _ptr(vals), _ptr(nsel),
             C.cast(pq, C.c_void_p) if pq is not None else None, C.byref(st)))
         return out, ids, vals, nsel, (list(pq) if pq is not None else None), st
+
+    # ---- weighted local clustering: the sweep cut by relationship weight, in quanta (include/pprhip.h)
+    def weighted_sweep_cut(self, normalize=True, max_size=0, max_vol=0.0, cap=None):
+        """sweep_cut by relationship weight (pprhip_weighted_sweep_cut): the support ordered by x(v) / qdeg(v)
+        (normalize False: by x(v)), ties by id, and the prefix of least weighted conductance.  Returns (order, vol_q,
+        cut_q, WeightedSweep): volume and cut of every prefix in quanta (uint64), one weight unit being 2**shift quanta.
+        max_vol: a bound in weight units (0: none); max_size and cap as in sweep_cut."""
+        return _sweep_call(self.n, max_size, cap, lambda o, v, c, k, info: lib().pprhip_weighted_sweep_cut(
+            self.h, int(bool(normalize)), int(max_size), float(max_vol), o, v, c, k, info), WeightedSweep)
+
+    def weighted_local_cluster(self, seeds, alpha, rmax, weights=None, normalize=True, max_size=0, max_vol=0.0,
+                               cap=None):
+        """PageRank-Nibble on the weighted graph (pprhip_weighted_local_cluster_seeds): weighted_forward_push_seeds(seeds,
+        alpha, rmax, weights) left in HBM, then weighted_sweep_cut.  Returns (members, WeightedSweep, Stats)."""
+        s, w = _seed_arrays(seeds, weights)
+        room = self.n if not max_size else min(self.n, int(max_size))
+        cap = room if cap is None else min(int(cap), room)
+        members = np.empty(cap, dtype=np.int32) if cap else None
+        info, st = WeightedSweep(), Stats()
+        _check(lib().pprhip_weighted_local_cluster_seeds(self.h, _ptr(s), _ptr(w), s.size, alpha, rmax,
+                                                         int(bool(normalize)), int(max_size), float(max_vol),
+                                                         _ptr(members), cap, C.byref(info), C.byref(st)))
+        k = min(cap, info.best_size)
+        return (members[:k].copy() if cap else np.zeros(0, dtype=np.int32)), info, st
 
     # ---- the backward direction over the weights: the unweighted namesakes' arguments and return shapes
     def weighted_backward_push(self, target, alpha, rmax):

@@ -400,6 +400,7 @@ struct WalkShare : TerminalTable {  // (usage: [2] walks served from the cache /
 constexpr uint32_t kSweepTile = 4096;        // adjacency slots one workgroup turn of the edge scan covers
 constexpr uint32_t kSweepBestBlocks = 1024;  // partial minima of the best-prefix reduction
 constexpr int kSweepHdrWords = 8;            // [0] support, [1] best_size, [2] best_cut, [3] best_vol, [4] phi bits, [5] edge slots
+                                             // (the weighted sweep: [2] / [3] / [5] in quanta, [6] edge slots)
 struct SweepWs {
   unsigned long long* key[2] = {nullptr, nullptr};  // [n] sort keys (inverted score bits), double-buffered
   uint32_t* id[2] = {nullptr, nullptr};             // [n] original ids riding along
@@ -417,6 +418,9 @@ struct SweepWs {
   unsigned long long* hdr = nullptr;                // [kSweepHdrWords]
   void* tmp = nullptr;                              // scratch of the library sorts and scans
   size_t tmp_bytes = 0;
+  // the weighted sweep alone (weighted_sweep.cpp; allocated by the handle's first weighted sweep): the exclusive vol in
+  // quanta, qvolx[i + 1] = vol_q[i].  The positions' qdeg are staged in `cut` until the edge scan's result lands there.
+  unsigned long long* qvolx = nullptr;              // [n + 1]
 };
 
 // Workspace of the sparse getters (sparse.cpp, kernels_compact.hip; DESIGN.md §2 "Sparse results"): three groups, each
@@ -526,6 +530,13 @@ struct GraphData {
   // `widx` and never read by the unweighted calls, as `widx` is never read by the weighted ones; built from the weights
   // and dropped before they change (walk_index.cpp: free_weighted_walk_index)
   WalkIndex* widx_w = nullptr;
+  // the weighted sweep cut's fixed-point weights (weighted_sweep.cpp; include/pprhip.h "weighted local clustering"):
+  // qdeg[v] = the sum of the quanta q(e) over v's out-row and in-row, q_shift the shift s of the quantum rule, q_total
+  // the total volume 2 * sum q.  Built by the first weighted sweep after the weights were set, counted by
+  // pprhip_weights_info while it exists (qdeg_bytes), gone with the weights (free_weights)
+  unsigned long long* qdeg = nullptr;
+  int q_shift = 0;
+  uint64_t q_total = 0, qdeg_bytes = 0;
 };
 
 // The handle's batched-call state: the workspaces ("slots") of its batched queries and the arrays their dense levels
@@ -910,7 +921,31 @@ int launch_sweep_sort(pprhip_graph* g, SweepWs* w, uint32_t count);
 int launch_sweep_rank(pprhip_graph* g, SweepWs* w, uint32_t profiled);
 int launch_sweep_edges(pprhip_graph* g, SweepWs* w, uint32_t profiled, hipEvent_t before, hipEvent_t after);
 int launch_sweep_best(pprhip_graph* g, SweepWs* w, uint32_t profiled, uint64_t max_vol);
+// the steps that do not care what the u64 arrays they are given count (the weighted sweep calls them too): a library
+// scan, the tiles' first nodes from w->volx, the best prefix over any (exclusive vol, cut) pair and its total volume
+int sweep_scan(pprhip_graph* g, SweepWs* w, const unsigned long long* in, unsigned long long* out, uint32_t count);
+int launch_sweep_tile_starts(pprhip_graph* g, SweepWs* w, uint32_t profiled);
+int launch_sweep_best_over(pprhip_graph* g, SweepWs* w, const unsigned long long* volx, const unsigned long long* cut,
+                           uint32_t profiled, uint64_t total_vol, uint64_t max_vol);
+// grids under the test switches PPRHIP_SWEEP_ITEM_GRID (workgroups of 256 for `items`, at most cap) / _EDGE_GRID
+uint32_t sweep_item_grid(uint64_t items, uint32_t cap);
+uint32_t sweep_edge_grid(uint32_t grid);
 int init_kernels_sweep();
+
+// ---- kernels_weighted_sweep.hip (the weighted sweep cut's own steps; weighted_sweep.cpp drives them)
+// the largest of the m weights, as its bits -> *cell (a zeroed cell; positive doubles order like their bits)
+int launch_wsweep_wmax(pprhip_graph* g, unsigned long long* cell);
+// qdeg[v] for all n nodes at `shift`, their sum (the total volume in quanta) added to the zeroed *total; the rows of
+// kQdegHubRow entries or more go through a list in w->tile_node (two words each) counted in the zeroed *hub_count
+constexpr uint32_t kQdegHubRow = 8192;
+int launch_wsweep_qdeg(pprhip_graph* g, SweepWs* w, int shift, unsigned long long* qdeg, unsigned long long* total,
+                       unsigned long long* hub_count);
+int launch_wsweep_support(pprhip_graph* g, SweepWs* w, const double* x, int normalize);  // count -> w->hdr[0]
+// launch_sweep_rank with the positions' qdeg beside their count degree: w->volx and w->qvolx
+int launch_wsweep_rank(pprhip_graph* g, SweepWs* w, uint32_t profiled);
+// launch_sweep_edges adding +q / -q: delta, w->cut (in quanta), w->hdr[6] = edge slots
+int launch_wsweep_edges(pprhip_graph* g, SweepWs* w, uint32_t profiled, hipEvent_t before, hipEvent_t after);
+int init_kernels_weighted_sweep();
 
 // ---- kernels_compact.hip (ordered stream compaction of result vectors; sparse.cpp drives the steps)
 // x: `rows` vectors of n doubles in internal order, one behind the other.  Kept entries: x(v) > threshold.

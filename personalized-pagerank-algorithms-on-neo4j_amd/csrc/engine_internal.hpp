@@ -252,6 +252,10 @@ void free_walk_share(BatchState* B);
 
 // ---- sweep.cpp
 void free_sweep(pprhip_graph* g);  // the handle's sweep-cut workspace, if it has one
+int ensure_sweep(pprhip_graph* g);  // ... allocated when it has none
+
+// ---- weighted_sweep.cpp
+void free_weight_quanta(GraphData* D);  // the weighted sweep's qdeg, shift and total volume, if they were built
 
 // ---- sparse.cpp
 void free_sparse(pprhip_graph* g);  // the handle's workspace of the sparse getters, if it has one

@@ -112,6 +112,8 @@ __global__ __launch_bounds__(256) void k_sweep_tile_starts(const u64* __restrict
 // run of slots of one node in a register; sums go to the node's LDS cell, a wave whose lanes all ended on the same node
 // adds them up first.  Nodes inside the tile store their delta; the (at most two) nodes that cross a tile boundary add
 // their partial with one 64-bit atomic.
+// (k_wsweep_edges in kernels_weighted_sweep.hip is this kernel's twin with a weight stream and 64-bit sums: the tile,
+// search and boundary logic is the same text there, and a fix to it here belongs there too.)
 __global__ __launch_bounds__(256) void k_sweep_edges(const u64* __restrict__ volx, uint32_t profiled,
                                                       const uint32_t* __restrict__ tile_node,
                                                       const uint4* __restrict__ rec, const uint32_t* __restrict__ rank,
@@ -229,7 +231,9 @@ __global__ __launch_bounds__(256) void k_sweep_best(const u64* __restrict__ volx
   }
 }
 
-// header words: [1] best_size, [2] best_cut, [3] best_vol, [4] bits of best_conductance, [5] edge slots scanned
+// header words: [1] best_size, [2] best_cut, [3] best_vol, [4] bits of best_conductance, [5] volx[profiled] - the edge
+// slots scanned when volx counts slots (the unweighted sweep); the weighted sweep passes the volume in quanta, so its
+// [2], [3] and [5] are quanta and k_wsweep_edges keeps the edge slots in [6], which this kernel leaves alone
 __global__ __launch_bounds__(256) void k_sweep_best_final(const double* __restrict__ part_phi,
                                                            const u64* __restrict__ part_idx, uint32_t n_part,
                                                            const u64* __restrict__ volx, const u64* __restrict__ cut,
@@ -277,6 +281,10 @@ static uint32_t sweep_grid(uint64_t items, uint32_t cap) {
   const uint64_t b = (items + 255) / 256;
   return sweep_grid_cap("PPRHIP_SWEEP_ITEM_GRID", (uint32_t)(b < 1 ? 1 : (b > cap ? cap : b)));
 }
+
+// the two grids for the launchers of kernels_weighted_sweep.hip, which the same switches cap
+uint32_t sweep_item_grid(uint64_t items, uint32_t cap) { return sweep_grid(items, cap); }
+uint32_t sweep_edge_grid(uint32_t grid) { return sweep_grid_cap("PPRHIP_SWEEP_EDGE_GRID", grid); }
 
 int launch_sweep_support(pprhip_graph* g, SweepWs* w, const double* x, int normalize) {
   const GraphData* D = g->gr;
@@ -330,7 +338,7 @@ int launch_sweep_sort(pprhip_graph* g, SweepWs* w, uint32_t count) {
   return PPRHIP_OK;
 }
 
-static int sweep_scan(pprhip_graph* g, SweepWs* w, const u64* in, u64* out, uint32_t count) {
+int sweep_scan(pprhip_graph* g, SweepWs* w, const u64* in, u64* out, uint32_t count) {
   size_t b = 0;
   if (rocprim::inclusive_scan(nullptr, b, in, out, (size_t)count, rocprim::plus<u64>(), g->stream) != hipSuccess) {
     set_error("sweep: sizing the device scan failed");
@@ -355,13 +363,19 @@ int launch_sweep_rank(pprhip_graph* g, SweepWs* w, uint32_t profiled) {
   return sweep_scan(g, w, w->deg, w->volx + 1, profiled);
 }
 
+int launch_sweep_tile_starts(pprhip_graph* g, SweepWs* w, uint32_t profiled) {
+  const uint64_t max_tiles = std::max<uint64_t>(1, (2 * g->gr->m + kSweepTile - 1) / kSweepTile);  // (<= w->tile_cap)
+  hipLaunchKernelGGL(k_sweep_tile_starts, dim3(sweep_grid(max_tiles, 1024)), dim3(256), 0, g->stream, w->volx, profiled,
+                     w->tile_node);
+  PPRHIP_CHECK_HIP(hipGetLastError());
+  return PPRHIP_OK;
+}
+
 // delta over the slot space, then cut = its scan
 int launch_sweep_edges(pprhip_graph* g, SweepWs* w, uint32_t profiled, hipEvent_t before, hipEvent_t after) {
   const GraphData* D = g->gr;
   const uint64_t max_tiles = std::max<uint64_t>(1, (2 * D->m + kSweepTile - 1) / kSweepTile);  // (<= w->tile_cap)
-  hipLaunchKernelGGL(k_sweep_tile_starts, dim3(sweep_grid(max_tiles, 1024)), dim3(256), 0, g->stream, w->volx, profiled,
-                     w->tile_node);
-  PPRHIP_CHECK_HIP(hipGetLastError());
+  PPRHIP_TRY(launch_sweep_tile_starts(g, w, profiled));
   PPRHIP_CHECK_HIP(hipEventRecord(before, g->stream));
   PPRHIP_CHECK_HIP(hipMemsetAsync(w->delta, 0, sizeof(long long) * (size_t)profiled, g->stream));
   // 32 KB of LDS per workgroup: five of them share a CU
@@ -374,14 +388,19 @@ int launch_sweep_edges(pprhip_graph* g, SweepWs* w, uint32_t profiled, hipEvent_
   return sweep_scan(g, w, reinterpret_cast<const u64*>(w->delta), w->cut, profiled);
 }
 
-int launch_sweep_best(pprhip_graph* g, SweepWs* w, uint32_t profiled, uint64_t max_vol) {
+int launch_sweep_best_over(pprhip_graph* g, SweepWs* w, const u64* volx, const u64* cut, uint32_t profiled,
+                           uint64_t total_vol, uint64_t max_vol) {
   const uint32_t grid = sweep_grid(profiled, kSweepBestBlocks);
-  hipLaunchKernelGGL(k_sweep_best, dim3(grid), dim3(256), 0, g->stream, w->volx, w->cut, profiled, 2ull * g->gr->m,
-                     (u64)max_vol, w->part_phi, w->part_idx);
-  hipLaunchKernelGGL(k_sweep_best_final, dim3(1), dim3(256), 0, g->stream, w->part_phi, w->part_idx, grid, w->volx, w->cut,
+  hipLaunchKernelGGL(k_sweep_best, dim3(grid), dim3(256), 0, g->stream, volx, cut, profiled, (u64)total_vol, (u64)max_vol,
+                     w->part_phi, w->part_idx);
+  hipLaunchKernelGGL(k_sweep_best_final, dim3(1), dim3(256), 0, g->stream, w->part_phi, w->part_idx, grid, volx, cut,
                      profiled, w->hdr);
   PPRHIP_CHECK_HIP(hipGetLastError());
   return PPRHIP_OK;
+}
+
+int launch_sweep_best(pprhip_graph* g, SweepWs* w, uint32_t profiled, uint64_t max_vol) {
+  return launch_sweep_best_over(g, w, w->volx, w->cut, profiled, 2ull * g->gr->m, max_vol);
 }
 
 int init_kernels_sweep() {  // loads this file's code object on the current device (see init_kernels_push)

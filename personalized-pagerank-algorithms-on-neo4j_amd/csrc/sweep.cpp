@@ -18,18 +18,20 @@ void free_sweep(pprhip_graph* g) {
   SweepWs* w = g->sweep;
   if (!w) return;
   void* ptrs[] = {w->key[0], w->key[1], w->id[0], w->id[1], w->rank, w->rec, w->deg, w->volx, w->tile_node, w->delta,
-                  w->cut, w->part_phi, w->part_idx, w->hdr, w->tmp};
+                  w->cut, w->part_phi, w->part_idx, w->hdr, w->tmp, w->qvolx};
   for (void* p : ptrs)
     if (p) (void)hipFree(p);
   delete w;
   g->sweep = nullptr;
 }
 
-static int ensure_sweep(pprhip_graph* g) {
+int ensure_sweep(pprhip_graph* g) {
   if (g->sweep) return PPRHIP_OK;
   SweepWs* w = g->sweep = new (std::nothrow) SweepWs();
   if (!w) return PPRHIP_ERR_OOM;
   const size_t n = g->gr->n;
+  // (weighted_sweep.cpp also keeps the one-off list of hub rows here, two words per row of kQdegHubRow entries or more:
+  // ensure_quanta checks that this capacity holds it)
   w->tile_cap = (size_t)((2 * g->gr->m + kSweepTile - 1) / kSweepTile) + 2;
   int rc = PPRHIP_OK;
   for (int i = 0; i < 2 && !rc; ++i) {

@@ -161,6 +161,7 @@ void free_weights(GraphData* D) {
   D->wsurvival_alpha = 0.0;
   D->w_bytes = 0;
   free_weighted_in_rec(D);
+  free_weight_quanta(D);
 }
 
 void free_weighted_in_rec(GraphData* D) {
@@ -296,7 +297,8 @@ int pprhip_weights_info(const pprhip_graph_t* g, int* present, uint64_t* bytes) 
     return PPRHIP_ERR_INVALID;
   }
   if (present) *present = g->gr->w_bytes ? 1 : 0;
-  if (bytes) *bytes = g->gr->w_bytes + g->gr->in_wrec_bytes;  // (the weighted All-Pair records once they exist)
+  // (the weighted All-Pair records and the weighted sweep's qdeg once they exist)
+  if (bytes) *bytes = g->gr->w_bytes + g->gr->in_wrec_bytes + g->gr->qdeg_bytes;
   return PPRHIP_OK;
 }
 
