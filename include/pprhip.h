@@ -926,8 +926,15 @@ int pprhip_weighted_walk_index_usage(pprhip_graph_t* g, uint64_t* served, uint64
  * Pairs: value(s, t) = p_t(s) / S_w(s) + (1 / w) sum_{i < w} r_t(V_i), V_i the terminal of the weighted walk (seed,
  * PPRHIP_PAIR_WALK_STREAM, s, i) without the forced first hop - pprhip_weighted_random_walk_batch's function; r_max and
  * w are pprhip_pair_params', unchanged.  A pair's walk sums are formed without atomics in a fixed order.
- * Weighted targets and pairs run one set / one distinct target after another on the handle's own workspace (the batched
- * sweeps of the unweighted calls are not shared).  Checks as above: parameter ranges, the handle (an open query stream:
+ * A target call of q >= 2 queries runs with up to PPRHIP_BATCH of them in flight on the handle's batch workspaces, the
+ * queries that stand at a dense level sharing one 16-column sweep over the out-rows; it allocates the batch state on
+ * first use, as pprhip_ppr_targets does (PPRHIP_RELEASE_BATCH hands it back; PPRHIP_BATCH_WORKSPACES limits the
+ * columns).  Query i takes, level by level, the decisions of the call of that one query - the same dense / sparse rule
+ * on its own frontier, the same threshold test, the same start rules - and batching changes the order of additions
+ * inside dense levels only; per-query push_ms / total_ms are the host's clock, stats_sum carries the call's kernel
+ * classes (class_launches[PPRHIP_KERNEL_DENSE_PULL_BATCH]: the shared sweeps).  A call of q == 1 and the pairs'
+ * distinct targets run one after another on the handle's own workspace and allocate no batch state.
+ * Checks as above: parameter ranges, the handle (an open query stream:
  * PPRHIP_ERR_STATE), PPRHIP_ERR_STATE without weights, then ids and sets before any device work, the handle untouched. */
 /* the contract of pprhip_backward_push (in-degree 0: reserve(t) = 1 and no push); results stay in HBM for the getters,
  * the sparse getters, pprhip_topk_select and pprhip_sweep_cut */

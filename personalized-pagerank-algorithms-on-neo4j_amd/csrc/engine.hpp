@@ -1040,6 +1040,24 @@ int launch_wb_pair_walk(pprhip_graph* g, const int32_t* d_src, uint32_t n_pairs,
                         uint64_t walks, double alpha, uint64_t seed, double* d_part, unsigned long long* d_steps);
 int init_kernels_weighted_bwd();
 
+// ---- kernels_weighted_bwd_batch.hip (the dense level of kBatch weighted backward pushes at once;
+// weighted_bwd_batch.cpp drives them)
+// S: a batch slot whose column of the parent's c8 arrays is slot_index; its kernels run on S->stream.
+// launch_wb_prepare with the contributions of list fbuf (nf entries) scattered into S's column of c8[c8cur] (all-zero
+// before)
+int launch_wbb_scatter(pprhip_graph* S, const PushArgs& a, int fbuf, uint32_t nf);
+// S's column of c8[c8cur] back to list form with the prefix of the in-degrees: F / eoff [out_fbuf] and cF, the column
+// handed back all-zero; *d_counter: 0 before, entries << 36 | in-edges after
+int launch_wbb_compact(pprhip_graph* S, int out_fbuf, unsigned long long* d_counter);
+// behind the first sweep that read a scattered list: the members of list fbuf without out-edges - rows the sweep never
+// rewrites - are zeroed in S's column of both arrays
+int launch_wbb_leave(pprhip_graph* S, int fbuf, uint32_t nf);
+// one batched weighted backward sweep of the columns staged as active in parent->batch->h_slot_args (res, reserve, ctr,
+// alpha, rmax, out_slot): c8[c8cur] -> c8[c8cur ^ 1], c8cur flipped; an active column's new frontier counter goes to its
+// ctr->packed[out_slot] and to sweep_out[column].  ensure_bwd_layout first; acc8 all-zero in the backward layout.
+int launch_wbb_sweep(pprhip_graph* parent);
+int init_kernels_weighted_bwd_batch();
+
 // ---- kernels_select.hip
 int launch_select_hist(pprhip_graph* g, const double* x, uint32_t n, unsigned long long prefix, int prefix_bits,
                        int digit_bits, bool first_pass);

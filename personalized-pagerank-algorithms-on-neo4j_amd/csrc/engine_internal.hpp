@@ -7,7 +7,7 @@
 // All-Pair-Backward-Search; index.cpp: its inverted index; pairs.cpp, targets.cpp: single pairs and single targets;
 // weighted.cpp: relationship weights, the weighted level loop and power method; weighted_bwd.cpp: the backward
 // direction over the weights; weighted_query.cpp: the weighted top-k rounds; weighted_batch.cpp: the batched weighted
-// FORA calls).
+// FORA calls; weighted_bwd_batch.cpp: the batched weighted target calls).
 #pragma once
 
 #include <sys/mman.h>
@@ -572,6 +572,13 @@ int batch_run(pprhip_graph_t* g, BatchJob& J, pprhip_stats_t* stats_sum);
 // delivery of query r.query of J, finished on the workspace r.g with the statistics r.st: the vector into the result
 // store and / or the caller's array, the top-J.k selection, the per-query statistics
 int deliver_vector(BatchJob& J, ForaRun& r);
+
+// ---- weighted_bwd_batch.cpp
+// pprhip_weighted_ppr_targets for q >= 2 behind its checks: the plan's sets (tp.survival = S_w) with up to kBatch in
+// flight on the handle's batch workspaces (built on first use), delivered as the serial path delivers them
+int weighted_targets_batch(pprhip_graph_t* g, const TargetPlan& tp, int q, pprhip_results* keep, double* values_out, int k,
+                           int32_t* ids_out, double* vals_out, int* n_out, pprhip_stats_t* per_query,
+                           pprhip_stats_t* stats_sum);
 
 // ---- forward_calls.cpp
 int check_weighted_fora_params(double eps, const pprhip_fora_conf_t* conf, double rmax, const char* fn);

@@ -1,8 +1,9 @@
 // weighted_bwd.cpp — the backward direction over weighted relationships (include/pprhip.h "weighted relationships",
 // DESIGN.md §2 "Weighted backward direction"): the weighted backward push, the weighted survival vector S_w, single
 // targets / target sets and single pairs over P(u, v) = w / W(u), as a small driver over kernels_weighted_bwd.hip.
-// Weighted queries run one after another on the handle's own workspace: the 16-column batched sweeps are not shared.
-// What is specific to the weights is here - which kernels run and the serial loops over a call's sets and targets.
+// A target call of two or more queries runs batched, its dense levels on a shared 16-column sweep
+// (weighted_bwd_batch.cpp); a call of one, the pairs' targets and All-Pair's whole-vector searches run one after another
+// on the handle's own workspace.  What is specific to the weights is here - which kernels run and the serial loops.
 // Everything else is shared with the unweighted calls: the level loop (weighted.cpp: run_weighted_levels), the front of
 // a target call (targets.cpp: target_plan), the front and back of a pair call and the survival iteration (pairs.cpp:
 // pair_plan / pair_upload / pair_collect, survival_jacobi), a pair target's walk blocks (bwd_runs.cpp:
@@ -108,12 +109,16 @@ int pprhip_weighted_ppr_targets(pprhip_graph_t* g, const int32_t* targets, const
   PPRHIP_TRY(target_plan(g, targets, weights, offsets, q, alpha, rmax, keep, k, ids_out, vals_out, stats_sum, fn, true, tp));
   if (q == 0) return PPRHIP_OK;
   PPRHIP_TRY(ensure_weighted_survival(g, alpha));
+  if (q >= 2) {  // up to kBatch queries in flight on the batch workspaces, their dense levels on one shared sweep
+    tp.survival = g->gr->wsurvival;
+    return weighted_targets_batch(g, tp, q, keep, values_out, k, ids_out, vals_out, n_out, per_query, stats_sum);
+  }
   pprhip_stats_t sum;
   std::memset(&sum, 0, sizeof sum);
   g->topk_active = false;
   if (keep) keep->count = 0;
   const size_t n = g->gr->n;
-  for (int i = 0; i < q; ++i) {  // one set at a time on the handle's own workspace
+  for (int i = 0; i < q; ++i) {  // the call of one, on the handle's own workspace
     const int32_t single = tp.single[(size_t)i];
     pprhip_stats_t st;
     std::memset(&st, 0, sizeof st);
