@@ -882,6 +882,50 @@ int pprhip_weighted_fora_batch_seeds(pprhip_graph_t* g, const int32_t* seeds, co
                                      int32_t* ids_out, double* vals_out, int* n_out, pprhip_stats_t* per_query,
                                      pprhip_stats_t* stats_sum);
 
+/* ---- batched weighted top-k ("Batched weighted top-k"): q weighted top-k queries in one call, up
+ * to 16 of them in flight on the handle's batch workspaces (PPRHIP_BATCH_WORKSPACES: fewer; the first such call
+ * allocates the batch state).  conf is a top-k conf (pprhip_conf_fora_topk), k is conf->k.  Query i IS
+ * pprhip_weighted_fora_topk(srcs[i], eps, conf, seed + i, ...) / pprhip_weighted_fora_topk_seeds(set i, ..., seed + i,
+ * ...): the same schedule on delta, the same rmax_j and omega_j per round, the same first frontier per round (the live
+ * seeds, then every node active at rmax_j), the same dense / sparse rule on its own frontier, the same walk plan and the
+ * same walks (seed + i, stream = round, node, index; no forced first hop), the same selection and the same stop rule;
+ * no parking, no push ahead, no cost model.  Batching changes the order of fp64 additions (sweeps, terminal atomics) and
+ * nothing else.  The dense levels of the queries in flight share the batched weighted sweep; a column at a dense level
+ * never waits for another column.  The walk plans of all columns whose round has reached its walk phase run in ONE
+ * launch, the waves dealt to the columns by their walk counts (pprhip_walk_multi_shares is the rule).  The weighted walk
+ * index is never read.  A call with q == 1 runs the single call's loop on the handle's own workspace.
+ * ids_out / vals_out: q x k, rows padded -1 / 0; n_out (NULL: none): q counts as the single call's n_out; keep (NULL:
+ * none) receives query i's estimate vector - what pprhip_get_reserve returns after the single call - in slot i;
+ * per_query (NULL: none): q statistics filled as the single call fills them (rounds, levels, dense_levels, pops,
+ * dense_nodes, enqueues, walks, walk_steps, mc_sources, dead_end_pops, kth_value, rsum, rmax_final, omega.  push_ms,
+ * mc_ms and select_ms are NOT the single call's event times: they are host times of the driver rounds the query took
+ * part in - mc_ms the time to queue the round's walk plans, merged launch and selections, select_ms the wait for the
+ * selection (the merged walk's device time and, for a later column, the deliveries of the columns before it fall into
+ * it), push_ms the rest - and a phase shared with other columns is counted for each); stats_sum: their sums
+ * and the call's kernel classes - the sweeps are class PPRHIP_KERNEL_DENSE_PULL_BATCH (busy columns per sweep =
+ * dense_levels / class_launches[5]), the merged walk launches class PPRHIP_KERNEL_WALK (columns per launch = rounds /
+ * class_launches[3]).  A dead-end source or a set without a live seed: rounds = 0, the estimate is p, one selection.
+ * Checks, all before any device work: eps, the conf, q < 0 and NULL rows with q > 0 (PPRHIP_ERR_INVALID), then the
+ * handle (an open query stream: PPRHIP_ERR_STATE), PPRHIP_ERR_STATE without weights, keep, then every source / every
+ * set (the message names the set).  q = 0 is PPRHIP_OK with keep->count = 0 and zeroed stats_sum.  An error on any
+ * workspace ends the call; the handle stays usable. */
+int pprhip_weighted_fora_batch_topk(pprhip_graph_t* g, const int32_t* srcs, int q, double eps,
+                                    const pprhip_fora_conf_t* conf, uint64_t seed, pprhip_results_t* keep,
+                                    int32_t* ids_out, double* vals_out, int* n_out, pprhip_stats_t* per_query,
+                                    pprhip_stats_t* stats_sum);
+/* ... over q seed sets described like a CSR (pprhip_fora_batch_seeds) */
+int pprhip_weighted_fora_batch_topk_seeds(pprhip_graph_t* g, const int32_t* seeds, const double* weights,
+                                          const uint64_t* offsets, int q, double eps, const pprhip_fora_conf_t* conf,
+                                          uint64_t seed, pprhip_results_t* keep, int32_t* ids_out, double* vals_out,
+                                          int* n_out, pprhip_stats_t* per_query, pprhip_stats_t* stats_sum);
+/* The dealing rule of the merged walk launch, without a device.  counts[c]: the walks of column c's plan (0: idle);
+ * base_waves >= 1: the waves of a single walk launch.  T = the sum of the counts, per = ceil(ceil(T / 64) / base_waves)
+ * * 64 (0 when T is 0); column c owns the ceil(counts[c] / per) consecutive waves from first_out[c], wave b of them runs
+ * the column's walks [(b - first_out[c]) * per, min(.. + per, counts[c])); no wave spans two columns; first_out[16] =
+ * the waves in use <= base_waves + 15, which is the grid the launch uses.  The launch's base_waves is n_cus * 16: a top-k
+ * plan derives its walk budget on the device, so the host has no bound of the walk count to trim the grid by. */
+int pprhip_walk_multi_shares(const uint64_t counts[16], uint32_t base_waves, uint64_t* per_out, uint32_t first_out[17]);
+
 /* ---- weighted walk index (FORA+ for pprhip_weighted_fora and pprhip_weighted_fora_seeds; DESIGN.md section 2,
  * "Weighted walk index"): the walk index above, over the weighted walks.  Both weighted whole-graph calls plan with the
  * unweighted plan and draw the weighted walks (seed, stream 0, v, 0 .. omega_v - 1) with the forced first hop for a

@@ -121,6 +121,7 @@ EXPORTS = [
     "pprhip_weighted_walk_index_build", "pprhip_weighted_walk_index_drop", "pprhip_weighted_walk_index_info",
     "pprhip_weighted_walk_index_fetch", "pprhip_weighted_walk_index_usage",
     "pprhip_weighted_fora_batch", "pprhip_weighted_fora_batch_seeds",
+    "pprhip_weighted_fora_batch_topk", "pprhip_weighted_fora_batch_topk_seeds", "pprhip_walk_multi_shares",
     "pprhip_weight_quantum", "pprhip_weighted_sweep_cut", "pprhip_results_weighted_sweep_cut",
     "pprhip_weighted_local_cluster_seeds",
 ]
@@ -279,6 +280,10 @@ def lib():
     L.pprhip_weighted_fora_batch.argtypes = [vp, vp, ci, dbl, P(ForaConf), u64, dbl, vp, vp, ci, vp, vp, vp, vp, P(Stats)]
     L.pprhip_weighted_fora_batch_seeds.argtypes = [vp, vp, vp, vp, ci, dbl, P(ForaConf), u64, dbl, vp, vp, ci, vp, vp, vp,
                                                    vp, P(Stats)]
+    L.pprhip_weighted_fora_batch_topk.argtypes = [vp, vp, ci, dbl, P(ForaConf), u64, vp, vp, vp, vp, vp, P(Stats)]
+    L.pprhip_weighted_fora_batch_topk_seeds.argtypes = [vp, vp, vp, vp, ci, dbl, P(ForaConf), u64, vp, vp, vp, vp, vp,
+                                                        P(Stats)]
+    L.pprhip_walk_multi_shares.argtypes = [vp, u32, P(u64), vp]
     L.pprhip_weighted_backward_push.argtypes = [vp, i32, dbl, dbl, vp, vp, P(Stats)]
     L.pprhip_weighted_walk_survival.argtypes = [vp, dbl, vp]
     L.pprhip_weighted_ppr_targets.argtypes = [vp, vp, vp, vp, ci, dbl, dbl, vp, vp, ci, vp, vp, vp, vp, P(Stats)]
@@ -448,6 +453,19 @@ def weight_table_host(out_rp, weights):
     cum, ws = np.empty(m), np.empty(max(n, 1))
     _check(lib().pprhip_weight_table_host(n, m, _ptr(rp), _ptr(w), _ptr(cum), _ptr(ws)))
     return cum, ws[:n]
+
+
+def walk_multi_shares(counts, base_waves):
+    """The dealing rule of the batched weighted top-k's merged walk launch without a device
+    (pprhip_walk_multi_shares).  counts: the walks of the BATCH columns' plans (0: idle); base_waves: the waves of a
+    single walk launch.  Returns (per, first[BATCH + 1]): column c owns the waves [first[c], first[c + 1]), wave b of
+    them the column's walks [(b - first[c]) * per, min(.. + per, counts[c]))."""
+    c = np.ascontiguousarray(counts, dtype=np.uint64).ravel()
+    if c.size != BATCH:
+        raise ValueError("counts: %d entries for %d columns" % (c.size, BATCH))
+    per, first = C.c_uint64(), np.zeros(BATCH + 1, dtype=np.uint32)
+    _check(lib().pprhip_walk_multi_shares(_ptr(c), int(base_waves), C.byref(per), _ptr(first)))
+    return per.value, first
 
 
 def weight_quantum(weights):
@@ -1382,6 +1400,38 @@ class Graph:
             keep.h if keep is not None else None, _ptr(out), k, _ptr(ids), _ptr(vals), _ptr(nsel),
             C.cast(pq, C.c_void_p) if pq is not None else None, C.byref(st)))
         return out, ids, vals, nsel, (list(pq) if pq is not None else None), st
+
+    # ---- batched weighted top-k: query i is weighted_fora_topk(srcs[i], ..., seed + i)
+    def _weighted_batch_topk(self, call, head, q, k, eps, alpha, seed, conf, per_query, keep):
+        conf = conf or conf_topk(self.n, self.m, k, alpha)
+        if conf.k != k:
+            raise ValueError("conf.k = %d, k = %d" % (conf.k, k))
+        ids = np.empty((q, k), dtype=np.int32)
+        vals = np.empty((q, k))
+        nsel = np.zeros(q, dtype=np.int32)
+        pq = (Stats * q)() if per_query and q else None
+        st = Stats()
+        _check(call(self.h, *head, q, eps, C.byref(conf), seed, keep.h if keep is not None else None, _ptr(ids),
+                    _ptr(vals), _ptr(nsel), C.cast(pq, C.c_void_p) if pq is not None else None, C.byref(st)))
+        return (ids, vals, nsel, st) + ((list(pq) if pq is not None else [],) if per_query else ())
+
+    def weighted_fora_batch_topk(self, srcs, k, eps, alpha, seed, conf=None, per_query=False, keep=None):
+        """q weighted_fora_topk queries in one call, BATCH of them in flight: their dense levels in one shared sweep,
+        the walk phases that are ready in one launch (pprhip_weighted_fora_batch_topk).  Query i is
+        weighted_fora_topk(srcs[i], eps, alpha, k, seed + i); conf defaults to conf_topk(n, m, k, alpha); keep: a Results
+        store that receives the estimate vectors.  Returns (ids[q, k], vals[q, k], n_out[q], summed Stats[, per-query
+        Stats])."""
+        srcs = np.ascontiguousarray(srcs, dtype=np.int32).ravel()
+        return self._weighted_batch_topk(lib().pprhip_weighted_fora_batch_topk, (_ptr(srcs),), int(srcs.size), k, eps,
+                                         alpha, seed, conf, per_query, keep)
+
+    def weighted_fora_batch_topk_seeds(self, sets, k, eps, alpha, seed, weights=None, conf=None, per_query=False,
+                                       keep=None):
+        """weighted_fora_batch_topk over seed sets: query i is weighted_fora_topk_seeds(sets[i], ..., seed + i,
+        weights[i]); sets and weights as fora_batch_seeds takes them; the same return tuple."""
+        s, w, offsets = _seed_set_arrays(sets, weights)
+        return self._weighted_batch_topk(lib().pprhip_weighted_fora_batch_topk_seeds, (_ptr(s), _ptr(w), _ptr(offsets)),
+                                         int(offsets.size - 1), k, eps, alpha, seed, conf, per_query, keep)
 
     # ---- weighted local clustering: the sweep cut by relationship weight, in quanta (include/pprhip.h)
     def weighted_sweep_cut(self, normalize=True, max_size=0, max_vol=0.0, cap=None):

@@ -1021,6 +1021,22 @@ int launch_wbat_sweep(pprhip_graph* parent);
 int launch_wbat_collect(pprhip_graph* parent, const unsigned long long* const* cells);
 int init_kernels_weighted_batch();
 
+// ---- kernels_weighted_topk_batch.hip (the merged walk launch of the batched weighted top-k; weighted_topk_batch.cpp)
+struct WalkMultiCol {  // one column of k_w_walk_plan_multi's table (ctr nullptr: idle)
+  const WalkPlanRec* plan_rec;  // the column's latest plan
+  double* target;               // its estimate
+  DevCounters* ctr;
+  int cell;                     // the plan's cell: ctr->mc_plan[cell] = sources << 36 | walks
+  uint32_t k0, k1;              // the two halves of the column's walk seed
+  uint32_t stream;              // ... and its Philox stream (the query's round)
+};
+// The latest walk plans of the workspaces cols[c] (kBatch entries, nullptr: idle) in ONE launch on the parent's stream:
+// column c's walks are (seeds[c], streams[c], node, index) without the forced first hop, added into targets[c]; the
+// waves are dealt by walk_multi_deal (weighted_batch.hpp).  Consumes the workspaces' walk hints.
+int launch_w_walk_multi(pprhip_graph* parent, pprhip_graph* const* cols, const uint64_t* seeds, const uint32_t* streams,
+                        double* const* targets, double alpha);
+int init_kernels_weighted_topk_batch();
+
 // ---- kernels_weighted_bwd.hip (the backward direction over the weights; weighted_bwd.cpp drives them)
 // step 1 of a backward level that starts from the list fbuf (nf entries): every entry gives up its residue; c =
 // (1 - alpha) r goes to cF[i], or (scatter_dense) to cdense[cbuf][node].  Clears *next_counter.

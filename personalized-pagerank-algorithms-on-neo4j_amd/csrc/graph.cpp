@@ -52,6 +52,7 @@ int init_device_once(int device) {
   PPRHIP_TRY(init_kernels_weighted_bwd());
   PPRHIP_TRY(init_kernels_weighted_query());
   PPRHIP_TRY(init_kernels_weighted_batch());
+  PPRHIP_TRY(init_kernels_weighted_topk_batch());
   PPRHIP_TRY(init_kernels_weighted_bwd_batch());
   PPRHIP_TRY(init_kernels_weighted_sweep());
   if ((size_t)device >= g_dev_inited.size()) g_dev_inited.resize((size_t)device + 1, 0);

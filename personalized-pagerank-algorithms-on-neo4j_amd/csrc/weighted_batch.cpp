@@ -6,120 +6,20 @@
 // batched sweep, and one read-back brings every counter.  A query whose frontier is empty runs its walk phase and its
 // delivery on its workspace, which then takes the call's next query.  Query i takes, level by level, the decisions of
 // pprhip_weighted_fora(srcs[i]) / pprhip_weighted_fora_seeds(set i); batching changes the order of additions only.
+// One level of a column, the shared sweep and the call's bring-up (weighted_batch.hpp) also serve the batched weighted
+// top-k driver (weighted_topk_batch.cpp).
 #include <algorithm>
 #include <cmath>
 #include <cstring>
 #include <string>
 
-#include "run.hpp"
+#include "weighted_batch.hpp"
 
 using namespace pprhip;
 using namespace pprhip::detail;
 
-namespace {
-
-struct WbatQuery {  // the query a column's workspace is running
-  int query = -1;  // index in the call (-1: the column is free)
-  WLevels L;       // (L.prepared: the frontier is held as contributions in the column; ccur goes unused)
-  PushArgs a{};
-  pprhip_stats_t st;
-  bool seeded = false, live = false;
-  double t0 = 0.0;  // host clock at the query's begin (ms)
-};
-
-struct WbatCall {
-  pprhip_graph* P = nullptr;
-  BatchJob* J = nullptr;
-  double alpha = 0.0, rmax = 0.0, omega = 0.0;
-  unsigned long long dense_thresh = 0;
-  int n_cols = kBatch;
-  int next = 0;  // the call's next query
-  WbatQuery q[kBatch];
-};
-
-pprhip_graph* slot_of(const WbatCall& C, int c) { return C.P->batch->slots[(size_t)c]; }
-
-// Query i begins on column c's workspace as weighted_fora begins it on the handle's (forward_calls.cpp): the workspace
-// reset, the plan installed, the first frontier - none for a dead-end source (reserve = e_s) or a set without a live
-// seed (reserve = p).
-int wbat_begin(WbatCall& C, int c, int i) {
-  pprhip_graph* S = slot_of(C, c);
-  BatchJob& J = *C.J;
-  WbatQuery& Q = C.q[c];
-  Q = WbatQuery();
-  std::memset(&Q.st, 0, sizeof Q.st);
-  S->tun = C.P->tun;
-  S->seed_on = false;
-  S->topk_active = false;
-  SeedTable* plan = J.srcs ? nullptr : &J.sets[(size_t)i];
-  const int32_t src = plan ? -1 : C.P->gr->h_old2new[J.srcs[i]];
-  PPRHIP_TRY(reset_query_state(S, false, plan ? plan->max_id : src));
-  if (plan) PPRHIP_TRY(seed_upload(S, *plan));
-  Q.a = PushArgs{C.alpha, C.rmax, 0.0, src, kFwdWhole};
-  Q.seeded = plan != nullptr;
-  Q.t0 = host_ms();
-  if (plan) {
-    PPRHIP_TRY(seed_start(S, Q.L));
-    S->seed_on = true;  // (until the query's pushes are over)
-  } else {
-    const uint32_t d = hdeg_out(S, src);
-    if (d == 0) {
-      PPRHIP_TRY(launch_set_f64(S, S->reserve, (uint32_t)src, 1.0));
-    } else {
-      PPRHIP_TRY(launch_set_f64(S, S->residue, (uint32_t)src, 1.0));
-      PPRHIP_TRY(launch_seed_one(S, Q.L.fcur, src));
-      Q.L.nf = 1;
-      Q.L.ef = d;
-    }
-  }
-  Q.live = Q.L.nf != 0;
-  Q.query = i;
-  return PPRHIP_OK;
-}
-
-// The query's push is over: the walk phase of weighted_fora on its workspace (the same plan, the same walks - the
-// call's seed, stream 0, forced first hop; served from the weighted walk index as the single call is), the dead-end
-// pops, the delivery.  The column is free afterwards.
-int wbat_finish(WbatCall& C, int c) {
-  pprhip_graph* S = slot_of(C, c);
-  BatchJob& J = *C.J;
-  WbatQuery& Q = C.q[c];
-  if (Q.L.prepared) {  // (the last level was a dense one: its column holds zeros but for the rows the sweep does not write)
-    PPRHIP_TRY(launch_wbat_leave(S, Q.a.src));
-    Q.L.prepared = false;
-  }
-  S->seed_on = false;
-  double sum = 0.0;
-  if (Q.live) PPRHIP_TRY(device_sum(S, S->residue, &sum));
-  const double t1 = host_ms();
-  const double rsum = sum * (1 - C.alpha);
-  if (Q.live) {
-    const double nrw_d = C.omega * rsum;
-    const long long nrw = (nrw_d == nrw_d && nrw_d > 0.0) ? (long long)nrw_d : 0;
-    PPRHIP_TRY(launch_walk_plan(S, 0, C.alpha, rsum, nrw, S->reserve, 0.0));
-    ktimer().begin(PPRHIP_KERNEL_WALK, 0);
-    PPRHIP_TRY(launch_w_walk_run(S, C.alpha, J.seed, S->reserve, 0u, true));
-    ktimer().end();
-  }
-  PPRHIP_TRY(read_dead_pops(S, Q.st));
-  const double t2 = host_ms();
-  Q.st.rounds = 1;
-  Q.st.rsum = rsum;
-  Q.st.rmax_final = C.rmax;
-  Q.st.omega = C.omega;
-  Q.st.push_ms = t1 - Q.t0;  // the host's clock: the workspace shares its stream with the other columns
-  Q.st.mc_ms = t2 - t1;
-  Q.st.total_ms = t2 - Q.t0;
-  ForaRun r;
-  r.g = S;
-  r.query = Q.query;
-  r.kind = QueryKind::kFora;
-  r.st = Q.st;
-  PPRHIP_TRY(deliver_vector(J, r));
-  add_stats(J.sum, r.st);
-  Q.query = -1;
-  return PPRHIP_OK;
-}
+namespace pprhip {
+namespace detail {
 
 // One sparse level of column c's query on its own workspace: run_weighted_levels' sparse branch without its read-back
 // (the round's collect brings the counter).  *cell: where the level leaves the next frontier's counter.
@@ -207,6 +107,160 @@ int wbat_sweep(WbatCall& C, const bool* dense, int n_dense) {
   return PPRHIP_OK;
 }
 
+// A batched weighted call's bring-up and its end around `rounds` (the call's driver loop): the batch state, C filled
+// but for what only the caller knows (rmax, omega), the workspaces on the handle's stream, a timer of the call's own,
+// the shared arrays cleared; afterwards the class totals into J.sum and stats_sum, or - after an error - free_batch and
+// the message kept.  `what` names the call in the messages.
+int wbat_run(pprhip_graph_t* g, BatchJob& J, WbatCall& C, int (*rounds)(WbatCall&, void*), void* arg, const char* what,
+             pprhip_stats_t* stats_sum) {
+  PPRHIP_TRY(ensure_batch(g));
+  BatchState* bs = g->batch;
+  C.P = g;
+  C.J = &J;
+  C.alpha = J.conf->alpha;
+  C.dense_thresh = (unsigned long long)std::ceil(g->tun.dense_frac * (double)g->gr->m);
+  // one column per batch workspace: fewer than kBatch when the handle is told to keep fewer
+  C.n_cols = (int)std::min<size_t>((size_t)kBatch, bs->slots.size());
+  if (const char* e = tuning_env("PPRHIP_BATCH_WORKSPACES")) C.n_cols = std::max(1, std::min(C.n_cols, atoi(e)));
+  for (pprhip_graph* S : bs->slots) {
+    S->stream = g->stream;
+    S->c8_via_parent = false;
+    S->sync = nullptr;
+  }
+  if (bs->share) bs->share->on = false;  // (the unweighted calls' terminal cache)
+  std::memset(&J.sum, 0, sizeof J.sum);
+  g->ktimer.stream = g->stream;
+  g->ktimer.reset();
+  const double t0 = host_ms();
+  KernelTimer local;  // (the caller's timer may be in use)
+  KernelTimer* const saved = g_timer_cur;
+  g_timer_cur = &local;
+  local.stream = g->stream;
+  int rc = PPRHIP_OK;
+  // A column nobody owns holds zeros, in both arrays: the calls before may have left entries on rows this sweep does
+  // not rewrite (an unweighted sweep's rows without in-edges, a backward call's entry preparation), and row sums in the
+  // other layout.
+  const size_t c8_bytes = sizeof(double) * (size_t)g->gr->n * kBatch;
+  if (hipMemsetAsync(bs->c8[0], 0, c8_bytes, g->stream) != hipSuccess ||
+      hipMemsetAsync(bs->c8[1], 0, c8_bytes, g->stream) != hipSuccess ||
+      (bs->acc8_dir != 0 &&
+       hipMemsetAsync(bs->acc8, 0, sizeof(double) * ((size_t)g->gr->n + 1) * kBatch, g->stream) != hipSuccess)) {
+    set_error("%s: clearing the shared arrays failed: %s", what, hipGetErrorString(hipGetLastError()));
+    rc = PPRHIP_ERR_HIP;
+  }
+  bs->acc8_dir = 0;
+  try {
+    if (rc == PPRHIP_OK) rc = rounds(C, arg);
+  } catch (const std::exception& ex) {  // (no exception may cross the C ABI: the seed tables' vectors allocate)
+    set_error("%s: %s", what, ex.what());
+    rc = PPRHIP_ERR_OOM;
+  }
+  const std::string msg = rc != PPRHIP_OK ? get_error() : std::string();
+  (void)hipStreamSynchronize(g->stream);
+  double tot[8] = {0};
+  uint64_t bytes[8] = {0};
+  uint32_t cnt[8] = {0};
+  local.resolve(tot, bytes, cnt);
+  local.destroy();
+  g_timer_cur = saved;
+  if (rc != PPRHIP_OK) {
+    free_batch(g);  // workspaces may hold half-pushed levels and seed tables: the next batched call builds clean ones
+    set_error("%s", msg.c_str());
+    return rc;
+  }
+  J.sum.total_ms = host_ms() - t0;
+  fold_class_totals(J.sum, tot, bytes, cnt);
+  if (stats_sum) *stats_sum = J.sum;
+  return PPRHIP_OK;
+}
+
+}  // namespace detail
+}  // namespace pprhip
+
+namespace {
+
+// Query i begins on column c's workspace as weighted_fora begins it on the handle's (forward_calls.cpp): the workspace
+// reset, the plan installed, the first frontier - none for a dead-end source (reserve = e_s) or a set without a live
+// seed (reserve = p).
+int wbat_begin(WbatCall& C, int c, int i) {
+  pprhip_graph* S = slot_of(C, c);
+  BatchJob& J = *C.J;
+  WbatQuery& Q = C.q[c];
+  Q = WbatQuery();
+  std::memset(&Q.st, 0, sizeof Q.st);
+  S->tun = C.P->tun;
+  S->seed_on = false;
+  S->topk_active = false;
+  SeedTable* plan = J.srcs ? nullptr : &J.sets[(size_t)i];
+  const int32_t src = plan ? -1 : C.P->gr->h_old2new[J.srcs[i]];
+  PPRHIP_TRY(reset_query_state(S, false, plan ? plan->max_id : src));
+  if (plan) PPRHIP_TRY(seed_upload(S, *plan));
+  Q.a = PushArgs{C.alpha, C.rmax, 0.0, src, kFwdWhole};
+  Q.seeded = plan != nullptr;
+  Q.t0 = host_ms();
+  if (plan) {
+    PPRHIP_TRY(seed_start(S, Q.L));
+    S->seed_on = true;  // (until the query's pushes are over)
+  } else {
+    const uint32_t d = hdeg_out(S, src);
+    if (d == 0) {
+      PPRHIP_TRY(launch_set_f64(S, S->reserve, (uint32_t)src, 1.0));
+    } else {
+      PPRHIP_TRY(launch_set_f64(S, S->residue, (uint32_t)src, 1.0));
+      PPRHIP_TRY(launch_seed_one(S, Q.L.fcur, src));
+      Q.L.nf = 1;
+      Q.L.ef = d;
+    }
+  }
+  Q.live = Q.L.nf != 0;
+  Q.query = i;
+  return PPRHIP_OK;
+}
+
+// The query's push is over: the walk phase of weighted_fora on its workspace (the same plan, the same walks - the
+// call's seed, stream 0, forced first hop; served from the weighted walk index as the single call is), the dead-end
+// pops, the delivery.  The column is free afterwards.
+int wbat_finish(WbatCall& C, int c) {
+  pprhip_graph* S = slot_of(C, c);
+  BatchJob& J = *C.J;
+  WbatQuery& Q = C.q[c];
+  if (Q.L.prepared) {  // (the last level was a dense one: its column holds zeros but for the rows the sweep does not write)
+    PPRHIP_TRY(launch_wbat_leave(S, Q.a.src));
+    Q.L.prepared = false;
+  }
+  S->seed_on = false;
+  double sum = 0.0;
+  if (Q.live) PPRHIP_TRY(device_sum(S, S->residue, &sum));
+  const double t1 = host_ms();
+  const double rsum = sum * (1 - C.alpha);
+  if (Q.live) {
+    const double nrw_d = C.omega * rsum;
+    const long long nrw = (nrw_d == nrw_d && nrw_d > 0.0) ? (long long)nrw_d : 0;
+    PPRHIP_TRY(launch_walk_plan(S, 0, C.alpha, rsum, nrw, S->reserve, 0.0));
+    ktimer().begin(PPRHIP_KERNEL_WALK, 0);
+    PPRHIP_TRY(launch_w_walk_run(S, C.alpha, J.seed, S->reserve, 0u, true));
+    ktimer().end();
+  }
+  PPRHIP_TRY(read_dead_pops(S, Q.st));
+  const double t2 = host_ms();
+  Q.st.rounds = 1;
+  Q.st.rsum = rsum;
+  Q.st.rmax_final = C.rmax;
+  Q.st.omega = C.omega;
+  Q.st.push_ms = t1 - Q.t0;  // the host's clock: the workspace shares its stream with the other columns
+  Q.st.mc_ms = t2 - t1;
+  Q.st.total_ms = t2 - Q.t0;
+  ForaRun r;
+  r.g = S;
+  r.query = Q.query;
+  r.kind = QueryKind::kFora;
+  r.st = Q.st;
+  PPRHIP_TRY(deliver_vector(J, r));
+  add_stats(J.sum, r.st);
+  Q.query = -1;
+  return PPRHIP_OK;
+}
+
 int wbat_rounds(WbatCall& C) {
   pprhip_graph* P = C.P;
   BatchState* bs = P->batch;
@@ -254,71 +308,14 @@ int wbat_rounds(WbatCall& C) {
 int weighted_batch_run(pprhip_graph_t* g, BatchJob& J, double rmax, pprhip_stats_t* stats_sum) {
   double rmax0 = 0.0, omega = 0.0;
   PPRHIP_TRY(pprhip_fora_whole_params(J.conf, J.eps, &rmax0, &omega));
-  PPRHIP_TRY(ensure_batch(g));
-  BatchState* bs = g->batch;
   WbatCall* Cp = new (std::nothrow) WbatCall();
   if (!Cp) return PPRHIP_ERR_OOM;
-  WbatCall& C = *Cp;
-  C.P = g;
-  C.J = &J;
-  C.alpha = J.conf->alpha;
-  C.rmax = rmax == 0.0 ? rmax0 : rmax;
-  C.omega = omega;
-  C.dense_thresh = (unsigned long long)std::ceil(g->tun.dense_frac * (double)g->gr->m);
-  // one column per batch workspace: fewer than kBatch when the handle is told to keep fewer
-  C.n_cols = (int)std::min<size_t>((size_t)kBatch, bs->slots.size());
-  if (const char* e = tuning_env("PPRHIP_BATCH_WORKSPACES")) C.n_cols = std::max(1, std::min(C.n_cols, atoi(e)));
-  for (pprhip_graph* S : bs->slots) {
-    S->stream = g->stream;
-    S->c8_via_parent = false;
-    S->sync = nullptr;
-  }
-  if (bs->share) bs->share->on = false;  // (the unweighted calls' terminal cache)
-  std::memset(&J.sum, 0, sizeof J.sum);
-  g->ktimer.stream = g->stream;
-  g->ktimer.reset();
-  const double t0 = host_ms();
-  KernelTimer local;  // (the caller's timer may be in use)
-  KernelTimer* const saved = g_timer_cur;
-  g_timer_cur = &local;
-  local.stream = g->stream;
-  int rc = PPRHIP_OK;
-  // A column nobody owns holds zeros, in both arrays: the calls before may have left entries on rows this sweep does
-  // not rewrite (an unweighted sweep's rows without in-edges, a backward call's entry preparation), and row sums in the
-  // other layout.
-  const size_t c8_bytes = sizeof(double) * (size_t)g->gr->n * kBatch;
-  if (hipMemsetAsync(bs->c8[0], 0, c8_bytes, g->stream) != hipSuccess ||
-      hipMemsetAsync(bs->c8[1], 0, c8_bytes, g->stream) != hipSuccess ||
-      (bs->acc8_dir != 0 &&
-       hipMemsetAsync(bs->acc8, 0, sizeof(double) * ((size_t)g->gr->n + 1) * kBatch, g->stream) != hipSuccess)) {
-    set_error("batched weighted FORA: clearing the shared arrays failed: %s", hipGetErrorString(hipGetLastError()));
-    rc = PPRHIP_ERR_HIP;
-  }
-  bs->acc8_dir = 0;
-  try {
-    if (rc == PPRHIP_OK) rc = wbat_rounds(C);
-  } catch (const std::exception& ex) {  // (no exception may cross the C ABI: the seed tables' vectors allocate)
-    set_error("batched weighted FORA: %s", ex.what());
-    rc = PPRHIP_ERR_OOM;
-  }
-  const std::string msg = rc != PPRHIP_OK ? get_error() : std::string();
-  (void)hipStreamSynchronize(g->stream);
-  double tot[8] = {0};
-  uint64_t bytes[8] = {0};
-  uint32_t cnt[8] = {0};
-  local.resolve(tot, bytes, cnt);
-  local.destroy();
-  g_timer_cur = saved;
+  Cp->rmax = rmax == 0.0 ? rmax0 : rmax;
+  Cp->omega = omega;
+  const int rc = wbat_run(g, J, *Cp, [](WbatCall& C, void*) { return wbat_rounds(C); }, nullptr, "batched weighted FORA",
+                          stats_sum);
   delete Cp;
-  if (rc != PPRHIP_OK) {
-    free_batch(g);  // workspaces may hold half-pushed levels and seed tables: the next batched call builds clean ones
-    set_error("%s", msg.c_str());
-    return rc;
-  }
-  J.sum.total_ms = host_ms() - t0;
-  fold_class_totals(J.sum, tot, bytes, cnt);
-  if (stats_sum) *stats_sum = J.sum;
-  return PPRHIP_OK;
+  return rc;
 }
 
 // what both entry points check behind the parameters, the handle and the weights

@@ -6,7 +6,7 @@
 // the getters are the unweighted engine's.  The weighted seed-set push and FORA calls are in forward_calls.cpp.
 #include <cstring>
 
-#include "run.hpp"
+#include "weighted_batch.hpp"
 
 using namespace pprhip;
 using namespace pprhip::detail;
@@ -32,10 +32,13 @@ int topk_checks(pprhip_graph* g, const int32_t* src, double eps, const pprhip_fo
   return topk_args_ok(conf, eps, cap, ids_out, vals_out, fn) ? PPRHIP_OK : PPRHIP_ERR_INVALID;
 }
 
+}  // namespace
+
 // The weighted top-k loop on delta (Fora_Topk.java's schedule: nothing in it depends on the weights) from the seed
 // table `plan`.
-int topk_drive(pprhip_graph* g, SeedTable& plan, double eps, const pprhip_fora_conf_t* conf, uint64_t seed,
-               int32_t* ids_out, double* vals_out, int cap, int* n_out, double* reserve_out, pprhip_stats_t* stats) {
+int pprhip::detail::weighted_topk_drive(pprhip_graph* g, SeedTable& plan, double eps, const pprhip_fora_conf_t* conf,
+                                        uint64_t seed, int32_t* ids_out, double* vals_out, int cap, int* n_out,
+                                        double* reserve_out, pprhip_stats_t* stats) {
   const double alpha = conf->alpha;
   const TopkSchedule sc(eps * 0.5, conf);
   pprhip_stats_t st;
@@ -120,8 +123,6 @@ int topk_drive(pprhip_graph* g, SeedTable& plan, double eps, const pprhip_fora_c
   return PPRHIP_OK;
 }
 
-}  // namespace
-
 extern "C" {
 
 int pprhip_weighted_fora_topk(pprhip_graph_t* g, int32_t src, double eps, const pprhip_fora_conf_t* conf, uint64_t seed,
@@ -131,7 +132,7 @@ int pprhip_weighted_fora_topk(pprhip_graph_t* g, int32_t src, double eps, const 
   PPRHIP_TRY(topk_checks(g, &src, eps, conf, cap, ids_out, vals_out, fn));
   SeedTable plan;
   PPRHIP_TRY(seed_plan(g, &src, nullptr, 1, conf->alpha, fn, plan));  // the set {src} with weight 1
-  return topk_drive(g, plan, eps, conf, seed, ids_out, vals_out, cap, n_out, reserve_out, stats);
+  return weighted_topk_drive(g, plan, eps, conf, seed, ids_out, vals_out, cap, n_out, reserve_out, stats);
 }
 
 int pprhip_weighted_fora_topk_seeds(pprhip_graph_t* g, const int32_t* seeds, const double* weights, int n_seeds,
@@ -141,7 +142,7 @@ int pprhip_weighted_fora_topk_seeds(pprhip_graph_t* g, const int32_t* seeds, con
   PPRHIP_TRY(topk_checks(g, nullptr, eps, conf, cap, ids_out, vals_out, fn));
   SeedTable plan;
   PPRHIP_TRY(seed_plan(g, seeds, weights, n_seeds, conf->alpha, fn, plan));
-  return topk_drive(g, plan, eps, conf, seed, ids_out, vals_out, cap, n_out, reserve_out, stats);
+  return weighted_topk_drive(g, plan, eps, conf, seed, ids_out, vals_out, cap, n_out, reserve_out, stats);
 }
 
 }  // extern "C"
