@@ -190,6 +190,7 @@ int topk_session_reset(pprhip_graph* g, int32_t src, SeedTable* plan, double alp
   g->topk_seeded = plan != nullptr;
   g->topk_alpha = alpha;
   g->topk_rsum = rsum;
+  g->topk_dead_pops = 0;
   return PPRHIP_OK;
 }
 
@@ -382,7 +383,12 @@ int pprhip_fwdpush_topk_round(pprhip_graph_t* g, double min_rmax, double rmax, d
       PPRHIP_TRY(device_sum(g, g->residue, &g->topk_rsum));
     }
   }
+  // the device counts dead-end pops since the reset; a round reports its own, as it reports every other counter
+  st.dead_end_pops = g->topk_dead_pops;
   PPRHIP_TRY(read_dead_pops(g, st));
+  const uint64_t dead_seen = st.dead_end_pops;
+  st.dead_end_pops = dead_seen >= g->topk_dead_pops ? dead_seen - g->topk_dead_pops : dead_seen;
+  g->topk_dead_pops = dead_seen;
   tm.mark(1);
   tm.finish(st);
   st.push_ms = CallTimer::ms(g->ev[0], g->ev[1]);

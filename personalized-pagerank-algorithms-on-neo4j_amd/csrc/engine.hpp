@@ -700,6 +700,7 @@ struct pprhip_graph {
   bool topk_seeded = false;  // the session runs from the seed table (topk_src is -1)
   double topk_alpha = 0.0;
   double topk_rsum = 1.0;
+  uint64_t topk_dead_pops = 0;  // DevCounters::dead_pops as the session's last public round read it (it runs since the reset)
   // what `reserve`/`est` currently hold
   bool result_in_est = false;
   // seed-set query in progress (seeds.cpp: SeedScope): dead-end mass lands on the seed table, PushArgs::src is -1

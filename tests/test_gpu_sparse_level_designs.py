@@ -9,8 +9,9 @@ vector is compared with the plain reference bit for bit and every counter for eq
      every level (PPRHIP_COMB_MIN_EDGES=1), with the table on none, and once more - the same bytes and counters each time,
      so nothing is left behind in the level counters, the dead-end cell or the table
   b  the resumable top-k push over three rounds, thresholds falling by 4 and min_rmax the last one, on the B, W, T and N
-     designs.  The armed and parked path has no plain reference here: the oracle twin's topk_push is its reference, bit
-     for bit all the same
+     designs, against the oracle twin's topk_push, bit for bit.  Every round's rmax is >= min_rmax, so this covers
+     parking and the round start from the parked set and arms no node; armed nodes, dropped nodes and rounds below
+     min_rmax have designs and a plain reference of their own in tests/test_gpu_topk_round_designs.py
   c  the B, W and G designs without the one-workgroup kernel: PPRHIP_SPARSE_WG is read once per process, so one child
      process (tests/fixtures/sparse_level_child.py) runs them all with PPRHIP_SPARSE_WG=0 and its bytes equal this
      process's"""
